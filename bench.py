@@ -14,14 +14,19 @@ against the WHOLE database: score pass on each shard, RCCL all-gather of the
 shards' group maxima, fp64 re-score of the groups that can hold a global top-k
 row, RCCL all-gather of the per-shard [256,20] parts, certifying fp64 merge
 (deeploopcloser_amd.matching.MatchPipeline).  Database and queries are resident
-in HBM before the timed region.  With N > 1 the collectives are exercised and
-the pipeline's result is checked against a second, independent exchange BEFORE
-anything is timed (`rccl_smoke` in the line).
+in HBM before the timed region.  With N > 1 and --full the collectives are
+exercised and the pipeline's result is checked against a second, independent
+exchange BEFORE anything is timed (`rccl_smoke` in the line).
 
 Rank 0 prints ONE JSON line (the driver's contract) carrying also
   roofline     -- the dominant kernel (the MFMA score GEMM): algorithmic bytes
                   per launch / mean launch duration from HIP events recorded on
-                  the launch stream inside the timed region;
+                  the launch stream inside the timed region.
+A plain run stops there: set up, warm up, time the steps, print the line.
+`--dump-outputs DIR` writes the last timed step's top-k (scores and row
+indices, [queries, k]) as .npy files; the inputs are seeded, so two builds
+can be compared output for output.  `--full` adds the rest (and, with N > 1,
+the RCCL check before the timed region), among them
   cpu_baseline -- the CPU oracle (oracle/cosine.py, a port: fp64 NumPy) timed
                   on this host's cores on a bounded sample at N=1;
   paths        -- (N=1 only, outside the timed region) the other rows of the hot path at
@@ -89,6 +94,13 @@ def parse():
                     help="rehearsal of the sharded exhaustive round: the database row query 0 is planted on is copied to kg*8+1 "
                          "places spread over the whole database (every shard), so that query's k-th score ties with a row every "
                          "selection leaves behind -- no merge can certify it and every batch goes through MatchPipeline._resolve")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: N>1 the RCCL check before the timed region; N=1 the "
+                         "selection stage timed on its own, the power probe + steady state, the emulated 2 / 4 / 8-GPU step, the "
+                         "configs[3] / configs[4] rows, the `paths` rows, the CPU baseline and the RCCL child (each still off "
+                         "with its --no-* flag).  Without it: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's top-k as DIR/topk_scores.npy and DIR/topk_indices.npy")
     return ap.parse_args()
 
 
@@ -1263,6 +1275,16 @@ def write_detail(out, path=None):
             print("[bench] could not write %s: %s" % (t, e), file=sys.stderr)
 
 
+def dump_outputs(dirname, scores, idx):
+    """What the timed path returned for its last step, as a caller receives it: the [queries, k] top-k scores (float32, or
+    float64 where the path returns fp64) and database row indices (float64: exact below 2**53) -- a few tens of KB."""
+    os.makedirs(dirname, exist_ok=True)
+    s = scores.detach().cpu()
+    s = s.numpy() if s.dtype == torch.float64 else s.float().numpy()
+    np.save(os.path.join(dirname, "topk_scores.npy"), np.ascontiguousarray(s))
+    np.save(os.path.join(dirname, "topk_indices.npy"), np.ascontiguousarray(idx.detach().cpu().numpy().astype(np.float64)))
+
+
 def rccl_world1_smoke(timeout=240):
     """N = 1 only, after everything else: `python -m deeploopcloser_amd.dist --world1-smoke` as a CHILD process (a process
     group of its own, a watchdog of its own: a hang in the library's bring-up costs this key, never the line) -- a one-rank
@@ -1402,7 +1424,7 @@ def main():
     pipe = dlc.MatchPipeline(db, k, depth=2 if world == 1 else 3) if use_pipe else None
     torch.cuda.synchronize()
     smoke = None
-    if world > 1:
+    if world > 1 and args.full:
         smoke = rccl_smoke(eng, dlc, db, pipe if pipe is not None else dlc.MatchPipeline(db, k, depth=1), queries, k, lo, world)
     last = [None]
 
@@ -1444,11 +1466,14 @@ def main():
     scores, idx = res if pipe is None else pipe.result(last[0])
     gemm_ms = eng.profile_gemm_ms(min(args.steps, 256))
     eng.set_profiling(False)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, scores, idx)
+    extras = args.full and rank == 0 and world == 1             # everything below that the headline figure does not need
 
     # ---- the step's second stage on its own (N=1, untimed above): selection + fp64 re-score + certificate (+ the early-exit
     # launch of the exhaustive pass), HIP events around dlc_cosine_select_topk behind a score pass into the same workspace
     finish_ms = None
-    if world == 1 and pipe is None:
+    if extras and pipe is None:
         qs = db.prepare_queries(queries)
         ws2 = torch.empty(eng.topk_workspace_bytes(nq, db.rows.shape[0], d, k), dtype=torch.uint8, device=eng.device)
         o_s = torch.empty((nq, k), dtype=torch.float32, device=eng.device)
@@ -1530,7 +1555,7 @@ def main():
 
     # ---- package power / clock while the same loop runs on (untimed; rank 0, N=1 only): the score GEMM
     # sits on the board's power cap, which is what bounds it -------------------------
-    if rank == 0 and world == 1 and not args.no_power_probe:
+    if extras and not args.no_power_probe:
         pp = out["roofline"]["power_probe"] = power_probe(step, seconds=2.5)
         # joules per step = the probe's median package power x the probe loop's own mean step (the same loop, the same
         # operating point); the board's energy accumulator over the same stretch rides along in power_probe when it exists
@@ -1550,22 +1575,22 @@ def main():
 
     # ---- what ONE rank of a 2 / 4 / 8-GPU run would do per batch, emulated on this GPU (no RCCL): driver-timed every
     # round, since an 8-GPU node is not always at hand (rank 0, N=1 only; untimed above) ------------------------------
-    if rank == 0 and world == 1 and not args.no_shard_emulation and n >= 8 * 2048:
+    if extras and not args.no_shard_emulation and n >= 8 * 2048:
         out["multi_gpu_emulation"] = bench_shard_emulation(eng, dlc, db.rows, queries, k, idx)
 
     # ---- BASELINE configs[3] and configs[4] on this one GPU, each a timed row of its own, and one rank's step of their
     # 8-GPU form (rank 0, N=1 only; untimed above) -------------------------------------------------------------------
-    if rank == 0 and world == 1 and not args.no_configs and not args.crowded:
+    if extras and not args.no_configs and not args.crowded:
         out["baseline_configs"] = bench_configs(eng, dlc, args, db.rows, queries, planted, noise, sigma, planted_rows)
 
     # ---- the other rows of the hot path at configs[1] / configs[2] size (rank 0, N=1 only; untimed above) ----
-    if rank == 0 and world == 1 and not args.no_paths:
+    if extras and not args.no_paths:
         del rows, planted, noise
         out["paths"] = bench_paths(eng, args.path_frames)
 
     # ---- CPU baseline + index agreement on a bounded sample (rank 0, N=1 only).  LAST: its BLAS / torch thread pools keep
     # spinning for a while and took 10 ms out of the host-to-host rows above when it ran in front of them ----------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if extras and not args.no_cpu_baseline:
         from oracle import cosine as ocos
         ns = min(args.cpu_sample_rows, n)
         qh = queries.float().cpu().numpy().astype(np.float64)
@@ -1628,7 +1653,7 @@ def main():
         out["topk_index_agreement_rows"] = ns
         out["topk_score_max_abs_err_vs_oracle"] = float(np.abs(s_gpu.cpu().numpy() - best_s).max())
 
-    if rank == 0 and world == 1 and not args.no_rccl_smoke:
+    if extras and not args.no_rccl_smoke:
         out["rccl_world1_smoke"], out["rccl_world1_smoke_full"] = rccl_world1_smoke()
 
     # the collectives come down FIRST (whatever the library prints on the way out must not follow the line), then rank 0

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Sample rocm-smi while the bench loops (GPU box only).
 cd "$(dirname "$0")/.."
-python bench.py --steps 2000 --warmup 3 --no-cpu-baseline > /tmp/bench_long.log 2>&1 &
+LOG=$(mktemp)
+python bench.py --full --steps 2000 --warmup 3 --no-cpu-baseline > "$LOG" 2>&1 &
 BP=$!
 sleep 6
 for i in 1 2 3; do
@@ -10,4 +11,5 @@ for i in 1 2 3; do
   sleep 1
 done
 wait $BP
-tail -1 /tmp/bench_long.log | cut -c1-200
+tail -1 "$LOG" | cut -c1-200
+rm -f "$LOG"

@@ -1,7 +1,7 @@
 # GPU box only: bench.py at the full size with 1, 2 and 4 ranks (the N > 1 runs: all ranks on the box's ONE GPU over gloo),
 # plain and --crowded; the one-line summaries go to gpurun_out/rehearsal.txt (copy to profiles/<round>_multirank_rehearsal.txt).
 set -e
-F="--steps 20 --warmup 5 --no-paths --no-cpu-baseline --no-power-probe --no-shard-emulation --no-configs --no-rccl-smoke"
+F="--full --steps 20 --warmup 5 --no-paths --no-cpu-baseline --no-power-probe --no-shard-emulation --no-configs --no-rccl-smoke"
 for n in 1 2 4; do
   if [ $n = 1 ]; then X=""; else X="--backend gloo --share-gpu"; fi
   timeout -k 10 500 python bench.py --gpus $n $X $F --detail gpurun_out/reh_$n.detail.json > gpurun_out/reh_$n.json 2> gpurun_out/reh_$n.err

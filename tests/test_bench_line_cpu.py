@@ -69,6 +69,21 @@ def test_path_ids_are_distinct():
     assert len(set(ids)) == len(ids), ids
 
 
+def test_dump_outputs_float_arrays(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    idx = torch.tensor([[5, 2**40 + 3], [0, 7]], dtype=torch.int64)
+    for scores, want in ((torch.tensor([[0.9, 0.5], [0.25, -1.0]], dtype=torch.bfloat16), np.float32),
+                         (torch.tensor([[0.9, 0.5], [0.25, -1.0]], dtype=torch.float32), np.float32),
+                         (torch.tensor([[0.9, 0.5], [0.25, -1.0]], dtype=torch.float64), np.float64)):
+        d = str(tmp_path / str(want.__name__) / "new")
+        b.dump_outputs(d, scores, idx)
+        s, i = np.load(os.path.join(d, "topk_scores.npy")), np.load(os.path.join(d, "topk_indices.npy"))
+        assert s.dtype == want and np.array_equal(s, scores.double().numpy())
+        assert i.dtype == np.float64 and np.array_equal(i.astype(np.int64), idx.numpy())
+
+
 def test_detail_file_roundtrip(tmp_path):
     b = _bench()
     full = _full_results()[-1]

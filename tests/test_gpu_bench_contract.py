@@ -46,7 +46,7 @@ def run_bench(extra, launcher=None, timeout=900, want_line=False):
 
 def test_bench_json_contract():
     d, line = run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--rows", "30000", "--cpu-sample-rows", "30000",
-                         "--no-power-probe", "--path-frames", "24"], want_line=True)
+                         "--no-power-probe", "--path-frames", "24", "--full"], want_line=True)
     # the line itself: the contract keys, roofline, cpu_baseline, the agreement, one triple per other row of the hot path
     for key, typ in [("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str),
@@ -150,12 +150,40 @@ def test_bench_json_contract():
     assert paths["SDAV.transform"]["roofline"]["kernel_launches_timed"] == 5
 
 
+def test_plain_bench_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the run only sets up, warms up, times the steps and prints the line; --dump-outputs writes the last
+    timed step's top-k, the same arrays on every run with the same arguments, and they are the result the digests name."""
+    import hashlib
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out_dir = str(tmp_path / ("dump%d" % run))
+        d, line = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "30000", "--dump-outputs", out_dir],
+                            want_line=True)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["recall_at_1"] == 1.0
+        assert abs(d["value"] - 256 * 3 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 1e-6
+        assert d["roofline"]["kernel_ms"] > 0 and d["finish_ms"] is None
+        for key in ("cpu_baseline", "paths", "baseline_configs", "multi_gpu_emulation", "steady_state", "rccl_world1_smoke"):
+            assert key not in d and key not in line, key
+        assert "power_probe" not in d["roofline"]
+        s = np.load(os.path.join(out_dir, "topk_scores.npy"))
+        i = np.load(os.path.join(out_dir, "topk_indices.npy"))
+        assert s.shape == i.shape == (256, 20) and s.dtype in (np.float32, np.float64) and i.dtype == np.float64
+        assert np.all(np.isfinite(s)) and np.all(np.diff(s, axis=1) <= 0)
+        assert np.array_equal(i, np.round(i)) and i.min() >= 0 and i.max() < 30000
+        assert hashlib.sha256(np.ascontiguousarray(i.astype(np.int64)).tobytes()).hexdigest() == d["topk_idx_sha256"]
+        assert hashlib.sha256(np.ascontiguousarray(s).tobytes()).hexdigest() == d["topk_scores_sha256"]
+        dumps.append((s, i))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 def test_bench_two_ranks_equal_one_rank():
     """`bench.py --gpus 2` as the driver launches it (python -m torch.distributed.run, one process per rank),
     with --backend gloo --share-gpu so that both ranks can use this box's single GPU: MatchPipeline's sharded
     protocol (group selection -> all-gather of the group maxima -> filtered re-score -> all-gather of the
     packed per-shard top-k -> merge) must give recall 1.0 and exactly the one-rank result."""
-    common = ["--steps", "6", "--warmup", "2", "--rows", "40000", "--no-cpu-baseline", "--no-power-probe", "--no-paths", "--no-rccl-smoke"]
+    common = ["--steps", "6", "--warmup", "2", "--rows", "40000", "--no-cpu-baseline", "--no-power-probe", "--no-paths", "--no-rccl-smoke",
+              "--full"]
     one = run_bench(["--gpus", "1"] + common)
     port = 29600 + os.getpid() % 300
     two = run_bench(["--gpus", "2", "--backend", "gloo", "--share-gpu"] + common,
@@ -179,7 +207,8 @@ def test_bench_launches_its_own_ranks():
     command line would call it) starts its two rank processes itself, before it touches the GPU, relays rank 0's one
     JSON line and exit code, and gets the one-rank digests.  Four ranks on the one GPU as well (12 500-row shards: the
     small-database plan on every rank, another plan than the one-rank run's -- same digests)."""
-    common = ["--steps", "4", "--warmup", "1", "--rows", "50000", "--no-cpu-baseline", "--no-power-probe", "--no-paths", "--no-rccl-smoke"]
+    common = ["--steps", "4", "--warmup", "1", "--rows", "50000", "--no-cpu-baseline", "--no-power-probe", "--no-paths", "--no-rccl-smoke",
+              "--full"]
     one = run_bench(["--gpus", "1"] + common)
     for ranks in (2, 4):
         got = run_bench(["--gpus", str(ranks), "--backend", "gloo", "--share-gpu"] + common)
@@ -195,7 +224,7 @@ def test_sharded_exhaustive_round_across_processes():
     a third all-gather, a merge -- for every batch, agree on the flags (nobody hangs in a collective the other skipped),
     drop nothing and return exactly the one-rank lists."""
     common = ["--steps", "5", "--warmup", "2", "--rows", "40000", "--no-cpu-baseline", "--no-power-probe", "--no-paths",
-              "--no-shard-emulation", "--no-rccl-smoke", "--crowded"]
+              "--no-shard-emulation", "--no-rccl-smoke", "--crowded", "--full"]
     one = run_bench(["--gpus", "1"] + common)
     port = 29900 + os.getpid() % 90
     two = run_bench(["--gpus", "2", "--backend", "gloo", "--share-gpu"] + common,
