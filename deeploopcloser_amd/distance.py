@@ -56,3 +56,118 @@ class DistanceCalculator:
         if d.dim() != 2:
             raise ValueError("descriptors must be [N, D] int8")
         return e.cnnvtl_distance_matrix(d).cpu().numpy()
+
+
+class CnnVtlKeyframeDatabase:
+    """cnn_vtl key-frame descriptors (int8 [n, dim]) resident in HBM, searched by the reference's distance.
+
+    Rows are stored zero-padded to a multiple of 16 bytes (the top-k kernel's row alignment) in a capacity-reserved
+    buffer that doubles when an append() outgrows it; `rows` is the view of the first len(db) rows.  nearest() is
+    dlc_cnnvtl_distance_topk: distance ascending, ties -> the lower id, (-1, -1) past the rows there are."""
+
+    FORMAT = "dlc-cnnvtl-keyframes-v1"
+
+    def __init__(self, descriptors, capacity=None, device=None):
+        self.engine = default_engine(device)
+        x = self.engine.to_device(descriptors)
+        if x.dim() != 2 or x.dtype != torch.int8:
+            raise ValueError("cnn_vtl descriptors must be [n, dim] int8")
+        if x.shape[1] < 1:
+            raise ValueError("cnn_vtl descriptors must have dim >= 1")
+        self.dim = int(x.shape[1])
+        self._n = 0
+        n = int(x.shape[0])
+        cap = max(n, 1 if capacity is None else int(capacity))
+        self._store = torch.zeros((cap, self.stored_width(self.dim)), dtype=torch.int8, device=self.engine.device)
+        if n:
+            self._store[:n, :self.dim] = x
+            self._n = n
+
+    @staticmethod
+    def stored_width(dim):
+        return (int(dim) + 15) // 16 * 16
+
+    @classmethod
+    def empty(cls, dim, capacity=4096, device=None):
+        """A database of `dim`-byte descriptors with no key-frames yet and room for `capacity`."""
+        if dim < 1 or capacity < 1:
+            raise ValueError("CnnVtlKeyframeDatabase.empty: dim and capacity must be positive")
+        eng = default_engine(device)
+        return cls(torch.empty((0, int(dim)), dtype=torch.int8, device=eng.device), capacity=capacity, device=device)
+
+    @property
+    def rows(self):
+        """[len, stored_width(dim)] int8: the stored rows, padding bytes included."""
+        return self._store[:self._n]
+
+    @property
+    def capacity(self):
+        return self._store.shape[0]
+
+    def __len__(self):
+        return self._n
+
+    def reserve(self, capacity):
+        """Room for at least `capacity` key-frames (one device-to-device copy when it grows)."""
+        if capacity > self.capacity:
+            grown = torch.zeros((int(capacity), self._store.shape[1]), dtype=torch.int8, device=self.engine.device)
+            grown[:self._n] = self._store[:self._n]
+            self._store = grown
+
+    def append(self, descriptors):
+        """Store further key-frames [B, dim] int8; returns their ids (first, last+1).  Stream-ordered on the current
+        stream."""
+        x = self.engine.to_device(descriptors)
+        if x.dim() != 2 or x.dtype != torch.int8 or x.shape[1] != self.dim:
+            raise ValueError("append: descriptors must be [B, %d] int8" % self.dim)
+        b = int(x.shape[0])
+        if self._n + b > self.capacity:
+            self.reserve(max(2 * self.capacity, self._n + b))
+        self._store[self._n:self._n + b, :self.dim] = x
+        first = self._n
+        self._n += b
+        return first, first + b
+
+    def prefix(self, n):
+        """The first n key-frames as a database of their own (a copy: a database owns its reservation)."""
+        if not 0 <= n <= self._n:
+            raise ValueError("prefix: n=%d outside 0..%d" % (n, self._n))
+        return CnnVtlKeyframeDatabase(self._store[:n, :self.dim], device=self.engine.device)
+
+    def nearest(self, queries, k, limit0=None, limit_step=0):
+        """(dist [Q, k] int64, ids [Q, k] int64) on the device: the k stored key-frames nearest to each query row
+        ([Q, dim] int8) by the reference's distance.  limit0 / limit_step: query r sees the first limit0 + r * limit_step
+        key-frames (default: all)."""
+        q = self.engine.to_device(queries)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.dtype != torch.int8 or q.shape[1] != self.dim:
+            raise ValueError("nearest: queries must be [Q, %d] int8" % self.dim)
+        return self.engine.cnnvtl_distance_topk(q, self.rows, int(k), d=self.dim,
+                                                limit0=self._n if limit0 is None else limit0, limit_step=limit_step)
+
+    # ---- on-disk format: one .npz ------------------------------------------------------------------------------------
+    def save(self, path):
+        """The descriptors' raw bytes [n, dim] and dim."""
+        np.savez(path, rows_i8=self.rows[:, :self.dim].cpu().numpy(), dim=np.array(self.dim, dtype=np.int64),
+                 format=np.array(self.FORMAT))
+
+    @classmethod
+    def load(cls, path, capacity=None, device=None):
+        z = np.load(path)
+        if "format" not in z or str(z["format"]) != cls.FORMAT:
+            raise ValueError("%s is not a %s file" % (path, cls.FORMAT))
+        rows = z["rows_i8"].astype(np.int8, copy=False).reshape(-1, int(z["dim"]))
+        return cls(torch.from_numpy(np.ascontiguousarray(rows)), capacity=capacity, device=device)
+
+
+def distance_topk(desc_q, desc_db, k):
+    """(dist [Q, k] int64, idx [Q, k] int64) numpy arrays: the k rows of desc_db [N, D] int8 nearest to each row of
+    desc_q [Q, D] int8 by the reference's distance; distance ascending, ties -> the lower row, (-1, -1) past N."""
+    q = np.ascontiguousarray(np.asarray(desc_q, dtype=np.int8))
+    db = np.ascontiguousarray(np.asarray(desc_db, dtype=np.int8))
+    if q.ndim != 2 or db.ndim != 2 or q.shape[1] != db.shape[1]:
+        raise ValueError("distance_topk: desc_q [Q, D] and desc_db [N, D] with one D")
+    e = default_engine()
+    dist, idx = e.cnnvtl_distance_topk(e.to_device(q, torch.int8), e.to_device(db, torch.int8), int(k))
+    return dist.cpu().numpy(), idx.cpu().numpy()

@@ -734,6 +734,55 @@ class Engine:
                                                          self._stream()))
         return out
 
+    def _rows16(self, x, d):
+        """x [n, >= d] int8 as rows the top-k kernel takes (16-byte aligned base and stride): x itself when it already is,
+        else a zero-padded copy of its first d columns."""
+        if x.stride(1) == 1 and x.stride(0) % 16 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) >= d:
+            return x
+        padded = torch.zeros((x.shape[0], (d + 15) // 16 * 16), dtype=torch.int8, device=self.device)
+        padded[:, :d] = x[:, :d]
+        return padded
+
+    def cnnvtl_distance_topk(self, q, db, k, d=None, limit0=None, limit_step=0, out=None):
+        """(dist [Q, k] int64, idx [Q, k] int64): the k rows of db [N, D] int8 nearest to each query row of q [Q, D] int8 by
+        the cnn_vtl distance, distance ascending, ties -> the lower row; query r sees the first min(N, limit0 + r *
+        limit_step) rows (limit0 None = N); (-1, -1) where it sees fewer than k.  d: the descriptor length when the rows are
+        padded (the bytes past d are ignored); out: a caller-kept (dist, idx) pair."""
+        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
+            raise ValueError("cnnvtl_distance_topk: q and db must be 2-D int8")
+        if q.device != self.device or db.device != self.device:
+            raise ValueError("cnnvtl_distance_topk: q and db must be on %s" % self.device)
+        if d is None:
+            if q.shape[1] != db.shape[1]:
+                raise ValueError("cnnvtl_distance_topk: q and db widths differ (%d, %d)" % (q.shape[1], db.shape[1]))
+            d = q.shape[1]
+        d = int(d)
+        if d > q.shape[1] or d > db.shape[1]:
+            raise ValueError("cnnvtl_distance_topk: d=%d exceeds the rows' width" % d)
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("cnnvtl_distance_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        nq, n = q.shape[0], db.shape[0]
+        if out is None:
+            dist = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        else:
+            dist = self._check_out("out[0] (dist)", out[0], (nq, k), torch.int64)
+            idx = self._check_out("out[1] (idx)", out[1], (nq, k), torch.int64)
+        if nq == 0:
+            return dist, idx
+        if n == 0 or d == 0:
+            dist.fill_(-1)
+            idx.fill_(-1)
+            return dist, idx
+        q = self._rows16(q, d)
+        db = self._rows16(db, d)
+        need = self.lib.dlc_cnnvtl_distance_topk_workspace_bytes(nq, n, d, k)
+        ws = self.workspace("distance_topk", need)
+        self._check(self.lib.dlc_cnnvtl_distance_topk(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
+                                                       n if limit0 is None else int(limit0), int(limit_step), int(k),
+                                                       _ptr(dist), _ptr(idx), _ptr(ws), ws.numel(), self._stream()))
+        return dist, idx
+
     # ---- cosine + top-k -----------------------------------------------------------------
     @staticmethod
     def stored_width(d):

@@ -250,6 +250,52 @@ class SdavLoopClosureDetector:
                 if i[r, c] >= 0 and s[r, c] >= self.threshold]
 
 
+class CnnVtlLoopClosureDetector:
+    """The streaming question asked with the REFERENCE's cnn_vtl measure (DistanceCalculator.calculate_distance,
+    src/cnn_vtl/similarity/DistanceCalculator.py:4-12) instead of the cosine of the descriptors: every new frame's int8
+    descriptor is compared with all resident frames more than `exclusion` frames older, and the k nearest (distance
+    ascending, ties -> the older frame) at or below `max_distance` (all of them when None) are the loop candidates.
+    A batch of B frames is one top-k launch: frame first + r sees the frames below first + r - exclusion
+    (dlc_cnnvtl_distance_topk with limit_step = 1), so the lists do not depend on how the frames are batched."""
+
+    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None):
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if exclusion < 0:
+            raise ValueError("exclusion must be >= 0")
+        if max_distance is not None and max_distance < 0:
+            raise ValueError("max_distance must be >= 0 (or None)")
+        if dim < 1 or capacity < 1:
+            raise ValueError("dim and capacity must be positive")
+        self.k, self.exclusion = int(k), int(exclusion)
+        self.max_distance = None if max_distance is None else int(max_distance)
+        from .distance import CnnVtlKeyframeDatabase
+        self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+
+    def __len__(self):
+        return len(self.db)
+
+    def query_and_insert(self, descriptors):
+        """The next B frames' int8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (dist [B, k] int64,
+        ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
+        key-frames afterwards."""
+        db = self.db
+        x = db.engine.to_device(descriptors)
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        first, _ = db.append(x)
+        b = x.shape[0]
+        return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
+                                              limit0=first - self.exclusion, limit_step=1)
+
+    def loops(self, dist, ids, first_id):
+        """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance."""
+        d, i = dist.cpu().numpy(), ids.cpu().numpy()
+        lim = self.max_distance
+        return [(first_id + r, int(i[r, c]), int(d[r, c])) for r in range(d.shape[0]) for c in range(d.shape[1])
+                if i[r, c] >= 0 and (lim is None or d[r, c] <= lim)]
+
+
 def _frame_files(dataset_path, pattern):
     files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
     if not files:
@@ -280,14 +326,16 @@ def describe_sdav(files, network=None, key_points_fn=None):
     return desc.view(len(files), -1)
 
 
-def describe_cnn_vtl(files, network=None):
-    """Frames -> CnnVtl int8 descriptors [B, D'] as float32 for the cosine engine, a DEVICE tensor (pipeline.py)."""
+def describe_cnn_vtl(files, network=None, as_int8=False):
+    """Frames -> CnnVtl int8 descriptors [B, D'] as float32 for the cosine engine (as_int8: as they are, for the distance
+    search), a DEVICE tensor (pipeline.py)."""
     from . import pipeline
     from .cnn_vtl import CnnVtl
     from .input import read_ppm
     frames = np.stack([read_ppm(f)[..., ::-1] for f in files])           # BGR, as create_distance_matrix.py:23
     network = network or CnnVtl(input_shape=[len(files)] + list(frames.shape[1:]))
-    return pipeline.cnn_vtl_descriptors_from_frames(frames, network).to(torch.float32)
+    desc = pipeline.cnn_vtl_descriptors_from_frames(frames, network)
+    return desc if as_int8 else desc.to(torch.float32)
 
 
 def main(argv=None):
@@ -298,12 +346,18 @@ def main(argv=None):
     ap.add_argument("--weights", help=".npz written by SDAV.save_weights (sdav) / AlexNet .npy blob (cnn_vtl)")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--threshold", type=float, default=0.9)
+    ap.add_argument("--metric", choices=["cosine", "distance"], default="cosine",
+                    help="cosine of the descriptors, or the reference's cnn_vtl distance (needs --network cnn_vtl)")
+    ap.add_argument("--max-distance", type=int, default=None,
+                    help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
     ap.add_argument("--no-latency-mode", action="store_true",
                     help="keep the one-pass GEMMs (bit-identical to a large-batch encode) for small batches too")
     args = ap.parse_args(argv)
+    if args.metric == "distance" and args.network != "cnn_vtl":
+        ap.error("--metric distance needs --network cnn_vtl")
 
     files = _frame_files(args.dataset_path, args.pattern)
     from .engine import default_engine
@@ -327,22 +381,25 @@ def _stream(args, files):
         net = CnnVtl(input_shape=[args.batch] + list(shape))
         if args.weights:
             net.load_alexnet_npy(args.weights)
-        describe = lambda fs: describe_cnn_vtl(fs, net)
+        describe = lambda fs: describe_cnn_vtl(fs, net, as_int8=args.metric == "distance")
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
         chunk = files[lo:lo + args.batch]
         t0 = time.perf_counter()
         desc = describe(chunk)
-        if det is None:
+        if det is None and args.metric == "distance":
+            det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
+                                            exclusion=args.exclusion, capacity=max(4096, len(files)))
+        elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))
         s, i = det.query_and_insert(desc)
         found = det.loops(s, i, lo)                              # (the one host read of the step)
         lat.append(((time.perf_counter() - t0) * 1e3, len(chunk)))
         for frame, match, score in found:
-            print("loop\t%d\t%s\t%d\t%s\t%.4f" % (frame, os.path.basename(files[frame]), match,
-                                                 os.path.basename(files[match]), score))
+            print(("loop\t%d\t%s\t%d\t%s\t" + ("%d" if args.metric == "distance" else "%.4f"))
+                  % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
     print("frames\t%d\tkey-frames\t%d" % (len(files), len(det)), file=sys.stderr)
     # the first step pays one-time costs (the library's first launches, workspaces, the database's reservation): reported apart
     steady = lat[1:] if len(lat) > 1 else lat

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 9
+#define DLC_ABI_VERSION 10
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -420,6 +420,25 @@ int dlc_topk_rows_f64(dlc_ctx* ctx, const double* scores, int64_t rows, int64_t 
  */
 int dlc_cnnvtl_distance_matrix(dlc_ctx* ctx, const int8_t* desc, int64_t N, int64_t D, int64_t ldd,
                                int64_t* out, void* stream);
+/*
+ * k nearest db rows by the same distance, fused (no [Q, N] matrix is formed): for every query row r of queries [Q, D]
+ * (row stride ldq), the k rows with the smallest distance among the first L_r = min(N, limit0 + r * limit_step) rows of
+ * db [N, D] (row stride ldd); none when L_r <= 0.  limit_step = 0, limit0 = N: a plain k-nearest search; limit_step = 1:
+ * a batch of streamed frames, row r sees one frame more than row r - 1 (the convention of dlc_topk_rows_f64).
+ * Order: distance ascending, ties -> the lower db row (the older frame).  out_dist / out_idx [Q, k] (int64, row-major):
+ * (-1, -1) in the slots past min(k, L_r).  Integers throughout: the result is exact and does not depend on the plan.
+ * Rows: both bases 16-byte aligned, ldq and ldd multiples of 16 bytes (>= D); bytes D .. ld-1 of a row may hold
+ * anything and change nothing.  queries may be rows of db itself (both are only read); the outputs and the workspace
+ * must not overlap the operands or each other.  1 <= k <= DLC_MAX_K, D <= 2^28 (int32 sums), N < 2^32.
+ * Workspace: dlc_cnnvtl_distance_topk_workspace_bytes(Q, N, D, k) bytes (0 = bad arguments: k outside 1..DLC_MAX_K
+ * or an empty operand), 256-byte aligned.  Two launches on `stream`.
+ */
+size_t dlc_cnnvtl_distance_topk_workspace_bytes(int64_t Q, int64_t N, int64_t D, int k);
+int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int64_t ldq,
+                             const int8_t* db, int64_t N, int64_t ldd, int64_t D,
+                             int64_t limit0, int64_t limit_step, int k,
+                             int64_t* out_dist, int64_t* out_idx,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
