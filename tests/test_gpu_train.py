@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from test_gpu_train_routes import assert_step_delta
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +35,7 @@ def test_train_step_small_vs_oracle(layer):
     bes = [rng.standard_normal(b) * 0.1 for b in dims[1:]]
     bds = [rng.standard_normal(a) * 0.1 for a in dims[:-1]]
     masks = [corruption_mask((patches, d), 0.3, rng) for d in dims[:-1]]
-    want_loss, (cd, cs, cc), _, _, _ = ot.loss_and_grads(layer, x, masks, ws, bes, bds[layer])
+    want_loss, (cd, cs, cc), g_ws, g_bes, g_bdec = ot.loss_and_grads(layer, x, masks, ws, bes, bds[layer])
     _, w1, be1, bd1 = ot.sgd_step(layer, x, masks, ws, bes, bds, lr=0.1)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
     W, BE, BD, M = [dev(w) for w in ws], [dev(b) for b in bes], [dev(b) for b in bds], [dev(m) for m in masks]
@@ -47,7 +48,11 @@ def test_train_step_small_vs_oracle(layer):
         assert close(W[l].cpu().numpy(), w1[l]) and close(BE[l].cpu().numpy(), be1[l])
         if l > layer:
             assert np.array_equal(W[l].cpu().numpy(), ws[l])                   # untouched
+        else:                                                                   # the step itself, to 1e-9 of its size
+            assert_step_delta(ws[l], W[l].cpu().numpy(), -0.1 * g_ws[l], what="W[%d]" % l)
+            assert_step_delta(bes[l], BE[l].cpu().numpy(), -0.1 * g_bes[l], what="b_enc[%d]" % l)
     assert close(BD[layer].cpu().numpy(), bd1[layer])
+    assert_step_delta(bds[layer], BD[layer].cpu().numpy(), -0.1 * g_bdec, what="b_dec[%d]" % layer)
 
 
 def test_sdav_train_step_real_shape_and_fit_surface(tmp_path):
@@ -61,12 +66,17 @@ def test_sdav_train_step_real_shape_and_fit_surface(tmp_path):
     masks = [net._mask(l).cpu().numpy() for l in range(2)]
     assert masks[0].shape == (30, 1681) and int((masks[0] == 0).sum()) == int(np.round(30 * 1681 * 0.3))
     want_loss, w1, be1, bd1 = ot.sgd_step(1, x, masks, ws, bs, bds, lr=net.learning_rate)
+    _, _, g_ws, g_bes, g_bdec = ot.loss_and_grads(1, x, masks, ws, bs, bds[1])
     loss = net.train_step(1, x, masks=masks)
     assert close(loss[0].item(), want_loss)
     w_new, b_new = net.get_weights()
     for l in range(5):
         assert close(w_new[l], w1[l]) and close(b_new[l], be1[l])
+        if l <= 1:                                                              # the step itself, to 1e-9 of its size
+            assert_step_delta(ws[l], w_new[l], -net.learning_rate * g_ws[l], what="W[%d]" % l)
+            assert_step_delta(bs[l], b_new[l], -net.learning_rate * g_bes[l], what="b_enc[%d]" % l)
     assert close(net._biases_dec[1].cpu().numpy(), bd1[1]) and net.global_step == 1
+    assert_step_delta(bds[1], net._biases_dec[1].cpu().numpy(), -net.learning_rate * g_bdec, what="b_dec[1]")
     # the loss goes down on repeated steps of one layer (same batch), as SDAV.fit drives it
     net.epochs = 3
     l0 = float(net.train_step(0, x)[0])
