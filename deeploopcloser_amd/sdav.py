@@ -40,6 +40,10 @@ def _init_weights(dims, seed, dtype, device, scale="reference"):
 
 
 class SDAV:
+    """The reference's SDAV network (SDAV.py).  dtype "float64" (default) matches the reference; "float32" runs the
+    same chain in fp32; "f16x2" is the tolerance mode (include/dlc.h: dlc_sdav_encode_split), whose inputs must lie in
+    [-16, 16]: a row holding a larger value, an infinity or a NaN comes out as NaN, the other rows are unaffected."""
+
     def __init__(self, verbosity=logging.WARNING, seed=0, dtype="float64", device=None, weight_scale="reference",
                  hidden_units=None):
         self.logger = logging.getLogger()

@@ -533,6 +533,34 @@ def test_gemm_dma_every_element_repeated(dlc):
         del p, got
 
 
+@pytest.mark.parametrize("scale", ["reference", "fan_in"])
+def test_split_encoder_every_element_repeated(dlc, scale):
+    """Race screen for the tolerance-mode encoder's LDS ring (dlc_sdav_encode_split: 2 1/2 slices with counted waits,
+    a stale slot shows up as a few wrong elements): the reference's 1063 frames (31 890 rows) through 1681 -> 2500 x 5,
+    three launches on fresh data, every element against the fp64 chain within the propagated bound of
+    tests/precision_bounds.py; a repeat on the same data gives the same bits."""
+    import precision_bounds as pb
+    eng = dlc.default_engine()
+    g = torch.Generator(device="cuda")
+    dims = [1681] + [2500] * 5
+    worst = 0.0
+    for rep in range(3):
+        g.manual_seed(900 + rep)
+        x = torch.rand((31890, 1681), generator=g, device="cuda", dtype=torch.float64)
+        ws = [torch.randn((k, n), generator=g, device="cuda", dtype=torch.float64) / (k ** 0.5 if scale == "fan_in" else 1.0)
+              for k, n in zip(dims[:-1], dims[1:])]
+        bs = [0.1 * torch.randn((n,), generator=g, device="cuda", dtype=torch.float64) for n in dims[1:]]
+        panels = eng.sdav_split_panels(ws)
+        got = eng.sdav_encode_split(x, dims, panels, bs)
+        again = eng.sdav_encode_split(x, dims, panels, bs)
+        assert torch.equal(got, again), rep
+        (h, e), = pb.split_chain_bound(x, ws, bs)[-1:]
+        worst = max(worst, pb.ratio(got - h, e))
+        assert worst <= 1.0, (rep, worst)
+        del x, ws, panels, got, again, h, e
+    print("split encoder, 31 890 rows, %s weights, 3 launches: worst err/bound %.3g" % (scale, worst))
+
+
 @pytest.mark.parametrize("batch", [32, 50])
 def test_streaming_detector_kennedylong_two_batches_in_flight(dlc, descriptors, batch):
     """configs[1]'s 1063 frames arriving in batches, with the REFERENCE's similarity (create_similarity_matrix.py:34-38 as a
