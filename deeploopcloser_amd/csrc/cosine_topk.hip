@@ -1980,16 +1980,10 @@ inline bool small_direct(const MatchCall& mc, int k) {
 }
 
 int run_score(dlc_ctx* ctx, int dtype, MatchCall& mc, hipStream_t st, bool partials_only = false) {
-    const int slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-    if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[slot], st));
-    int rc = (dtype == DLC_BF16) ? launch_scores<dlc_bf16_tag>(ctx, mc.a, false, st, mc.w.dense, partials_only)
-                                 : launch_scores<dlc_f16_tag>(ctx, mc.a, false, st, mc.w.dense, partials_only);
-    if (rc != DLC_OK) return rc;
-    if (ctx->profiling) {
-        DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[slot], st));
-        ctx->prof_calls++;
-    }
-    return DLC_OK;
+    return dlc::profiled(ctx, st, [&]() -> int {
+        return (dtype == DLC_BF16) ? launch_scores<dlc_bf16_tag>(ctx, mc.a, false, st, mc.w.dense, partials_only)
+                                   : launch_scores<dlc_f16_tag>(ctx, mc.a, false, st, mc.w.dense, partials_only);
+    });
 }
 
 // Arguments every selection kernel of a prepared match shares.

@@ -15,7 +15,7 @@ struct dlc_ctx {
     int device;
     char err[512];
     int profiling;
-    long long prof_calls;                       // cosine_topk calls recorded since profiling was enabled
+    long long prof_calls;                       // ring entries (product-kernel launches, dlc::profiled) since profiling was enabled
     hipEvent_t ev_start[DLC_PROFILE_RING];
     hipEvent_t ev_stop[DLC_PROFILE_RING];
     void* scratch;                              // caller-owned split-K scratch (dlc_set_scratch), may be null
@@ -73,6 +73,20 @@ inline int fail(dlc_ctx* ctx, int status, const char* fmt, ...) {
             return dlc::fail((ctx), DLC_ERR_HIP, "launch of %s failed: %s", (what),           \
                              hipGetErrorString(e__));                                         \
     } while (0)
+
+// bench.py's kernel-only timing (dlc_set_profiling): one ring entry, a hipEvent pair on the stream around the ONE product
+// kernel launch() makes (a split-K reduce or a min / max fold over its output is launched outside it).
+template <typename F>
+inline int profiled(dlc_ctx* ctx, hipStream_t st, F&& launch) {
+    if (!ctx->profiling) return launch();
+    const int slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
+    DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[slot], st));
+    const int rc = launch();
+    if (rc != DLC_OK) return rc;
+    DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[slot], st));
+    ctx->prof_calls++;
+    return DLC_OK;
+}
 
 __host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

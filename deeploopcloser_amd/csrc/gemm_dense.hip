@@ -400,14 +400,13 @@ __global__ __launch_bounds__(256) void splitk_bias_act_kernel(const T* __restric
 // CUs, or a little more than a whole number of rounds, waste the difference.  The plan minimises
 // rounds x (K steps per chunk x t_step + 6 us) + the partial tiles written and read back + the
 // second launch, and splits only for a clear gain.
-template <typename T>
-int plan_split(const dlc_ctx* ctx, int64_t M, int64_t N, int64_t K, long long* kchunk) {
+static int plan_split(const dlc_ctx* ctx, size_t esize, int64_t M, int64_t N, int64_t K, int64_t* kchunk) {
     const int64_t wgs = dlc::cdiv(M, TM) * dlc::cdiv(N, TN), ksteps = dlc::cdiv(K, TK);
     *kchunk = ksteps * TK;
     if (!ctx->scratch || wgs >= 1024 || ksteps < 16) return 1;
-    const double t_step = sizeof(T) == 8 ? 1.9 : 1.0, t_fix = 6.0, t_launch = 5.0, bytes_per_us = 3.0e6;
-    const double part_bytes = (double)M * (double)N * sizeof(T);
-    const int64_t fit = (int64_t)(ctx->scratch_bytes / ((size_t)M * (size_t)N * sizeof(T)));
+    const double t_step = esize == 8 ? 1.9 : 1.0, t_fix = 6.0, t_launch = 5.0, bytes_per_us = 3.0e6;
+    const double part_bytes = (double)M * (double)N * esize;
+    const int64_t fit = (int64_t)(ctx->scratch_bytes / ((size_t)M * (size_t)N * esize));
     double best_t = (double)dlc::cdiv(wgs, (int64_t)256) * ((double)ksteps * t_step + t_fix);
     int64_t best_steps = ksteps;
     for (int64_t s_ = 2; s_ <= std::min<int64_t>(std::min<int64_t>(ksteps / 8, fit), 64); ++s_) {
@@ -440,109 +439,102 @@ int launch_kernel(dlc_ctx* ctx, const Args<T>& a, long long nwg, hipStream_t st)
 // pass that sums the chunks in chunk order and applies bias + activation.  A 64-row workgroup keeps a CU's fp64 matrix
 // pipes busy on its own, so a launch costs about (its MFMA work) / (the CUs it reaches): the chunk count is the one that
 // fills the 512 slots (two such workgroups per CU) once.  Needs the context's scratch (latency mode; the training step
-// lends it).  K: the reduction length as A has it (even), Kb <= K as B has it.  DLC_OK, 1 = not taken, < 0 = error.
-static int dma_splitk_f64(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int64_t K, int64_t Kb, const double* A,
-                          int64_t lda, const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st) {
-    if (!ctx->scratch || N <= 96) return 1;
+// lends it).  A chunk is at least 8 K tiles (want <= nkt / 8).
+static bool plan_dma_splitk(const dlc_ctx* ctx, const GemmCall& c, GemmPlan* p) {
+    const int64_t M = c.M, N = c.N, K = c.K;
+    if (!ctx->scratch || N <= 96) return false;                   // (the 96-column form keeps the 256-row tile)
     const int64_t tiles = dlc::cdiv(M, (int64_t)64) * dlc::cdiv(N, (int64_t)128), nkt = dlc::cdiv(K, (int64_t)16);
-    if (tiles >= 256) return 1;
+    if (tiles >= 256) return false;
     const int64_t fit = (int64_t)(ctx->scratch_bytes / ((size_t)M * (size_t)N * sizeof(double)));
     const int64_t want = std::min<int64_t>(std::min<int64_t>(512 / tiles, nkt / 8), std::min<int64_t>(fit, 64));
-    if (want < 2) return 1;
+    if (want < 2) return false;
     const int64_t kchunk = dlc::cdiv(nkt, want) * 16, chunks = dlc::cdiv(K, kchunk);
-    if (chunks < 2) return 1;
-    double* part = (double*)ctx->scratch;
-    if (gemm_dma_f64_splitk(ctx, blayout, M, N, K, Kb, A, lda, B, ldb, part, kchunk, st, true) != DLC_OK) return 1;
-    const int prof_slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-    if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[prof_slot], st));
-    const int rc = gemm_dma_f64_splitk(ctx, blayout, M, N, K, Kb, A, lda, B, ldb, part, kchunk, st, false);
-    if (rc != DLC_OK) return rc < 0 ? rc : dlc::fail(ctx, DLC_ERR_HIP, "gemm: the split-K launch was refused after its dry run");
-    if (ctx->profiling) {
-        DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[prof_slot], st));
-        ctx->prof_calls++;
+    if (chunks < 2 || !plan_dma_launch(ctx, c, 64, 0, M, kchunk, &p->dma[0])) return false;
+    p->route = ROUTE_DMA_SPLITK;
+    p->chunks = (int)chunks;
+    return true;
+}
+
+// The route of a call and all its launch parameters; every refusal happens here, before anything is launched.  In order:
+//   ROUTE_DMA_SPLITK    the LDS-DMA kernel on 64-row tiles, split-K into the scratch, then the reduce (plain fp64 operands)
+//   ROUTE_DMA(_TWO_PART) its one-pass forms (plan_dma_forms; fp64, where the kernel below runs in one pass, or c.dma_first)
+//   ROUTE_STAGED(_SPLITK) the register-staged kernel, split-K into the scratch as plan_split says, then the reduce
+// An ACT_AXPY call has the LDS-DMA one-pass forms only: 1 when they do not take it.
+static int plan_gemm(dlc_ctx* ctx, const GemmCall& c, GemmPlan* p) {
+    if (c.act == ACT_AXPY) return plan_dma_forms(ctx, c, p) ? DLC_OK : 1;
+    const bool f64 = c.dtype == DLC_F64;
+    if (f64 && !c.cv && !c.tri && plan_dma_splitk(ctx, c, p)) return DLC_OK;
+    p->chunks = plan_split(ctx, f64 ? 8 : 4, c.M, c.N, c.kb(), &p->kchunk);
+    if (f64 && (p->chunks == 1 || c.dma_first) && plan_dma_forms(ctx, c, p)) return DLC_OK;
+    p->route = p->chunks > 1 ? ROUTE_STAGED_SPLITK : ROUTE_STAGED;
+    // block of 64 tiles: 8 x 8, narrower along a dimension with fewer than 8 tiles (powers of two)
+    const int64_t tiles_m = dlc::cdiv(c.M, TM), tiles_n = dlc::cdiv(c.N, TN);
+    int bc = 8;
+    while (bc > 1 && bc / 2 >= tiles_n) bc /= 2;
+    int br = 64 / bc;
+    if (tiles_m < br) {                                      // few row tiles: widen along N instead
+        br = 1;
+        while (br < tiles_m) br *= 2;
+        bc = 64 / br;
     }
-    long long blocks = dlc::cdiv(M * N, (int64_t)256);
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(splitk_bias_act_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)part, (int)chunks, bias, C,
-                       (long long)ldc, (long long)M, (long long)N, act);
-    DLC_LAUNCH_CHECK(ctx, "splitk_bias_act_kernel");
+    p->br = br; p->bc = bc;
+    const int64_t nblocks = dlc::cdiv(tiles_m, (int64_t)br) * dlc::cdiv(tiles_n, (int64_t)bc);
+    p->nwg = p->chunks > 1 ? tiles_m * tiles_n * p->chunks : dlc::cdiv(nblocks, (int64_t)8) * 8 * 64;
+    if (p->nwg > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "gemm: M x N too large for one launch");
+    // this kernel does not fold per-image minima / maxima in its epilogue: a pass over its output does (gemm)
+    if (c.cv && c.cv->mm_keys && c.ldc != c.N)
+        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "conv2d: per-image statistics need a contiguous output");
     return DLC_OK;
 }
 
 template <typename T>
-int launch(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-           const void* B, int64_t ldb, const void* bias, void* C, int64_t ldc, hipStream_t st,
-           const ConvGeom* cv = nullptr, const TriSkip* tri = nullptr) {
+static int launch_staged(dlc_ctx* ctx, const GemmCall& c, const GemmPlan& p) {
     Args<T> a;
-    a.A = (const T*)A; a.lda = lda; a.B = (const T*)B; a.ldb = ldb; a.bias = (const T*)bias;
-    a.C = (T*)C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.act = act;
-    a.cv = cv ? *cv : ConvGeom{};
-    a.tri_p = tri ? tri->p : 0;
-    a.tri_row0 = tri ? tri->row0 : 0;
-    a.tri_col0 = tri ? tri->col0 : 0;
-    a.tiles_m = dlc::cdiv(M, TM);
-    a.tiles_n = dlc::cdiv(N, TN);
-    if constexpr (sizeof(T) == 8) {
-        if (!cv && !tri) {
-            const int rc_sk = dma_splitk_f64(ctx, blayout, act, M, N, K, K, (const double*)A, lda, (const double*)B, ldb,
-                                             (const double*)bias, (double*)C, ldc, st);
-            if (rc_sk <= 0) return rc_sk;
-        }
-    }
-    const int chunks = plan_split<T>(ctx, M, N, K, &a.kchunk);
-    if constexpr (sizeof(T) == 8) {
-        // large aligned fp64 launches: the LDS-DMA kernel (gemm_dma_f64.hip); anything else stays here
-        if (chunks == 1 && (!cv || cv->C % 8 == 0)) {
-            const int rc_dma = launch_dma_f64(ctx, blayout, act, M, N, K, (const double*)A, lda, (const double*)B, ldb,
-                                              (const double*)bias, (double*)C, ldc, st, cv, tri);
-            if (rc_dma <= 0) return rc_dma;
-        }
-    }
-    // the kernel below does not fold per-image minima / maxima in its epilogue: a pass over its output does (end of this function)
-    unsigned long long* const fold_keys = cv ? cv->mm_keys : nullptr;
-    a.chunks = chunks;
-    a.P = chunks > 1 ? (T*)ctx->scratch : nullptr;
-    // block of 64 tiles: 8 x 8, narrower along a dimension with fewer than 8 tiles (powers of two)
-    int bc = 8;
-    while (bc > 1 && bc / 2 >= a.tiles_n) bc /= 2;
-    int br = 64 / bc;
-    if (a.tiles_m < br) {                                    // few row tiles: widen along N instead
-        br = 1;
-        while (br < a.tiles_m) br *= 2;
-        bc = 64 / br;
-    }
-    a.br = br; a.bc = bc;
-    a.nbr = dlc::cdiv(a.tiles_m, (int64_t)br);
-    a.nblocks = a.nbr * dlc::cdiv(a.tiles_n, (int64_t)bc);
-    const long long nwg = chunks > 1 ? a.tiles_m * a.tiles_n * chunks : dlc::cdiv(a.nblocks, (int64_t)8) * 8 * 64;
-    if (nwg > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "gemm: M x N too large for one launch");
-    // bench.py's kernel-only timing (dlc_set_profiling): an event pair around the GEMM kernel on its stream
-    const int prof_slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-    if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[prof_slot], st));
-    int rc;
-    if (cv && cv->C % 8 == 0) rc = launch_kernel<T, DLC_B_KN, 1>(ctx, a, nwg, st);
-    else if (cv) rc = launch_kernel<T, DLC_B_KN, 2>(ctx, a, nwg, st);
-    else if (blayout == DLC_B_KN) rc = launch_kernel<T, DLC_B_KN, 0>(ctx, a, nwg, st);
-    else rc = launch_kernel<T, DLC_B_NK, 0>(ctx, a, nwg, st);
+    a.A = (const T*)c.A; a.lda = c.lda; a.B = (const T*)c.B; a.ldb = c.ldb; a.bias = (const T*)c.bias;
+    a.C = (T*)c.C; a.ldc = c.ldc; a.M = c.M; a.N = c.N; a.K = c.kb(); a.act = c.act;
+    a.cv = c.cv ? *c.cv : ConvGeom{};
+    a.kchunk = p.kchunk;
+    a.P = p.chunks > 1 ? (T*)ctx->scratch : nullptr;
+    a.tiles_m = dlc::cdiv(c.M, TM); a.tiles_n = dlc::cdiv(c.N, TN);
+    a.chunks = p.chunks; a.br = p.br; a.bc = p.bc;
+    a.nbr = dlc::cdiv(a.tiles_m, (int64_t)p.br);
+    a.nblocks = a.nbr * dlc::cdiv(a.tiles_n, (int64_t)p.bc);
+    a.tri_p = c.tri ? c.tri->p : 0; a.tri_row0 = c.tri ? c.tri->row0 : 0; a.tri_col0 = c.tri ? c.tri->col0 : 0;
+    return dlc::profiled(ctx, c.st, [&]() -> int {
+        int rc;
+        if (c.cv && c.cv->C % 8 == 0) rc = launch_kernel<T, DLC_B_KN, 1>(ctx, a, p.nwg, c.st);
+        else if (c.cv) rc = launch_kernel<T, DLC_B_KN, 2>(ctx, a, p.nwg, c.st);
+        else if (c.blayout == DLC_B_KN) rc = launch_kernel<T, DLC_B_KN, 0>(ctx, a, p.nwg, c.st);
+        else rc = launch_kernel<T, DLC_B_NK, 0>(ctx, a, p.nwg, c.st);
+        if (rc != DLC_OK) return rc;
+        DLC_LAUNCH_CHECK(ctx, "gemm_bias_act_kernel");
+        return DLC_OK;
+    });
+}
+
+int gemm(dlc_ctx* ctx, const GemmCall& c) {
+    GemmPlan p;
+    int rc = plan_gemm(ctx, c, &p);
     if (rc != DLC_OK) return rc;
-    DLC_LAUNCH_CHECK(ctx, "gemm_bias_act_kernel");
-    if (ctx->profiling) {
-        DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[prof_slot], st));
-        ctx->prof_calls++;
-    }
-    if (chunks > 1) {
-        long long blocks = dlc::cdiv(M * N, (int64_t)256);
+    const bool f64 = c.dtype == DLC_F64, staged = p.route == ROUTE_STAGED || p.route == ROUTE_STAGED_SPLITK;
+    if (staged) rc = f64 ? launch_staged<double>(ctx, c, p) : launch_staged<float>(ctx, c, p);
+    else rc = launch_dma(ctx, c, p.dma[0]);
+    if (rc == DLC_OK && p.route == ROUTE_DMA_TWO_PART) rc = launch_dma(ctx, c, p.dma[1]);
+    if (rc != DLC_OK) return rc;
+    if (p.chunks > 1) {                                      // split-K: sum the chunks in chunk order, + bias, activation
+        long long blocks = dlc::cdiv(c.M * c.N, (int64_t)256);
         if (blocks > 256 * 32) blocks = 256 * 32;
-        hipLaunchKernelGGL(splitk_bias_act_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)a.P, chunks,
-                           (const T*)bias, (T*)C, (long long)ldc, (long long)M, (long long)N, act);
+        if (f64)
+            hipLaunchKernelGGL(splitk_bias_act_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, c.st, (const double*)ctx->scratch,
+                               p.chunks, (const double*)c.bias, (double*)c.C, (long long)c.ldc, (long long)c.M, (long long)c.N, c.act);
+        else
+            hipLaunchKernelGGL(splitk_bias_act_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, c.st, (const float*)ctx->scratch,
+                               p.chunks, (const float*)c.bias, (float*)c.C, (long long)c.ldc, (long long)c.M, (long long)c.N, c.act);
         DLC_LAUNCH_CHECK(ctx, "splitk_bias_act_kernel");
     }
-    if constexpr (sizeof(T) == 8) {
-        if (fold_keys) {
-            if (ldc != N) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "conv2d: per-image statistics need a contiguous output");
-            const int64_t per_img = (int64_t)cv->OH * cv->OW;
-            return dlc_cnn::fold_minmax_f64(ctx, (const double*)C, M / per_img, per_img * N, fold_keys, st);
-        }
+    if (staged && c.cv && c.cv->mm_keys) {
+        const int64_t per_img = (int64_t)c.cv->OH * c.cv->OW;
+        return dlc_cnn::fold_minmax_f64(ctx, (const double*)c.C, c.M / per_img, per_img * c.N, c.cv->mm_keys, c.st);
     }
     return DLC_OK;
 }
@@ -555,32 +547,33 @@ int gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act, int64_t M, int6
     if (act < DLC_ACT_NONE || act > DLC_ACT_RELU) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "gemm: act %d", act);
     if (lda < K || ldc < N || (blayout == DLC_B_KN ? ldb < N : ldb < K))
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "gemm: leading dimension smaller than the row");
-    if (dtype == DLC_F64) return launch<double>(ctx, blayout, act, M, N, K, A, lda, B, ldb, bias, C, ldc, st);
-    if (dtype == DLC_F32) return launch<float>(ctx, blayout, act, M, N, K, A, lda, B, ldb, bias, C, ldc, st);
-    return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "gemm: dtype %d (need DLC_F64 or DLC_F32)", dtype);
-}
-
-// Gram block of the SDAV similarity (match_ref.hip): C = A . B^T in fp64 (B stored [N,K], or its transpose stored
-// [K,N]), tiles that hold no (row frame < column frame) entry skipped (their part of C stays unwritten, never read).
-int gram_upper_f64(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                   const double* B, int64_t ldb, double* C, int64_t ldc, int patches, int64_t row0, int64_t col0,
-                   hipStream_t st) {
-    TriSkip tri{patches, row0, col0};
-    return launch<double>(ctx, blayout, DLC_ACT_NONE, M, N, K, A, lda, B, ldb, nullptr, C, ldc, st, nullptr, &tri);
+    if (dtype != DLC_F64 && dtype != DLC_F32)
+        return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "gemm: dtype %d (need DLC_F64 or DLC_F32)", dtype);
+    return gemm(ctx, {dtype, blayout, act, M, N, K, A, lda, B, ldb, bias, C, ldc, st});
 }
 
 int gemm_bias_act_padded_f64(dlc_ctx* ctx, int act, int64_t M, int64_t N, int64_t K, int64_t Kpad, const double* A,
                              const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st) {
-    const int rc_sk = dma_splitk_f64(ctx, DLC_B_KN, act, M, N, Kpad, K, A, Kpad, B, ldb, bias, C, ldc, st);
-    if (rc_sk <= 0) return rc_sk;
-    const int rc = launch_dma_f64(ctx, DLC_B_KN, act, M, N, Kpad, A, Kpad, B, ldb, bias, C, ldc, st, nullptr, nullptr, K);
-    if (rc <= 0) return rc;
-    return launch<double>(ctx, DLC_B_KN, act, M, N, K, A, Kpad, B, ldb, bias, C, ldc, st);
+    GemmCall c{DLC_F64, DLC_B_KN, act, M, N, Kpad, A, Kpad, B, ldb, bias, C, ldc, st};
+    c.Kb = K;
+    c.dma_first = true;
+    return gemm(ctx, c);
 }
 
-int conv2d_f64(dlc_ctx* ctx, int act, int64_t M, int64_t N, int64_t K, const double* x, const double* w,
-               const double* bias, double* out, const ConvGeom& cv, hipStream_t st) {
-    return launch<double>(ctx, DLC_B_KN, act, M, N, K, x, 0, w, N, bias, out, N, st, &cv);
+int gemm_axpy_dma_f64(dlc_ctx* ctx, int blayout, double alpha, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double* C, int64_t ldc, hipStream_t st) {
+    GemmCall c{DLC_F64, blayout, ACT_AXPY, M, N, K, A, lda, B, ldb, nullptr, C, ldc, st};
+    c.alpha = alpha;
+    return gemm(ctx, c);
+}
+
+int gram_upper_f64(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                   const double* B, int64_t ldb, double* C, int64_t ldc, int patches, int64_t row0, int64_t col0,
+                   hipStream_t st) {
+    const TriSkip tri{patches, row0, col0};
+    GemmCall c{DLC_F64, blayout, DLC_ACT_NONE, M, N, K, A, lda, B, ldb, nullptr, C, ldc, st};
+    c.tri = &tri;
+    return gemm(ctx, c);
 }
 
 }  // namespace dlc_gemm
@@ -595,24 +588,18 @@ extern "C" int dlc_conv2d_nhwc_f64_stats(dlc_ctx* ctx, const double* x, int64_t 
     if (act < DLC_ACT_NONE || act > DLC_ACT_RELU) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "conv2d: act %d", act);
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    dlc_gemm::ConvGeom cv{h, w, c, kw, stride, pad_top, pad_left, oh, ow, (unsigned long long*)frame_keys};
-    return dlc_gemm::conv2d_f64(ctx, act, n * oh * ow, cout, (int64_t)kh * kw * c, x, kernel, bias, out, cv,
-                                (hipStream_t)stream);
+    const dlc_gemm::ConvGeom cv{h, w, c, kw, stride, pad_top, pad_left, oh, ow, (unsigned long long*)frame_keys};
+    dlc_gemm::GemmCall call{DLC_F64, DLC_B_KN, act, n * oh * ow, cout, (int64_t)kh * kw * c, x, 0, kernel, cout, bias, out, cout,
+                            (hipStream_t)stream};
+    call.cv = &cv;
+    return dlc_gemm::gemm(ctx, call);
 }
 
 extern "C" int dlc_conv2d_nhwc_f64(dlc_ctx* ctx, const double* x, int64_t n, int h, int w, int c, const double* kernel,
                                    const double* bias, int kh, int kw, int cout, int stride, int pad_top, int pad_left,
                                    int oh, int ow, int act, double* out, void* stream) {
-    if (!ctx) return DLC_ERR_BAD_ARG;
-    if (!x || !kernel || !out || n < 1 || h < 1 || w < 1 || c < 1 || kh < 1 || kw < 1 || cout < 1 || stride < 1 ||
-        pad_top < 0 || pad_left < 0 || oh < 1 || ow < 1)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "conv2d: bad argument");
-    if (act < DLC_ACT_NONE || act > DLC_ACT_RELU) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "conv2d: act %d", act);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    dlc_gemm::ConvGeom cv{h, w, c, kw, stride, pad_top, pad_left, oh, ow, nullptr};
-    return dlc_gemm::conv2d_f64(ctx, act, n * oh * ow, cout, (int64_t)kh * kw * c, x, kernel, bias, out, cv,
-                                (hipStream_t)stream);
+    return dlc_conv2d_nhwc_f64_stats(ctx, x, n, h, w, c, kernel, bias, kh, kw, cout, stride, pad_top, pad_left, oh, ow, act, out,
+                                     nullptr, stream);
 }
 
 extern "C" int dlc_gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act, int64_t M, int64_t N, int64_t K,

@@ -265,7 +265,6 @@ __device__ __forceinline__ void dma_b2s(unsigned o0, unsigned o1, const char* ba
         : "memory", "scc");
 }
 
-constexpr int ACT_AXPY = 16;                      // internal: the product is added into C (the SGD step of a weight gradient)
 __device__ __forceinline__ double act_f64(double z, int act) {
     if (act == DLC_ACT_SIGMOID) return 1.0 / (1.0 + exp(-z));
     if (act == DLC_ACT_RELU) return z > 0.0 ? z : 0.0;
@@ -727,32 +726,74 @@ int launch_one(dlc_ctx* ctx, const DmaArgs& a, long long nwg, hipStream_t st) {
 
 }  // namespace
 
-// One launch.  m_base: CONV, the output pixel index of row 0 (A stays the whole input, C points at row 0's outputs);
-// force_tm: 128 / 256 rows per tile; dry: only say whether the launch would be taken (DLC_OK / 1).
-static int launch_dma_part(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                           const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st,
-                           const ConvGeom* cv, const TriSkip* tri, int64_t Kb, int64_t m_base, int force_tm, bool dry, double alpha = 0.0,
-                           int64_t kchunk = 0, double* partials = nullptr) {
-    if (Kb <= 0 || Kb > K) Kb = K;
+// The kernel arguments of launch l of call c.  A part of the rows (row0 > 0): CONV, m_base is the output pixel index of row
+// 0 (A stays the whole input); plain, A starts at that row.  Split-K: partial tiles into the context's scratch.
+static DmaArgs dma_args(const dlc_ctx* ctx, const GemmCall& c, const DmaLaunch& l) {
+    const ConvGeom* cv = c.cv;
+    const bool split = l.kchunk > 0;
+    double* const part = (double*)ctx->scratch;
+    DmaArgs a;
+    a.A = (const char*)c.A + (cv ? 0 : l.row0 * c.lda * 8); a.lda_b = c.lda * 8; a.B = (const char*)c.B; a.ldb_b = c.ldb * 8;
+    a.bias = split ? nullptr : (const double*)c.bias;
+    a.C = split ? part : (double*)c.C + l.row0 * c.ldc;
+    a.ldc = split ? c.N : c.ldc;
+    a.M = l.M; a.N = c.N; a.K = c.K; a.Kb = c.kb();
+    a.act = split ? DLC_ACT_NONE : c.act; a.alpha = split ? 0.0 : c.alpha;
+    a.cv = cv ? *cv : ConvGeom{};
+    a.m_base = cv ? l.row0 : 0;
+    a.cv_all_valid = 0;
+    if (cv) {
+        const int64_t KH = c.K / ((int64_t)cv->KW * cv->C);
+        a.cv_all_valid = cv->pad_t == 0 && cv->pad_l == 0 && (int64_t)(cv->OH - 1) * cv->stride + KH <= cv->H &&
+                         (int64_t)(cv->OW - 1) * cv->stride + cv->KW <= cv->W;
+    }
+    a.zero = (const char*)ctx->zero_page;
+    a.kchunk = l.kchunk; a.P = split ? part : nullptr;
+    a.nchunks = split ? (int)dlc::cdiv(c.K, l.kchunk) : 1;
+    a.tiles_m = dlc::cdiv(l.M, (int64_t)l.tm); a.tiles_n = dlc::cdiv(c.N, (int64_t)l.tn);
+    a.tri_p = c.tri ? c.tri->p : 0; a.tri_row0 = c.tri ? c.tri->row0 : 0; a.tri_col0 = c.tri ? c.tri->col0 : 0;
+    a.lg_blk = 0;
+    while ((1 << a.lg_blk) < l.br * l.bc) ++a.lg_blk;
+    a.br = l.br; a.bc = l.bc;
+    a.nbr = dlc::cdiv(a.tiles_m, (int64_t)l.br);
+    a.tri_nbc = dlc::cdiv(a.tiles_n, (int64_t)l.bc);
+    a.nblocks = a.nbr * a.tri_nbc;
+    a.tri_blk_cols = l.bc * l.tn; a.tri_rem0 = 0; a.tri_step = 0; a.tri_lg_rows = 0;
+    if (a.tri_p > 0) {
+        while ((1 << a.tri_lg_rows) < l.br * l.tm) ++a.tri_lg_rows;     // br is a power of two, and so is the tile height
+        a.tri_step = a.tri_blk_cols % a.tri_p;
+        TriWalk tw{a.tri_col0 + a.tri_blk_cols - 1, (int)((a.tri_col0 + a.tri_blk_cols - 1) % a.tri_p)};
+        a.tri_rem0 = tw.rem;
+        a.nblocks = 0;
+        for (long long col = 0; col < a.tri_nbc; ++col, tw.step(a)) a.nblocks += tw.count(a);
+    }
+    return a;
+}
+
+// Whether the kernel takes rows row0 .. row0 + M - 1 of call c on tm-row tiles (kchunk > 0: split-K in chunks of kchunk,
+// a multiple of the K tile), and with what grid.  Every refusal is here: launch_dma never refuses a plan.
+bool plan_dma_launch(const dlc_ctx* ctx, const GemmCall& c, int tm, int64_t row0, int64_t M, int64_t kchunk, DmaLaunch* l) {
+    const ConvGeom* cv = c.cv;
+    const int64_t N = c.N, K = c.K, Kb = c.kb();
     // 16-byte pieces: operand rows must start on 16-byte boundaries and K, N be even (a piece = 2 doubles)
     // ([N,K] operands: B's rows are K long and C is stored element by element, so N may be odd there)
-    if (!ctx->zero_page || (K & 1) || ((N & 1) && blayout != DLC_B_NK) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || (ldb & 1)) return 1;
-    if (Kb != K && blayout != DLC_B_KN) return 1;          // a shorter B is a [K,N] operand with fewer rows
-    if (Kb < (dlc::cdiv(K, (int64_t)TK3) - 1) * TK3) return 1;   // ... whose missing rows all lie in the last K tile
+    if (!ctx->zero_page || (K & 1) || ((N & 1) && c.blayout != DLC_B_NK) || ((uintptr_t)c.A & 15) || ((uintptr_t)c.B & 15) ||
+        (c.ldb & 1))
+        return false;
+    if (Kb != K && c.blayout != DLC_B_KN) return false;        // a shorter B is a [K,N] operand with fewer rows
+    if (Kb < (dlc::cdiv(K, (int64_t)TK3) - 1) * TK3) return false;   // ... whose missing rows all lie in the last K tile
     // per-lane source offsets inside a tile are 32-bit: 256 rows of A, 128 rows ([N,K]) or 16 k-rows ([K,N]) of B
-    if (!cv && lda * 8 * TM3 > 0xffffffffll) return 1;
-    if (ldb * 8 * (blayout == DLC_B_NK ? TN3 : TK3) + 4096 > 0xffffffffll) return 1;
+    if (!cv && c.lda * 8 * TM3 > 0xffffffffll) return false;
+    if (c.ldb * 8 * (c.blayout == DLC_B_NK ? TN3 : TK3) + 4096 > 0xffffffffll) return false;
     if (cv) {
-        if (blayout != DLC_B_KN || cv->C % TK3 != 0) return 1;
-    } else if (lda & 1) {
-        return 1;
+        if (c.blayout != DLC_B_KN || cv->C % TK3 != 0) return false;
+    } else if (c.lda & 1) {                                    // (and so every row0 of a part starts on 16 bytes too)
+        return false;
     }
     // worth a 256 x 128 tile per CU only when the launch fills the chip a few times over
     // N <= 96 (conv1's 96 filters): 96-column tiles, so that no quarter of the MFMAs works on padding
-    const bool narrow = N <= 96;
-    const int tn = narrow ? 96 : TN3;
-    // tile height: the caller's choice (launch_dma_f64); triangular launches and the 96-column form keep the large tile
-    int tm = (((force_tm == TM3 / 2 && !tri) || force_tm == TM3 / 4) && !narrow) ? force_tm : TM3;
+    // (the planner takes smaller tiles than 256 rows only for N > 96: the 96-column form keeps the large tile)
+    const int tn = N <= 96 ? 96 : TN3;
     // (conv1's 96-column form on 64-row tiles, two workgroups per CU: CnnVtl.transform 29.1 against 28.75 ms -- not kept)
     const int64_t tiles_m = dlc::cdiv(M, (int64_t)tm), tiles_n = dlc::cdiv(N, (int64_t)tn);
     // From 16 tiles on, and with more than 3/4 of a tile's rows real (scripts/exp_dma_threshold.py: below that the
@@ -765,30 +806,14 @@ static int launch_dma_part(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_
     // K loop is the slower one even at a quarter of the tile's rows; the 256-row tile wants 3/4 of its rows real)
     // (the 128-row form has as many workgroups as the register-staged kernel and the faster K loop: it is taken at any
     // tile count -- CnnVtl.transform of 1 / 8 frames 2.0 / 2.6 -> 1.5 ms)
-    if ((tm == TM3 && (tiles_m * tiles_n < DLC_DMA_MIN_TILES || M < TM3 * 3 / 4)) || K < 4 * TK3) return 1;
-    if (dry) return DLC_OK;
-    DmaArgs a;
-    a.A = (const char*)A; a.lda_b = lda * 8; a.B = (const char*)B; a.ldb_b = ldb * 8;
-    a.bias = bias; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.Kb = Kb; a.act = act; a.alpha = alpha;
-    a.cv = cv ? *cv : ConvGeom{};
-    a.m_base = m_base;
-    a.cv_all_valid = 0;
-    if (cv && cv->mm_keys && (int64_t)cv->OH * cv->OW < 64) return 1;     // the epilogue folds at most two images per wave
+    if ((tm == TM3 && (tiles_m * tiles_n < DLC_DMA_MIN_TILES || M < TM3 * 3 / 4)) || K < 4 * TK3) return false;
+    if (cv && cv->mm_keys && (int64_t)cv->OH * cv->OW < 64) return false;   // the epilogue folds at most two images per wave
     if (cv) {
         // per-lane offsets of the A operand are 32-bit and must stay below the descriptor's num_records: a tile's
         // 256 output pixels span at most cdiv(256, OH * OW) + 1 images
         const int64_t img_bytes = (int64_t)cv->H * cv->W * cv->C * 8;
-        if ((dlc::cdiv((int64_t)TM3, (int64_t)cv->OH * cv->OW) + 1) * img_bytes >= 0x7ff00000ll) return 1;
-        const int64_t KH = K / ((int64_t)cv->KW * cv->C);
-        a.cv_all_valid = cv->pad_t == 0 && cv->pad_l == 0 && (int64_t)(cv->OH - 1) * cv->stride + KH <= cv->H &&
-                         (int64_t)(cv->OW - 1) * cv->stride + cv->KW <= cv->W;
+        if ((dlc::cdiv((int64_t)TM3, (int64_t)cv->OH * cv->OW) + 1) * img_bytes >= 0x7ff00000ll) return false;
     }
-    a.zero = (const char*)ctx->zero_page;
-    a.kchunk = kchunk; a.P = partials;
-    const int chunks = kchunk > 0 ? (int)dlc::cdiv(K, kchunk) : 1;
-    a.nchunks = chunks;
-    a.tiles_m = tiles_m; a.tiles_n = tiles_n;
-    a.tri_p = tri ? tri->p : 0; a.tri_row0 = tri ? tri->row0 : 0; a.tri_col0 = tri ? tri->col0 : 0;
     // block of 32 tiles (one XCD's 32 CUs): 4 row tiles x 8 column tiles = 1024 x 1024 outputs, narrower where the
     // matrix has fewer tiles along a dimension (powers of two).  Blocks go round-robin to the XCDs, so a launch of a
     // few blocks can leave some XCDs with twice the tiles of others (conv3 of 128 frames: 195 tiles in 9 blocks -- XCD 0
@@ -803,7 +828,7 @@ static int launch_dma_part(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_
         while (br < tiles_m) br *= 2;
         bc = 32 / br;
     }
-    if (!tri) {
+    if (!c.tri) {
         auto busiest_rounds = [&](int r, int c) {           // rounds the fullest shader engine (8 CUs) of any XCD runs
             const int64_t nr = dlc::cdiv(tiles_m, (int64_t)r), nc = dlc::cdiv(tiles_n, (int64_t)c);
             int64_t load[8][4] = {};
@@ -827,81 +852,41 @@ static int launch_dma_part(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_
             }
         }
     }
-    int lg_blk = 0;
-    while ((1 << lg_blk) < br * bc) ++lg_blk;
-    a.lg_blk = lg_blk;
-    a.br = br; a.bc = bc;
-    a.nbr = dlc::cdiv(tiles_m, (int64_t)br);
-    a.tri_nbc = dlc::cdiv(tiles_n, (int64_t)bc);
-    a.nblocks = a.nbr * a.tri_nbc;
-    a.tri_blk_cols = bc * tn; a.tri_rem0 = 0; a.tri_step = 0; a.tri_lg_rows = 0;
-    if (a.tri_p > 0) {
-        while ((1 << a.tri_lg_rows) < br * tm) ++a.tri_lg_rows;         // br is a power of two, and so is the tile height
-        a.tri_step = a.tri_blk_cols % a.tri_p;
-        TriWalk tw{a.tri_col0 + a.tri_blk_cols - 1, (int)((a.tri_col0 + a.tri_blk_cols - 1) % a.tri_p)};
-        a.tri_rem0 = tw.rem;
-        a.nblocks = 0;
-        for (long long c = 0; c < a.tri_nbc; ++c, tw.step(a)) a.nblocks += tw.count(a);
-        if (a.nblocks == 0) return DLC_OK;                               // nothing wanted (the caller never reads this block)
-    }
-    const long long nwg = kchunk > 0 ? tiles_m * tiles_n * chunks : (dlc::cdiv(a.nblocks, (int64_t)8) * 8) << a.lg_blk;
-    if (nwg > 0x7fffffffll) return 1;
-    const int prof_slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-    if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[prof_slot], st));
-    int rc;
-    if (tm == TM3) {
-        if (cv) rc = narrow ? launch_one<DLC_B_KN, true, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_KN, true, 4, 4>(ctx, a, nwg, st);
-        else if (blayout == DLC_B_KN) rc = narrow ? launch_one<DLC_B_KN, false, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_KN, false, 4, 4>(ctx, a, nwg, st);
-        else rc = narrow ? launch_one<DLC_B_NK, false, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_NK, false, 4, 4>(ctx, a, nwg, st);
-    } else if (tm == TM3 / 2) {
-        if (cv) rc = launch_one<DLC_B_KN, true, 4, 2>(ctx, a, nwg, st);
-        else if (blayout == DLC_B_KN) rc = launch_one<DLC_B_KN, false, 4, 2>(ctx, a, nwg, st);
-        else rc = launch_one<DLC_B_NK, false, 4, 2>(ctx, a, nwg, st);
-    } else {
-        if (cv) rc = launch_one<DLC_B_KN, true, 4, 1>(ctx, a, nwg, st);
-        else if (blayout == DLC_B_KN) rc = launch_one<DLC_B_KN, false, 4, 1>(ctx, a, nwg, st);
-        else rc = launch_one<DLC_B_NK, false, 4, 1>(ctx, a, nwg, st);
-    }
-    if (rc != DLC_OK) return rc;
-    DLC_LAUNCH_CHECK(ctx, "gemm_dma_f64_kernel");
-    if (ctx->profiling) {
-        DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[prof_slot], st));
-        ctx->prof_calls++;
-    }
-    return DLC_OK;
+    *l = DmaLaunch{tm, tn, br, bc, row0, M, kchunk, 0};
+    const DmaArgs a = dma_args(ctx, c, *l);
+    if (a.nblocks == 0) return true;                       // nothing wanted (the caller never reads this triangle block)
+    l->nwg = kchunk > 0 ? tiles_m * tiles_n * a.nchunks : (dlc::cdiv(a.nblocks, (int64_t)8) * 8) << a.lg_blk;
+    return l->nwg <= 0x7fffffffll;
 }
 
-// The public entry chooses between four forms by the rounds of the chip's 256 CUs each would take (a 128-row tile
-// costs 0.51 of a 256-row tile at full occupancy -- SDAV.transform on 128-row tiles only: 28.3 against 27.8 ms; a
-// 64-row tile 0.248, two of its workgroups sharing a CU -- 26.8 ms; 0.27 in the convolution form):
+// The one-pass forms, chosen by the rounds of the chip's 256 CUs each would take (a 128-row tile costs 0.51 of a
+// 256-row tile at full occupancy -- SDAV.transform on 128-row tiles only: 28.3 against 27.8 ms; a 64-row tile 0.248,
+// two of its workgroups sharing a CU -- 26.8 ms; 0.27 in the convolution form):
 //   one launch of 256-row tiles;  one of 128-row tiles;  one of 64-row tiles (small launches: a workgroup's K loop is
 //   what they wait for; and plain operands at any size);  or 256-row tiles for the whole rounds and a second launch of
 //   128-row tiles for the rows behind them (conv3-5 of 1063 frames: 6.3 / 6.3 / 4.2 rounds).
 // Rows are independent and every form sums k in the same order: the same bits whichever is taken.
-int launch_dma_f64(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                   const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st,
-                   const ConvGeom* cv, const TriSkip* tri, int64_t Kb, double alpha) {
+bool plan_dma_forms(const dlc_ctx* ctx, const GemmCall& c, GemmPlan* p) {
+    const int64_t M = c.M, N = c.N;
     int tm = TM3;
-    if (!tri && N > 96) {
+    if (!c.tri && N > 96) {
         constexpr double HALF = 0.51;
         const int64_t tn_ = dlc::cdiv(N, (int64_t)TN3), t4 = dlc::cdiv(M, (int64_t)TM3) * tn_;
         const int64_t t2 = dlc::cdiv(M, (int64_t)(TM3 / 2)) * tn_;
         const double whole4 = (double)dlc::cdiv(t4, (int64_t)256);
         const double whole2 = HALF * (double)dlc::cdiv(t2, (int64_t)256) + 0.01;
-        const double quarter = (cv ? 0.27 : 0.248) * (double)dlc::cdiv(dlc::cdiv(M, (int64_t)(TM3 / 4)) * tn_, (int64_t)256) + 0.02;
+        const double quarter = (c.cv ? 0.27 : 0.248) * (double)dlc::cdiv(dlc::cdiv(M, (int64_t)(TM3 / 4)) * tn_, (int64_t)256) + 0.02;
         if (t4 > 256 && t4 % 256 != 0) {
             const int64_t rm = (t4 / 256) * 256 / tn_;                    // row tiles of the main launch
             const int64_t m1 = rm * TM3, m2 = M - m1;
             if (rm > 0 && m2 > 0) {
                 const int64_t tt = dlc::cdiv(m2, (int64_t)(TM3 / 2)) * tn_;
                 const double split = (double)dlc::cdiv(rm * tn_, (int64_t)256) + HALF * (double)dlc::cdiv(tt, (int64_t)256) + 0.05;
-                const double* a2 = cv ? A : A + m1 * lda;
                 if (split < whole4 - 0.15 && split < whole2 - 0.03 && split < quarter - 0.03 &&
-                    launch_dma_part(ctx, blayout, act, m1, N, K, A, lda, B, ldb, bias, C, ldc, st, cv, tri, Kb, 0, TM3, true, alpha) == DLC_OK &&
-                    launch_dma_part(ctx, blayout, act, m2, N, K, a2, lda, B, ldb, bias, C + m1 * ldc, ldc, st, cv, tri, Kb, cv ? m1 : 0, TM3 / 2, true, alpha) == DLC_OK) {
-                    const int rc = launch_dma_part(ctx, blayout, act, m1, N, K, A, lda, B, ldb, bias, C, ldc, st, cv, tri, Kb, 0, TM3, false, alpha);
-                    if (rc != DLC_OK) return rc;
-                    return launch_dma_part(ctx, blayout, act, m2, N, K, a2, lda, B, ldb, bias, C + m1 * ldc, ldc, st, cv, tri, Kb, cv ? m1 : 0, TM3 / 2, false, alpha);
+                    plan_dma_launch(ctx, c, TM3, 0, m1, 0, &p->dma[0]) && plan_dma_launch(ctx, c, TM3 / 2, m1, m2, 0, &p->dma[1])) {
+                    p->route = ROUTE_DMA_TWO_PART;
+                    p->chunks = 1;
+                    return true;
                 }
             }
         }
@@ -913,31 +898,43 @@ int launch_dma_f64(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int
         // only: 26.8 against 27.8 ms, i.e. 0.248 of a 256-row tile each; the convolution form pays its per-tile
         // tap bookkeeping four times over (CnnVtl.transform 29.2 against 28.8 ms): 0.27
         const int64_t t1 = dlc::cdiv(M, (int64_t)(TM3 / 4)) * tn_;
-        const double whole1 = (cv ? 0.27 : 0.248) * (double)dlc::cdiv(t1, (int64_t)256) + 0.02;
+        const double whole1 = (c.cv ? 0.27 : 0.248) * (double)dlc::cdiv(t1, (int64_t)256) + 0.02;
         if (whole1 < whole4 - 0.1 && whole1 < whole2 - 0.05) tm = TM3 / 4;
     }
     // the Gram blocks of the similarity: 64-row tiles for the same reason (similarity of 1063 frames 39.8 -> 39.0 ms)
-    if (tri && N > 96 && dlc::cdiv(M, (int64_t)TM3) * dlc::cdiv(N, (int64_t)TN3) > 512) tm = TM3 / 4;
-    return launch_dma_part(ctx, blayout, act, M, N, K, A, lda, B, ldb, bias, C, ldc, st, cv, tri, Kb, 0, tm, false, alpha);
+    if (c.tri && N > 96 && dlc::cdiv(M, (int64_t)TM3) * dlc::cdiv(N, (int64_t)TN3) > 512) tm = TM3 / 4;
+    if (!plan_dma_launch(ctx, c, tm, 0, M, 0, &p->dma[0])) return false;
+    p->route = ROUTE_DMA;
+    p->chunks = 1;
+    return true;
 }
 
-// Split-K on 64-row tiles (plain operands, no triangle): `chunks` chunks of kchunk (a multiple of the K tile) into the
-// partial tiles P[chunks][M][N]; the caller sums them in chunk order and applies bias + activation (splitk_reduce_f64,
-// gemm_dense.hip).  DLC_OK, or 1 when the shape / alignment is not one the kernel handles (dry: only say which).
-int gemm_dma_f64_splitk(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, int64_t Kb, const double* A, int64_t lda,
-                        const double* B, int64_t ldb, double* partials, int64_t kchunk, hipStream_t st, bool dry) {
-    if (kchunk <= 0 || kchunk % TK3 != 0 || kchunk < 4 * TK3 || !partials) return 1;
-    if (N <= 96) return 1;                                   // (the 96-column form keeps the 256-row tile)
-    return launch_dma_part(ctx, blayout, DLC_ACT_NONE, M, N, K, A, lda, B, ldb, nullptr, partials, N, st, nullptr, nullptr, Kb, 0,
-                           TM3 / 4, dry, 0.0, kchunk, partials);
+// One planned launch (plan_dma_launch), with its ring entry when profiling.
+int launch_dma(dlc_ctx* ctx, const GemmCall& c, const DmaLaunch& l) {
+    if (l.nwg == 0) return DLC_OK;
+    const DmaArgs a = dma_args(ctx, c, l);
+    const long long nwg = l.nwg;
+    const bool narrow = l.tn != TN3;
+    hipStream_t st = c.st;
+    return dlc::profiled(ctx, st, [&]() -> int {
+        int rc;
+        if (l.tm == TM3) {
+            if (c.cv) rc = narrow ? launch_one<DLC_B_KN, true, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_KN, true, 4, 4>(ctx, a, nwg, st);
+            else if (c.blayout == DLC_B_KN) rc = narrow ? launch_one<DLC_B_KN, false, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_KN, false, 4, 4>(ctx, a, nwg, st);
+            else rc = narrow ? launch_one<DLC_B_NK, false, 3, 4>(ctx, a, nwg, st) : launch_one<DLC_B_NK, false, 4, 4>(ctx, a, nwg, st);
+        } else if (l.tm == TM3 / 2) {
+            if (c.cv) rc = launch_one<DLC_B_KN, true, 4, 2>(ctx, a, nwg, st);
+            else if (c.blayout == DLC_B_KN) rc = launch_one<DLC_B_KN, false, 4, 2>(ctx, a, nwg, st);
+            else rc = launch_one<DLC_B_NK, false, 4, 2>(ctx, a, nwg, st);
+        } else {
+            if (c.cv) rc = launch_one<DLC_B_KN, true, 4, 1>(ctx, a, nwg, st);
+            else if (c.blayout == DLC_B_KN) rc = launch_one<DLC_B_KN, false, 4, 1>(ctx, a, nwg, st);
+            else rc = launch_one<DLC_B_NK, false, 4, 1>(ctx, a, nwg, st);
+        }
+        if (rc != DLC_OK) return rc;
+        DLC_LAUNCH_CHECK(ctx, "gemm_dma_f64_kernel");
+        return DLC_OK;
+    });
 }
-
-// C += alpha * (A . B) in the epilogue of the LDS-DMA kernel (the SGD step of a weight gradient: W -= lr * dW without dW
-// ever reaching memory -- SDAV.py:223-226).  DLC_OK, or 1 when the shape / alignment is not one the kernel handles.
-int gemm_axpy_dma_f64(dlc_ctx* ctx, int blayout, double alpha, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                      const double* B, int64_t ldb, double* C, int64_t ldc, hipStream_t st) {
-    return launch_dma_f64(ctx, blayout, ACT_AXPY, M, N, K, A, lda, B, ldb, nullptr, C, ldc, st, nullptr, nullptr, 0, alpha);
-}
-
 
 }  // namespace dlc_gemm

@@ -22,23 +22,70 @@ struct TriSkip {
     long long row0, col0;
 };
 
-// The LDS-DMA form of the fp64 GEMM (gemm_dma_f64.hip).  Returns DLC_OK after launching, or 1 when the shape /
-// alignment is not one it handles (the caller then takes the register-staged kernel of gemm_dense.hip).
-// Kb (0 = K): the reduction length of the B operand when A has been zero-padded past it (an odd K such as SDAV's
-// 1681 input columns, copied into rows of 1696): B's missing k-rows read as zeros.
-int launch_dma_f64(dlc_ctx* ctx, int blayout, int act, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                   const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st,
-                   const ConvGeom* cv, const TriSkip* tri, int64_t Kb = 0, double alpha = 0.0);
-int gemm_axpy_dma_f64(dlc_ctx* ctx, int blayout, double alpha, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                      const double* B, int64_t ldb, double* C, int64_t ldc, hipStream_t st);
-// split-K on the kernel's 64-row tiles: chunks of kchunk (a multiple of 16) into partials[chunks][M][N] (gemm_dma_f64.hip)
-int gemm_dma_f64_splitk(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, int64_t Kb, const double* A, int64_t lda,
-                        const double* B, int64_t ldb, double* partials, int64_t kchunk, hipStream_t st, bool dry);
+constexpr int ACT_AXPY = 16;        // internal activation: C += alpha * (A . B), no bias (the SGD step of a weight gradient)
 
-// A zero-padded by the caller to lda = Kpad columns (columns K .. Kpad-1 are zeros): act(A[:, :K] . B + bias) with the
-// LDS-DMA kernel when it applies (it then walks Kpad), else the register-staged kernel on the first K columns.
+// One dense fp64 / fp32 GEMM call: C = act(A . B + bias), B stored [K,N] (DLC_B_KN) or [N,K] (DLC_B_NK).
+struct GemmCall {
+    int dtype, blayout, act;                    // DLC_F64 / DLC_F32, DLC_B_*, DLC_ACT_* or ACT_AXPY
+    int64_t M, N, K;                            // K: the reduction length as A has it
+    const void* A; int64_t lda;
+    const void* B; int64_t ldb;
+    const void* bias;
+    void* C; int64_t ldc;
+    hipStream_t st;
+    // Kb (0 = K): B's reduction length when A is zero-padded past it (SDAV's 1681 input columns copied into rows of 1696):
+    // the LDS-DMA kernel walks K and reads B's missing k-rows as zeros, the register-staged kernel walks Kb
+    int64_t Kb = 0;
+    double alpha = 0.0;                         // ACT_AXPY
+    const ConvGeom* cv = nullptr;               // implicit im2col (A is the NHWC input, lda unused)
+    const TriSkip* tri = nullptr;
+    bool dma_first = false;                     // the LDS-DMA one-pass forms even where the register-staged kernel would split K
+    int64_t kb() const { return Kb > 0 && Kb < K ? Kb : K; }
+};
+
+// One launch of the LDS-DMA kernel (gemm_dma_f64.hip): rows row0 .. row0 + M - 1 of the call.
+struct DmaLaunch {
+    int tm, tn;                                 // tile: 256 / 128 / 64 rows x 128 / 96 columns
+    int br, bc;                                 // block of br x bc tiles
+    int64_t row0, M;
+    int64_t kchunk;                             // > 0: split-K in chunks of kchunk into the context's scratch
+    int64_t nwg;                                // workgroups (0: no tile holds a wanted entry of the triangle, nothing to launch)
+};
+
+// How a call runs (plan_gemm, gemm_dense.hip, describes the routes): every launch parameter, fixed before any launch.
+enum GemmRoute { ROUTE_DMA_SPLITK, ROUTE_DMA, ROUTE_DMA_TWO_PART, ROUTE_STAGED_SPLITK, ROUTE_STAGED };
+struct GemmPlan {
+    int route;
+    int chunks;                                 // split-K: K chunks, summed by the reduce (1 = one pass)
+    DmaLaunch dma[2];                           // ROUTE_DMA*: its launches (two for ROUTE_DMA_TWO_PART)
+    int64_t kchunk, nwg;                        // ROUTE_STAGED*: K per chunk (>= K in one pass), workgroups, ...
+    int br, bc;                                 // ... in blocks of br x bc tiles
+};
+
+// The call, planned and launched.  DLC_OK; 1 for an ACT_AXPY call the LDS-DMA kernel does not take (nothing is launched);
+// < 0 = error.  The wrappers below fill the call in.
+int gemm(dlc_ctx* ctx, const GemmCall& c);
+// The LDS-DMA planning and launcher (gemm_dma_f64.hip): false when the kernel does not take the launch.
+bool plan_dma_launch(const dlc_ctx* ctx, const GemmCall& c, int tm, int64_t row0, int64_t M, int64_t kchunk, DmaLaunch* l);
+bool plan_dma_forms(const dlc_ctx* ctx, const GemmCall& c, GemmPlan* p);
+int launch_dma(dlc_ctx* ctx, const GemmCall& c, const DmaLaunch& l);
+
+// act(A . B + bias) with its arguments checked (dlc_gemm_bias_act)
+int gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act, int64_t M, int64_t N, int64_t K, const void* A,
+                  int64_t lda, const void* B, int64_t ldb, const void* bias, void* C, int64_t ldc, hipStream_t st);
+// A zero-padded by the caller to lda = Kpad columns (columns K .. Kpad-1 are zeros), B [K,N]: act(A[:, :K] . B + bias),
+// the LDS-DMA forms (which walk Kpad) ahead of the register-staged kernel (on the first K columns)
 int gemm_bias_act_padded_f64(dlc_ctx* ctx, int act, int64_t M, int64_t N, int64_t K, int64_t Kpad, const double* A,
                              const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st);
+// C += alpha * (A . B) in the epilogue of the LDS-DMA kernel (the SGD step of a weight gradient: W -= lr * dW without dW
+// ever reaching memory -- SDAV.py:223-226).  DLC_OK, or 1 when the kernel does not take the shape (nothing launched).
+int gemm_axpy_dma_f64(dlc_ctx* ctx, int blayout, double alpha, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double* C, int64_t ldc, hipStream_t st);
+// Gram block of the SDAV similarity (match_ref.hip): C = A . B^T in fp64 (B stored [N,K], or its transpose stored
+// [K,N]), tiles that hold no (row frame < column frame) entry skipped (their part of C stays unwritten, never read).
+int gram_upper_f64(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                   const double* B, int64_t ldb, double* C, int64_t ldc, int patches, int64_t row0, int64_t col0,
+                   hipStream_t st);
 
 // The SDAV similarity's arg-min filter (gram_i8.hip): descriptors as three signed fixed-point digits of their offset from
 // the column's centre, their exact integer products, and the bound of what the rounding misses.

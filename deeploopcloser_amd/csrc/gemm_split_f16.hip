@@ -577,15 +577,13 @@ int split_encode(dlc_ctx* ctx, int64_t rows, int n_layers, const int64_t* dims, 
         a.per_xcd = tiles / 8; a.extra = tiles % 8;
         const long long nwg = (a.per_xcd + (a.extra ? 1 : 0)) * 8;
         if (nwg > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_encode_split: too many tiles");
-        const int prof_slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-        if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[prof_slot], st));
-        if (fin) hipLaunchKernelGGL(gemm_split_f16_kernel<true>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
-        else hipLaunchKernelGGL(gemm_split_f16_kernel<false>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
-        DLC_LAUNCH_CHECK(ctx, "gemm_split_f16_kernel");
-        if (ctx->profiling) {
-            DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[prof_slot], st));
-            ctx->prof_calls++;
-        }
+        const int rc = dlc::profiled(ctx, st, [&]() -> int {
+            if (fin) hipLaunchKernelGGL(gemm_split_f16_kernel<true>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
+            else hipLaunchKernelGGL(gemm_split_f16_kernel<false>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
+            DLC_LAUNCH_CHECK(ctx, "gemm_split_f16_kernel");
+            return DLC_OK;
+        });
+        if (rc != DLC_OK) return rc;
         off += L.total;
     }
     return DLC_OK;

@@ -849,16 +849,11 @@ int gram_argmin_i8(dlc_ctx* ctx, int64_t N, int64_t P, int64_t H, const char* X,
         ctx->func_attr_set |= 1ull << DLC_ATTR_GRAM_I8;
     }
     const unsigned grid = (unsigned)(((a.nsup + 7) / 8) * 8 * 32);
-    // bench.py's kernel-only timing (dlc_set_profiling): an event pair around the kernel on its stream
-    const int prof_slot = (int)(ctx->prof_calls % DLC_PROFILE_RING);
-    if (ctx->profiling) DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_start[prof_slot], st));
-    hipLaunchKernelGGL(gram_i8_kernel, dim3(grid), dim3(256), lds, st, a);
-    DLC_LAUNCH_CHECK(ctx, "gram_i8_kernel");
-    if (ctx->profiling) {
-        DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[prof_slot], st));
-        ctx->prof_calls++;
-    }
-    return DLC_OK;
+    return dlc::profiled(ctx, st, [&]() -> int {
+        hipLaunchKernelGGL(gram_i8_kernel, dim3(grid), dim3(256), lds, st, a);
+        DLC_LAUNCH_CHECK(ctx, "gram_i8_kernel");
+        return DLC_OK;
+    });
 }
 
 // ---- a strip of the triangle: the column frames f_first .. f_last against every older row patch ----------------------

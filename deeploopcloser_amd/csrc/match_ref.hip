@@ -13,12 +13,6 @@
 #include <cstring>
 #include "gemm_internal.h"
 
-namespace dlc_gemm {
-int gram_upper_f64(dlc_ctx* ctx, int blayout, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                   const double* B, int64_t ldb, double* C, int64_t ldc, int patches, int64_t row0, int64_t col0,
-                   hipStream_t st);
-}
-
 namespace {
 
 // ---------------------------------------------------------------------------

@@ -4,18 +4,7 @@
 // All matrix products go through the fp64 MFMA GEMM (gemm_dense.hip); the loss gradients are
 // row / elementwise HIP kernels.  Restated (and pinned by finite differences) in
 // oracle/sdav_train.py.
-#include "dlc_internal.h"
-
-namespace dlc_gemm {
-int gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act, int64_t M, int64_t N, int64_t K, const void* A,
-                  int64_t lda, const void* B, int64_t ldb, const void* bias, void* C, int64_t ldc, hipStream_t st);
-int gemm_axpy_dma_f64(dlc_ctx* ctx, int blayout, double alpha, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                      const double* B, int64_t ldb, double* C, int64_t ldc, hipStream_t st);      // gemm_dma_f64.hip
-// A zero-padded to lda = Kpad columns, B [K, N] (gemm_dense.hip): the LDS-DMA forms (split-K on 64-row tiles when the context
-// has scratch and the tiles are few) where they apply, else the register-staged kernel on the first K columns
-int gemm_bias_act_padded_f64(dlc_ctx* ctx, int act, int64_t M, int64_t N, int64_t K, int64_t Kpad, const double* A,
-                             const double* B, int64_t ldb, const double* bias, double* C, int64_t ldc, hipStream_t st);
-}
+#include "gemm_internal.h"
 
 namespace {
 

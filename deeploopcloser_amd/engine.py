@@ -1073,8 +1073,9 @@ class Engine:
         self._check(self.lib.dlc_set_profiling(self.ctx, 1 if enabled else 0))
 
     def profile_gemm_ms(self, capacity=256):
-        """Durations (ms) of the score-GEMM launches of the last calls, from HIP events
-        recorded on the launch stream (blocks until they complete)."""
+        """Durations (ms) of the last product-kernel launches (score GEMM, dense and Gram GEMMs;
+        one entry per launch, split-K reduces not included), from HIP events recorded on the
+        launch stream (blocks until they complete)."""
         buf = (C.c_float * capacity)()
         n = self.lib.dlc_profile_gemm_ms(self.ctx, buf, capacity)
         if n < 0:

@@ -673,15 +673,15 @@ int dlc_set_scratch(dlc_ctx* ctx, void* scratch, size_t bytes);
 
 /* ---- introspection used by bench.py (kernel-only timing with HIP events) -- */
 /*
- * With profiling enabled every dlc_cosine_topk / dlc_cosine_score_groups call records a
- * hipEvent pair on the call's stream around its dominant kernel (the MFMA score GEMM), and so
- * does every launch of the dense fp64 / fp32 GEMM kernel (dlc_gemm_bias_act, dlc_conv2d_nhwc_f64,
- * the layers of dlc_sdav_encode, the int8 / fp64 Gram kernels of dlc_sdav_similarity_matrix), into one
- * ring of DLC_PROFILE_RING slots.  dlc_profile_gemm_ms() waits for the recorded
- * events and writes the durations (milliseconds, oldest first) of the last
- * min(calls, capacity, DLC_PROFILE_RING) calls to the HOST array out_ms; it
- * returns how many it wrote (negative dlc_status on error).  Enabling resets
- * the ring.
+ * With profiling enabled every launch of a product kernel records a hipEvent pair around it on
+ * its stream, one entry of a ring of DLC_PROFILE_RING slots: the MFMA score GEMM of dlc_cosine_topk /
+ * dlc_cosine_score_groups, the dense fp64 / fp32 GEMM kernels (dlc_gemm_bias_act, dlc_conv2d_nhwc_f64,
+ * dlc_sdav_encode(_split), dlc_sdav_train_step) and the int8 / fp64 Gram kernels of
+ * dlc_sdav_similarity_matrix.  A split-K reduce or min / max fold is not timed; a GEMM run as two
+ * launches records two entries.  dlc_profile_gemm_ms() waits for the recorded events and writes the
+ * durations (milliseconds, oldest first) of the last min(entries, capacity, DLC_PROFILE_RING) entries
+ * to the HOST array out_ms; it returns how many it wrote (negative dlc_status on error).  Enabling
+ * resets the ring.
  */
 #define DLC_PROFILE_RING 256
 int dlc_set_profiling(dlc_ctx* ctx, int enabled);

@@ -537,6 +537,19 @@ def test_normalize_rows(eng):
 
 
 # --------------------------------------------------------------------------- dense layers / SDAV
+def _one_launch(eng, fn):
+    """fn() with profiling on: its result, after asserting that it recorded exactly one ring entry (one launch of a
+    product kernel; a split-K reduce is not one) of a positive duration."""
+    eng.set_profiling(True)
+    try:
+        out = fn()
+        ms = eng.profile_gemm_ms()
+    finally:
+        eng.set_profiling(False)
+    assert len(ms) == 1 and ms[0] > 0, ms
+    return out
+
+
 @pytest.mark.parametrize("m,n,k", [(37, 53, 29), (128, 128, 16), (600, 2500, 1681), (1, 1, 1), (130, 384, 3456)])
 @pytest.mark.parametrize("blayout", [0, 1])
 def test_gemm_bias_act_f64(eng, m, n, k, blayout):
@@ -556,7 +569,8 @@ def test_gemm_bias_act_f64(eng, m, n, k, blayout):
 @pytest.mark.parametrize("m,n,k,blayout", [(30, 2500, 2500, "kn"), (130, 384, 3456, "kn"), (60, 300, 1681, "nk"), (1, 129, 4000, "kn")])
 def test_gemm_split_k_latency_mode(eng, m, n, k, blayout):
     """Few rows x long K (one frame's SDAV layer / conv3-5) run split-K through the engine's scratch:
-    same result as one pass up to the summation order, bit-reproducible, 1e-10 from NumPy."""
+    same result as one pass up to the summation order, bit-reproducible, 1e-10 from NumPy; either way ONE product launch
+    (profiling: one ring entry per call)."""
     from deeploopcloser_amd import _lib as L
     rng = np.random.RandomState(m + n)
     a = rng.standard_normal((m, k)) / np.sqrt(k)
@@ -565,10 +579,10 @@ def test_gemm_split_k_latency_mode(eng, m, n, k, blayout):
     ref = 1.0 / (1.0 + np.exp(-(a @ (b if blayout == "kn" else b.T) + bias)))
     ta, tb, tbias = (torch.from_numpy(v).to(eng.device) for v in (a, b, bias))
     lay = L.DLC_B_KN if blayout == "kn" else L.DLC_B_NK
-    one_pass = eng.gemm_bias_act(ta, tb, tbias, act=L.DLC_ACT_SIGMOID, blayout=lay)
+    one_pass = _one_launch(eng, lambda: eng.gemm_bias_act(ta, tb, tbias, act=L.DLC_ACT_SIGMOID, blayout=lay))
     eng.set_scratch()
     try:
-        split = eng.gemm_bias_act(ta, tb, tbias, act=L.DLC_ACT_SIGMOID, blayout=lay)
+        split = _one_launch(eng, lambda: eng.gemm_bias_act(ta, tb, tbias, act=L.DLC_ACT_SIGMOID, blayout=lay))
         again = eng.gemm_bias_act(ta, tb, tbias, act=L.DLC_ACT_SIGMOID, blayout=lay)
     finally:
         eng.set_scratch(0)
@@ -585,7 +599,7 @@ def test_gemm_dma_split_k_shapes(eng, m, n, k, blayout):
     """Few 64-row tiles and a long even K: split-K on the LDS-DMA kernel's 64-row tiles (r06: the training step's 300-row
     products, an encode of a few frames) -- chunk tails (K % 16, K % chunk), an odd N for [N,K] operands, a single row, a K too
     short to split (one pass), every activation: 1e-11 from NumPy's fp64 product, the same bits run after run, and within the
-    summation order of the one-pass result."""
+    summation order of the one-pass result; one product launch (one profiling ring entry) in either mode."""
     from deeploopcloser_amd import _lib as L
     from oracle import tensor_ops
     rng = np.random.RandomState(m * 7 + n + k)
@@ -596,9 +610,9 @@ def test_gemm_dma_split_k_shapes(eng, m, n, k, blayout):
     ta, tb, tbias = (torch.from_numpy(np.ascontiguousarray(v)).to(eng.device) for v in (a, b, bias))
     lay = L.DLC_B_KN if blayout == "kn" else L.DLC_B_NK
     for act, fn in ((L.DLC_ACT_NONE, lambda v: v), (L.DLC_ACT_SIGMOID, tensor_ops.sigmoid), (L.DLC_ACT_RELU, lambda v: np.maximum(v, 0))):
-        one_pass = eng.gemm_bias_act(ta, tb, tbias, act=act, blayout=lay)
+        one_pass = _one_launch(eng, lambda: eng.gemm_bias_act(ta, tb, tbias, act=act, blayout=lay))
         with eng.latency_mode():
-            split = eng.gemm_bias_act(ta, tb, tbias, act=act, blayout=lay)
+            split = _one_launch(eng, lambda: eng.gemm_bias_act(ta, tb, tbias, act=act, blayout=lay))
             again = eng.gemm_bias_act(ta, tb, tbias, act=act, blayout=lay)
             nobias = eng.gemm_bias_act(ta, tb, None, act=L.DLC_ACT_NONE, blayout=lay)
         ref = fn(z)

@@ -12,14 +12,14 @@ gradient that is off by a few per cent on its small entries through: one step mo
 its size).  {loss, cd, cs, cc} each within 1e-10 of the oracle's, and everything of the layers above the trained one
 bit for bit as it was.
 
-Routes, read from the dispatch code (gemm_bias_act_padded_f64 / dma_splitk_f64 / launch / plan_split in gemm_dense.hip,
-launch_dma_f64 / launch_dma_part / gemm_axpy_dma_f64 in gemm_dma_f64.hip, weight_step in train.hip).  rows = batch x P.
+Routes, read from the dispatch code (plan_gemm / plan_dma_splitk / plan_split in gemm_dense.hip, plan_dma_forms /
+plan_dma_launch in gemm_dma_f64.hip, weight_step in train.hip).  rows = batch x P.
 
  case | shape                                    | routes
  -----+------------------------------------------+---------------------------------------------------------------------
   A   | (1681, 2500 x 5), P 30, batch 10,        | layer 0 on the even pitch 1682: forward and dh = dz2 W through
       | layers 0..4, latency off / on            | gemm_bias_act_padded_f64 with Kb = 1681 < K = 1682 -- off: the LDS-DMA
-      |                                          | kernel (64-row tiles); on: dma_splitk_f64 with the shorter B (5 chunks
+      |                                          | kernel (64-row tiles); on: DMA split-K with the shorter B (5 chunks
       |                                          | of 352) + splitk_bias_act_kernel.  Decoder (h W^T, [N,K]) and dz1 W^T
       |                                          | on the LDS-DMA kernel (split-K when on).  Every layer's weight product
       |                                          | fused with its SGD step (gemm_axpy_dma_f64, K = 600 / 300).  Encoder
