@@ -4,7 +4,7 @@ The hot path of nschejtman/deepLoopCloser (encode -> all-vs-all similarity ->
 top-k match) as hand-written HIP kernels for gfx950 behind the C ABI of
 include/dlc.h, with the reference's Python call surface on top:
 
-    SDAV, DA                      (src/sdav/network)
+    SDAV, DA, SDA                 (src/sdav/network; python -m deeploopcloser_amd.train_sdav / .train_da: the CLIs)
     CnnVtl                        (src/cnn_vtl/network)
     CvInputParser                 (src/sdav/input; key-points supplied by the caller)
     SimilarityCalculator          (src/sdav/similarity; + SimilarityStream: one new frame against the resident ones)
@@ -20,6 +20,7 @@ from . import _lib
 from .math_utils import MathUtils
 from .engine import Engine, default_engine
 from .sdav import SDAV, DA
+from .sda import SDA
 from .cnn_vtl import CnnVtl
 from .similarity import SimilarityCalculator, SimilarityStream
 from .distance import DistanceCalculator, CnnVtlKeyframeDatabase
@@ -29,7 +30,7 @@ from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, 
 from . import tensor_wrapper
 from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector
 
-__all__ = ["LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

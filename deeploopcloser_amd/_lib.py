@@ -16,7 +16,7 @@ DLC_BF16, DLC_F16, DLC_F32, DLC_F64, DLC_I8 = 0, 1, 2, 3, 4
 DLC_ACT_NONE, DLC_ACT_SIGMOID, DLC_ACT_RELU = 0, 1, 2
 DLC_B_KN, DLC_B_NK = 0, 1
 DLC_MAX_K = 128
-DLC_ABI_VERSION = 10         # include/dlc.h; load() refuses a library built from another header
+DLC_ABI_VERSION = 11         # include/dlc.h; load() refuses a library built from another header
 DLC_SELECT_COOP = 1
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 
@@ -42,6 +42,11 @@ SIGNATURES = {
     "dlc_sdav_train_step": (_int, [_vp, _int, _i64, _i64, _int, C.POINTER(_i64), _vp, C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(_vp), _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _sz, _vp]),
     "dlc_random_mask_f64": (_int, [_vp, _vp, _i64, _i64, C.c_uint64, C.c_uint64, _vp]),
+    "dlc_salt_pepper_mask_f64": (_int, [_vp, _vp, _vp, _i64, _i64, C.c_uint64, C.c_uint64, _vp]),
+    "dlc_da_corrupt_f64": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "dlc_da_train_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "dlc_da_train_step": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _sz,
+                                _vp]),
     "dlc_rgb_to_gray_u8": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "dlc_harris_keypoints_workspace_bytes": (_sz, [_i64, _int, _int]),
     "dlc_harris_keypoints_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

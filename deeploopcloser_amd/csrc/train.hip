@@ -4,6 +4,9 @@
 // All matrix products go through the fp64 MFMA GEMM (gemm_dense.hip); the loss gradients are
 // row / elementwise HIP kernels.  Restated (and pinned by finite differences) in
 // oracle/sdav_train.py.
+// The DA step (DenoisingAutoencoderVariant.py:103-148; dlc_da_train_step) is the same routine at layer 0 with the caller's
+// x~ (the DA's static salt-and-pepper noise, drawn once: dlc_salt_pepper_mask_f64, dlc_da_corrupt_f64) and the sparsity
+// term's 2-D denominator; restated in tests/da_oracle.py.
 #include "gemm_internal.h"
 
 namespace {
@@ -53,6 +56,12 @@ __device__ __forceinline__ unsigned mask_key(unsigned s0, unsigned s1, unsigned 
     return h;
 }
 
+// (seed, counter) -> the two 32-bit words mask_key mixes in
+__device__ __forceinline__ void mask_seeds(unsigned long long seed, unsigned long long counter, unsigned& s0, unsigned& s1) {
+    s0 = (unsigned)seed ^ (unsigned)(counter >> 32) * 0x27d4eb2fu;
+    s1 = (unsigned)(seed >> 32) + (unsigned)counter * 0x165667b1u;
+}
+
 constexpr int RM_THREADS = 1024;
 #define IDX(j) ((long long)tid + (long long)(j) * RM_THREADS)
 // (Forms that kept a thread's keys in registers between three histogram passes over ALL keys -- 80, then 52 keys per thread
@@ -64,8 +73,8 @@ __global__ __launch_bounds__(RM_THREADS) void random_mask_kernel(double* __restr
     __shared__ unsigned sel_bin, sel_below;
     __shared__ unsigned eq_cnt[RM_THREADS];
     const int tid = threadIdx.x;
-    const unsigned s0 = (unsigned)seed ^ (unsigned)(counter >> 32) * 0x27d4eb2fu;
-    const unsigned s1 = (unsigned)(seed >> 32) + (unsigned)counter * 0x165667b1u;
+    unsigned s0, s1;
+    mask_seeds(seed, counter, s0, s1);
     // thread t owns the indices t, t + 1024, ...: the mask is written in coalesced rows (a contiguous range per thread wrote
     // 50 000 scattered doubles from one CU: 30 us); a key is recomputed wherever it is wanted
     auto key_at = [&](int j) { return mask_key(s0, s1, (unsigned)IDX(j)); };
@@ -207,6 +216,32 @@ __global__ __launch_bounds__(RM_THREADS) void random_mask_kernel(double* __restr
     for (int j = 0; IDX(j) < n; ++j) put(j, key_at(j));
 }
 #undef IDX
+
+// The salt half of the DA's static salt-and-pepper noise (DenoisingAutoencoderVariant.py:182-202): among the zeros of
+// `zeros` (random_mask_kernel's draw), each element independently becomes 1 with probability 1/2 -- the top bit of a key
+// from a second stream over the same (seed, counter): the same mix, both words offset by constants, so the salt bits
+// do not follow the zeros' keys.
+__global__ __launch_bounds__(256) void salt_kernel(const double* __restrict__ zeros, double* __restrict__ ones, long long n,
+                                                   unsigned long long seed, unsigned long long counter) {
+    unsigned s0, s1;
+    mask_seeds(seed, counter, s0, s1);
+    s0 ^= 0x68e31da4u;
+    s1 ^= 0xb5297a4du;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256)
+        ones[e] = (zeros[e] == 0.0 && (mask_key(s0, s1, (unsigned)e) >> 31)) ? 1.0 : 0.0;
+}
+
+// x_tilde[r, c] = x[r, c] * m0[r, c] + m1[r, c]    (DenoisingAutoencoderVariant.py:201-202: masks of the whole flat batch)
+// out has pitch ldo >= cols, its columns cols .. ldo - 1 written as zeros (mask_rows_kernel's form, for the LDS-DMA GEMM)
+__global__ __launch_bounds__(256) void corrupt_rows_kernel(const double* __restrict__ x, const double* __restrict__ m0,
+                                                           const double* __restrict__ m1, long long rows, long long cols,
+                                                           double* __restrict__ out, long long ldo) {
+    const long long total = rows * ldo;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long r = e / ldo, c = e - r * ldo;
+        out[e] = c < cols ? x[r * cols + c] * m0[r * cols + c] + m1[r * cols + c] : 0.0;
+    }
+}
 
 // softmax_cross_entropy_with_logits_v2(labels, logits = y) per row (SDAV.py:172), mean over rows.
 // dz2 = d(cd)/d(y) * y(1-y);  dlab (optional) = d(cd)/d(labels) = -log_softmax(y)/rows.
@@ -455,14 +490,15 @@ struct TrainWs {
 
 inline int64_t even_pitch(int64_t cols) { return cols + (cols & 1); }
 
-TrainWs train_ws(int64_t rows, int batch, const int64_t* dims, int layer) {
+// own_xt0 = false: layer 0's x~ is the caller's (the DA step), no room for it here
+TrainWs train_ws(int64_t rows, int batch, const int64_t* dims, int layer, bool own_xt0 = true) {
     TrainWs w;
     size_t o = 0;
     auto take = [&](size_t elems) { size_t at = o; o += dlc::align_up(elems * 8, 256); return at; };
     int64_t wmax = 0;
     for (int l = 0; l <= layer + 1; ++l) wmax = dims[l] > wmax ? dims[l] : wmax;
     for (int l = 0; l <= layer; ++l) {
-        w.xt[l] = take((size_t)rows * even_pitch(dims[l]));
+        w.xt[l] = take(l == 0 && !own_xt0 ? 0 : (size_t)rows * even_pitch(dims[l]));
         // behind the trained layer's h: the first dz1 (hidden_grad_kernel's output) -- [h ; dz1] is the K-stacked B operand
         // of the fused weight-gradient product
         w.h[l] = take((size_t)rows * dims[l + 1] * (l == layer ? 2 : 1));
@@ -487,34 +523,19 @@ TrainWs train_ws(int64_t rows, int batch, const int64_t* dims, int layer) {
     return w;
 }
 
-}  // namespace
-
-extern "C" size_t dlc_sdav_train_workspace_bytes(int64_t batch, int64_t patches, const int64_t* dims, int n_layers,
-                                                 int layer) {
-    if (batch < 2 || patches < 1 || !dims || n_layers < 1 || n_layers > 8 || layer < 0 || layer >= n_layers) return 0;
-    return train_ws(batch * patches, (int)batch, dims, layer).total;
-}
-
-extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64_t patches, int n_layers,
-                                   const int64_t* dims, const double* x, const double* const* masks, double* const* W,
-                                   double* const* b_enc, double* b_dec, double sparse_level, double sparse_penalty,
-                                   double consecutive_penalty, double learning_rate, double* loss_out, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-    if (!ctx) return DLC_ERR_BAD_ARG;
-    if (!dims || !x || !masks || !W || !b_enc || !b_dec || n_layers < 1 || n_layers > 8 || layer < 0 || layer >= n_layers ||
-        patches < 1)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_train_step: bad argument");
-    if (batch < 2)
-        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: a batch needs >= 2 frames (consecutive-frame term, SDAV.py:176-183)");
-    if (batch * patches > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: batch too large");
-    if (dims[1] != dims[layer + 1])
-        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: hidden_units[0] != hidden_units[layer] (the slice of SDAV.py:178-181 needs equal widths)");
-    for (int l = 0; l <= layer; ++l)
-        if (!masks[l] || !W[l] || !b_enc[l]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_train_step: null parameter of layer %d", l);
+// The body of both training steps (dlc_sdav_train_step, dlc_da_train_step), arguments checked by them.  xt0: layer 0's
+// corrupted input x~ at pitch even_pitch(dims[0]) when the caller prepared it (the DA's static salt-and-pepper noise) --
+// no mask_rows_kernel then, and masks[0] is not read; NULL: x~ = x * masks[0] here (SDAV).  cs_den: the sparsity term's
+// denominator (frame_norm_kernel).  The trained layer's half -- decoder product, xent_grad, frame_norm, hidden_grad, the
+// fused weight-gradient product with its SGD epilogue, update_kernel -- is the same launches for both.
+int train_step_impl(dlc_ctx* ctx, const char* what, int layer, int64_t batch, int64_t patches, const int64_t* dims,
+                    const double* x, const double* const* masks, const double* xt0, double* const* W, double* const* b_enc,
+                    double* b_dec, double cs_den, double sparse_level, double sparse_penalty, double consecutive_penalty,
+                    double learning_rate, double* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     const long long rows = batch * patches;
-    const TrainWs w = train_ws(rows, (int)batch, dims, layer);
+    const TrainWs w = train_ws(rows, (int)batch, dims, layer, xt0 == nullptr);
     if (!workspace || workspace_bytes < w.total)
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sdav_train_step: workspace %zu < %zu bytes", workspace_bytes, w.total);
+        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, w.total);
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;
@@ -529,12 +550,18 @@ extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64
 
     // ---- forward through layers 0..layer (old parameters everywhere)
     const double* cur = x;
+    const double* xt_of[8] = {};                                    // x~ of each layer, pitch even_pitch(dims[l])
     for (int l = 0; l <= layer; ++l) {
         const long long kp = even_pitch(dims[l]);                  // (1681 -> 1682: a zero column the weights have no row for)
-        hipLaunchKernelGGL(mask_rows_kernel, dim3(grid_for(rows * kp)), dim3(256), 0, st, cur, masks[l], rows, Pn,
-                           (long long)dims[l], P(w.xt[l]), kp);
+        if (l == 0 && xt0) {
+            xt_of[0] = xt0;
+        } else {
+            hipLaunchKernelGGL(mask_rows_kernel, dim3(grid_for(rows * kp)), dim3(256), 0, st, cur, masks[l], rows, Pn,
+                               (long long)dims[l], P(w.xt[l]), kp);
+            xt_of[l] = P(w.xt[l]);
+        }
         {
-            const int rc_ = dlc_gemm::gemm_bias_act_padded_f64(ctx, DLC_ACT_SIGMOID, rows, dims[l + 1], dims[l], kp, P(w.xt[l]), W[l],
+            const int rc_ = dlc_gemm::gemm_bias_act_padded_f64(ctx, DLC_ACT_SIGMOID, rows, dims[l + 1], dims[l], kp, xt_of[l], W[l],
                                                               dims[l + 1], b_enc[l], P(w.h[l]), dims[l + 1], st);
             if (rc_ != DLC_OK) return rc_;
         }
@@ -544,14 +571,12 @@ extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64
     const double* h = P(w.h[layer]);
     GEMM(DLC_B_NK, DLC_ACT_SIGMOID, rows, K, N, h, N, W[layer], N, b_dec, P(w.y), K);            // y = sigmoid(h W^T + b_d)
     const long long Kp = even_pitch(K);                            // pitch of x~ and dz2 at the trained layer
-    const double* labels = layer == 0 ? x : P(w.xt[layer]);       // (x: the caller's, pitch K; x~ of a deeper layer: K is even there
+    const double* labels = layer == 0 ? x : xt_of[layer];         // (x: the caller's, pitch K; x~ of a deeper layer: K is even there
     const long long ld_labels = layer == 0 ? K : Kp;              //  or the pitch is Kp)
 
     // ---- loss pieces and the gradient at the trained layer
     hipLaunchKernelGGL(xent_grad_kernel, dim3((unsigned)rows), dim3(256), 0, st, P(w.y), labels, ld_labels, rows, (int)K, P(w.dz2), Kp,
                        layer > 0 ? P(w.dlab) : (double*)nullptr, P(w.cd_part));
-    // tf.norm(h - s, axis=1, ord=1) + reduce_mean (SDAV.py:174): h is [B,P,N] at layer 0, [B*P,N] afterwards
-    const double cs_den = layer == 0 ? (double)batch * (double)N : (double)rows;
     int fn_slices = 1;
     {
         long long slices = dlc::cdiv((long long)patches * N, (long long)256 * 16);      // >= 16 elements per thread
@@ -565,7 +590,7 @@ extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64
         if (rc_ != DLC_OK) return rc_;
     }
     double* dz1 = P(w.h[layer]) + rows * N;                   // right behind h
-    if ((size_t)batch * 8 > 48 * 1024) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: batch too large");
+    if ((size_t)batch * 8 > 48 * 1024) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: batch too large", what);
     hipLaunchKernelGGL(hidden_grad_kernel, dim3(grid_for(rows * N)), dim3(256), (size_t)batch * 8, st, h, P(w.dh), P(w.nrm_part),
                        fn_slices, (int)batch, (long long)patches * N, cs_den, sparse_level, sparse_penalty, consecutive_penalty, dz1);
     // A layer's weight gradient and its SGD step in ONE launch where the LDS-DMA GEMM takes the shape: W += -lr * (A . B)
@@ -605,12 +630,12 @@ extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64
             // run well: 80 us apiece): d/dW = dz2^T h (decoder use) + x~^T dz1 (encoder use) = [dz2^T | x~^T] . [h ; dz1],
             // K = 2 rows (dz1 lies right behind h).
             hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)dlc::cdiv(K, 32), (unsigned)dlc::cdiv(rows, 32), 2), dim3(256), 0, st,
-                               P(w.dz2), Kp, rows, K, P(w.tr), 2 * rows, (const double*)P(w.xt[layer]), Kp, P(w.tr) + rows);
+                               P(w.dz2), Kp, rows, K, P(w.tr), 2 * rows, xt_of[layer], Kp, P(w.tr) + rows);
             const int rc_ = weight_step(l, K, N, 2 * rows, h);
             if (rc_ != DLC_OK) return rc_;
         } else {
             hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)dlc::cdiv(Kl, 32), (unsigned)dlc::cdiv(rows, 32)), dim3(256), 0,
-                               st, P(w.xt[l]), even_pitch(Kl), rows, Kl, P(w.tr), rows);
+                               st, xt_of[l], even_pitch(Kl), rows, Kl, P(w.tr), rows);
             const int rc_ = weight_step(l, Kl, Nl, rows, dz1);                                          // x~^T dz1
             if (rc_ != DLC_OK) return rc_;
         }
@@ -651,8 +676,65 @@ extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64
         hipLaunchKernelGGL(update_kernel, dim3((unsigned)(blk + 1)), dim3(256), 0, st, u);
     }
 #undef GEMM
-    DLC_LAUNCH_CHECK(ctx, "sdav_train_step kernels");
+    DLC_LAUNCH_CHECK(ctx, what);
     return DLC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dlc_sdav_train_workspace_bytes(int64_t batch, int64_t patches, const int64_t* dims, int n_layers,
+                                                 int layer) {
+    if (batch < 2 || patches < 1 || !dims || n_layers < 1 || n_layers > 8 || layer < 0 || layer >= n_layers) return 0;
+    return train_ws(batch * patches, (int)batch, dims, layer).total;
+}
+
+extern "C" int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64_t patches, int n_layers,
+                                   const int64_t* dims, const double* x, const double* const* masks, double* const* W,
+                                   double* const* b_enc, double* b_dec, double sparse_level, double sparse_penalty,
+                                   double consecutive_penalty, double learning_rate, double* loss_out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (!dims || !x || !masks || !W || !b_enc || !b_dec || n_layers < 1 || n_layers > 8 || layer < 0 || layer >= n_layers ||
+        patches < 1)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_train_step: bad argument");
+    if (batch < 2)
+        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: a batch needs >= 2 frames (consecutive-frame term, SDAV.py:176-183)");
+    if (batch * patches > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: batch too large");
+    if (dims[1] != dims[layer + 1])
+        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_train_step: hidden_units[0] != hidden_units[layer] (the slice of SDAV.py:178-181 needs equal widths)");
+    for (int l = 0; l <= layer; ++l)
+        if (!masks[l] || !W[l] || !b_enc[l]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_train_step: null parameter of layer %d", l);
+    // tf.norm(h - s, axis=1, ord=1) + reduce_mean (SDAV.py:174): h is [B,P,N] at layer 0, [B*P,N] afterwards
+    const double cs_den = layer == 0 ? (double)batch * (double)dims[1] : (double)(batch * patches);
+    return train_step_impl(ctx, "sdav_train_step", layer, batch, patches, dims, x, masks, nullptr, W, b_enc, b_dec, cs_den,
+                           sparse_level, sparse_penalty, consecutive_penalty, learning_rate, loss_out, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" size_t dlc_da_train_workspace_bytes(int64_t batch, int64_t patches, int64_t in_units, int64_t hidden_units) {
+    if (batch < 2 || patches < 1 || in_units < 1 || hidden_units < 1) return 0;
+    const int64_t dims[2] = {in_units, hidden_units};
+    return train_ws(batch * patches, (int)batch, dims, 0, false).total;
+}
+
+extern "C" int dlc_da_train_step(dlc_ctx* ctx, int64_t batch, int64_t patches, int64_t in_units, int64_t hidden_units,
+                                 const double* x, const double* x_tilde, double* W, double* b_enc, double* b_dec,
+                                 double sparse_level, double sparse_penalty, double consecutive_penalty, double learning_rate,
+                                 double* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (!x || !x_tilde || !W || !b_enc || !b_dec || patches < 1 || in_units < 1 || hidden_units < 1)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_train_step: bad argument");
+    if (batch < 2)
+        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "da_train_step: a batch needs >= 2 frames (consecutive-frame term, DenoisingAutoencoderVariant.py:128-136)");
+    if (batch * patches > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "da_train_step: batch too large");
+    const int64_t dims[2] = {in_units, hidden_units};
+    double* Wl[1] = {W};
+    double* bl[1] = {b_enc};
+    // h is 2-D [B*P, N] (DenoisingAutoencoderVariant.py:117,125-126): the L1 norm over the units, the mean over B*P rows
+    const double cs_den = (double)(batch * patches);
+    return train_step_impl(ctx, "da_train_step", 0, batch, patches, dims, x, nullptr, x_tilde, Wl, bl, b_dec, cs_den,
+                           sparse_level, sparse_penalty, consecutive_penalty, learning_rate, loss_out, workspace,
+                           workspace_bytes, stream);
 }
 
 extern "C" int dlc_random_mask_f64(dlc_ctx* ctx, double* mask, int64_t n, int64_t n_zeros, uint64_t seed, uint64_t counter,
@@ -665,5 +747,35 @@ extern "C" int dlc_random_mask_f64(dlc_ctx* ctx, double* mask, int64_t n, int64_
     hipLaunchKernelGGL(random_mask_kernel, dim3(1), dim3(RM_THREADS), 0, (hipStream_t)stream, mask, (long long)n,
                        (long long)n_zeros, (unsigned long long)seed, (unsigned long long)counter);
     DLC_LAUNCH_CHECK(ctx, "random_mask_kernel");
+    return DLC_OK;
+}
+
+extern "C" int dlc_salt_pepper_mask_f64(dlc_ctx* ctx, double* zeros, double* ones, int64_t n, int64_t n_zeros, uint64_t seed,
+                                        uint64_t counter, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (!zeros || !ones || zeros == ones || n < 1 || n_zeros < 0 || n_zeros > n)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "salt_pepper_mask: bad argument");
+    if (n > (1ll << 26)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "salt_pepper_mask: n=%lld too large (one workgroup walks the keys)", (long long)n);
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(random_mask_kernel, dim3(1), dim3(RM_THREADS), 0, st, zeros, (long long)n, (long long)n_zeros,
+                       (unsigned long long)seed, (unsigned long long)counter);
+    hipLaunchKernelGGL(salt_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const double*)zeros, ones, (long long)n,
+                       (unsigned long long)seed, (unsigned long long)counter);
+    DLC_LAUNCH_CHECK(ctx, "salt_pepper_mask kernels");
+    return DLC_OK;
+}
+
+extern "C" int dlc_da_corrupt_f64(dlc_ctx* ctx, const double* x, const double* zeros, const double* ones, int64_t rows,
+                                  int64_t cols, double* out, int64_t ldo, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (!x || !zeros || !ones || !out || rows < 1 || cols < 1 || ldo < cols)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_corrupt: bad argument");
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    hipLaunchKernelGGL(corrupt_rows_kernel, dim3(grid_for(rows * ldo)), dim3(256), 0, (hipStream_t)stream, x, zeros, ones,
+                       (long long)rows, (long long)cols, out, (long long)ldo);
+    DLC_LAUNCH_CHECK(ctx, "corrupt_rows_kernel");
     return DLC_OK;
 }

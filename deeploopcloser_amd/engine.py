@@ -486,6 +486,69 @@ class Engine:
                                                   int(counter) & (2 ** 64 - 1), self._stream()))
         return out
 
+    def salt_pepper_mask(self, zeros, ones, n_zeros, seed, counter):
+        """The DA's static salt-and-pepper masks (dlc_salt_pepper_mask_f64) into two fp64 tensors of one size: exactly
+        n_zeros zeros in `zeros`, and in `ones` a fair bit (salt) at each of those zeros, 0 elsewhere."""
+        for name, t in (("zeros", zeros), ("ones", ones)):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("salt_pepper_mask: %s must be a contiguous float64 tensor on %s" % (name, self.device))
+        if zeros.numel() != ones.numel() or zeros.data_ptr() == ones.data_ptr():
+            raise ValueError("salt_pepper_mask: two distinct tensors of one size")
+        self._check(self.lib.dlc_salt_pepper_mask_f64(self.ctx, _ptr(zeros), _ptr(ones), zeros.numel(), int(n_zeros),
+                                                       int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                                       self._stream()))
+        return zeros, ones
+
+    @staticmethod
+    def even_pitch(cols):
+        """The row pitch of a corrupted input x~ (dlc_da_corrupt_f64 / dlc_da_train_step): odd widths get a zero column."""
+        return cols + (cols & 1)
+
+    def da_corrupt(self, x2d, zeros, ones, out=None):
+        """x~ = zeros * x + ones (dlc_da_corrupt_f64): x2d [rows, K] fp64 and the masks of its size -> [rows, even_pitch(K)]
+        (the pad column zero), into `out` when given."""
+        rows, k = x2d.shape
+        for name, t in (("x", x2d), ("zeros", zeros), ("ones", ones)):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device or t.numel() != rows * k:
+                raise ValueError("da_corrupt: %s must be a contiguous float64 tensor of %d elements on %s" % (name, rows * k, self.device))
+        if out is None:
+            out = torch.empty((rows, self.even_pitch(k)), dtype=torch.float64, device=self.device)
+        self._check_out("da_corrupt: out", out, (rows, self.even_pitch(k)), torch.float64)
+        self._check(self.lib.dlc_da_corrupt_f64(self.ctx, _ptr(x2d), _ptr(zeros), _ptr(ones), rows, k, _ptr(out),
+                                                 out.stride(0), self._stream()))
+        return out
+
+    def da_train_workspace(self, batch, patches, in_units, hidden_units):
+        """A workspace tensor of dlc_da_train_step's size for this shape."""
+        need = self.lib.dlc_da_train_workspace_bytes(batch, patches, in_units, hidden_units)
+        if need == 0:
+            raise ValueError("da_train_step: batch must be >= 2 frames")
+        return torch.empty(int(need), dtype=torch.uint8, device=self.device)
+
+    def da_train_step(self, x2d, xt, batch, patches, w, b_enc, b_dec, sparse_level, sparse_penalty, consecutive_penalty,
+                      learning_rate, loss_out=None, ws=None):
+        """One in-place SGD step of a DA (dlc_da_train_step): x2d [batch*patches, K] the clean batch, xt its corruption
+        [batch*patches, even_pitch(K)] (da_corrupt), w [K, N], b_enc [N], b_dec [K]; loss_out: 4 doubles; ws: the caller's
+        own workspace (da_train_workspace) instead of the engine's."""
+        k, n = w.shape
+        rows = batch * patches
+        for name, t, shape in (("x", x2d, (rows, k)), ("x_tilde", xt, (rows, self.even_pitch(k))), ("W", w, (k, n)),
+                               ("b_enc", b_enc, (n,)), ("b_dec", b_dec, (k,))):
+            self._check_out("da_train_step: " + name, t, shape, torch.float64)
+        if loss_out is not None:
+            self._check_out("da_train_step: loss_out", loss_out, (4,), torch.float64)
+        need = self.lib.dlc_da_train_workspace_bytes(batch, patches, k, n)
+        if need == 0:
+            raise ValueError("da_train_step: batch must be >= 2 frames")
+        if ws is None:
+            ws = self.workspace("da_train", need)
+        else:
+            self._check_ws(ws)
+        self._check(self.lib.dlc_da_train_step(self.ctx, batch, patches, k, n, _ptr(x2d), _ptr(xt), _ptr(w), _ptr(b_enc),
+                                                _ptr(b_dec), float(sparse_level), float(sparse_penalty),
+                                                float(consecutive_penalty), float(learning_rate), _ptr(loss_out),
+                                                _ptr(ws), ws.numel(), self._stream()))
+
     # ---- SDAV patch front-end --------------------------------------------------------------
     def rgb_to_gray(self, rgb):
         rgb = rgb.contiguous()

@@ -125,3 +125,22 @@ class CvInputParser:
     def parse_from_path(self, image_path, key_points=None):
         """CvInputParser.parse_from_path (:30-33) for PPM frames; grey conversion as cv2.imread does it."""
         return self.parse(read_ppm(str(image_path)), key_points)
+
+
+def load_frames(file_pattern, input_shape, key_points_fn=None, device=None):
+    """The parsed frames of every file matching `file_pattern` (InputGenerator.py:17-27), in SORTED file order (the
+    reference's glob order is the file system's, and the consecutive-frame term depends on it): a list of float64
+    [input_shape[0], input_shape[1]] arrays.  key_points_fn(shape) -> key-points, or None for the build's Harris
+    detector.  An empty match logs the reference's message and returns []."""
+    from glob import glob
+    import logging
+    files = sorted(glob(file_pattern))
+    if len(files) == 0:
+        logging.getLogger().error("Specified dataset is empty or could not find dataset")   # InputGenerator.py:21-23
+        return []
+    parser = CvInputParser(input_shape[0], int(round(np.sqrt(input_shape[1]))), device=device)
+    frames = []
+    for f in files:
+        img = read_ppm(f)
+        frames.append(parser.parse(img, key_points_fn(img.shape[:2]) if key_points_fn else None))
+    return frames

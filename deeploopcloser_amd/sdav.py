@@ -2,7 +2,8 @@
 
 Mirrors src/sdav/network/SDAV.py (class SDAV: ctor :14, hyper-parameters
 :30-39, transform :293-302) and src/sdav/network/DenoisingAutoencoderVariant.py
-(class DA: ctor :15-26, transform :254-259).  The forward chain is one C-ABI
+(class DA: ctor :15-26, transform :254-259; its greedy training :103-243 through
+dlc_da_train_step, see DA).  The forward chain is one C-ABI
 call (dlc_sdav_encode): five fp64 MFMA GEMMs with fused bias + sigmoid,
 weights resident in HBM instead of a checkpoint restore / re-initialisation on
 every call (SDAV.py:232-240).
@@ -359,39 +360,235 @@ class SDAV:
                 self.train_steps(i, xb, self.epochs)
 
 
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def validate_da_params(input_shape, hidden_units, sparse_level, sparse_penalty, consecutive_penalty, batch_size,
+                       learning_rate, epochs, layer_n, corruption_level):
+    """DA._validate_params (DenoisingAutoencoderVariant.py:66-90) as ValueErrors, with two deliberate differences: ints
+    pass for the float parameters and layer_n = 0 passes (the reference's own rules reject its defaults: `positive()`
+    on layer_n = 0, `float_()` on SDA's sparse_penalty = 1).  Touches no device."""
+    if (not isinstance(input_shape, (list, tuple)) or len(input_shape) != 2 or
+            any(not _is_int(v) or v <= 0 for v in input_shape)):
+        raise ValueError("input_shape must be a list of two positive ints")      # v8n rule, :89-90
+    if not _is_int(hidden_units) or hidden_units <= 0:
+        raise ValueError("hidden_units must be a positive int")                  # :83-84
+    for name, v in (("learning_rate", learning_rate), ("sparse_level", sparse_level)):          # :70-72
+        if not _is_number(v) or not v > 0:
+            raise ValueError("%s must be a positive number, got %r" % (name, v))
+    for name, v in (("sparse_penalty", sparse_penalty), ("consecutive_penalty", consecutive_penalty),
+                    ("corruption_level", corruption_level)):                                    # :74-77
+        if not _is_number(v) or not 0 <= v <= 1:
+            raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
+    if not _is_int(layer_n) or layer_n < 0:
+        raise ValueError("layer_n must be an int >= 0, got %r" % (layer_n,))
+    for name, v in (("batch_size", batch_size), ("epochs", epochs)):                           # :79-83
+        if not _is_int(v) or v <= 0:
+            raise ValueError("%s must be a positive int, got %r" % (name, v))
+
+
 class DA:
-    """One denoising-autoencoder layer; only the transform path
-    (DenoisingAutoencoderVariant.py:116-119, 254-259)."""
+    """One denoising-autoencoder layer (DenoisingAutoencoderVariant.py): transform (:116-119, 254-259) and greedy
+    training (:103-148 step, :182-202 corruption, :210-243 fit_dataset) through dlc_da_train_step.
+
+    Defined where the reference is not:
+      * weights N(0,1), biases zero (:92-101), drawn once at construction from the seed: np.random.RandomState(seed) at
+        layer_n 0, RandomState([seed, layer_n]) above it (the layers of an SDA draw apart);
+      * the static salt-and-pepper corruption -- int(batch_size*P*K*corruption_level) zeros over the whole flat batch,
+        salt on half of them -- is a function of (seed, layer_n) (dlc_salt_pepper_mask_f64), drawn once and reused for
+        every batch and step, as the reference's graph constant is;
+      * training is float64 only; a batch must hold exactly batch_size frames (the masks' shape), at least 2;
+      * the reference never checkpoints (`step + 1 % 10` is never 0, :234); here checkpoint_file (a path prefix, None by
+        default) saves an .npz at the end of fit_dataset; fit() visits files in sorted order (input.load_frames);
+      * validation (validate_da_params) accepts layer_n >= 0 and ints for the float parameters, and runs before any
+        device is touched.
+    """
 
     def __init__(self, input_shape, hidden_units, sparse_level=0.05, sparse_penalty=1.0, consecutive_penalty=0.2,
                  batch_size=10, learning_rate=0.1, epochs=100, layer_n=0, corruption_level=0.3, seed=0,
                  dtype="float64", device=None):
-        if (not isinstance(input_shape, (list, tuple)) or len(input_shape) != 2 or
-                any((not isinstance(v, (int, np.integer))) or v <= 0 for v in input_shape)):
-            raise ValueError("input_shape must be a list of two positive ints")      # v8n rule, :89-90
-        if not isinstance(hidden_units, (int, np.integer)) or hidden_units <= 0:
-            raise ValueError("hidden_units must be a positive int")                  # :83-84
-        self.input_shape = list(input_shape)
+        validate_da_params(input_shape, hidden_units, sparse_level, sparse_penalty, consecutive_penalty, batch_size,
+                           learning_rate, epochs, layer_n, corruption_level)
+        self.input_shape = [int(v) for v in input_shape]
         self.hidden_units = int(hidden_units)
         self.sparse_level, self.sparse_penalty = sparse_level, sparse_penalty
-        self.consecutive_penalty, self.batch_size = consecutive_penalty, batch_size
-        self.learning_rate, self.epochs = learning_rate, epochs
-        self.corruption_level, self.layer_n = corruption_level, layer_n
+        self.consecutive_penalty, self.batch_size = consecutive_penalty, int(batch_size)
+        self.learning_rate, self.epochs = learning_rate, int(epochs)
+        self.corruption_level, self.layer_n = corruption_level, int(layer_n)
+        self.seed = int(seed)
         self.engine = default_engine(device)
         self.dtype = {"float64": torch.float64, "float32": torch.float32}[dtype]
-        ws, bs = _init_weights([self.input_shape[1], self.hidden_units], seed, self.dtype, self.engine.device)
+        w_seed = self.seed if self.layer_n == 0 else [self.seed & 0xffffffff, self.layer_n]
+        ws, bs = _init_weights([self.input_shape[1], self.hidden_units], w_seed, self.dtype, self.engine.device)
         self._w0, self._b0 = ws[0], bs[0]
+        self._b1 = torch.zeros(self.input_shape[1], dtype=self.dtype, device=self.engine.device)      # :99-101
+        self._masks = None
+        self._step_graph = None
+        self.global_step = 0
+        self.checkpoint_file = None
 
-    def set_weights(self, w, b=None):
+    # ---- weights ------------------------------------------------------------------
+    def set_weights(self, w, b=None, b_dec=None):
         w = self.engine.to_device(w, self.dtype)
         if tuple(w.shape) != (self.input_shape[1], self.hidden_units):
             raise ValueError("W must be %s" % ((self.input_shape[1], self.hidden_units),))
-        self._w0 = w
-        self._b0 = self.engine.to_device(b if b is not None else np.zeros(self.hidden_units), self.dtype)
+        b = self.engine.to_device(b if b is not None else np.zeros(self.hidden_units), self.dtype)
+        bd = self.engine.to_device(b_dec if b_dec is not None else np.zeros(self.input_shape[1]), self.dtype)
+        if b.numel() != self.hidden_units or bd.numel() != self.input_shape[1]:
+            raise ValueError("b must have %d entries, b_dec %d" % (self.hidden_units, self.input_shape[1]))
+        self._w0, self._b0, self._b1 = w.contiguous(), b.reshape(-1).contiguous(), bd.reshape(-1).contiguous()
 
+    def get_weights(self):
+        """(W [in, hidden], b_enc [hidden], b_dec [in]) as float64 host arrays."""
+        return tuple(t.to(torch.float64).cpu().numpy() for t in (self._w0, self._b0, self._b1))
+
+    def save_weights(self, path):
+        w, b, bd = self.get_weights()
+        np.savez(path, w=w, b_enc=b, b_dec=bd, global_step=np.array(self.global_step))
+
+    def load_weights(self, path):
+        z = np.load(path)
+        self.set_weights(z["w"], z["b_enc"], z["b_dec"])
+        self.global_step = int(z["global_step"])
+
+    # ---- encode ---------------------------------------------------------------------
     def transform(self, x, batch_n: int = -1):
         x = self.engine.to_device(x, self.dtype)
         if list(x.shape) != self.input_shape:
             raise ValueError("expected input of shape %s, got %s" % (self.input_shape, tuple(x.shape)))
         h = self.engine.gemm_bias_act(x, self._w0, self._b0, act=L.DLC_ACT_SIGMOID)
         return h.to(torch.float64).cpu().numpy()
+
+    def transform_tensor(self, x):
+        """A batch x [B, P, in] (or [rows, in]) on any device -> sigmoid(x W + b_enc) [B*P, hidden] on the GPU."""
+        x = self.engine.to_device(x, self.dtype)
+        if x.dim() not in (2, 3) or x.shape[-1] != self.input_shape[1] or (x.dim() == 3 and x.shape[1] != self.input_shape[0]):
+            raise ValueError("expected input of shape [B, %d, %d], got %s" % (self.input_shape[0], self.input_shape[1],
+                                                                              tuple(x.shape)))
+        x2 = x.reshape(-1, self.input_shape[1])
+        if x2.shape[0] == 0:
+            return torch.empty((0, self.hidden_units), dtype=self.dtype, device=self.engine.device)
+        return self.engine.gemm_bias_act(x2, self._w0, self._b0, act=L.DLC_ACT_SIGMOID)
+
+    # ---- training -----------------------------------------------------------------
+    def corruption_masks(self):
+        """The static (zeros, ones) masks [batch_size*P, in] (_corrupt_tensor, :182-202), drawn on first use: read-only
+        views for tests -- training reads the masks themselves."""
+        m = self._corruption_masks()
+        return tuple(t.view(self.batch_size * self.input_shape[0], self.input_shape[1]).detach().clone() for t in m)
+
+    def _corruption_masks(self):
+        if self._masks is None:
+            n = self.batch_size * self.input_shape[0] * self.input_shape[1]
+            zeros = torch.empty(n, dtype=torch.float64, device=self.engine.device)
+            ones = torch.empty(n, dtype=torch.float64, device=self.engine.device)
+            self.engine.salt_pepper_mask(zeros, ones, int(n * self.corruption_level), self.seed, self.layer_n)
+            self._masks = (zeros, ones)
+        return self._masks
+
+    def _check_batch(self, x):
+        if self.dtype != torch.float64:
+            raise ValueError("training runs in float64, like the reference")
+        x = self.engine.to_device(x, torch.float64)
+        if x.dim() != 3 or list(x.shape[1:]) != self.input_shape:
+            raise ValueError("expected a batch of shape [%d, %d, %d], got %s" % (self.batch_size, self.input_shape[0],
+                                                                                 self.input_shape[1], tuple(x.shape)))
+        if x.shape[0] < 2:
+            raise ValueError("a training batch needs at least 2 frames (the consecutive-frame loss term)")
+        if x.shape[0] != self.batch_size:
+            raise ValueError("a training batch holds batch_size=%d frames (the corruption masks' shape), got %d"
+                             % (self.batch_size, x.shape[0]))
+        return x.contiguous()
+
+    def _step(self, x2, xt, loss, ws=None):
+        self.engine.da_train_step(x2, xt, self.batch_size, self.input_shape[0], self._w0, self._b0, self._b1,
+                                  self.sparse_level, self.sparse_penalty, self.consecutive_penalty, self.learning_rate,
+                                  loss_out=loss, ws=ws)
+
+    def train_step(self, x):
+        """One sess.run(self.train_step) (:231) on a batch x [batch_size, P, in]; returns {loss, cd, cs, cc} (GPU tensor
+        of 4 doubles) evaluated before the update."""
+        x = self._check_batch(x)
+        zeros, ones = self._corruption_masks()
+        x2 = x.reshape(-1, self.input_shape[1])
+        xt = self.engine.da_corrupt(x2, zeros, ones)
+        loss = torch.empty(4, dtype=torch.float64, device=self.engine.device)
+        self._step(x2, xt, loss)
+        self.global_step += 1
+        return loss
+
+    def train_steps(self, x, n_steps):
+        """n_steps consecutive train_step on ONE batch (the inner loop of fit_dataset, :230-236).  x~ is fixed within a
+        batch, so it is formed once here; the step is captured ONCE as a HIP graph over fixed buffers (batch, x~,
+        workspace, loss) and replayed, re-captured when a parameter tensor, the split-K scratch or a hyper-parameter (a
+        kernel argument baked into the graph) changes -- as SDAV.train_steps.  Same arithmetic as train_step, same bits.
+        Returns the loss tensor {loss, cd, cs, cc} of the last step (before its update)."""
+        x = self._check_batch(x)
+        eng = self.engine
+        sig = (self._w0.data_ptr(), self._b0.data_ptr(), self._b1.data_ptr(),
+               eng._scratch.data_ptr() if eng._scratch is not None else 0,
+               float(self.learning_rate), float(self.sparse_level), float(self.sparse_penalty), float(self.consecutive_penalty))
+        g = self._step_graph
+        if g is None or g["sig"] != sig:
+            rows = self.batch_size * self.input_shape[0]
+            g = {"sig": sig, "x": torch.empty((rows, self.input_shape[1]), dtype=torch.float64, device=eng.device),
+                 "xt": torch.empty((rows, eng.even_pitch(self.input_shape[1])), dtype=torch.float64, device=eng.device),
+                 "loss": torch.zeros(4, dtype=torch.float64, device=eng.device), "graph": None,
+                 "ws": eng.da_train_workspace(self.batch_size, self.input_shape[0], self.input_shape[1], self.hidden_units)}
+            self._step_graph = g
+        zeros, ones = self._corruption_masks()
+        g["x"].copy_(x.reshape(-1, self.input_shape[1]))
+        eng.da_corrupt(g["x"], zeros, ones, out=g["xt"])
+
+        def one_step():
+            self._step(g["x"], g["xt"], g["loss"], ws=g["ws"])
+
+        done = 0
+        if g["graph"] is None and n_steps >= 3:
+            one_step()                                       # eager first: kernel attributes and pools exist before capture
+            done = 1
+            torch.cuda.synchronize(eng.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):                    # (a capture records the launches, it does not run them)
+                one_step()
+            g["graph"] = graph
+        for _ in range(done, n_steps):
+            if g["graph"] is not None:
+                g["graph"].replay()
+            else:
+                one_step()
+        self.global_step += n_steps
+        return g["loss"]
+
+    def _fit_batches(self, batches):
+        """fit_dataset's loop over device batches [b, P, in]: `epochs` steps per full batch, a short batch ends the fit
+        with the reference's warning (:224-228); one loss line per batch (the last step's, before its update)."""
+        with self.engine.latency_mode():
+            for batch_n, b in enumerate(batches):
+                if b.shape[0] != self.batch_size:
+                    logging.warning("Ignored last batch because it was smaller than the specified batch size. To avoid "
+                                    "this choose a batch size that is a factor of the dataset size.")
+                    break
+                loss = self.train_steps(b, self.epochs)
+                if logging.getLogger().isEnabledFor(logging.INFO):
+                    logging.info("    Layer:%d Batch:%d fit, Epoch:%d/%d, Loss:%s" %
+                                 (self.layer_n, batch_n, self.epochs, self.epochs, float(loss[0].item())))
+        if self.checkpoint_file:
+            self.save_weights("%s-%d.npz" % (self.checkpoint_file, self.global_step))
+
+    def fit_dataset(self, dataset):
+        """DA.fit_dataset (:210-243): frames [P, in] (host or device) in batches of batch_size."""
+        frames = [self.engine.to_device(f, torch.float64) for f in dataset]
+        bs = self.batch_size
+        self._fit_batches([torch.stack(frames[i:i + bs]) for i in range(0, len(frames), bs)])
+
+    def fit(self, file_pattern, key_points_fn=None):
+        """DA.fit (:204-208): the parsed frames of the files matching file_pattern (sorted), then fit_dataset."""
+        from .input import load_frames
+        logging.info("  Layer:%d fit" % self.layer_n)
+        self.fit_dataset(load_frames(file_pattern, self.input_shape, key_points_fn, device=self.engine.device))

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 10
+#define DLC_ABI_VERSION 11
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -162,6 +162,42 @@ int dlc_sdav_train_step(dlc_ctx* ctx, int layer, int64_t batch, int64_t patches,
  */
 int dlc_random_mask_f64(dlc_ctx* ctx, double* mask, int64_t n, int64_t n_zeros, uint64_t seed, uint64_t counter,
                         void* stream);
+
+/* ---- DA training step (the surface train-sdav.py drives: SDA.fit, one DA layer at a time) ------ */
+/*
+ * The DA's static salt-and-pepper corruption (src/sdav/network/DenoisingAutoencoderVariant.py:182-202): `zeros` gets
+ * EXACTLY n_zeros zeros among n ones, every placement equally likely (the draw of dlc_random_mask_f64 for the same
+ * (seed, counter); the reference's count is int(n * corruption_level), a truncation), and `ones` gets 1 where `zeros` is 0
+ * and an independent fair bit is set (salt), 0 everywhere else -- so ones <= 1 - zeros.  The bits are a function of
+ * (seed, counter), from a key stream apart from the zeros' keys.  zeros, ones: DEVICE fp64 [n], distinct; n <= 2^26.
+ */
+int dlc_salt_pepper_mask_f64(dlc_ctx* ctx, double* zeros, double* ones, int64_t n, int64_t n_zeros, uint64_t seed,
+                             uint64_t counter, void* stream);
+/*
+ * x~ = zeros * x + ones (DenoisingAutoencoderVariant.py:201-202), elementwise over x [rows, cols] (pitch cols) and the
+ * two masks of the same shape, into out [rows, ldo] (ldo >= cols; columns cols .. ldo - 1 written as zeros).  Give
+ * dlc_da_train_step an even ldo: cols + (cols & 1).
+ */
+int dlc_da_corrupt_f64(dlc_ctx* ctx, const double* x, const double* zeros, const double* ones, int64_t rows, int64_t cols,
+                       double* out, int64_t ldo, void* stream);
+/*
+ * One `sess.run(self.train_step)` of a DA (DenoisingAutoencoderVariant.py:103-148,201-202,231): h = sigmoid(x~ W + b_enc),
+ * y = sigmoid(h W^T + b_dec) (tied decoder), loss cd + sparse_penalty*cs + consecutive_penalty*cc with
+ * cd = mean over rows of softmax_cross_entropy(labels = x, logits = y) (the clean batch as labels),
+ * cs = mean over the batch*patches rows of ||h - sparse_level||_1 (h is 2-D here: the denominator is batch*patches, not
+ * the batch*N of dlc_sdav_train_step's layer 0), cc = mean over frames of ||H_t - H_t+1||_F; plain gradient descent
+ * with `learning_rate` on W, b_enc, b_dec, in place.  fp64.  The same kernels as dlc_sdav_train_step's layer 0, with x~
+ * taken from the caller instead of drawn per step.
+ * x [batch*patches, in_units] (pitch in_units), x_tilde [batch*patches, in_units + (in_units & 1)] (dlc_da_corrupt_f64's
+ * output, pad columns zero), W [in_units, hidden_units], b_enc [hidden_units], b_dec [in_units]: DEVICE.  batch >= 2.
+ * loss_out (DEVICE, 4 doubles, may be NULL) receives {loss, cd, cs, cc} evaluated BEFORE the update.  Stream-ordered,
+ * no synchronisation.
+ */
+size_t dlc_da_train_workspace_bytes(int64_t batch, int64_t patches, int64_t in_units, int64_t hidden_units);
+int dlc_da_train_step(dlc_ctx* ctx, int64_t batch, int64_t patches, int64_t in_units, int64_t hidden_units, const double* x,
+                      const double* x_tilde, double* W, double* b_enc, double* b_dec, double sparse_level,
+                      double sparse_penalty, double consecutive_penalty, double learning_rate, double* loss_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- encode: SDAV patch front-end after key-point detection -------------------------------- */
 /*
