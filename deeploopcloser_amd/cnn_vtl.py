@@ -7,6 +7,13 @@ NHWC tensor, no im2col matrix -- 8 channels per load for conv2..conv5, element b
 conv1's 3 input channels); pooling, per-row min/max, the 0..255 scaling, the int8 cast and the
 column gather are HIP kernels too.
 
+``dtype="f16x2"`` selects the TOLERANCE mode (include/dlc.h: dlc_cnnvtl_encode_split): every convolution as
+three fp16 MFMA products of two-piece splits with one activation exponent per frame and layer, fp32 between the layers,
+the reference's fp64 quantisation on the fp32 features.  No byte parity with the fp64 mode: a byte may differ by one
+step where the fp64 scaled value lies within ~2e-3 of an integer -- and since about 47 % of a frame's features are exact
+ReLU zeros sharing ONE scaled value, a frame whose zero class lies that close to an integer can have half its bytes move
+at once (a few frames in 10 000).  ``dtype="float64"`` (the default) is the parity mode and is unchanged.
+
 The reference's weights (bvlc_alexnet.npy, cnn_vtl.py:137-149) are a git-LFS
 pointer upstream, so weights here are seeded synthetic AlexNet-shaped tensors
 unless set_weights()/load_alexnet_npy() is used.  The reference's column mask
@@ -91,7 +98,9 @@ def _out_size(n, k, s, padding):
 
 class CnnVtl:
     def __init__(self, input_shape=(1, 224, 224, 3), batch_size: int = 10, compress_factor: float = 99.59,
-                 seed=0, mask_seed=0, device=None, frame_chunk=2048):
+                 seed=0, mask_seed=0, device=None, frame_chunk=2048, dtype="float64"):
+        if dtype not in ("float64", "f16x2"):
+            raise ValueError("dtype must be 'float64' (the parity mode) or 'f16x2' (the tolerance mode), got %r" % (dtype,))
         if len(input_shape) != 4 or any(int(v) <= 0 for v in input_shape) or input_shape[3] != 3:
             raise ValueError("input_shape must be [N, H, W, 3] with positive entries")
         if not (0 <= compress_factor <= 100):
@@ -100,6 +109,8 @@ class CnnVtl:
         self.batch_size = batch_size
         self.compress_factor = compress_factor
         self.frame_chunk = int(frame_chunk)
+        self.dtype = dtype
+        self._panels = None
         self.engine = default_engine(device)
         # cnn_vtl.py:30,128 keep the graph's placeholder and output TENSORS as attributes (basic_example.py never reads
         # them; a caller could only sess.run them).  There is no graph here -- transform() is the eager equivalent -- so
@@ -153,6 +164,7 @@ class CnnVtl:
             ws.append(self.engine.to_device(w.reshape(kh * kw * cin, cout), torch.float64))
             bs.append(self.engine.to_device(np.asarray(b, dtype=np.float64).reshape(cout), torch.float64))
         self._w, self._b = ws, bs
+        self._panels = None                     # the tolerance mode's prepared weights follow the current ones
         # Strided VALID layers whose input is a whole number of stride blocks (conv1: 11x11 / 4 on 192x240 or 224x224)
         # run as a stride-1 convolution over the space-to-depth input: 3 input channels become 48, which the implicit
         # GEMM's loaders fetch 8 / 16 at a time (the element-wise gather of a 3-channel input ran at 30 TF, the
@@ -189,7 +201,64 @@ class CnnVtl:
             h = e.maxpool3x3s2(y) if pool else y
         return outs
 
+    def _split_plan(self):
+        """(geometry, s2d block, panels) of the tolerance mode; the panels are rebuilt after set_weights."""
+        geom, ws, s2d = [], [], 1
+        for l, ((kh, kw, cin, cout, s, ph, pw, oh, ow, relu, pool), w) in enumerate(zip(self._geom, self._w)):
+            act = L.DLC_ACT_RELU if relu else L.DLC_ACT_NONE
+            if l in self._s2d:
+                s2d, k2h, k2w, wp = self._s2d[l]
+                geom.append((k2h, k2w, s2d * s2d * cin, cout, 1, 0, 0, oh, ow, act, int(pool)))
+                ws.append(wp)
+            else:
+                geom.append((kh, kw, cin, cout, s, ph, pw, oh, ow, act, int(pool)))
+                ws.append(w)
+        if self._panels is None:
+            self._panels = self.engine.cnnvtl_split_panels(geom, ws)
+        return geom, s2d, self._panels
+
+    def _check_status(self, status):
+        bits = int(status.item())
+        if bits:
+            raise ValueError("CnnVtl(dtype='f16x2'): non-finite values in %s; the tolerance mode accepts finite frames only"
+                             % ("the frames or a layer's input" if bits & 1 else "a layer's output"))
+
+    def _transform_split(self, x, status):
+        """transform_tensor of the tolerance mode; the non-finite flags of every chunk are ORed into `status`."""
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.uint8, torch.float32, torch.float64):
+            x = self.engine.to_device(x, torch.float64)
+        else:
+            x = self.engine.to_device(x)            # uint8 frames stay uint8: the kernel reads them as they are
+        if x.dim() != 4 or list(x.shape[1:]) != list(self.input_shape[1:]):
+            raise ValueError("expected input of shape [N, %d, %d, 3], got %s" %
+                             (self.input_shape[1], self.input_shape[2], tuple(x.shape)))
+        geom, s2d, panels = self._split_plan()
+        n = x.shape[0]
+        if n == 0:
+            return torch.empty((0, self.columns.size), dtype=torch.int8, device=self.engine.device)
+        n_chunks = max(1, -(-n // max(1, min(self.frame_chunk, 65535))))
+        step = -(-n // n_chunks)
+        parts = [self.engine.cnnvtl_encode_split(x[lo:lo + step], geom, s2d, panels, self._b, self._columns_dev, status)
+                 for lo in range(0, n, step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def features_split(self, x):
+        """Tolerance mode only (tests, diagnosis): (bytes int8 [n, D'], the five layers' pre-quantisation fp32 outputs)."""
+        if self.dtype != "f16x2":
+            raise ValueError("features_split: the network is not in the f16x2 mode")
+        x = self.engine.to_device(x) if isinstance(x, torch.Tensor) else self.engine.to_device(np.asarray(x))
+        geom, s2d, panels = self._split_plan()
+        status = torch.zeros(1, dtype=torch.int32, device=self.engine.device)
+        out = self.engine.cnnvtl_encode_split(x, geom, s2d, panels, self._b, self._columns_dev, status, feats=True)
+        self._check_status(status)
+        return out
+
     def transform_tensor(self, x):
+        if self.dtype == "f16x2":
+            status = torch.zeros(1, dtype=torch.int32, device=self.engine.device)
+            out = self._transform_split(x, status)
+            self._check_status(status)
+            return out
         x = self.engine.to_device(x, torch.float64)
         if x.dim() != 4 or list(x.shape[1:]) != list(self.input_shape[1:]):
             raise ValueError("expected input of shape [N, %d, %d, 3], got %s" %
@@ -231,4 +300,9 @@ class CnnVtl:
         cf = int(chunk_frames or max(1, self.frame_chunk // 4))
         n_chunks = max(1, -(-n // cf))
         step = -(-n // n_chunks)
+        if self.dtype == "f16x2":
+            status = torch.zeros(1, dtype=torch.int32, device=self.engine.device)
+            out = self.engine.run_chunked(x, step, lambda c: self._transform_split(c, status))
+            self._check_status(status)
+            return out
         return self.engine.run_chunked(x, step, self.transform_tensor)

@@ -48,6 +48,9 @@
 // (r04 .. the first r05 form dealt whole blocks of 6 x 5 tiles to the XCDs: 1250 tiles = 42 blocks = SIX rounds on two of
 // the XCDs where 1250 / 256 = 4.9 fit in five -- a sixth of the kernel's time, found through the in-kernel stamps: the k
 // loop accounted for 140 of a tile's 186 us.)
+//
+// The same k loop serves CnnVtl's tolerance mode (dlc_cnnvtl_encode_split) through a third epilogue, MODE SP_CONV: the
+// second half of this file.
 #include "gemm_internal.h"
 
 namespace dlc_gemm {
@@ -144,8 +147,26 @@ __device__ __forceinline__ void sp_barrier() {
     asm volatile("" ::: "memory");
 }
 
-template <bool FINAL>
-__global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(SplitArgs p) {
+// SplitArgs + what the convolution epilogue of the CnnVtl tolerance mode needs (O, C, ldc, oslice_b are unused there)
+struct ConvSplitArgs : SplitArgs {
+    float* Cf;                  // [M, N] fp32: the layer's NHWC output
+    const float* xinv;          // [frames] 2^-sx of each frame's activation exponent
+    unsigned rows_per_frame;    // oh * ow: row m belongs to frame m / rows_per_frame
+    int relu;
+    unsigned long long* keys;   // [frames, 2] ordered keys the outputs' per-frame min / max are folded into, or null
+    int* status;                // bit 1 <- a non-finite output (only with keys)
+};
+constexpr int SP_HIDDEN = 0, SP_FINAL = 1, SP_CONV = 2;
+template <int MODE> struct SpArgsOf { typedef SplitArgs type; };
+template <> struct SpArgsOf<SP_CONV> { typedef ConvSplitArgs type; };
+
+// MODE SP_HIDDEN: hidden SDAV layer (sigmoid, the next layer's pieces); SP_FINAL: last SDAV layer (sigmoid, fp64 out);
+// SP_CONV: a convolution layer of the CnnVtl tolerance mode (per-frame descale, bias, ReLU / none, fp32 [M, N] = NHWC out).
+// The k loop is the same statement for all three.
+template <int MODE>
+__global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename SpArgsOf<MODE>::type p) {
+    constexpr bool FINAL = MODE == SP_FINAL;
+    constexpr bool CONV = MODE == SP_CONV;
     extern __shared__ __attribute__((aligned(16))) char smem_sp[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -277,7 +298,8 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(SplitArgs
     float bias_l = 0.0f;
     if (tid < SP_BM) {
         const int n = tile_n * SP_BM + tid;
-        bias_l = (float)(-1.4426950408889634 * ((p.bias && n < p.N) ? p.bias[n] : 0.0) - (FINAL ? 0.0 : (double)SP_X_SHIFT));
+        if constexpr (CONV) bias_l = (float)((p.bias && n < p.N) ? p.bias[n] : 0.0);
+        else bias_l = (float)(-1.4426950408889634 * ((p.bias && n < p.N) ? p.bias[n] : 0.0) - (FINAL ? 0.0 : (double)SP_X_SHIFT));
     }
     // ---- prologue: early waves issue (W2, h2) of slices 0, 1; late waves (W1, h1) of slices 0, 1, 2; slice 0 landed and
     // visible; W1, h1 (0) read
@@ -324,6 +346,9 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(SplitArgs
     }
     constexpr int SP_TP = 68;                                 // floats per row of a wave's 64 x 64 block: 16 rows of float4 writes / a row of float2 reads each sweep the 64 banks once
     float* tl = (float*)(smem_sp + 4096) + wid * 64 * SP_TP;  // (behind the biases; 8 waves x 17 KiB)
+    // SP_CONV: this lane's running min / max of its row of each c (over both column halves), and "saw a non-finite value"
+    float rmn[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, rmx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    bool bad = false;
 #pragma unroll
     for (int th = 0; th < 2; ++th) {
         const int n0 = tile_n * SP_BM + wr * 128 + th * 64 + 16 * lg;
@@ -340,8 +365,43 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(SplitArgs
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const long long m = tile_m * SP_BN + wc * 64 + c * 16 + i;
-            if (m >= p.M) continue;
             float hv[16];
+            if constexpr (CONV) {
+                // y = acc 2^-(sx + sw) + b with sx the exponent of row m's FRAME (both factors powers of two: exact), ReLU
+                // (cnn_vtl.py:33-93) or none, fp32 [M, N]: the NHWC output.  A NaN stays a NaN (v < 0 is false for it).
+                // Rows past M store nothing and fold nothing.
+                const long long m0 = tile_m * SP_BN + wc * 64 + c * 16;         // the wave's 16 rows of this c (wave-uniform)
+                if (m0 >= p.M) continue;
+                const bool valid = m < p.M;
+                const float xi = p.xinv[(unsigned)(valid ? m : p.M - 1) / p.rows_per_frame];
+                const float wi = 1.0f / p.wscale[0];
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float v = fmaf(acc[th * 4 + tt][c][r] * xi, wi, bv[4 * tt + r]);
+                        v = (p.relu && v < 0.0f) ? 0.0f : v;
+                        hv[4 * tt + r] = v;
+                        if (valid && (whole || n0 + 4 * tt + r < p.N)) {
+                            rmn[c] = fminf(rmn[c], v);
+                            rmx[c] = fmaxf(rmx[c], v);
+                            bad |= !(fabsf(v) <= 3.402823466e38f);
+                        }
+                    }
+                if (valid) {
+                    float* dst = p.Cf + m * p.N + n0;
+                    if (whole && (p.N & 3) == 0) {
+#pragma unroll
+                        for (int j = 0; j < 16; j += 4) *(float4*)(dst + j) = make_float4(hv[j], hv[j + 1], hv[j + 2], hv[j + 3]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j)
+                            if (n0 + j < p.N) dst[j] = hv[j];
+                    }
+                }
+                continue;
+            }
+            if (m >= p.M) continue;
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -413,6 +473,52 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(SplitArgs
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the next half's rows overwrite the block
             __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if constexpr (CONV) {
+        // per-frame min / max of the outputs into the ordered fp64 keys (dlc_f64_key; cnn_vtl.py:110-112 takes them over the
+        // whole descriptor of a frame).  Wave-uniform tests: the wave's 64 rows in ONE frame -> one reduction and one pair
+        // of atomics; otherwise per block of 16 rows, and a block that spans frames leaves a pair per row.
+        if (p.keys) {
+            if (bad) atomicOr(p.status, 2);
+            const long long w0 = tile_m * SP_BN + wc * 64;
+            if (w0 < p.M) {
+                const long long wl = w0 + 63 < p.M ? w0 + 63 : p.M - 1;
+                const unsigned fw = (unsigned)w0 / p.rows_per_frame;
+                if (fw == (unsigned)wl / p.rows_per_frame) {
+                    float mn = fminf(fminf(rmn[0], rmn[1]), fminf(rmn[2], rmn[3]));
+                    float mx = fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3]));
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+                    if (lane == 0 && mn <= mx) {
+                        atomicMin(&p.keys[2 * (size_t)fw], dlc_f64_key((double)mn));
+                        atomicMax(&p.keys[2 * (size_t)fw + 1], dlc_f64_key((double)mx));
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const long long m0 = w0 + c * 16, m = m0 + i;
+                        if (m0 >= p.M) continue;
+                        float mn = rmn[c], mx = rmx[c];
+                        mn = fminf(mn, __shfl_xor(mn, 32)); mx = fmaxf(mx, __shfl_xor(mx, 32));     // the four lanes of a row
+                        mn = fminf(mn, __shfl_xor(mn, 16)); mx = fmaxf(mx, __shfl_xor(mx, 16));
+                        const long long ml = m0 + 15 < p.M ? m0 + 15 : p.M - 1;
+                        const unsigned f0 = (unsigned)m0 / p.rows_per_frame;
+                        if (f0 == (unsigned)ml / p.rows_per_frame) {
+#pragma unroll
+                            for (int o = 8; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+                            if (lane == 0 && mn <= mx) {
+                                atomicMin(&p.keys[2 * (size_t)f0], dlc_f64_key((double)mn));
+                                atomicMax(&p.keys[2 * (size_t)f0 + 1], dlc_f64_key((double)mx));
+                            }
+                        } else if (lg == 0 && m < p.M && mn <= mx) {
+                            const unsigned f = (unsigned)m / p.rows_per_frame;
+                            atomicMin(&p.keys[2 * (size_t)f], dlc_f64_key((double)mn));
+                            atomicMax(&p.keys[2 * (size_t)f + 1], dlc_f64_key((double)mx));
+                        }
+                    }
+                }
+            }
         }
     }
 }
@@ -553,8 +659,8 @@ int split_encode(dlc_ctx* ctx, int64_t rows, int n_layers, const int64_t* dims, 
         DLC_LAUNCH_CHECK(ctx, "sp_split_rows_kernel");
     }
     if (!(ctx->func_attr_set & (1ull << DLC_ATTR_SPLIT_F16))) {
-        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)gemm_split_f16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
-        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)gemm_split_f16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
+        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)gemm_split_f16_kernel<SP_HIDDEN>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
+        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)gemm_split_f16_kernel<SP_FINAL>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
         ctx->func_attr_set |= 1ull << DLC_ATTR_SPLIT_F16;
     }
     size_t off = 0;
@@ -578,8 +684,8 @@ int split_encode(dlc_ctx* ctx, int64_t rows, int n_layers, const int64_t* dims, 
         const long long nwg = (a.per_xcd + (a.extra ? 1 : 0)) * 8;
         if (nwg > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sdav_encode_split: too many tiles");
         const int rc = dlc::profiled(ctx, st, [&]() -> int {
-            if (fin) hipLaunchKernelGGL(gemm_split_f16_kernel<true>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
-            else hipLaunchKernelGGL(gemm_split_f16_kernel<false>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
+            if (fin) hipLaunchKernelGGL(gemm_split_f16_kernel<SP_FINAL>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
+            else hipLaunchKernelGGL(gemm_split_f16_kernel<SP_HIDDEN>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, a);
             DLC_LAUNCH_CHECK(ctx, "gemm_split_f16_kernel");
             return DLC_OK;
         });
@@ -635,4 +741,441 @@ extern "C" int dlc_sdav_encode_split(dlc_ctx* ctx, int64_t rows, int n_layers, c
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     return dlc_gemm::split_encode(ctx, rows, n_layers, dims, x, (const char*)panels, b, out, (char*)workspace, (hipStream_t)stream);
+}
+
+// ======================================================================================================================
+// CnnVtl in the same TOLERANCE mode (dlc_cnnvtl_encode_split; cnn_vtl.py:28-128): every convolution y = act(conv(x, W) + b)
+// is the split GEMM above over the convolution's im2col rows.  What differs from the SDAV chain:
+//   * activations are not in [0, 1] (ReLU, pixels 0 .. 255 fed unscaled: create_distance_matrix.py:23,27), so the activation
+//     exponent is ONE POWER OF TWO PER FRAME AND LAYER, from that frame's own max |x| of the layer's input: x 2^sx, the
+//     frame's largest scaled magnitude in [1024, 2048) (sx = 0 for an all-zero frame).  Per frame, not per chunk: a
+//     frame's descriptor does not depend on the batch it is encoded in;
+//   * the activation operand is written by cs_im2col_split_kernel: im2col and split in one pass over the fp32 NHWC
+//     input, zero padding and the zero k-tail written as zeros, straight into the K32-major pieces;
+//   * the epilogue (MODE SP_CONV) descales per row's frame, adds the bias, applies ReLU / none in fp32 and stores fp32 NHWC;
+//     max-pool runs on those fp32 values; the features that reach the quantiser are the fp32 layer outputs, promoted to
+//     fp64 for the reference's formula (cnn_vtl.py:108-128) -- the per-frame min / max folded by the same epilogue into
+//     the ordered keys the fp64 mode folds (dlc_f64_key; a tile may span several frames).
+// Non-finite values (in the input or produced on the way: a frame whose max |x| is inf / NaN, an output that is) set
+// bits of a device status word instead of travelling on as bytes: 1 = a layer input, 2 = a layer output.
+namespace dlc_gemm {
+namespace {
+
+constexpr int CS_GEOM = 11;     // ints per layer of the geometry array: kh kw cin cout stride pad_top pad_left oh ow act pool
+struct CsGeom { int kh, kw, cin, cout, stride, pt, pl, oh, ow, act, pool; };
+CsGeom cs_geom(const int32_t* g, int l) {
+    const int32_t* q = g + (size_t)l * CS_GEOM;
+    return CsGeom{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10]};
+}
+bool cs_geom_ok(const CsGeom& g) {
+    return g.kh >= 1 && g.kw >= 1 && g.cin >= 1 && g.cout >= 1 && g.stride >= 1 && g.pt >= 0 && g.pl >= 0 && g.oh >= 1 && g.ow >= 1 &&
+           (g.act == DLC_ACT_NONE || g.act == DLC_ACT_RELU) && (g.pool == 0 || (g.pool == 1 && g.oh >= 3 && g.ow >= 3)) &&
+           (long long)g.kh * g.kw * g.cin <= (1 << 24) && g.cout <= (1 << 20);
+}
+
+// frames [n, h, w, c] (uint8 / fp32 / fp64) -> fp32 [n, h/s, w/s, s*s*c], space-to-depth with block s (s = 1: a plain
+// conversion; the index map of dlc_space_to_depth_nhwc_f64)
+template <typename T>
+__global__ __launch_bounds__(256) void cs_input_kernel(const T* __restrict__ x, long long n, int h, int w, int c, int s,
+                                                       float* __restrict__ y) {
+    const int oh = h / s, ow = w / s, sc = s * c, oc = s * sc;
+    const long long total = n * oh * ow * oc;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int k = (int)(e % oc);
+        long long t = e / oc;
+        const int ox = (int)(t % ow);
+        t /= ow;
+        const int oy = (int)(t % oh);
+        const long long img = t / oh;
+        const int dy = k / sc, rem = k - dy * sc;
+        y[e] = (float)x[((img * h + (long long)oy * s + dy) * w + (long long)ox * s) * c + rem];
+    }
+}
+
+// per-frame max |x| as the bits of a non-negative float (they order like the values; inf and every NaN sort on top)
+__global__ __launch_bounds__(256) void cs_frame_absmax_kernel(const float* __restrict__ x, long long per, unsigned* __restrict__ amax) {
+    const float* p = x + (long long)blockIdx.y * per;
+    unsigned m = 0;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
+        const unsigned b = __float_as_uint(p[e]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned q = (unsigned)__shfl_xor((int)m, o); m = q > m ? q : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&amax[blockIdx.y], m);
+}
+// 2^sx per frame with max |x| 2^sx in [1024, 2048) (sx = 0 for a zero frame, |sx| <= 100), and 2^-sx
+__global__ void cs_frame_scale_kernel(const unsigned* __restrict__ amax, long long n, float* __restrict__ xscale,
+                                      float* __restrict__ xinv, int* status) {
+    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n) return;
+    const unsigned b = amax[f];
+    int s = 0;
+    if (b >= 0x7f800000u) atomicOr(status, 1);
+    else if (b) {
+        int e;
+        (void)frexpf(__uint_as_float(b), &e);                       // m = f 2^e, f in [0.5, 1): m 2^(11 - e) in [1024, 2048)
+        s = 11 - e;
+        s = s > 100 ? 100 : (s < -100 ? -100 : s);
+    }
+    xscale[f] = ldexpf(1.0f, s);
+    xinv[f] = ldexpf(1.0f, -s);
+}
+
+struct Im2colArgs {
+    const float* x;             // [n, h, w, c] fp32
+    const float* xscale;        // [n] 2^sx
+    long long M, mp;            // rows n * oh * ow, and the pieces' padded row count
+    int h, w, c, kh, kw, stride, pt, pl, oh, ow;
+    int K, ns;                  // kh * kw * c, slices of 32
+    unsigned short *p1, *p2;
+};
+// im2col + split: a workgroup writes 64 rows x every slice (4 KiB contiguous per slice and piece); thread (row, q) the 8
+// consecutive k of slot q -- with c % 8 == 0 eight channels of one tap, two 16-byte loads; otherwise element by element
+__global__ __launch_bounds__(256) void cs_im2col_split_kernel(Im2colArgs a) {
+    const long long m = (long long)blockIdx.x * 64 + (threadIdx.x >> 2);
+    if (m >= a.M) return;
+    const int q = threadIdx.x & 3;
+    const int ox = (int)(m % a.ow);
+    const long long t = m / a.ow;
+    const int oy = (int)(t % a.oh);
+    const long long img = t / a.oh;
+    const float sc = a.xscale[img];
+    const int iy0 = oy * a.stride - a.pt, ix0 = ox * a.stride - a.pl;
+    const float* xi = a.x + img * a.h * a.w * a.c;
+    const bool vec = (a.c & 7) == 0;
+    for (int sl = 0; sl < a.ns; ++sl) {
+        const int k0 = sl * 32 + q * 8;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 0.0f;
+        if (vec) {
+            if (k0 < a.K) {
+                const int tap = k0 / a.c, ch = k0 - tap * a.c;
+                const int ky = tap / a.kw, kx = tap - ky * a.kw;
+                const int iy = iy0 + ky, ix = ix0 + kx;
+                if (iy >= 0 && iy < a.h && ix >= 0 && ix < a.w) {
+                    const float4* s4 = (const float4*)(xi + ((long long)iy * a.w + ix) * a.c + ch);
+                    const float4 u0 = s4[0], u1 = s4[1];
+                    v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = k0 + j;
+                if (k < a.K) {
+                    const int tap = k / a.c, ch = k - tap * a.c;
+                    const int ky = tap / a.kw, kx = tap - ky * a.kw;
+                    const int iy = iy0 + ky, ix = ix0 + kx;
+                    if (iy >= 0 && iy < a.h && ix >= 0 && ix < a.w) v[j] = xi[((long long)iy * a.w + ix) * a.c + ch];
+                }
+            }
+        }
+        unsigned w1[4], w2[4];
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const f32x2_t s2 = {v[j] * sc, v[j + 1] * sc};
+            const f16x2_t h1 = __builtin_convertvector(s2, f16x2_t);
+            const f16x2_t h2 = __builtin_convertvector(s2 - __builtin_convertvector(h1, f32x2_t), f16x2_t);
+            w1[j >> 1] = __builtin_bit_cast(unsigned, h1);
+            w2[j >> 1] = __builtin_bit_cast(unsigned, h2);
+        }
+        const long long o = ((long long)sl * a.mp + m) * SP_KS + q * 8;
+        *(uint4*)(a.p1 + o) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
+        *(uint4*)(a.p2 + o) = make_uint4(w2[0], w2[1], w2[2], w2[3]);
+    }
+}
+
+// tf.layers.max_pooling2d(3x3, stride 2, VALID) on NHWC fp32 (cnn_vtl.py:42-45,58-61)
+__global__ __launch_bounds__(256) void cs_maxpool_kernel(const float* __restrict__ x, long long n, int h, int w, int c, int oh, int ow,
+                                                         float* __restrict__ y) {
+    const long long total = n * oh * ow * c;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int ch = (int)(e % c);
+        long long t = e / c;
+        const int ox = (int)(t % ow);
+        t /= ow;
+        const int oy = (int)(t % oh);
+        const long long img = t / oh;
+        const float* p = x + ((img * h + 2 * oy) * w + 2 * ox) * c + ch;
+        float m = p[0];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const float v = p[((long long)dy * w + dx) * c];
+                m = (v > m || v != v) ? v : m;                          // a NaN is kept
+            }
+        y[e] = m;
+    }
+}
+
+__global__ void cs_keys_init_kernel(unsigned long long* __restrict__ keys, long long n) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < n) { keys[r * 2] = ~0ull; keys[r * 2 + 1] = 0ull; }
+}
+
+constexpr int CS_MAX_LAYERS = 8;
+struct FSegs {
+    const float* ptr[CS_MAX_LAYERS];
+    long long size[CS_MAX_LAYERS];
+    long long start[CS_MAX_LAYERS + 1];
+    int n;
+};
+// out[r, j] = int8(trunc((d[r, cols[j]] - min_r) * (255 / (max_r - min_r)))), wrap mod 256 -- cnn_vtl.py:108-128 in fp64 on
+// the promoted fp32 features, operation for operation what quant_gather_kernel (cnnvtl.hip) does
+__global__ __launch_bounds__(256) void cs_quant_gather_kernel(FSegs s, const long long* __restrict__ cols, long long n_cols,
+                                                              const unsigned long long* __restrict__ keys, int8_t* __restrict__ out) {
+    const long long r = blockIdx.y;
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_cols) return;
+    const long long col = cols[j];
+    if (col < 0 || col >= s.start[s.n]) { out[r * n_cols + j] = 0; return; }
+    int g = 0;
+    while (g + 1 < s.n && col >= s.start[g + 1]) ++g;
+    const double v = (double)s.ptr[g][r * s.size[g] + (col - s.start[g])];
+    const double mn = dlc_f64_unkey(keys[r * 2]), mx = dlc_f64_unkey(keys[r * 2 + 1]);
+    const double scaled = (v - mn) * (255.0 / (mx - mn));
+    long long t = 0;
+    if (scaled == scaled && fabs(scaled) < 9.0e18) t = (long long)scaled;
+    out[r * n_cols + j] = (int8_t)(unsigned char)(t & 0xff);
+}
+
+size_t a256(size_t v) { return dlc::align_up(v, 256); }
+
+// the workspace of n frames whose first layer reads [h, w, c]: offsets of its parts
+struct ConvWs {
+    size_t in0, out[CS_MAX_LAYERS], pool[CS_MAX_LAYERS], piece[2], amax, xscale, xinv, keys, status, total;
+    int ih[CS_MAX_LAYERS], iw[CS_MAX_LAYERS], ic[CS_MAX_LAYERS];      // each layer's input
+};
+bool conv_ws(int64_t n, int h, int w, int c, int n_layers, const int32_t* geom, ConvWs* W) {
+    size_t off = 0, pmax = 0;
+    W->in0 = off; off += a256((size_t)n * h * w * c * 4);
+    for (int l = 0; l < n_layers; ++l) {
+        const CsGeom g = cs_geom(geom, l);
+        if (!cs_geom_ok(g) || g.cin != c) return false;
+        W->ih[l] = h; W->iw[l] = w; W->ic[l] = c;
+        const long long M = (long long)n * g.oh * g.ow;
+        if (M > 0x7fffffffll * 64 / 4096) return false;
+        W->out[l] = off; off += a256((size_t)M * g.cout * 4);
+        const size_t pb = (size_t)split_rows_pad(M) * (size_t)dlc::cdiv((int64_t)g.kh * g.kw * g.cin, SP_KS) * SP_ROWB;
+        pmax = pb > pmax ? pb : pmax;
+        h = g.oh; w = g.ow; c = g.cout;
+        W->pool[l] = off;
+        if (g.pool) {
+            h = (h - 3) / 2 + 1; w = (w - 3) / 2 + 1;
+            off += a256((size_t)n * h * w * c * 4);
+        }
+    }
+    W->piece[0] = off; off += a256(pmax);
+    W->piece[1] = off; off += a256(pmax);
+    W->amax = off; off += a256((size_t)n * 4);
+    W->xscale = off; off += a256((size_t)n * 4);
+    W->xinv = off; off += a256((size_t)n * 4);
+    W->keys = off; off += a256((size_t)n * 16);
+    W->status = off; off += 256;
+    W->total = off;
+    return true;
+}
+
+unsigned cs_blocks(long long total) {
+    long long b = dlc::cdiv(total, (int64_t)256);
+    return (unsigned)(b > 256 * 32 ? 256 * 32 : (b < 1 ? 1 : b));
+}
+// slices of a frame for the per-frame reductions: a handful of frames still fills the chip
+unsigned cs_slices(int64_t n, long long per) {
+    long long s = dlc::cdiv(per, (int64_t)(256 * 16)), cap = dlc::cdiv((int64_t)4096, n);
+    s = s > cap ? cap : s;
+    return (unsigned)(s < 1 ? 1 : s);
+}
+
+size_t conv_panels_offset(int n_layers, const int32_t* geom, int upto) {
+    size_t t = 0;
+    for (int l = 0; l < upto && l < n_layers; ++l) {
+        const CsGeom g = cs_geom(geom, l);
+        t += panel_layout((int64_t)g.kh * g.kw * g.cin, g.cout).total;
+    }
+    return t;
+}
+
+// layers a .. b on n frames; `x` = layer a's fp32 input [n, ih[a], iw[a], ic[a]].  feats[l - a] (may be null, entries too):
+// where layer l's output goes instead of the workspace.  keys (may be null): per-frame min / max of every output folded in.
+int conv_run_layers(dlc_ctx* ctx, int64_t n, const ConvWs& W, int n_layers, const int32_t* geom, int a, int b, const float* x,
+                    const char* panels, const double* const* bias, float* const* feats, const float** outs, char* ws,
+                    unsigned long long* keys, int* status, hipStream_t st) {
+    if (!(ctx->func_attr_set & (1ull << DLC_ATTR_CONV_SPLIT_F16))) {
+        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)gemm_split_f16_kernel<SP_CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
+        ctx->func_attr_set |= 1ull << DLC_ATTR_CONV_SPLIT_F16;
+    }
+    unsigned* amax = (unsigned*)(ws + W.amax);
+    float* xscale = (float*)(ws + W.xscale);
+    float* xinv = (float*)(ws + W.xinv);
+    const float* h = x;
+    for (int l = a; l <= b; ++l) {
+        const CsGeom g = cs_geom(geom, l);
+        const int ih = W.ih[l], iw = W.iw[l], ic = W.ic[l];
+        const long long per_in = (long long)ih * iw * ic, rpf = (long long)g.oh * g.ow, M = n * rpf;
+        const int K = g.kh * g.kw * g.cin, ns = (int)dlc::cdiv((int64_t)K, SP_KS);
+        const long long mp = split_rows_pad(M);
+        // this layer's exponent per frame
+        DLC_HIP_CHECK(ctx, hipMemsetAsync(amax, 0, (size_t)n * 4, st));
+        hipLaunchKernelGGL(cs_frame_absmax_kernel, dim3(cs_slices(n, per_in), (unsigned)n), dim3(256), 0, st, h, per_in, amax);
+        hipLaunchKernelGGL(cs_frame_scale_kernel, dim3((unsigned)dlc::cdiv(n, (int64_t)256)), dim3(256), 0, st, (const unsigned*)amax,
+                           (long long)n, xscale, xinv, status);
+        Im2colArgs ia;
+        ia.x = h; ia.xscale = xscale; ia.M = M; ia.mp = mp;
+        ia.h = ih; ia.w = iw; ia.c = ic; ia.kh = g.kh; ia.kw = g.kw; ia.stride = g.stride; ia.pt = g.pt; ia.pl = g.pl; ia.oh = g.oh; ia.ow = g.ow;
+        ia.K = K; ia.ns = ns;
+        ia.p1 = (unsigned short*)(ws + W.piece[0]); ia.p2 = (unsigned short*)(ws + W.piece[1]);
+        hipLaunchKernelGGL(cs_im2col_split_kernel, dim3((unsigned)dlc::cdiv(M, (int64_t)64)), dim3(256), 0, st, ia);
+        DLC_LAUNCH_CHECK(ctx, "cs_im2col_split_kernel");
+        float* out = (feats && feats[l - a]) ? feats[l - a] : (float*)(ws + W.out[l]);
+        const PanelLayout L = panel_layout(K, g.cout);
+        const char* base = panels + conv_panels_offset(n_layers, geom, l);
+        ConvSplitArgs p;
+        p.W[0] = base + L.p1; p.W[1] = base + L.p2; p.wslice_b = L.np * SP_ROWB;
+        p.X[0] = ws + W.piece[0]; p.X[1] = ws + W.piece[1]; p.xslice_b = mp * SP_ROWB;
+        p.M = M; p.N = g.cout; p.ns = ns;
+        p.bias = bias ? bias[l] : nullptr;
+        p.wscale = (const float*)(base + L.scale);
+        p.O[0] = p.O[1] = nullptr; p.oslice_b = 0; p.C = nullptr; p.ldc = g.cout;
+        p.tiles_m = dlc::cdiv(M, (int64_t)SP_BN);
+        p.tiles_n = (int)(L.np / SP_BM);
+        const long long tiles = p.tiles_m * p.tiles_n;
+        p.per_xcd = tiles / 8; p.extra = tiles % 8;
+        p.Cf = out; p.xinv = xinv; p.rows_per_frame = (unsigned)rpf; p.relu = g.act == DLC_ACT_RELU;
+        p.keys = keys; p.status = status;
+        const long long nwg = (p.per_xcd + (p.extra ? 1 : 0)) * 8;
+        if (nwg > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cnnvtl_encode_split: too many tiles");
+        const int rc = dlc::profiled(ctx, st, [&]() -> int {
+            hipLaunchKernelGGL(gemm_split_f16_kernel<SP_CONV>, dim3((unsigned)nwg), dim3(SP_THREADS), SP_LDS, st, p);
+            DLC_LAUNCH_CHECK(ctx, "gemm_split_f16_kernel<SP_CONV>");
+            return DLC_OK;
+        });
+        if (rc != DLC_OK) return rc;
+        if (outs) outs[l] = out;
+        h = out;
+        if (g.pool && l < b) {
+            const int ph = (g.oh - 3) / 2 + 1, pw = (g.ow - 3) / 2 + 1;
+            float* y = (float*)(ws + W.pool[l]);
+            hipLaunchKernelGGL(cs_maxpool_kernel, dim3(cs_blocks(n * ph * pw * g.cout)), dim3(256), 0, st, (const float*)out, (long long)n,
+                               g.oh, g.ow, g.cout, ph, pw, y);
+            h = y;
+        }
+        DLC_LAUNCH_CHECK(ctx, "cnnvtl split layer");
+    }
+    return DLC_OK;
+}
+
+int conv_check_common(dlc_ctx* ctx, const char* who, int64_t n, int n_layers, const int32_t* geom, const void* panels, const void* ws) {
+    if (!geom || !panels || n < 1 || n_layers < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: null/empty argument", who);
+    if (n_layers > CS_MAX_LAYERS) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: at most %d layers", who, CS_MAX_LAYERS);
+    if (n > 65535) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: more than 65535 frames per call", who);
+    if (((uintptr_t)ws & 255) || ((uintptr_t)panels & 255)) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: workspace and panels must be 256-byte aligned", who);
+    return DLC_OK;
+}
+
+}  // namespace
+}  // namespace dlc_gemm
+
+extern "C" size_t dlc_cnnvtl_split_panels_bytes(int n_layers, const int32_t* geom) {
+    if (!geom || n_layers < 1 || n_layers > dlc_gemm::CS_MAX_LAYERS) return 0;
+    for (int l = 0; l < n_layers; ++l)
+        if (!dlc_gemm::cs_geom_ok(dlc_gemm::cs_geom(geom, l))) return 0;
+    return dlc_gemm::conv_panels_offset(n_layers, geom, n_layers);
+}
+
+extern "C" int dlc_cnnvtl_split_prepare(dlc_ctx* ctx, int n_layers, const int32_t* geom, const double* const* W, void* panels,
+                                        size_t panels_bytes, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (!geom || !W || !panels || n_layers < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_split_prepare: null/empty argument");
+    const size_t need = dlc_cnnvtl_split_panels_bytes(n_layers, geom);
+    if (need == 0) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cnnvtl_split_prepare: bad geometry");
+    if (panels_bytes < need) return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cnnvtl_split_prepare: panels %zu < %zu bytes", panels_bytes, need);
+    if ((uintptr_t)panels & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_split_prepare: panels must be 256-byte aligned");
+    for (int l = 0; l < n_layers; ++l)
+        if (!W[l]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_split_prepare: W[%d] is null", l);
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    for (int l = 0; l < n_layers; ++l) {
+        const dlc_gemm::CsGeom g = dlc_gemm::cs_geom(geom, l);
+        const int64_t dims[2] = {(int64_t)g.kh * g.kw * g.cin, g.cout};
+        const int rc = dlc_gemm::split_prepare(ctx, 1, dims, W + l, (char*)panels + dlc_gemm::conv_panels_offset(n_layers, geom, l),
+                                               (hipStream_t)stream);
+        if (rc != DLC_OK) return rc;
+    }
+    return DLC_OK;
+}
+
+extern "C" size_t dlc_cnnvtl_encode_split_workspace_bytes(int64_t n, int h, int w, int c, int n_layers, const int32_t* geom) {
+    if (n < 1 || n > 65535 || h < 1 || w < 1 || c < 1 || !geom || n_layers < 1 || n_layers > dlc_gemm::CS_MAX_LAYERS) return 0;
+    dlc_gemm::ConvWs W;
+    return dlc_gemm::conv_ws(n, h, w, c, n_layers, geom, &W) ? W.total : 0;
+}
+
+extern "C" int dlc_cnnvtl_encode_split(dlc_ctx* ctx, int dtype, const void* x, int64_t n, int h, int w, int c, int s2d, int n_layers,
+                                       const int32_t* geom, const void* panels, const double* const* b, const int64_t* cols,
+                                       int64_t n_cols, int8_t* out, float* const* feats, int32_t* status, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    int rc = dlc_gemm::conv_check_common(ctx, "cnnvtl_encode_split", n, n_layers, geom, panels, workspace);
+    if (rc != DLC_OK) return rc;
+    if (!x || !cols || !out || !status || n_cols < 1 || h < 1 || w < 1 || c < 1 || s2d < 1 || h % s2d || w % s2d)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_encode_split: bad argument");
+    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_U8)
+        return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "cnnvtl_encode_split: frames must be DLC_F64, DLC_F32 or DLC_U8");
+    const int h0 = h / s2d, w0 = w / s2d, c0 = c * s2d * s2d;
+    dlc_gemm::ConvWs W;
+    if (!dlc_gemm::conv_ws(n, h0, w0, c0, n_layers, geom, &W)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cnnvtl_encode_split: bad geometry");
+    if (!workspace || workspace_bytes < W.total)
+        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cnnvtl_encode_split: workspace %zu < %zu bytes", workspace_bytes, W.total);
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* in0 = (float*)(ws + W.in0);
+    const unsigned blocks = dlc_gemm::cs_blocks((long long)n * h * w * c);
+    if (dtype == DLC_F64) hipLaunchKernelGGL(dlc_gemm::cs_input_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)x, (long long)n, h, w, c, s2d, in0);
+    else if (dtype == DLC_F32) hipLaunchKernelGGL(dlc_gemm::cs_input_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, (long long)n, h, w, c, s2d, in0);
+    else hipLaunchKernelGGL(dlc_gemm::cs_input_kernel<unsigned char>, dim3(blocks), dim3(256), 0, st, (const unsigned char*)x, (long long)n, h, w, c, s2d, in0);
+    DLC_LAUNCH_CHECK(ctx, "cs_input_kernel");
+    unsigned long long* keys = (unsigned long long*)(ws + W.keys);
+    hipLaunchKernelGGL(dlc_gemm::cs_keys_init_kernel, dim3((unsigned)dlc::cdiv(n, (int64_t)256)), dim3(256), 0, st, keys, (long long)n);
+    const float* outs[dlc_gemm::CS_MAX_LAYERS];
+    rc = dlc_gemm::conv_run_layers(ctx, n, W, n_layers, geom, 0, n_layers - 1, in0, (const char*)panels, b, feats, outs, ws, keys,
+                                   (int*)status, st);
+    if (rc != DLC_OK) return rc;
+    dlc_gemm::FSegs s;
+    s.n = n_layers;
+    s.start[0] = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const dlc_gemm::CsGeom g = dlc_gemm::cs_geom(geom, l);
+        s.ptr[l] = outs[l];
+        s.size[l] = (long long)g.oh * g.ow * g.cout;
+        s.start[l + 1] = s.start[l] + s.size[l];
+    }
+    hipLaunchKernelGGL(dlc_gemm::cs_quant_gather_kernel, dim3((unsigned)dlc::cdiv(n_cols, (int64_t)256), (unsigned)n), dim3(256), 0, st, s,
+                       (const long long*)cols, (long long)n_cols, (const unsigned long long*)keys, out);
+    DLC_LAUNCH_CHECK(ctx, "cs_quant_gather_kernel");
+    return DLC_OK;
+}
+
+extern "C" int dlc_cnnvtl_layers_split(dlc_ctx* ctx, const float* x, int64_t n, int h, int w, int c, int n_layers, const int32_t* geom,
+                                       int layer_a, int layer_b, const void* panels, const double* const* b, float* const* feats,
+                                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    int rc = dlc_gemm::conv_check_common(ctx, "cnnvtl_layers_split", n, n_layers, geom, panels, workspace);
+    if (rc != DLC_OK) return rc;
+    if (!x || !feats || !status || layer_a < 0 || layer_b < layer_a || layer_b >= n_layers || h < 1 || w < 1 || c < 1)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_layers_split: bad argument");
+    dlc_gemm::ConvWs W;
+    if (!dlc_gemm::conv_ws(n, h, w, c, n_layers, geom, &W)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cnnvtl_layers_split: bad geometry");
+    if (!workspace || workspace_bytes < W.total)
+        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cnnvtl_layers_split: workspace %zu < %zu bytes", workspace_bytes, W.total);
+    for (int l = layer_a; l <= layer_b; ++l)
+        if (!feats[l - layer_a]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_layers_split: feats[%d] is null", l - layer_a);
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    return dlc_gemm::conv_run_layers(ctx, n, W, n_layers, geom, layer_a, layer_b, x, (const char*)panels, b, feats, nullptr,
+                                     (char*)workspace, nullptr, (int*)status, (hipStream_t)stream);
 }

@@ -443,6 +443,79 @@ class Engine:
                                                     _ptr(ws), ws.numel(), self._stream()))
         return out
 
+    # ---- CnnVtl tolerance mode (include/dlc.h: dlc_cnnvtl_encode_split) --------------------
+    @staticmethod
+    def _conv_geom_c(geom):
+        """geom: per layer (kh, kw, cin, cout, stride, pad_top, pad_left, oh, ow, act, pool) -> the C int32 array."""
+        flat = [int(v) for g in geom for v in g]
+        if not geom or len(flat) != 11 * len(geom):
+            raise ValueError("geometry: 11 integers per layer")
+        return (C.c_int32 * len(flat))(*flat)
+
+    def cnnvtl_split_panels(self, geom, weights):
+        """The tolerance-mode CnnVtl's prepared weights (dlc_cnnvtl_split_prepare): fp64 kernels [kh*kw*cin, cout] -> one
+        uint8 device tensor holding, per layer, the two fp16 pieces of W 2^s and 2^s."""
+        n_layers = len(geom)
+        for l, (g, w) in enumerate(zip(geom, weights)):
+            if w.dtype != torch.float64 or tuple(w.shape) != (g[0] * g[1] * g[2], g[3]) or not w.is_contiguous() or w.device != self.device:
+                raise ValueError("cnnvtl_split_panels: W[%d] must be a contiguous float64 [%d, %d] tensor on %s"
+                                 % (l, g[0] * g[1] * g[2], g[3], self.device))
+        geom_c = self._conv_geom_c(geom)
+        need = self.lib.dlc_cnnvtl_split_panels_bytes(n_layers, geom_c)
+        if need == 0:
+            raise ValueError("cnnvtl_split_panels: bad geometry")
+        panels = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        w_c = (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights])
+        self._check(self.lib.dlc_cnnvtl_split_prepare(self.ctx, n_layers, geom_c, w_c, _ptr(panels), panels.numel(), self._stream()))
+        return panels
+
+    def _cnnvtl_split_ws(self, n, h, w, c, geom_c, n_layers):
+        need = self.lib.dlc_cnnvtl_encode_split_workspace_bytes(n, h, w, c, n_layers, geom_c)
+        if need == 0:
+            raise ValueError("cnnvtl tolerance mode: bad shape or geometry (1 .. 65535 frames per call)")
+        return self.workspace("cnnvtl_split", need)
+
+    def cnnvtl_encode_split(self, x, geom, s2d, panels, biases, columns, status, feats=False):
+        """Frames x [n, h, w, c] (uint8, float32 or float64, on the device) -> int8 [n, columns.numel()] in the tolerance
+        mode (dlc_cnnvtl_encode_split).  status: int32 [1] device tensor the call ORs its non-finite flags into.
+        feats=True: also the layers' pre-quantisation fp32 outputs, (bytes, [fp32 [n, oh, ow, cout] per layer])."""
+        dt = {torch.uint8: L.DLC_U8, torch.float32: L.DLC_F32, torch.float64: L.DLC_F64}.get(x.dtype)
+        if dt is None or x.dim() != 4 or x.device != self.device:
+            raise ValueError("cnnvtl_encode_split: frames must be a uint8 / float32 / float64 [n, h, w, c] tensor on %s" % self.device)
+        x = x.contiguous()
+        n, h, w, c = x.shape
+        n_layers = len(geom)
+        geom_c = self._conv_geom_c(geom)
+        ws = self._cnnvtl_split_ws(n, h // s2d, w // s2d, c * s2d * s2d, geom_c, n_layers)
+        b_c = (C.c_void_p * n_layers)(*[(b.data_ptr() if b is not None else 0) for b in biases])
+        out = torch.empty((n, columns.numel()), dtype=torch.int8, device=self.device)
+        fs = [torch.empty((n, g[7], g[8], g[3]), dtype=torch.float32, device=self.device) for g in geom] if feats else None
+        f_c = (C.c_void_p * n_layers)(*[f.data_ptr() for f in fs]) if feats else None
+        self._check(self.lib.dlc_cnnvtl_encode_split(self.ctx, dt, _ptr(x), n, h, w, c, s2d, n_layers, geom_c, _ptr(panels), b_c,
+                                                      _ptr(columns), columns.numel(), _ptr(out), f_c, _ptr(status), _ptr(ws),
+                                                      ws.numel(), self._stream()))
+        return (out, fs) if feats else out
+
+    def cnnvtl_layers_split(self, x, in_shape, geom, layer_a, layer_b, panels, biases, status=None):
+        """Debug / test entry (dlc_cnnvtl_layers_split): layers layer_a .. layer_b of the tolerance mode on x, layer_a's own
+        fp32 input [n, h, w, c]; in_shape = (h, w, c) of LAYER 0's input.  -> the layers' fp32 outputs."""
+        if x.dtype != torch.float32 or x.dim() != 4 or x.device != self.device:
+            raise ValueError("cnnvtl_layers_split: x must be a float32 [n, h, w, c] tensor on %s" % self.device)
+        x = x.contiguous()
+        n = x.shape[0]
+        n_layers = len(geom)
+        geom_c = self._conv_geom_c(geom)
+        ws = self._cnnvtl_split_ws(n, in_shape[0], in_shape[1], in_shape[2], geom_c, n_layers)
+        b_c = (C.c_void_p * n_layers)(*[(b.data_ptr() if b is not None else 0) for b in biases])
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        fs = [torch.empty((n, g[7], g[8], g[3]), dtype=torch.float32, device=self.device) for g in geom[layer_a:layer_b + 1]]
+        f_c = (C.c_void_p * len(fs))(*[f.data_ptr() for f in fs])
+        self._check(self.lib.dlc_cnnvtl_layers_split(self.ctx, _ptr(x), n, in_shape[0], in_shape[1], in_shape[2], n_layers, geom_c,
+                                                      layer_a, layer_b, _ptr(panels), b_c, f_c, _ptr(status), _ptr(ws), ws.numel(),
+                                                      self._stream()))
+        return fs
+
     def train_workspace(self, layer, batch, patches, weights):
         """A workspace tensor of dlc_sdav_train_step's size for this shape (for a caller that keeps its own)."""
         n_layers = len(weights)

@@ -353,6 +353,9 @@ def main(argv=None):
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
+    ap.add_argument("--encoder-dtype", choices=["float64", "f16x2"], default="float64",
+                    help="the encoder's arithmetic: float64 (parity with the reference) or f16x2, the tolerance mode of "
+                         "SDAV / CnnVtl on the fp16 matrix cores (--dtype is the cosine database's storage type)")
     ap.add_argument("--no-latency-mode", action="store_true",
                     help="keep the one-pass GEMMs (bit-identical to a large-batch encode) for small batches too")
     args = ap.parse_args(argv)
@@ -370,7 +373,7 @@ def main(argv=None):
 def _stream(args, files):
     if args.network == "sdav":
         from .sdav import SDAV
-        net = SDAV()
+        net = SDAV(dtype=args.encoder_dtype)
         if args.weights:
             net.load_weights(args.weights)
         describe = lambda fs: describe_sdav(fs, net)
@@ -378,7 +381,7 @@ def _stream(args, files):
         from .cnn_vtl import CnnVtl
         from .input import read_ppm
         shape = read_ppm(files[0]).shape
-        net = CnnVtl(input_shape=[args.batch] + list(shape))
+        net = CnnVtl(input_shape=[args.batch] + list(shape), dtype=args.encoder_dtype)
         if args.weights:
             net.load_alexnet_npy(args.weights)
         describe = lambda fs: describe_cnn_vtl(fs, net, as_int8=args.metric == "distance")

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 11
+#define DLC_ABI_VERSION 12
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -53,7 +53,8 @@ typedef enum dlc_dtype {
     DLC_F16 = 1,
     DLC_F32 = 2,
     DLC_F64 = 3,
-    DLC_I8 = 4
+    DLC_I8 = 4,
+    DLC_U8 = 5                 /* 8-bit pixels as cv2.imread returns them (dlc_cnnvtl_encode_split) */
 } dlc_dtype;
 
 typedef enum dlc_act {
@@ -306,6 +307,56 @@ int dlc_conv2d_nhwc_f64_stats(dlc_ctx* ctx, const double* x, int64_t n, int h, i
 int dlc_quant_gather_i8(dlc_ctx* ctx, const double* const* segs, const int64_t* seg_sizes, int n_segs,
                         int64_t n, const int64_t* cols, int64_t n_cols, const uint64_t* keys, double* minmax,
                         int8_t* out, void* stream);
+
+/*
+ * CnnVtl.transform in the same TOLERANCE mode on the 16-bit matrix cores (opt-in; the fp64 calls above stay the parity mode
+ * and the default): conv1..conv5 of src/cnn_vtl/network/cnn_vtl.py:33-93 with every operand carried as two fp16 pieces of a
+ * power-of-two multiple of its value and each convolution computed as three v_mfma_f32_16x16x32_f16 products per 32-deep
+ * k-slice into fp32 accumulators (csrc/gemm_split_f16.hip), bias and ReLU in fp32, fp32 activations between the layers,
+ * max-pool on the fp32 values.  Weights carry one exponent per layer; activations ONE EXPONENT PER FRAME AND LAYER, from
+ * that frame's own max |x| of the layer's input (pixels are fed as 0..255 -- create_distance_matrix.py:23,27 -- and ReLU
+ * outputs are unbounded), so a frame's descriptor is bit-identical whatever batch it is encoded in.  The quantisation is
+ * the reference's fp64 formula on the promoted fp32 features (cnn_vtl.py:108-128: per-frame min / max, (d - min) * (255 /
+ * (max - min)), truncation, wrap modulo 256, column gather).
+ * What a caller may rely on: every layer within the derived elementwise bound of
+ * tests/conv_precision_bounds.py; end to end, measured on an MI355X against the fp64 oracle with seeded 1/sqrt(fan_in)
+ * weights (tests/test_gpu_cnn_vtl_f16x2.py): features within 5e-7 of the frame's range, scaled values within 2.9e-4 of a
+ * quantisation step (CPU emulation, scripts/emul_cnn_split.py: 2.0e-4), i.e. bytes that equal the fp64 mode's except where
+ * the fp64 scaled value lies within the tests' window of 1.6e-3 steps of an integer, where they may differ by one step
+ * (1 of 6 714 gathered bytes did; 0.0012 %% of all bytes over 1063 frames).  NOT byte parity, and no guarantee that a
+ * nearest-neighbour list built on the bytes equals the fp64 mode's.  Zero-class hazard: about 47 %% of a frame's features are exact ReLU zeros sharing
+ * ONE scaled value (0 - min) * 255 / (max - min); a frame for which that value lies within the mode's error of an integer can
+ * have close to half of its bytes move by one step at once (a few frames in 10 000).
+ * Accepted input: finite values (no [-16, 16] restriction: the per-frame exponent absorbs the range; fp64 frames are
+ * rounded to fp32 first, uint8 pixels are exact).  A non-finite value in a layer's input sets bit 0 of *status, one in a
+ * layer's output bit 1 (DEVICE int32 the caller zeroes; calls OR into it): the bytes of such a call are undefined.
+ *   geom   HOST int32 [n_layers][11]: kh, kw, cin, cout, stride, pad_top, pad_left, oh, ow, act (DLC_ACT_NONE / _RELU),
+ *          pool (1: tf.layers.max_pooling2d 3x3 / 2 VALID behind the layer); at most 8 layers;
+ *   dlc_cnnvtl_split_prepare   once per set of weights: W[l] DEVICE fp64 [kh*kw*cin, cout] (the HWIO kernel; W a HOST array)
+ *                              -> panels (DEVICE, dlc_cnnvtl_split_panels_bytes(), 256-byte aligned);
+ *   dlc_cnnvtl_encode_split    frames x [n, h, w, c] (DEVICE; dtype DLC_F64, DLC_F32 or DLC_U8), n <= 65535, -> out int8
+ *                              [n, n_cols] (cols as in dlc_minmax_quant_gather_i8, indices into the concatenated layer
+ *                              outputs).  s2d > 1: layer 0's geometry describes the stride-1 convolution over the
+ *                              space-to-depth(s2d) input [h / s2d, w / s2d, s2d * s2d * c] (dlc_space_to_depth_nhwc_f64) and
+ *                              the frames are rearranged on the way in.  b: HOST array of DEVICE fp64 biases (entries or
+ *                              b itself may be NULL).  feats (may be NULL, entries too): DEVICE fp32 [n, oh, ow, cout] per
+ *                              layer that receives the layer's pre-quantisation output.
+ *                              Workspace: dlc_cnnvtl_encode_split_workspace_bytes(n, h / s2d, w / s2d, s2d * s2d * c, ...);
+ *   dlc_cnnvtl_layers_split    debug / test entry: layers layer_a .. layer_b on x = layer_a's fp32 input (the [h, w, c] given
+ *                              are LAYER 0's input, the workspace is the encode call's); feats[l - layer_a] receives layer l.
+ * All are stream-ordered.
+ */
+size_t dlc_cnnvtl_split_panels_bytes(int n_layers, const int32_t* geom);
+int dlc_cnnvtl_split_prepare(dlc_ctx* ctx, int n_layers, const int32_t* geom, const double* const* W, void* panels,
+                             size_t panels_bytes, void* stream);
+size_t dlc_cnnvtl_encode_split_workspace_bytes(int64_t n, int h, int w, int c, int n_layers, const int32_t* geom);
+int dlc_cnnvtl_encode_split(dlc_ctx* ctx, int dtype, const void* x, int64_t n, int h, int w, int c, int s2d, int n_layers,
+                            const int32_t* geom, const void* panels, const double* const* b, const int64_t* cols,
+                            int64_t n_cols, int8_t* out, float* const* feats, int32_t* status, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int dlc_cnnvtl_layers_split(dlc_ctx* ctx, const float* x, int64_t n, int h, int w, int c, int n_layers, const int32_t* geom,
+                            int layer_a, int layer_b, const void* panels, const double* const* b, float* const* feats,
+                            int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- match: reference semantics --------------------------------------- */
 /*

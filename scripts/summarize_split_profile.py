@@ -15,12 +15,13 @@ with open(os.path.join(src, "stats", "sp_kernel_stats.csv")) as f, open(os.path.
 import subprocess
 out = {"tag": tag, "commit": subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=root, capture_output=True, text=True).stdout.strip(),
        "command": "rocprofv3 --kernel-trace [--stats | --pmc ... (separate passes)] -- python3 scripts/prof_sdav_split.py",
-       "workload": "SDAV.transform(dtype='f16x2') of 1063 frames: 4 launches of gemm_split_f16_kernel<false> + 1 of <true> per call",
+       "workload": "SDAV.transform(dtype='f16x2') of 1063 frames: 4 launches of gemm_split_f16_kernel<0> (hidden; <false> in profiles taken before the kernel had a convolution mode) + 1 of <1> (final; <true>) per call",
        "kernels": {}}
 for row in csv.DictReader(open(os.path.join(src, "stats", "sp_kernel_stats.csv"))):
     for k in KERNELS:
         if k in row["Name"]:
-            name = k + ("<final>" if "<true>" in row["Name"] else ("<hidden>" if "<false>" in row["Name"] else ""))
+            name = k + ("<final>" if ("<true>" in row["Name"] or "kernel<1>" in row["Name"]) else
+                        ("<hidden>" if ("<false>" in row["Name"] or "kernel<0>" in row["Name"]) else ""))
             out["kernels"][name] = {"calls": int(row["Calls"]), "avg_ns": float(row["AverageNs"])}
 pmc = collections.defaultdict(lambda: collections.defaultdict(float))
 n = collections.defaultdict(set)
@@ -29,7 +30,7 @@ for sub in ("pmc_sq", "pmc_fetch", "pmc_write"):
     if not os.path.exists(path):
         continue
     for r in csv.DictReader(open(path)):
-        if "gemm_split_f16_kernel<false>" in r["Kernel_Name"]:
+        if "gemm_split_f16_kernel<false>" in r["Kernel_Name"] or "gemm_split_f16_kernel<0>" in r["Kernel_Name"]:
             pmc[sub][r["Counter_Name"]] += float(r["Counter_Value"])
             n[sub].add(r["Dispatch_Id"])
 k = out["kernels"].get("gemm_split_f16_kernel<hidden>")
