@@ -1,0 +1,427 @@
+// Sequence-consistent loop search (the trajectory search of SeqSLAM, Milford & Wyeth, ICRA 2012) over a dense score
+// matrix, with the selection fused: dlc_sequence_topk (include/dlc.h).  The score of cell (r, j) along slope v is the sum
+// of L frame scores on a line through it, M[r - s][j - off[v][s]], s = 0 .. L-1, added in that order; the cell's score is
+// the best valid slope's, and a row's answer its k best cells.
+//
+//   scan   one workgroup per (block of rb output rows, slab of columns).  It walks the slab in tiles of ct columns; per
+//          tile the (rb + L - 1) x (ct + max offset) window of the matrix is staged ONCE in LDS as fp64 / int64 (elements
+//          outside the matrix or past their row's limit as NaN, so that a float sum through one is not valid without a
+//          test per element), and every slope of every cell is formed from it: the rows come from HBM (rb + L - 1) / rb
+//          times, not L x slopes times.  A wave owns rows w, w + 4, ... of the block and takes 64 columns at a time; a
+//          cell that beats the row's k-th best so far is inserted into the row's sorted list, which sits in the wave's
+//          registers while the wave is on that row (lane i holds entries i and 64 + i; an insertion is a shift by one
+//          lane) and in LDS in between.  The slab's lists go to the workspace: [row][slab][k] entries.
+//          Tables whose window does not fit in LDS (offsets of thousands of columns) read the matrix through the caches
+//          instead: same arithmetic, same order.
+//   merge  one workgroup per output row: the k best of its slabs' sorted lists.
+//
+// An entry is two words: a KEY whose unsigned order is the order of merit (larger = better: the ordered key of the fp64
+// sum, or the biased int64 sum, complemented when lower is better) and a TAG (~column << 32 | slope; larger = lower
+// column).  Entries of a row are distinct (the column is in them), so the result does not depend on the plan.  (0, 0) is
+// the empty slot: below every entry, since a column < 2^31 leaves the tag's top bit set.
+#include "dlc_internal.h"
+
+namespace {
+
+constexpr int SQ_MAX_L = 64, SQ_MAX_SLOPES = 16;
+constexpr int SQ_SLAB_UNIT = 256;          // columns a slab is counted in
+constexpr int SQ_MAX_RB = 32;              // output rows per workgroup, at most
+constexpr int SQ_TARGET_WG = 1024;         // workgroups a scan aims for; also the cap on slabs per row
+constexpr size_t SQ_LDS_SMALL = 64 * 1024, SQ_LDS_LARGE = 150 * 1024;
+constexpr unsigned long long SQ_SIGN = 0x8000000000000000ull;
+constexpr long long SQ_NAN_BITS = 0x7ff8000000000000ll;
+
+struct SqOffsets { short o[SQ_MAX_SLOPES * SQ_MAX_L]; };          // [slope][L], by value (2 KB of the kernel's arguments)
+
+struct SqArgs {
+    const void* M;
+    long long rows, row0, n, ld, limit0, limit_step, tiles_per_slab, ld_out;
+    unsigned long long* part;              // [rows - row0][G][k][2]; NULL: no lists (dense output only)
+    void* seq_out;
+    const long long* poison;
+    int L, V, maxoff, lower, k, rb, ct, wc;
+};
+
+__host__ __device__ inline long long sq_limit(long long r, long long n, long long limit0, long long limit_step) {
+    const long long l = limit0 + r * limit_step;
+    return l < 0 ? 0 : (l > n ? n : l);
+}
+
+// (ka, ta) ranks strictly before (kb, tb)
+__device__ __forceinline__ bool sq_before(unsigned long long ka, unsigned long long ta, unsigned long long kb,
+                                          unsigned long long tb) {
+    return ka > kb || (ka == kb && ta > tb);
+}
+
+template <int DT>
+__device__ __forceinline__ unsigned long long sq_load_bits(const void* M, long long at) {
+    if (DT == DLC_F64) return (unsigned long long)__double_as_longlong(((const double*)M)[at]);
+    if (DT == DLC_F32) return (unsigned long long)__double_as_longlong((double)((const float*)M)[at]);
+    return (unsigned long long)((const long long*)M)[at];
+}
+
+template <int DT, bool STAGED>
+__global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, const SqOffsets offs) {
+    constexpr bool IS_INT = DT == DLC_I64;
+    extern __shared__ __attribute__((aligned(16))) char sq_smem[];
+    const int L = a.L, rb = a.rb, k = a.k, wc = a.wc, ct = a.ct, maxoff = a.maxoff;
+    const int wr = rb + L - 1;                                    // window rows: global rows rbase - (L-1) .. rbase + rb - 1
+    unsigned long long* win = (unsigned long long*)sq_smem;       // [wr][wc], STAGED only
+    unsigned long long* lkey = win + (STAGED ? (size_t)wr * wc : 0);   // [rb][k] the slab's lists so far
+    unsigned long long* ltag = lkey + (a.part ? (size_t)rb * k : 0);
+    int* lims = (int*)(ltag + (a.part ? (size_t)rb * k : 0));     // [wr] columns each window row offers (0: no such row)
+    int* dtab = lims + wr;                                        // [V][L] window steps s * wc + off[v][s], STAGED only
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long long rbase = a.row0 + (long long)blockIdx.x * rb;
+    const long long G = gridDim.y, g = blockIdx.y;
+    const bool poisoned = a.poison && *a.poison != 0;
+
+    for (int i = tid; i < wr; i += 256) {
+        const long long gr = rbase - (L - 1) + i;
+        lims[i] = (gr < 0 || gr >= a.rows) ? 0 : (int)sq_limit(gr, a.n, a.limit0, a.limit_step);
+    }
+    if (STAGED)
+        for (int i = tid; i < a.V * L; i += 256) dtab[i] = (i % L) * wc + (int)offs.o[i];
+    if (a.part)
+        for (int lr = w; lr < rb; lr += 4)
+            for (int i = lane; i < k; i += 64) { lkey[lr * k + i] = 0ull; ltag[lr * k + i] = 0ull; }
+    // columns this block's rows may offer: limits are linear in the row, so the largest sits at an end.  The dense output
+    // wants every column of the matrix (what is not offered is written as such).
+    const long long rlast = (rbase + rb < a.rows ? rbase + rb : a.rows) - 1;
+    const long long la = sq_limit(rbase, a.n, a.limit0, a.limit_step), lb = sq_limit(rlast, a.n, a.limit0, a.limit_step);
+    const long long colend = (a.seq_out || poisoned) ? (a.seq_out ? a.n : 0) : (la > lb ? la : lb);
+    const long long slab0 = g * a.tiles_per_slab * SQ_SLAB_UNIT;
+    const long long slab1 = slab0 + a.tiles_per_slab * SQ_SLAB_UNIT < colend ? slab0 + a.tiles_per_slab * SQ_SLAB_UNIT : colend;
+    __syncthreads();
+
+    for (long long j0 = slab0; j0 < slab1; j0 += ct) {
+        if (STAGED) {
+            __syncthreads();                                      // the previous tile's reads are done
+            for (int wrow = w; wrow < wr; wrow += 4) {
+                const long long lim = lims[wrow];
+                const long long base = (rbase - (L - 1) + wrow) * a.ld;
+                for (int cc = lane; cc < wc; cc += 64) {
+                    const long long c = j0 - maxoff + cc;
+                    unsigned long long bits = IS_INT ? 0ull : (unsigned long long)SQ_NAN_BITS;
+                    if (c >= 0 && c < lim) bits = sq_load_bits<DT>(a.M, base + c);
+                    win[(size_t)wrow * wc + cc] = bits;
+                }
+            }
+            __syncthreads();
+        }
+        for (int lr = w; lr < rb; lr += 4) {
+            const long long r = rbase + lr;
+            if (r >= a.rows) break;
+            unsigned long long e0k = 0, e0t = 0, e1k = 0, e1t = 0, kthk = 0, ktht = 0;
+            const int kl = (k - 1) & 63;
+            // lane s holds what element s of a line needs (read back with v_readlane: no memory access per element)
+            const int lv = (STAGED && IS_INT && lane < L) ? lims[lr + L - 1 - lane] : 0;
+            if (a.part) {
+                if (lane < k) { e0k = lkey[lr * k + lane]; e0t = ltag[lr * k + lane]; }
+                if (lane + 64 < k) { e1k = lkey[lr * k + lane + 64]; e1t = ltag[lr * k + lane + 64]; }
+                kthk = k <= 64 ? __shfl(e0k, kl) : __shfl(e1k, kl);
+                ktht = k <= 64 ? __shfl(e0t, kl) : __shfl(e1t, kl);
+            }
+            for (int ch = 0; ch < ct && j0 + ch < slab1; ch += 64) {
+                const int jl = ch + lane;
+                const long long j = j0 + jl;
+                const bool active = j < slab1 && !poisoned;
+                bool have = false;
+                unsigned long long bk = 0ull;
+                int bv = 0;
+                for (int v = 0; v < a.V; ++v) {
+                    const short* o = offs.o + v * L;
+                    bool ok = true;
+                    unsigned long long key;
+                    if (STAGED && !IS_INT) {
+                        const int dl = lane < L ? dtab[v * L + lane] : 0;
+                        const unsigned long long* p = win + (size_t)(lr + L - 1) * wc + jl + maxoff;
+                        auto el = [&](int t) { return __longlong_as_double((long long)p[-__builtin_amdgcn_readlane(dl, t)]); };
+                        double acc = __longlong_as_double((long long)p[0]);
+                        int s = 1;
+                        for (; s + 4 <= L; s += 4) {              // four loads in flight, the additions in order
+                            const double x0 = el(s), x1 = el(s + 1), x2 = el(s + 2), x3 = el(s + 3);
+                            acc += x0; acc += x1; acc += x2; acc += x3;
+                        }
+                        for (; s < L; ++s) acc += el(s);
+                        ok = acc == acc;
+                        key = dlc_f64_key(acc);
+                    } else if (STAGED) {
+                        const int dl = lane < L ? dtab[v * L + lane] : 0;
+                        const unsigned long long* p = win + (size_t)(lr + L - 1) * wc + jl + maxoff;
+                        auto el = [&](int t) {
+                            const int d = __builtin_amdgcn_readlane(dl, t);
+                            const int jj = (int)j - (d - t * wc);
+                            ok &= jj >= 0 && jj < __builtin_amdgcn_readlane(lv, t);
+                            return p[-d];
+                        };
+                        unsigned long long acc = 0ull;
+                        int s = 0;
+                        for (; s + 4 <= L; s += 4) acc += (el(s) + el(s + 1)) + (el(s + 2) + el(s + 3));
+                        for (; s < L; ++s) acc += el(s);
+                        key = acc ^ SQ_SIGN;
+                    } else {
+                        double facc = 0.0;
+                        unsigned long long iacc = 0ull;
+                        for (int s = 0; s < L; ++s) {
+                            const long long jj = j - o[s];
+                            const bool in = active && jj >= 0 && jj < lims[lr + L - 1 - s];
+                            ok &= in;
+                            const unsigned long long bits = in ? sq_load_bits<DT>(a.M, (r - s) * a.ld + jj)
+                                                               : (IS_INT ? 0ull : (unsigned long long)SQ_NAN_BITS);
+                            if (IS_INT) iacc += bits;
+                            else facc = s == 0 ? __longlong_as_double((long long)bits) : facc + __longlong_as_double((long long)bits);
+                        }
+                        if (!IS_INT) ok = facc == facc;
+                        key = IS_INT ? (iacc ^ SQ_SIGN) : dlc_f64_key(facc);
+                    }
+                    if (a.lower) key = ~key;
+                    if (ok && (!have || key > bk)) { have = true; bk = key; bv = v; }
+                }
+                have = have && active;
+                if (a.seq_out && j < slab1) {
+                    const unsigned long long k2 = a.lower ? ~bk : bk;
+                    const long long at = (r - a.row0) * a.ld_out + j;
+                    if (IS_INT) ((long long*)a.seq_out)[at] = have ? (long long)(k2 ^ SQ_SIGN) : -1ll;
+                    else ((double*)a.seq_out)[at] = have ? dlc_f64_unkey(k2) : __longlong_as_double(SQ_NAN_BITS);
+                }
+                if (a.part) {
+                    const unsigned long long tag = ((unsigned long long)(~(unsigned)j) << 32) | (unsigned)bv;
+                    for (unsigned long long todo = __ballot(have && sq_before(bk, tag, kthk, ktht)); todo; todo &= todo - 1) {
+                        const int src = __ffsll((long long)todo) - 1;
+                        const unsigned long long xk = __shfl(bk, src), xt = __shfl(tag, src);
+                        if (!sq_before(xk, xt, kthk, ktht)) continue;     // (the k-th has moved up since the ballot)
+                        // E'[i] = E[i] before x ? E[i] : (E[i-1] before x ? x : E[i-1]), E[i] = lane i's e0, E[64+i] its e1
+                        unsigned long long p0k = __shfl_up(e0k, 1), p0t = __shfl_up(e0t, 1);
+                        unsigned long long p1k = __shfl_up(e1k, 1), p1t = __shfl_up(e1t, 1);
+                        const unsigned long long l0k = __shfl(e0k, 63), l0t = __shfl(e0t, 63);
+                        if (lane == 0) { p1k = l0k; p1t = l0t; }
+                        const bool lo0 = lane == 0 || sq_before(p0k, p0t, xk, xt);
+                        const bool lo1 = sq_before(p1k, p1t, xk, xt);
+                        if (!sq_before(e1k, e1t, xk, xt)) { e1k = lo1 ? xk : p1k; e1t = lo1 ? xt : p1t; }
+                        if (!sq_before(e0k, e0t, xk, xt)) { e0k = lo0 ? xk : p0k; e0t = lo0 ? xt : p0t; }
+                        kthk = k <= 64 ? __shfl(e0k, kl) : __shfl(e1k, kl);
+                        ktht = k <= 64 ? __shfl(e0t, kl) : __shfl(e1t, kl);
+                    }
+                }
+            }
+            if (a.part) {
+                if (lane < k) { lkey[lr * k + lane] = e0k; ltag[lr * k + lane] = e0t; }
+                if (lane + 64 < k) { lkey[lr * k + lane + 64] = e1k; ltag[lr * k + lane + 64] = e1t; }
+            }
+        }
+    }
+    if (a.part)                                                   // (a wave writes the rows it owns: no barrier)
+        for (int lr = w; lr < rb; lr += 4) {
+            const long long r = rbase + lr;
+            if (r >= a.rows) break;
+            unsigned long long* P = a.part + (((size_t)(r - a.row0) * G + g) * k) * 2;
+            for (int i = lane; i < k; i += 64) { P[2 * i] = lkey[lr * k + i]; P[2 * i + 1] = ltag[lr * k + i]; }
+        }
+}
+
+__device__ __forceinline__ unsigned long long sq_shfl_xor_u64(unsigned long long v, int o) {
+    return ((unsigned long long)(unsigned)__shfl_xor((int)(v >> 32), o) << 32) | (unsigned)__shfl_xor((int)v, o);
+}
+
+// One workgroup per output row: k rounds of "best head of the G sorted lists".  Entries are distinct, so exactly one
+// thread holds the round's winner and advances that list.
+template <bool IS_INT>
+__global__ __launch_bounds__(256) void sequence_merge_kernel(const unsigned long long* __restrict__ part, int G, int k, int lower,
+                                                             void* __restrict__ out_scores, long long* __restrict__ out_idx,
+                                                             int* __restrict__ out_slope, const long long* __restrict__ poison) {
+    __shared__ int head[SQ_TARGET_WG];
+    __shared__ unsigned long long wk[4], wt[4];
+    const int tid = threadIdx.x;
+    const long long q = blockIdx.x;
+    if (poison && *poison != 0) {
+        for (int t = tid; t < k; t += 256) {
+            ((double*)out_scores)[q * k + t] = __longlong_as_double(SQ_NAN_BITS);
+            out_idx[q * k + t] = -1;
+            if (out_slope) out_slope[q * k + t] = -1;
+        }
+        return;
+    }
+    const unsigned long long* P = part + (size_t)q * G * k * 2;
+    for (int g = tid; g < G; g += 256) head[g] = 0;
+    __syncthreads();
+    unsigned long long bk, bt;
+    int bg;
+    auto local_best = [&]() {
+        bk = 0ull; bt = 0ull; bg = -1;
+        for (int g = tid; g < G; g += 256) {
+            const int h = head[g];
+            if (h < k) {
+                const unsigned long long vk = P[((size_t)g * k + h) * 2], vt = P[((size_t)g * k + h) * 2 + 1];
+                if (sq_before(vk, vt, bk, bt)) { bk = vk; bt = vt; bg = g; }
+            }
+        }
+    };
+    local_best();
+    for (int i = 0; i < k; ++i) {
+        unsigned long long mk = bk, mt = bt;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ok = sq_shfl_xor_u64(mk, o), ot = sq_shfl_xor_u64(mt, o);
+            if (sq_before(ok, ot, mk, mt)) { mk = ok; mt = ot; }
+        }
+        if ((tid & 63) == 0) { wk[tid >> 6] = mk; wt[tid >> 6] = mt; }
+        __syncthreads();
+        mk = wk[0]; mt = wt[0];
+        for (int ww = 1; ww < 4; ++ww)
+            if (sq_before(wk[ww], wt[ww], mk, mt)) { mk = wk[ww]; mt = wt[ww]; }
+        __syncthreads();
+        const bool none = mt == 0ull;
+        if (tid == 0) {
+            const unsigned long long k2 = lower ? ~mk : mk;
+            if (IS_INT) ((long long*)out_scores)[q * k + i] = none ? -1ll : (long long)(k2 ^ SQ_SIGN);
+            else ((double*)out_scores)[q * k + i] = none ? (lower ? INFINITY : -INFINITY) : dlc_f64_unkey(k2);
+            out_idx[q * k + i] = none ? -1ll : (long long)(~(unsigned)(mt >> 32));
+            if (out_slope) out_slope[q * k + i] = none ? -1 : (int)(mt & 0xffffffffull);
+        }
+        if (!none && bg >= 0 && bk == mk && bt == mt) {
+            ++head[bg];
+            local_best();
+        }
+    }
+}
+
+int64_t sq_slabs_cap(int64_t rows, int64_t cols) {
+    const int64_t cap = dlc::cdiv(SQ_TARGET_WG, dlc::cdiv(rows, SQ_MAX_RB));
+    const int64_t tiles = dlc::cdiv(cols, SQ_SLAB_UNIT);
+    return tiles < cap ? tiles : cap;
+}
+
+// The scan's shape for a table: rows per block, columns per tile, staged or not, LDS bytes.
+struct SqPlan { int rb, ct, staged; size_t lds; };
+SqPlan sq_plan(int64_t rows_out, int L, int n_slopes, int maxoff, int k, bool lists, int rb_cap) {
+    const size_t per_list = lists ? (size_t)k * 16 : 0, tab = (size_t)n_slopes * L * 4;
+    const int want = rows_out < 8 ? (int)rows_out : 8;            // fewer rows per block than this: try a narrower tile
+    const size_t budgets[2] = {SQ_LDS_SMALL, SQ_LDS_LARGE};
+    const int cts[3] = {256, 128, 64};
+    for (size_t budget : budgets)
+        for (int ct : cts) {
+            const size_t wc = (size_t)ct + maxoff, fixed = (size_t)(L - 1) * (wc * 8 + 4) + tab, per = wc * 8 + 4 + per_list;
+            if (budget < fixed + per * want) continue;
+            int64_t rb = (int64_t)((budget - fixed) / per);
+            if (rb > rb_cap) rb = rb_cap;
+            if (rb > rows_out) rb = rows_out;
+            if (rb >= 4) rb &= ~(int64_t)3;                       // whole rounds of the four waves
+            return {(int)rb, ct, 1, dlc::align_up(fixed + per * (size_t)rb, 16)};
+        }
+    int64_t rb = (int64_t)((SQ_LDS_SMALL - (size_t)(L - 1) * 4) / (per_list + 4));
+    if (rb > rb_cap) rb = rb_cap;
+    if (rb > rows_out) rb = rows_out;
+    return {(int)rb, 256, 0, dlc::align_up((size_t)(L - 1) * 4 + (per_list + 4) * (size_t)rb, 16)};
+}
+
+}  // namespace
+
+extern "C" size_t dlc_sequence_topk_workspace_bytes(int64_t rows, int64_t n, int L, int n_slopes, int k) {
+    if (rows < 1 || n < 1 || n > 0x7fffffffll || L < 1 || L > SQ_MAX_L || n_slopes < 1 || n_slopes > SQ_MAX_SLOPES || k < 1 ||
+        k > DLC_MAX_K)
+        return 0;
+    return dlc::align_up((size_t)rows * (size_t)sq_slabs_cap(rows, n) * (size_t)k * 16, 256);
+}
+
+extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
+                                 int64_t limit0, int64_t limit_step, int L, int n_slopes, const int32_t* offsets,
+                                 int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_slope,
+                                 void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: dtype must be DLC_F64, DLC_F32 or DLC_I64");
+    if (!scores || !offsets || rows < 1 || row0 < 0 || row0 >= rows || n < 1 || ld < n)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: bad argument");
+    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: n must be below 2^31");
+    if (L < 1 || L > SQ_MAX_L) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: L=%d outside 1..%d", L, SQ_MAX_L);
+    if (n_slopes < 1 || n_slopes > SQ_MAX_SLOPES)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: n_slopes=%d outside 1..%d", n_slopes, SQ_MAX_SLOPES);
+    const bool lists = out_scores != nullptr || out_idx != nullptr || out_slope != nullptr;
+    if (lists && (!out_scores || !out_idx))
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: out_scores and out_idx come together");
+    if (!lists && !seq_out) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: no output given");
+    if (seq_out && ld_out < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: ld_out < n");
+    if (lists && (k < 1 || k > DLC_MAX_K))
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: k=%d outside 1..%d", k, DLC_MAX_K);
+    if (poison && dtype == DLC_I64)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: the poison word marks fp64 outputs; DLC_I64 has none");
+    SqOffsets offs;
+    memset(&offs, 0, sizeof(offs));
+    int maxoff = 0;
+    for (int v = 0; v < n_slopes; ++v)
+        for (int s = 0; s < L; ++s) {
+            const int32_t o = offsets[(size_t)v * L + s];
+            if (o < 0 || o > 32767 || (s == 0 && o != 0) || (s > 0 && o < offsets[(size_t)v * L + s - 1]))
+                return dlc::fail(ctx, DLC_ERR_BAD_ARG,
+                                 "sequence_topk: offsets[%d][%d]=%d (rows start at 0, never decrease, stay within 0..32767)", v, s,
+                                 (int)o);
+            offs.o[v * L + s] = (short)o;
+            if (o > maxoff) maxoff = o;
+        }
+    const int64_t rows_out = rows - row0;
+    size_t need = 0;
+    if (lists) {
+        need = dlc_sequence_topk_workspace_bytes(rows, n, L, n_slopes, k);
+        if (!workspace || workspace_bytes < need)
+            return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sequence_topk: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0,
+                             need);
+    }
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+
+    // columns any output row offers (limits are linear in the row); the dense output covers the matrix's n columns
+    const int64_t l0 = sq_limit(row0, n, limit0, limit_step), l1 = sq_limit(rows - 1, n, limit0, limit_step);
+    const int64_t cols = seq_out ? n : (l0 > l1 ? l0 : l1);
+    int64_t G = 1, tps = 1;
+    if (cols > 0) {
+        const int64_t tiles = dlc::cdiv(cols, SQ_SLAB_UNIT);
+        G = sq_slabs_cap(rows, cols);
+        tps = dlc::cdiv(tiles, G);
+        G = dlc::cdiv(tiles, tps);
+    }
+    // a few rows (a streamed batch): smaller row blocks, down to a row per wave, until the chip has a workgroup per CU --
+    // the window's extra rows then come from L2, and a wave's serial chain of additions is what the call takes
+    int rb_cap = SQ_MAX_RB;
+    while (rb_cap > 4 && dlc::cdiv(rows_out, rb_cap) * G < 256) rb_cap /= 2;
+    const SqPlan p = sq_plan(rows_out, L, n_slopes, maxoff, lists ? k : 1, lists, rb_cap);
+    SqArgs a;
+    a.M = scores; a.rows = rows; a.row0 = row0; a.n = n; a.ld = ld; a.limit0 = limit0; a.limit_step = limit_step;
+    a.tiles_per_slab = tps; a.ld_out = ld_out; a.part = lists ? (unsigned long long*)workspace : nullptr; a.seq_out = seq_out;
+    a.poison = (const long long*)poison; a.L = L; a.V = n_slopes; a.maxoff = maxoff; a.lower = lower_is_better ? 1 : 0; a.k = lists ? k : 1;
+    a.rb = p.rb; a.ct = p.ct; a.wc = p.ct + maxoff;
+    const int64_t blocks = dlc::cdiv(rows_out, p.rb);
+    if (blocks > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sequence_topk: too many rows for one launch");
+    auto launch = [&](auto kern) -> int {
+        DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)G), dim3(256), p.lds, st, a, offs);
+        DLC_LAUNCH_CHECK(ctx, "sequence_scan_kernel");
+        return DLC_OK;
+    };
+    int rc;
+    if (p.staged) {
+        if (dtype == DLC_F64) rc = launch(sequence_scan_kernel<DLC_F64, true>);
+        else if (dtype == DLC_F32) rc = launch(sequence_scan_kernel<DLC_F32, true>);
+        else rc = launch(sequence_scan_kernel<DLC_I64, true>);
+    } else {
+        if (dtype == DLC_F64) rc = launch(sequence_scan_kernel<DLC_F64, false>);
+        else if (dtype == DLC_F32) rc = launch(sequence_scan_kernel<DLC_F32, false>);
+        else rc = launch(sequence_scan_kernel<DLC_I64, false>);
+    }
+    if (rc != DLC_OK) return rc;
+    if (lists) {
+        if (dtype == DLC_I64)
+            hipLaunchKernelGGL(sequence_merge_kernel<true>, dim3((unsigned)rows_out), dim3(256), 0, st,
+                               (const unsigned long long*)workspace, (int)G, k, a.lower, out_scores, (long long*)out_idx,
+                               (int*)out_slope, (const long long*)poison);
+        else
+            hipLaunchKernelGGL(sequence_merge_kernel<false>, dim3((unsigned)rows_out), dim3(256), 0, st,
+                               (const unsigned long long*)workspace, (int)G, k, a.lower, out_scores, (long long*)out_idx,
+                               (int*)out_slope, (const long long*)poison);
+        DLC_LAUNCH_CHECK(ctx, "sequence_merge_kernel");
+    }
+    return DLC_OK;
+}

@@ -919,6 +919,59 @@ class Engine:
                                                        _ptr(dist), _ptr(idx), _ptr(ws), ws.numel(), self._stream()))
         return dist, idx
 
+    _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
+
+    def sequence_topk(self, scores, length, offsets, k=None, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,
+                      dense=False, poison=None):
+        """The sequence search of dlc_sequence_topk (include/dlc.h) over scores [rows, >= n] (fp64, fp32 or int64 on the
+        device; a row-strided view is taken as it is): the sum of L frame scores along each line of the HOST table
+        offsets [V, L] (int32) through every cell, the best valid line per cell, and per row r >= row0 the k best cells
+        among its first clamp(limit0 + r * limit_step, 0, n) (limit0 None = n).  Returns (scores [rows - row0, k],
+        idx int64, slope int32, dense): fp64 scores (int64 for int64 input); k None -> no lists (None three times);
+        dense: the [rows - row0, n] cell scores as well (NaN / -1 where a cell is not offered), else None.
+        poison: a device int64 [1] read by the kernels; non-zero -> every fp64 slot NaN, idx and slope -1."""
+        if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype not in self._SEQ_DTYPES:
+            raise ValueError("sequence_topk: scores must be a 2-D float64, float32 or int64 tensor")
+        if scores.device != self.device:
+            raise ValueError("sequence_topk: scores must be on %s" % self.device)
+        rows = scores.shape[0]
+        n = scores.shape[1] if n is None else int(n)
+        if rows < 1 or n < 1 or n > scores.shape[1]:
+            raise ValueError("sequence_topk: scores [%d, %d] with n=%d: nothing to search" % (rows, scores.shape[1], n))
+        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
+            scores = scores.contiguous()
+        ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
+        if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
+            raise ValueError("sequence_topk: offsets must be an integer table [n_slopes, L=%d]" % int(length))
+        if not 0 <= int(row0) < rows:
+            raise ValueError("sequence_topk: row0=%d outside 0..%d" % (row0, rows - 1))
+        if k is None and not dense:
+            raise ValueError("sequence_topk: neither lists (k) nor the dense scores were asked for")
+        if k is not None and not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("sequence_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if poison is not None:
+            self._check_out("poison", poison, (1,), torch.int64)
+        out_dtype = torch.int64 if scores.dtype == torch.int64 else torch.float64
+        ro = rows - int(row0)
+        o_s = o_i = o_v = seq = ws = None
+        if k is not None:
+            o_s = torch.empty((ro, k), dtype=out_dtype, device=self.device)
+            o_i = torch.empty((ro, k), dtype=torch.int64, device=self.device)
+            o_v = torch.empty((ro, k), dtype=torch.int32, device=self.device)
+            need = self.lib.dlc_sequence_topk_workspace_bytes(rows, n, int(length), off.shape[0], int(k))
+            if need == 0:
+                raise ValueError("sequence_topk: L=%d, %d slopes, k=%d, n=%d outside the supported sizes" % (length, off.shape[0], k, n))
+            ws = self.workspace("sequence_topk", need)
+        if dense:
+            seq = torch.empty((ro, n), dtype=out_dtype, device=self.device)
+        self._check(self.lib.dlc_sequence_topk(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(length), off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(lower_is_better)),
+            1 if k is None else int(k), _ptr(o_s), _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws),
+            ws.numel() if ws is not None else 0, self._stream()))
+        return o_s, o_i, o_v, seq
+
     # ---- cosine + top-k -----------------------------------------------------------------
     @staticmethod
     def stored_width(d):

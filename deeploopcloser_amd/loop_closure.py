@@ -113,16 +113,38 @@ class SdavLoopClosureDetector:
     src/sdav/similarity/SimilarityCalculator.py:12-49) instead of the cosine of flattened descriptors: every new frame's
     [P, H] SDAV descriptors are scored against all resident frames more than `exclusion` frames older through the
     streaming filter (similarity.SimilarityStream: the older frames' panel is resident, nothing is re-quantised), and the
-    k best (score descending, ties -> the older frame) at or above `threshold` are the loop candidates."""
+    k best (score descending, ties -> the older frame) at or above `threshold` are the loop candidates.
+
+    sequence = L (None: off, every path as it is without it) asks whether the match holds over the last L frames: a pair
+    (frame t, older frame j) is scored by the sum of the L frame scores along a line through (t, j) of the score matrix,
+    the best of the lines of `slopes` (an int32 table [V, L]; default sequence.slope_offsets(L)), and the k best sums are
+    the candidates (dlc_sequence_topk, include/dlc.h; Milford & Wyeth, ICRA 2012).  The detector keeps the last L - 1 score
+    rows resident in front of each batch's rows, so the lists do not depend on how the frames were batched; frame t's
+    line may only touch scores of frames old enough for the frame that produced them (row t - s offers the frames below
+    t - s - exclusion), and a frame with fewer than L - 1 predecessors gets (-inf, -1)."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, **stream_args):
+                 device=None, sequence=None, slopes=None, **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
         if exclusion < 0:
             raise ValueError("exclusion must be >= 0")
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
+        self.sequence = None if sequence is None else int(sequence)
+        if self.sequence is None:
+            if slopes is not None:
+                raise ValueError("slopes needs sequence=L")
+        else:
+            from .sequence import slope_offsets
+            if not 1 <= self.sequence <= 64:
+                raise ValueError("sequence=%d outside 1..64" % self.sequence)
+            if not 1 <= k <= L.DLC_MAX_K:
+                raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+            self.slopes = slope_offsets(self.sequence) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
+            if self.slopes.ndim != 2 or self.slopes.shape[1] != self.sequence or not 1 <= self.slopes.shape[0] <= 16:
+                raise ValueError("slopes must be an int32 table [1..16, %d]" % self.sequence)
+            self._seq_buf = None                                      # [L - 1 + batch, ld]: the last L - 1 score rows, then the batch's
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
 
@@ -142,6 +164,10 @@ class SdavLoopClosureDetector:
             x = x.unsqueeze(0)
         b = x.shape[0]
         first = st.append(x)                                          # all B frames become resident: one quantisation launch
+        if self.sequence is not None:
+            if first + b - 1 > 0:
+                eng.sdav_stream_query_batch(st.state, st.desc, first, b, st.score, st.a, st.b, out=self._seq_rows(b), stats=st.stats)
+            return self._seq_rank(first, b)
         if first + b - 1 == 0:                                        # the very first frame alone: nothing older
             none = torch.full((b, self.k), float("-inf"), dtype=torch.float64, device=eng.device)
             return (torch.where(self.poisoned != 0, float("nan"), none),
@@ -212,11 +238,47 @@ class SdavLoopClosureDetector:
         st, eng = self.stream, self.stream.engine
         slot = self._slots[self._pending % 2]
         torch.cuda.current_stream(eng.device).wait_event(slot["products"])
-        rows = slot["rows"][:slot["b"]]
+        rows = slot["rows"][:slot["b"]] if self.sequence is None else self._seq_rows(slot["b"])
         eng.sdav_stream_query_batch_staged(st.state, st.desc, slot["first"], slot["b"], st.score, 2, rows, slot["ws"], st.a, st.b,
                                            stats=st.stats)
-        slot["out"] = eng.topk_rows_f64(rows, slot["first"] - self.exclusion, 1, self.k, poison=self.poisoned)
+        if self.sequence is None:
+            slot["out"] = eng.topk_rows_f64(rows, slot["first"] - self.exclusion, 1, self.k, poison=self.poisoned)
+        else:
+            slot["out"] = self._seq_rank(slot["first"], slot["b"])
         self._pending = None
+
+    # ---- sequence=L: the last L - 1 score rows stay resident ---------------------------------------------------------------
+    def _seq_rows(self, b):
+        """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b of the context buffer (its leading dimension is
+        the stream's capacity; re-laid, the context kept, when the stream has grown or the batch is larger than any before)."""
+        ctx, cap, buf = self.sequence - 1, self.stream.capacity, self._seq_buf
+        if buf is None or buf.shape[1] < cap or buf.shape[0] < ctx + b:
+            new = torch.empty((ctx + max(b, 0 if buf is None else buf.shape[0] - ctx), cap if buf is None else max(cap, buf.shape[1])),
+                              dtype=torch.float64, device=self.stream.engine.device)
+            if buf is not None and ctx:
+                new[:ctx, :buf.shape[1]] = buf[:ctx]
+            self._seq_buf = buf = new
+        return buf[ctx:ctx + b]
+
+    def _seq_rank(self, first, b):
+        """The lists of stream frames first .. first + b - 1, whose score rows sit behind the context rows; then the last
+        L - 1 rows become the next batch's context.  Matrix row m is stream frame first - (L - 1) + m: it offers the frames
+        below that minus the exclusion (rows of frames before the stream began offer nothing and are never read)."""
+        eng, ctx, buf = self.stream.engine, self.sequence - 1, self._seq_buf
+        if buf is None:
+            self._seq_rows(b)
+            buf = self._seq_buf
+        if first + b - 1 > 0:
+            s, i, _, _ = eng.sequence_topk(buf[:ctx + b], self.sequence, self.slopes, k=self.k, row0=ctx, n=first + b - 1,
+                                           limit0=first - ctx - self.exclusion, limit_step=1, poison=self.poisoned)
+        else:                                                         # the very first frame alone: nothing older
+            none = torch.full((b, self.k), float("-inf"), dtype=torch.float64, device=eng.device)
+            s = torch.where(self.poisoned != 0, float("nan"), none)
+            i = torch.full((b, self.k), -1, dtype=torch.int64, device=eng.device)
+        if ctx:
+            keep = buf[b:b + ctx]
+            buf[:ctx] = keep.clone() if b < ctx else keep             # (source and destination overlap for short batches)
+        return s, i
 
     def result(self, ticket):
         """(scores [B, k] float64, ids [B, k] int64) of a submitted batch, in the current stream's order."""
@@ -345,9 +407,13 @@ def main(argv=None):
     ap.add_argument("--network", choices=["sdav", "cnn_vtl"], default="cnn_vtl")
     ap.add_argument("--weights", help=".npz written by SDAV.save_weights (sdav) / AlexNet .npy blob (cnn_vtl)")
     ap.add_argument("--k", type=int, default=5)
-    ap.add_argument("--threshold", type=float, default=0.9)
-    ap.add_argument("--metric", choices=["cosine", "distance"], default="cosine",
-                    help="cosine of the descriptors, or the reference's cnn_vtl distance (needs --network cnn_vtl)")
+    ap.add_argument("--threshold", type=float, default=None,
+                    help="report candidates at or above this score (default: 0.9 for cosine, all k for similarity)")
+    ap.add_argument("--metric", choices=["cosine", "distance", "similarity"], default="cosine",
+                    help="cosine of the descriptors, the reference's cnn_vtl distance (needs --network cnn_vtl) or the "
+                         "reference's SDAV similarity (needs --network sdav; the distinctive score comes from the first batch)")
+    ap.add_argument("--sequence", type=int, default=None, metavar="L",
+                    help="--metric similarity: rank by the sum of the scores along a line of L frames (sequence search)")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
@@ -361,6 +427,14 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
+    if args.metric == "similarity" and args.network != "sdav":
+        ap.error("--metric similarity needs --network sdav")
+    if args.sequence is not None and args.metric != "similarity":
+        ap.error("--sequence needs --metric similarity")
+    if args.sequence is not None and not 1 <= args.sequence <= 64:
+        ap.error("--sequence must be 1..64")
+    if args.threshold is None:
+        args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
     files = _frame_files(args.dataset_path, args.pattern)
     from .engine import default_engine
@@ -391,7 +465,14 @@ def _stream(args, files):
         chunk = files[lo:lo + args.batch]
         t0 = time.perf_counter()
         desc = describe(chunk)
-        if det is None and args.metric == "distance":
+        if args.metric == "similarity":
+            desc = desc.view(len(chunk), net.input_shape[0], -1)         # [B, P, H]: the frames' patch descriptors
+        if det is None and args.metric == "similarity":
+            # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
+            # has only seen its first batch when it must fix it
+            det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
+                                          exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence)
+        elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))
         elif det is None:

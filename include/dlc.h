@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 12
+#define DLC_ABI_VERSION 13
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -54,7 +54,8 @@ typedef enum dlc_dtype {
     DLC_F32 = 2,
     DLC_F64 = 3,
     DLC_I8 = 4,
-    DLC_U8 = 5                 /* 8-bit pixels as cv2.imread returns them (dlc_cnnvtl_encode_split) */
+    DLC_U8 = 5,                /* 8-bit pixels as cv2.imread returns them (dlc_cnnvtl_encode_split) */
+    DLC_I64 = 6                /* int64 score / distance matrices (dlc_sequence_topk)               */
 } dlc_dtype;
 
 typedef enum dlc_act {
@@ -526,6 +527,46 @@ int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int
                              int64_t limit0, int64_t limit_step, int k,
                              int64_t* out_dist, int64_t* out_idx,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- match: sequence-consistent search over a score matrix (not in the reference) ----------- */
+/*
+ * The trajectory search of SeqSLAM (Milford & Wyeth, ICRA 2012) over a dense score matrix -- rows of
+ * dlc_sdav_stream_query_batch, dlc_sdav_similarity_matrix (fp64 or int64) or dlc_cnnvtl_distance_matrix -- with the
+ * selection fused: "does the match of query frame r with key-frame j hold over the last L frames?".
+ * INPUT.  M = scores [rows, ld], n <= ld columns in use, dtype DLC_F64, DLC_F32 or DLC_I64.  Row r offers its first
+ * lim(r) = clamp(limit0 + r * limit_step, 0, n) entries (the convention of dlc_topk_rows_f64 and
+ * dlc_cnnvtl_distance_topk).  offsets: a HOST table [n_slopes, L] of int32, off[v][0] = 0, non-decreasing in s,
+ * 0 <= off <= 32767 (anything else: DLC_ERR_BAD_ARG); it is read during the call and may be freed on return.
+ * SEQUENCE SCORE of cell (r, j) along slope v:
+ *     Z_v(r, j) = M[r][j - off[v][0]] + M[r-1][j - off[v][1]] + ... + M[r-L+1][j - off[v][L-1]],
+ * added left to right in that order, in fp64 for DLC_F64 / DLC_F32 (the conversion is exact) and in int64 (wrapping)
+ * for DLC_I64: the sums are reproducible bit for bit, and exact on integers.  Z_v(r, j) is VALID when r - (L-1) >= 0,
+ * j < lim(r) and every element read satisfies 0 <= j - off[v][s] < lim(r - s); a NaN sum (a NaN element, +inf + -inf)
+ * is not valid.
+ * CELL SCORE.  S(r, j) = the best valid Z_v -- the maximum, or the minimum when lower_is_better is set; the winning
+ * slope is the lowest v that attains it; a cell with no valid slope is not offered.  fp64 values are compared as
+ * dlc_topk_rows_f64 compares them (the order of the numbers, -0.0 below +0.0).
+ * OUTPUT for rows row0 <= r < rows (rows below row0 are context only: how a streamed batch sees the L - 1 rows before
+ * it): the k best offered cells of the row, best first, ties -> the lower j.  out_scores [rows - row0, k] fp64 (int64
+ * for DLC_I64), out_idx int64, out_slope int32 (may be NULL); the slots past the offered count hold index -1, slope -1
+ * and the score -inf (+inf if lower_is_better) / -1 for DLC_I64.  seq_out [rows - row0, ld_out] (may be NULL; same type
+ * as out_scores; ld_out >= n) receives S itself in its first n columns, NaN / -1 where a cell is not offered.  At least
+ * one of (out_scores + out_idx) and seq_out must be given; without the lists k, workspace and out_slope are not used.
+ * poison (device, may be NULL; DLC_ERR_BAD_ARG with DLC_I64): the word of dlc_topk_rows_f64 -- non-zero turns every
+ * fp64 slot into (NaN, -1, slope -1) and seq_out into NaN.
+ * Limits: 1 <= L <= 64, 1 <= n_slopes <= 16, 1 <= k <= DLC_MAX_K, any rows, 0 <= row0 < rows, n < 2^31.
+ * With L = 1 and one slope the lists equal dlc_topk_rows_f64 on the same rows bit for bit.
+ * Two launches on `stream` (a scan over (row block x column slab) that keeps per-row running lists, then a merge; no
+ * [rows, n] intermediate unless seq_out asks for it); never synchronises.  Workspace:
+ * dlc_sequence_topk_workspace_bytes(rows, n, L, n_slopes, k) bytes (0 = bad arguments), 256-byte aligned.  The outputs
+ * and the workspace must not overlap the matrix or each other.
+ */
+size_t dlc_sequence_topk_workspace_bytes(int64_t rows, int64_t n, int L, int n_slopes, int k);
+int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
+                      int64_t limit0, int64_t limit_step, int L, int n_slopes, const int32_t* offsets,
+                      int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_slope,
+                      void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
+                      void* stream);
 
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
