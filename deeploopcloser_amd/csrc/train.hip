@@ -233,9 +233,10 @@ __global__ __launch_bounds__(256) void salt_kernel(const double* __restrict__ ze
 
 // x_tilde[r, c] = x[r, c] * m0[r, c] + m1[r, c]    (DenoisingAutoencoderVariant.py:201-202: masks of the whole flat batch)
 // out has pitch ldo >= cols, its columns cols .. ldo - 1 written as zeros (mask_rows_kernel's form, for the LDS-DMA GEMM)
-__global__ __launch_bounds__(256) void corrupt_rows_kernel(const double* __restrict__ x, const double* __restrict__ m0,
+// x and out carry no __restrict__: out may be x itself where ldo == cols (element e is read and written by one thread)
+__global__ __launch_bounds__(256) void corrupt_rows_kernel(const double* x, const double* __restrict__ m0,
                                                            const double* __restrict__ m1, long long rows, long long cols,
-                                                           double* __restrict__ out, long long ldo) {
+                                                           double* out, long long ldo) {
     const long long total = rows * ldo;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const long long r = e / ldo, c = e - r * ldo;
@@ -772,6 +773,8 @@ extern "C" int dlc_da_corrupt_f64(dlc_ctx* ctx, const double* x, const double* z
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!x || !zeros || !ones || !out || rows < 1 || cols < 1 || ldo < cols)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_corrupt: bad argument");
+    if (out == x && ldo != cols)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_corrupt: in place (out == x) needs ldo == cols");
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipLaunchKernelGGL(corrupt_rows_kernel, dim3(grid_for(rows * ldo)), dim3(256), 0, (hipStream_t)stream, x, zeros, ones,

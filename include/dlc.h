@@ -177,8 +177,10 @@ int dlc_salt_pepper_mask_f64(dlc_ctx* ctx, double* zeros, double* ones, int64_t 
                              uint64_t counter, void* stream);
 /*
  * x~ = zeros * x + ones (DenoisingAutoencoderVariant.py:201-202), elementwise over x [rows, cols] (pitch cols) and the
- * two masks of the same shape, into out [rows, ldo] (ldo >= cols; columns cols .. ldo - 1 written as zeros).  Give
- * dlc_da_train_step an even ldo: cols + (cols & 1).
+ * two masks of the same shape, into out [rows, ldo] (ldo >= cols; columns cols .. ldo - 1 written as zeros; nothing
+ * outside out[0 .. rows*ldo - 1] is written).  Give dlc_da_train_step an even ldo: cols + (cols & 1).
+ * out may be x itself where ldo == cols (in place); out == x at another pitch is DLC_ERR_BAD_ARG, and out must not
+ * overlap x in any other way, nor the masks.
  */
 int dlc_da_corrupt_f64(dlc_ctx* ctx, const double* x, const double* zeros, const double* ones, int64_t rows, int64_t cols,
                        double* out, int64_t ldo, void* stream);

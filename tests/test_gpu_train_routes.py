@@ -50,33 +50,12 @@ import numpy as np
 import pytest
 import torch
 
+from train_route_checks import assert_loss_parts, assert_step_delta    # (shared with test_gpu_da_train_routes.py)
+
 pytestmark = pytest.mark.gpu
 
 REAL = (1681,) + (2500,) * 5
 DEFAULT_HP = dict(sparse_level=0.05, sparse_penalty=1.0, consecutive_penalty=0.2)
-
-
-def step_delta_ratio(before, after, dref):
-    """max |(after - before) - dREF| / max |dREF| over one tensor."""
-    before, after, dref = (np.asarray(a, dtype=np.float64) for a in (before, after, dref))
-    scale = float(np.abs(dref).max())
-    assert scale > 0.0, "the oracle does not move this tensor: nothing to compare"
-    return float(np.abs((after - before) - dref).max()) / scale
-
-
-def assert_step_delta(before, after, dref, bound=1e-9, what=""):
-    """The change a step made to one parameter tensor is the oracle's change to within `bound` of its largest entry."""
-    r = step_delta_ratio(before, after, dref)
-    assert r <= bound, "%s: |dGPU - dREF| / max|dREF| = %.3g > %.0e" % (what, r, bound)
-    return r
-
-
-def assert_loss_parts(got, want, rel=1e-10, cc_floor=0.0):
-    """{loss, cd, cs, cc}, each against its own oracle value.  cc_floor: an absolute allowance for cc alone (see
-    CC_FLOOR)."""
-    for name, g, w in zip(("loss", "cd", "cs", "cc"), np.asarray(got), want):
-        tol = rel * abs(w) + (cc_floor if name == "cc" else 0.0)
-        assert abs(g - w) <= tol, "%s: %.17g vs %.17g" % (name, g, w)
 
 
 def problem(dims, patches, batch, seed, scale="fan_in"):
