@@ -8,11 +8,13 @@ include/dlc.h, with the reference's Python call surface on top:
     CnnVtl                        (src/cnn_vtl/network)
     CvInputParser                 (src/sdav/input; key-points supplied by the caller)
     SimilarityCalculator          (src/sdav/similarity; + SimilarityStream: one new frame against the resident ones)
-    DistanceCalculator            (src/cnn_vtl/similarity; + CnnVtlKeyframeDatabase: k nearest by that distance)
+    DistanceCalculator            (src/cnn_vtl/similarity; + distance_rows: a rectangular set of pairs in one call;
+                                   + CnnVtlKeyframeDatabase: k nearest by that distance, or the distance rows themselves)
     MathUtils                     (src/utils/MathUtils.py)
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
     sequence_topk / sequence_scores / slope_offsets   (sequence-consistent search over a score matrix; new)
+    LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; the last two take sequence=L)
 
 Importing the package is cheap and works without a GPU; constructing any of
 the classes needs libdlc_hip.so and a visible MI355X and raises otherwise.

@@ -11,30 +11,12 @@
 // Key of a (query, row) pair: (distance << 32) | row.  Ascending keys are the required order (distance ascending,
 // ties -> the lower row) and every key is distinct, so the result is the same however the rows were split.  An empty
 // slot is ~0.  No floating point anywhere: the result is exact.
-#include "gemm_internal.h"
+#include "distance_tile.h"
 
 namespace {
 
-constexpr int TK_CH = 64;                  // descriptor bytes per step (16 words)
-constexpr int TK_W = TK_CH / 4;
 constexpr int TK_TARGET_WG = 1024;         // workgroups a scan aims for; also the cap on slabs per query tile
 constexpr unsigned long long TK_EMPTY = ~0ull;
-
-// The three tile shapes (NTX threads across db rows, 256 / NTX across queries; QR queries x 4 db rows per thread).
-struct TkPlan {
-    int ntx, qr;
-    int qt() const { return (256 / ntx) * qr; }   // queries per tile
-    int db() const { return ntx * 4; }            // db rows per tile
-};
-
-// Few queries get a tall tile (every thread's 4 db rows against the same one or four queries: the query operand is an
-// LDS broadcast); many get the matrix kernel's 64 x 64.  Ties in padded work go to the larger query tile (fewer passes
-// over the db).
-TkPlan tk_plan(int64_t Q) {
-    if (Q <= 4) return {64, 1};
-    const int64_t big = dlc::cdiv(Q, 64) * 64, mid = dlc::cdiv(Q, 16) * 16;
-    return big <= mid ? TkPlan{16, 4} : TkPlan{64, 4};
-}
 
 int64_t tk_slabs_cap(const TkPlan& p, int64_t Q, int64_t rows) {
     const int64_t qtiles = dlc::cdiv(Q, p.qt());
@@ -45,30 +27,6 @@ int64_t tk_slabs_cap(const TkPlan& p, int64_t Q, int64_t rows) {
 
 size_t tk_lds_bytes(const TkPlan& p, int k) {
     return (size_t)p.qt() * (size_t)(k + p.db() + 1) * 8 + (size_t)p.qt() * 4;
-}
-
-__device__ __forceinline__ int64_t tk_limit(int64_t r, int64_t N, int64_t limit0, int64_t limit_step) {
-    const int64_t l = limit0 + r * limit_step;
-    return l < 0 ? 0 : (l > N ? N : l);
-}
-
-// 16 bytes of a row at byte k (a multiple of 16) as four words; bytes at and past D read as zero (the row's padding may
-// hold anything).  A 16-byte aligned block that holds byte k < D lies inside the row's allocation.
-__device__ __forceinline__ u32x4_t tk_load16(const int8_t* row, long long k, long long D) {
-    u32x4_t v = {0u, 0u, 0u, 0u};
-    if (k < D) {
-        v = *(const u32x4_t*)(row + k);
-        const long long left = D - k;
-        if (left < 16) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const long long lw = left - 4 * w;
-                const unsigned mask = lw >= 4 ? 0xffffffffu : (lw <= 0 ? 0u : ((1u << (8 * (int)lw)) - 1u));
-                v[w] &= mask;
-            }
-        }
-    }
-    return v;
 }
 
 template <int NTX, int QR>

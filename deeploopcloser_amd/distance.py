@@ -57,13 +57,26 @@ class DistanceCalculator:
             raise ValueError("descriptors must be [N, D] int8")
         return e.cnnvtl_distance_matrix(d).cpu().numpy()
 
+    @staticmethod
+    def distance_rows(queries, descriptors):
+        """The per-pair loop for a rectangular set of pairs: calculate_distance(queries[r], descriptors[j]) for every
+        r and j as one call (dlc_cnnvtl_distance_rows) -> numpy int64 [Q, N]."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int8))
+        x = np.ascontiguousarray(np.asarray(descriptors, dtype=np.int8))
+        if q.ndim != 2 or x.ndim != 2 or q.shape[1] != x.shape[1]:
+            raise ValueError("distance_rows: queries [Q, D] and descriptors [N, D] with one D")
+        e = default_engine()
+        return e.cnnvtl_distance_rows(e.to_device(q, torch.int8), e.to_device(x, torch.int8)).cpu().numpy()
+
 
 class CnnVtlKeyframeDatabase:
     """cnn_vtl key-frame descriptors (int8 [n, dim]) resident in HBM, searched by the reference's distance.
 
     Rows are stored zero-padded to a multiple of 16 bytes (the top-k kernel's row alignment) in a capacity-reserved
     buffer that doubles when an append() outgrows it; `rows` is the view of the first len(db) rows.  nearest() is
-    dlc_cnnvtl_distance_topk: distance ascending, ties -> the lower id, (-1, -1) past the rows there are."""
+    dlc_cnnvtl_distance_topk: distance ascending, ties -> the lower id, (-1, -1) past the rows there are; distances() is
+    dlc_cnnvtl_distance_rows: the [Q, len(db)] distances themselves, for callers that rank them another way (the
+    sequence search)."""
 
     FORMAT = "dlc-cnnvtl-keyframes-v1"
 
@@ -145,6 +158,19 @@ class CnnVtlKeyframeDatabase:
             raise ValueError("nearest: queries must be [Q, %d] int8" % self.dim)
         return self.engine.cnnvtl_distance_topk(q, self.rows, int(k), d=self.dim,
                                                 limit0=self._n if limit0 is None else limit0, limit_step=limit_step)
+
+    def distances(self, queries, limit0=None, limit_step=0, out=None):
+        """int64 [Q, len(self)] on the device: the reference's distance of each query row to every stored key-frame, as
+        rows (dlc_cnnvtl_distance_rows).  queries: [Q, dim] int8, or stored rows [Q, stored_width(dim)] such as a slice
+        of `rows` (the padding is ignored).  limit0 / limit_step: query r is written in its first limit0 + r * limit_step cells only (default: all); the others
+        keep what `out` held (a caller-kept int64 [Q, len(self)] tensor or row-strided view), or hold -1 when the result
+        is allocated here."""
+        q = self.engine.to_device(queries)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.dtype != torch.int8 or q.shape[1] not in (self.dim, self._store.shape[1]):
+            raise ValueError("distances: queries must be [Q, %d] int8" % self.dim)
+        return self.engine.cnnvtl_distance_rows(q, self.rows, d=self.dim, limit0=limit0, limit_step=limit_step, out=out)
 
     # ---- on-disk format: one .npz ------------------------------------------------------------------------------------
     def save(self, path):

@@ -919,6 +919,48 @@ class Engine:
                                                        _ptr(dist), _ptr(idx), _ptr(ws), ws.numel(), self._stream()))
         return dist, idx
 
+    def cnnvtl_distance_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
+        """int64 [Q, N]: the cnn_vtl distance of every query row of q [Q, D] int8 to the rows of db [N, D] int8
+        (dlc_cnnvtl_distance_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r * limit_step,
+        0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1 -- "not offered",
+        as sequence_scores writes it -- when the engine allocates the result.  d: the descriptor length when the rows
+        are padded (the bytes past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows
+        lie further apart than N (its columns past N are left alone too)."""
+        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
+            raise ValueError("cnnvtl_distance_rows: q and db must be 2-D int8")
+        if q.device != self.device or db.device != self.device:
+            raise ValueError("cnnvtl_distance_rows: q and db must be on %s" % self.device)
+        if d is None:
+            if q.shape[1] != db.shape[1]:
+                raise ValueError("cnnvtl_distance_rows: q and db widths differ (%d, %d)" % (q.shape[1], db.shape[1]))
+            d = q.shape[1]
+        d = int(d)
+        if d > q.shape[1] or d > db.shape[1]:
+            raise ValueError("cnnvtl_distance_rows: d=%d exceeds the rows' width" % d)
+        nq, n = q.shape[0], db.shape[0]
+        if out is None:
+            out = torch.empty((nq, n), dtype=torch.int64, device=self.device)
+            if limit0 is not None:
+                out.fill_(-1)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (nq, n) or out.dtype != torch.int64 or \
+                out.device != self.device or (n > 1 and out.stride(1) != 1) or (nq > 1 and out.stride(0) < n):
+            raise ValueError("cnnvtl_distance_rows: out must be an int64 tensor of shape (%d, %d) on %s with unit column "
+                             "stride and rows at least %d apart" % (nq, n, self.device, n))
+        if nq == 0 or n == 0:
+            return out
+        if d == 0:                                               # empty descriptors: every distance is 0
+            lim = (n if limit0 is None else int(limit0)) + int(limit_step) * torch.arange(nq, device=self.device)
+            out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
+            return out
+        q = self._rows16(q, d)
+        db = self._rows16(db, d)
+        ld_out = out.stride(0) if nq > 1 else n
+        self._check(self.lib.dlc_cnnvtl_distance_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
+                                                       n if limit0 is None else int(limit0), int(limit_step), _ptr(out),
+                                                       ld_out, self._stream()))
+        self._wrote(out)
+        return out
+
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
 
     def sequence_topk(self, scores, length, offsets, k=None, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,

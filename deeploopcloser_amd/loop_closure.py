@@ -108,6 +108,38 @@ class LoopClosureDetector:
         return out
 
 
+class _SequenceRows:
+    """The resident score rows of a detector with sequence=L: a [L - 1 + batch, ld] buffer of `dtype` whose first L - 1
+    rows are the context -- the score rows of the L - 1 frames before the batch -- and whose next rows receive the
+    batch's.  ld is the store's capacity, so a row never moves while the store does not grow."""
+
+    def __init__(self, length, dtype):
+        self.context, self.dtype, self.buf = int(length) - 1, dtype, None
+
+    def batch_rows(self, b, capacity, device):
+        """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b (the buffer is re-laid, the context kept, when
+        the store has grown past its leading dimension or the batch is larger than any before)."""
+        ctx, buf = self.context, self.buf
+        if buf is None or buf.shape[1] < capacity or buf.shape[0] < ctx + b:
+            new = torch.empty((ctx + max(b, 0 if buf is None else buf.shape[0] - ctx),
+                               capacity if buf is None else max(capacity, buf.shape[1])), dtype=self.dtype, device=device)
+            if buf is not None and ctx:
+                new[:ctx, :buf.shape[1]] = buf[:ctx]
+            self.buf = buf = new
+        return buf[ctx:ctx + b]
+
+    def window(self, b):
+        """The context rows and the batch's b rows behind them: what the sequence search reads."""
+        return self.buf[:self.context + b]
+
+    def advance(self, b):
+        """The last L - 1 rows of the window become the next batch's context."""
+        ctx, buf = self.context, self.buf
+        if ctx:
+            keep = buf[b:b + ctx]
+            buf[:ctx] = keep.clone() if b < ctx else keep             # (source and destination overlap for short batches)
+
+
 class SdavLoopClosureDetector:
     """The same question asked with the REFERENCE's similarity (SimilarityCalculator.similarity_score,
     src/sdav/similarity/SimilarityCalculator.py:12-49) instead of the cosine of flattened descriptors: every new frame's
@@ -144,7 +176,7 @@ class SdavLoopClosureDetector:
             self.slopes = slope_offsets(self.sequence) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
             if self.slopes.ndim != 2 or self.slopes.shape[1] != self.sequence or not 1 <= self.slopes.shape[0] <= 16:
                 raise ValueError("slopes must be an int32 table [1..16, %d]" % self.sequence)
-            self._seq_buf = None                                      # [L - 1 + batch, ld]: the last L - 1 score rows, then the batch's
+            self._seq = _SequenceRows(self.sequence, torch.float64)   # the last L - 1 score rows, then the batch's
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
 
@@ -249,35 +281,25 @@ class SdavLoopClosureDetector:
 
     # ---- sequence=L: the last L - 1 score rows stay resident ---------------------------------------------------------------
     def _seq_rows(self, b):
-        """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b of the context buffer (its leading dimension is
-        the stream's capacity; re-laid, the context kept, when the stream has grown or the batch is larger than any before)."""
-        ctx, cap, buf = self.sequence - 1, self.stream.capacity, self._seq_buf
-        if buf is None or buf.shape[1] < cap or buf.shape[0] < ctx + b:
-            new = torch.empty((ctx + max(b, 0 if buf is None else buf.shape[0] - ctx), cap if buf is None else max(cap, buf.shape[1])),
-                              dtype=torch.float64, device=self.stream.engine.device)
-            if buf is not None and ctx:
-                new[:ctx, :buf.shape[1]] = buf[:ctx]
-            self._seq_buf = buf = new
-        return buf[ctx:ctx + b]
+        """Where the next batch's b score rows go: behind the context rows (_SequenceRows; the leading dimension is the
+        stream's capacity)."""
+        return self._seq.batch_rows(b, self.stream.capacity, self.stream.engine.device)
 
     def _seq_rank(self, first, b):
         """The lists of stream frames first .. first + b - 1, whose score rows sit behind the context rows; then the last
         L - 1 rows become the next batch's context.  Matrix row m is stream frame first - (L - 1) + m: it offers the frames
         below that minus the exclusion (rows of frames before the stream began offer nothing and are never read)."""
-        eng, ctx, buf = self.stream.engine, self.sequence - 1, self._seq_buf
-        if buf is None:
+        eng, seq = self.stream.engine, self._seq
+        if seq.buf is None:
             self._seq_rows(b)
-            buf = self._seq_buf
         if first + b - 1 > 0:
-            s, i, _, _ = eng.sequence_topk(buf[:ctx + b], self.sequence, self.slopes, k=self.k, row0=ctx, n=first + b - 1,
-                                           limit0=first - ctx - self.exclusion, limit_step=1, poison=self.poisoned)
+            s, i, _, _ = eng.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b - 1,
+                                           limit0=first - seq.context - self.exclusion, limit_step=1, poison=self.poisoned)
         else:                                                         # the very first frame alone: nothing older
             none = torch.full((b, self.k), float("-inf"), dtype=torch.float64, device=eng.device)
             s = torch.where(self.poisoned != 0, float("nan"), none)
             i = torch.full((b, self.k), -1, dtype=torch.int64, device=eng.device)
-        if ctx:
-            keep = buf[b:b + ctx]
-            buf[:ctx] = keep.clone() if b < ctx else keep             # (source and destination overlap for short batches)
+        seq.advance(b)
         return s, i
 
     def result(self, ticket):
@@ -318,9 +340,18 @@ class CnnVtlLoopClosureDetector:
     descriptor is compared with all resident frames more than `exclusion` frames older, and the k nearest (distance
     ascending, ties -> the older frame) at or below `max_distance` (all of them when None) are the loop candidates.
     A batch of B frames is one top-k launch: frame first + r sees the frames below first + r - exclusion
-    (dlc_cnnvtl_distance_topk with limit_step = 1), so the lists do not depend on how the frames are batched."""
+    (dlc_cnnvtl_distance_topk with limit_step = 1), so the lists do not depend on how the frames are batched.
 
-    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None):
+    sequence = L (None: off, every path as it is without it -- the fused top-k, no distance rows are formed) asks
+    whether the match holds over the last L frames, as SdavLoopClosureDetector(sequence=L) does for the similarity: a pair
+    (frame t, older frame j) is scored by the SUM of the L frame distances along a line through (t, j) of the distance
+    matrix, the smallest over the lines of `slopes` (an int32 table [1..16, L]; default sequence.slope_offsets(L)), and the
+    k smallest sums are the candidates (dlc_cnnvtl_distance_rows into a resident int64 buffer that keeps the last L - 1
+    rows, then dlc_sequence_topk with lower_is_better).  The lists do not depend on the batching; a frame with fewer than
+    L - 1 predecessors gets (-1, -1).  max_distance is then compared with the sequence sum -- L distances, not one -- as the
+    SDAV detector's threshold is with its sum of scores."""
+
+    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -331,6 +362,18 @@ class CnnVtlLoopClosureDetector:
             raise ValueError("dim and capacity must be positive")
         self.k, self.exclusion = int(k), int(exclusion)
         self.max_distance = None if max_distance is None else int(max_distance)
+        self.sequence = None if sequence is None else int(sequence)
+        if self.sequence is None:
+            if slopes is not None:
+                raise ValueError("slopes needs sequence=L")
+        else:
+            from .sequence import slope_offsets
+            if not 1 <= self.sequence <= 64:
+                raise ValueError("sequence=%d outside 1..64" % self.sequence)
+            self.slopes = slope_offsets(self.sequence) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
+            if self.slopes.ndim != 2 or self.slopes.shape[1] != self.sequence or not 1 <= self.slopes.shape[0] <= 16:
+                raise ValueError("slopes must be an int32 table [1..16, %d]" % self.sequence)
+            self._seq = _SequenceRows(self.sequence, torch.int64)    # the last L - 1 distance rows, then the batch's
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -340,18 +383,32 @@ class CnnVtlLoopClosureDetector:
     def query_and_insert(self, descriptors):
         """The next B frames' int8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (dist [B, k] int64,
         ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
-        key-frames afterwards."""
+        key-frames afterwards.  With sequence=L dist is the sum of the L distances along the best line."""
         db = self.db
         x = db.engine.to_device(descriptors)
         if x.dim() == 1:
             x = x.unsqueeze(0)
         first, _ = db.append(x)
         b = x.shape[0]
-        return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
-                                              limit0=first - self.exclusion, limit_step=1)
+        if self.sequence is None:
+            return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
+                                                  limit0=first - self.exclusion, limit_step=1)
+        if b == 0:
+            none = torch.empty((0, self.k), dtype=torch.int64, device=db.engine.device)
+            return none, none.clone()
+        # frame first + r against the frames below first + r - exclusion, as rows behind the L - 1 rows before them; matrix
+        # row m is frame first - (L - 1) + m (rows of frames before the stream began offer nothing and are never read)
+        seq = self._seq
+        db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
+                     out=seq.batch_rows(b, db.capacity, db.engine.device)[:, :first + b])
+        s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b,
+                                             limit0=first - seq.context - self.exclusion, limit_step=1, lower_is_better=True)
+        seq.advance(b)
+        return s, i
 
     def loops(self, dist, ids, first_id):
-        """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance."""
+        """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance (with sequence=L: the
+        sum of the L distances along the candidate's line)."""
         d, i = dist.cpu().numpy(), ids.cpu().numpy()
         lim = self.max_distance
         return [(first_id + r, int(i[r, c]), int(d[r, c])) for r in range(d.shape[0]) for c in range(d.shape[1])

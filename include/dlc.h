@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 13
+#define DLC_ABI_VERSION 14
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -529,12 +529,34 @@ int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int
                              int64_t limit0, int64_t limit_step, int k,
                              int64_t* out_dist, int64_t* out_idx,
                              void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The same distance as rows: out[r * ld_out + j] = sum_k popcount(|q_r[k] ^ db_j[k]|) of query row r of queries [Q, D]
+ * (row stride ldq) against row j of db [N, D] (row stride ldd), written for 0 <= j < lim(r) with
+ * lim(r) = clamp(limit0 + r * limit_step, 0, N) -- the limit convention of dlc_cnnvtl_distance_topk, dlc_topk_rows_f64
+ * and dlc_sequence_topk; any limit_step, negative included.  limit_step = 0, limit0 = N: the full [Q, N] block;
+ * limit_step = 1: a batch of streamed frames, each seeing one frame more than the one before.
+ * EVERY OTHER WORD OF out KEEPS ITS VALUE: the cells at or past lim(r) and the columns N .. ld_out-1 (what
+ * dlc_sdav_stream_query_batch promises for its rows: a caller's context buffer, or its "not offered" fill, survives
+ * the call).  When every lim(r) is 0 nothing is launched and the call returns DLC_OK.
+ * out is int64 [Q, ld_out], ld_out >= N: the type dlc_sequence_topk(DLC_I64) and dlc_cnnvtl_distance_matrix use.
+ * Rows as in dlc_cnnvtl_distance_topk: both bases 16-byte aligned, ldq and ldd multiples of 16 bytes (>= D); bytes
+ * D .. ld-1 of a row may hold anything and change nothing; queries may be rows of db itself (both are only read); out
+ * must not overlap the operands.  D <= 2^28 (int32 sums), N < 2^32, Q <= 2^20.
+ * No workspace; one launch on `stream` (one workgroup per query tile x db tile below the largest lim(r), the tile
+ * shapes of the top-k scan, plain 8-byte stores: no memset, no atomics); never synchronises.  Integers throughout: the
+ * result is exact and does not depend on the plan, nor on how the queries are batched.
+ */
+int dlc_cnnvtl_distance_rows(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int64_t ldq,
+                             const int8_t* db, int64_t N, int64_t ldd, int64_t D,
+                             int64_t limit0, int64_t limit_step,
+                             int64_t* out, int64_t ld_out, void* stream);
 
 /* ---- match: sequence-consistent search over a score matrix (not in the reference) ----------- */
 /*
  * The trajectory search of SeqSLAM (Milford & Wyeth, ICRA 2012) over a dense score matrix -- rows of
- * dlc_sdav_stream_query_batch, dlc_sdav_similarity_matrix (fp64 or int64) or dlc_cnnvtl_distance_matrix -- with the
- * selection fused: "does the match of query frame r with key-frame j hold over the last L frames?".
+ * dlc_sdav_stream_query_batch, dlc_sdav_similarity_matrix (fp64 or int64), dlc_cnnvtl_distance_matrix or
+ * dlc_cnnvtl_distance_rows (a streamed batch's rows behind the L - 1 rows before it) -- with the selection fused:
+ * "does the match of query frame r with key-frame j hold over the last L frames?".
  * INPUT.  M = scores [rows, ld], n <= ld columns in use, dtype DLC_F64, DLC_F32 or DLC_I64.  Row r offers its first
  * lim(r) = clamp(limit0 + r * limit_step, 0, n) entries (the convention of dlc_topk_rows_f64 and
  * dlc_cnnvtl_distance_topk).  offsets: a HOST table [n_slopes, L] of int32, off[v][0] = 0, non-decreasing in s,
