@@ -28,13 +28,13 @@ __global__ __launch_bounds__(256) void distance_rows_kernel(const int8_t* __rest
     const long long q0 = (long long)blockIdx.y * QT;
     // rows this tile's queries may see: limits are linear in the query row, so the largest sits at an end
     const long long qlast = (q0 + QT < Q ? q0 + QT : Q) - 1;
-    const long long la = tk_limit(q0, N, limit0, limit_step), lb = tk_limit(qlast, N, limit0, limit_step);
+    const long long la = dlc::row_limit(q0, N, limit0, limit_step), lb = dlc::row_limit(qlast, N, limit0, limit_step);
     const long long lmax = la > lb ? la : lb;
     long long lq[QR];
 #pragma unroll
     for (int r = 0; r < QR; ++r) {
         const long long q = q0 + ty + NTY * r;
-        lq[r] = q < Q ? tk_limit(q, N, limit0, limit_step) : 0;
+        lq[r] = q < Q ? dlc::row_limit(q, N, limit0, limit_step) : 0;
     }
     for (long long j0 = (long long)blockIdx.x * DB; j0 < lmax; j0 += (long long)gridDim.x * DB) {
         u32x4_t va[PA], vb[PB];
@@ -131,7 +131,7 @@ extern "C" int dlc_cnnvtl_distance_rows(dlc_ctx* ctx, const int8_t* queries, int
     const int64_t qtiles = dlc::cdiv(Q, p.qt());
     if (qtiles > 65535) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_rows: Q must not exceed 2^20");
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t l0 = tk_limit(0, N, limit0, limit_step), l1 = tk_limit(Q - 1, N, limit0, limit_step);
+    const int64_t l0 = dlc::row_limit(0, N, limit0, limit_step), l1 = dlc::row_limit(Q - 1, N, limit0, limit_step);
     const int64_t lmax = l0 > l1 ? l0 : l1;
     if (lmax == 0) return DLC_OK;
     dlc::DeviceGuard guard(ctx->device);

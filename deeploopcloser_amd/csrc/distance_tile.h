@@ -1,5 +1,5 @@
 // What the two cnn_vtl distance kernels over (query tile x db tile) share: distance_topk.hip (the fused k-nearest scan)
-// and distance_rows.hip (the rectangular distance rows).  The tile shapes, the row limit and the masked 16-byte load.
+// and distance_rows.hip (the rectangular distance rows).  The tile shapes and the masked 16-byte load.
 #pragma once
 #include "gemm_internal.h"
 
@@ -22,11 +22,6 @@ inline TkPlan tk_plan(int64_t Q) {
     if (Q <= 4) return {64, 1};
     const int64_t big = dlc::cdiv(Q, 64) * 64, mid = dlc::cdiv(Q, 16) * 16;
     return big <= mid ? TkPlan{16, 4} : TkPlan{64, 4};
-}
-
-__host__ __device__ __forceinline__ int64_t tk_limit(int64_t r, int64_t N, int64_t limit0, int64_t limit_step) {
-    const int64_t l = limit0 + r * limit_step;
-    return l < 0 ? 0 : (l > N ? N : l);
 }
 
 // 16 bytes of a row at byte k (a multiple of 16) as four words; bytes at and past D read as zero (the row's padding may

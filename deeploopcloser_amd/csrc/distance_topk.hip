@@ -12,18 +12,11 @@
 // ties -> the lower row) and every key is distinct, so the result is the same however the rows were split.  An empty
 // slot is ~0.  No floating point anywhere: the result is exact.
 #include "distance_tile.h"
+#include "topk_list.h"
 
 namespace {
 
-constexpr int TK_TARGET_WG = 1024;         // workgroups a scan aims for; also the cap on slabs per query tile
 constexpr unsigned long long TK_EMPTY = ~0ull;
-
-int64_t tk_slabs_cap(const TkPlan& p, int64_t Q, int64_t rows) {
-    const int64_t qtiles = dlc::cdiv(Q, p.qt());
-    const int64_t cap = dlc::cdiv(TK_TARGET_WG, qtiles);
-    const int64_t tiles = dlc::cdiv(rows, p.db());
-    return tiles < cap ? tiles : cap;
-}
 
 size_t tk_lds_bytes(const TkPlan& p, int k) {
     return (size_t)p.qt() * (size_t)(k + p.db() + 1) * 8 + (size_t)p.qt() * 4;
@@ -54,13 +47,13 @@ __global__ __launch_bounds__(256) void distance_topk_scan_kernel(const int8_t* _
 
     // rows this tile's queries may see: limits are linear in the query row, so the largest sits at an end
     const long long qlast = (q0 + QT < Q ? q0 + QT : Q) - 1;
-    const long long la = tk_limit(q0, N, limit0, limit_step), lb = tk_limit(qlast, N, limit0, limit_step);
+    const long long la = dlc::row_limit(q0, N, limit0, limit_step), lb = dlc::row_limit(qlast, N, limit0, limit_step);
     const long long lmax = la > lb ? la : lb;
     long long lq[QR];
 #pragma unroll
     for (int r = 0; r < QR; ++r) {
         const long long q = q0 + ty + NTY * r;
-        lq[r] = q < Q ? tk_limit(q, N, limit0, limit_step) : 0;
+        lq[r] = q < Q ? dlc::row_limit(q, N, limit0, limit_step) : 0;
     }
     const long long slab0 = g * tiles_per_slab * DB;
     const long long slab1 = slab0 + tiles_per_slab * DB < lmax ? slab0 + tiles_per_slab * DB : lmax;
@@ -174,51 +167,15 @@ __global__ __launch_bounds__(256) void distance_topk_scan_kernel(const int8_t* _
     }
 }
 
-__device__ __forceinline__ unsigned long long tk_min_u64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-
-// One workgroup per query: k rounds of "smallest head of the G sorted lists".  Keys are distinct (the row is in them),
-// so exactly one thread holds the round's minimum and advances that list.
+// One workgroup per query: the k smallest keys of its G sorted lists.
 __global__ __launch_bounds__(256) void distance_topk_merge_kernel(const unsigned long long* __restrict__ part, int G, int k,
                                                                   long long* __restrict__ out_dist,
                                                                   long long* __restrict__ out_idx) {
-    __shared__ int head[TK_TARGET_WG];
-    __shared__ unsigned long long wmin[4];
-    const int tid = threadIdx.x;
     const long long q = blockIdx.x;
-    const unsigned long long* P = part + (size_t)q * G * k;
-    for (int g = tid; g < G; g += 256) head[g] = 0;
-    __syncthreads();
-    auto local_best = [&](int& bg) {
-        unsigned long long best = TK_EMPTY;
-        bg = -1;
-        for (int g = tid; g < G; g += 256) {
-            const int h = head[g];
-            if (h < k) {
-                const unsigned long long v = P[(size_t)g * k + h];
-                if (v < best) { best = v; bg = g; }
-            }
-        }
-        return best;
-    };
-    int bg;
-    unsigned long long best = local_best(bg);
-    for (int i = 0; i < k; ++i) {
-        unsigned long long m = best;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = tk_min_u64(m, __shfl_xor(m, off));
-        if ((tid & 63) == 0) wmin[tid >> 6] = m;
-        __syncthreads();
-        m = tk_min_u64(tk_min_u64(wmin[0], wmin[1]), tk_min_u64(wmin[2], wmin[3]));
-        __syncthreads();
-        if (tid == 0) {
-            out_dist[q * k + i] = m == TK_EMPTY ? -1 : (long long)(m >> 32);
-            out_idx[q * k + i] = m == TK_EMPTY ? -1 : (long long)(m & 0xffffffffull);
-        }
-        if (m != TK_EMPTY && best == m) {
-            ++head[bg];
-            best = local_best(bg);
-        }
-    }
+    tl_merge_slabs<TlWord>(part + (size_t)q * G * k, G, k, [&](int i, TlWord m) {
+        out_dist[q * k + i] = m.is_empty() ? -1 : (long long)(m.v >> 32);
+        out_idx[q * k + i] = m.is_empty() ? -1 : (long long)(m.v & 0xffffffffull);
+    });
 }
 
 }  // namespace
@@ -226,7 +183,8 @@ __global__ __launch_bounds__(256) void distance_topk_merge_kernel(const unsigned
 extern "C" size_t dlc_cnnvtl_distance_topk_workspace_bytes(int64_t Q, int64_t N, int64_t D, int k) {
     if (Q < 1 || N < 1 || D < 1 || k < 1 || k > DLC_MAX_K) return 0;
     const TkPlan p = tk_plan(Q);
-    return dlc::align_up((size_t)Q * (size_t)tk_slabs_cap(p, Q, N) * (size_t)k * 8, 256);
+    const int64_t slabs = dlc::max_slabs(dlc::cdiv(Q, p.qt()), dlc::cdiv(N, p.db()), TL_MAX_SLABS);
+    return dlc::align_up((size_t)Q * (size_t)slabs * (size_t)k * 8, 256);
 }
 
 extern "C" int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int64_t ldq, const int8_t* db,
@@ -250,22 +208,20 @@ extern "C" int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int
     hipStream_t st = (hipStream_t)stream;
 
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    auto lim = [&](int64_t r) { const int64_t l = limit0 + r * limit_step; return l < 0 ? 0 : (l > N ? N : l); };
-    const int64_t lmax = lim(0) > lim(Q - 1) ? lim(0) : lim(Q - 1);
+    const int64_t l0 = dlc::row_limit(0, N, limit0, limit_step), l1 = dlc::row_limit(Q - 1, N, limit0, limit_step);
+    const int64_t lmax = l0 > l1 ? l0 : l1;
     const TkPlan p = tk_plan(Q);
-    int64_t G = 0, tps = 0;
+    int64_t G = 0;
     if (lmax > 0) {
-        const int64_t tiles = dlc::cdiv(lmax, p.db());
-        G = tk_slabs_cap(p, Q, lmax);
-        tps = dlc::cdiv(tiles, G);
-        G = dlc::cdiv(tiles, tps);
         const int64_t qtiles = dlc::cdiv(Q, p.qt());
+        const dlc::SlabSplit slabs = dlc::split_slabs(qtiles, dlc::cdiv(lmax, p.db()), TL_MAX_SLABS);
+        G = slabs.G;
         const size_t lds = tk_lds_bytes(p, k);
         auto launch = [&](auto kern) -> int {
             DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(kern, dim3((unsigned)qtiles, (unsigned)G), dim3(256), lds, st, queries, (long long)Q,
                                (long long)ldq, db, (long long)N, (long long)ldd, (long long)D, (long long)limit0,
-                               (long long)limit_step, k, (long long)tps, (unsigned long long*)workspace);
+                               (long long)limit_step, k, (long long)slabs.tiles_per_slab, (unsigned long long*)workspace);
             DLC_LAUNCH_CHECK(ctx, "distance_topk_scan_kernel");
             return DLC_OK;
         };

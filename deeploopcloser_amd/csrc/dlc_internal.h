@@ -92,6 +92,24 @@ inline int profiled(dlc_ctx* ctx, hipStream_t st, F&& launch) {
 __host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Columns row r of a selection may see, of n: linear in the row, so over a range of rows the largest sits at one end.
+__host__ __device__ __forceinline__ int64_t row_limit(int64_t r, int64_t n, int64_t limit0, int64_t limit_step) {
+    const int64_t l = limit0 + r * limit_step;
+    return l < 0 ? 0 : (l > n ? n : l);
+}
+
+// A scan's column tiles shared out among G slabs so that row_tiles x G comes to about max_wg workgroups.  max_slabs
+// bounds G for every smaller col_tiles too (the split's own G is not monotonic in col_tiles): it sizes the workspace.
+struct SlabSplit { int64_t G, tiles_per_slab; };
+inline int64_t max_slabs(int64_t row_tiles, int64_t col_tiles, int64_t max_wg) {
+    const int64_t cap = cdiv(max_wg, row_tiles);
+    return col_tiles < cap ? col_tiles : cap;
+}
+inline SlabSplit split_slabs(int64_t row_tiles, int64_t col_tiles, int64_t max_wg) {
+    const int64_t tps = cdiv(col_tiles, max_slabs(row_tiles, col_tiles, max_wg));
+    return {cdiv(col_tiles, tps), tps};
+}
+
 // RAII-free device guard: the C ABI is re-entrant per context and each context
 // is bound to one device.
 struct DeviceGuard {

@@ -19,14 +19,13 @@
 // sum, or the biased int64 sum, complemented when lower is better) and a TAG (~column << 32 | slope; larger = lower
 // column).  Entries of a row are distinct (the column is in them), so the result does not depend on the plan.  (0, 0) is
 // the empty slot: below every entry, since a column < 2^31 leaves the tag's top bit set.
-#include "dlc_internal.h"
+#include "topk_list.h"
 
 namespace {
 
 constexpr int SQ_MAX_L = 64, SQ_MAX_SLOPES = 16;
 constexpr int SQ_SLAB_UNIT = 256;          // columns a slab is counted in
 constexpr int SQ_MAX_RB = 32;              // output rows per workgroup, at most
-constexpr int SQ_TARGET_WG = 1024;         // workgroups a scan aims for; also the cap on slabs per row
 constexpr size_t SQ_LDS_SMALL = 64 * 1024, SQ_LDS_LARGE = 150 * 1024;
 constexpr unsigned long long SQ_SIGN = 0x8000000000000000ull;
 constexpr long long SQ_NAN_BITS = 0x7ff8000000000000ll;
@@ -41,17 +40,6 @@ struct SqArgs {
     const long long* poison;
     int L, V, maxoff, lower, k, rb, ct, wc;
 };
-
-__host__ __device__ inline long long sq_limit(long long r, long long n, long long limit0, long long limit_step) {
-    const long long l = limit0 + r * limit_step;
-    return l < 0 ? 0 : (l > n ? n : l);
-}
-
-// (ka, ta) ranks strictly before (kb, tb)
-__device__ __forceinline__ bool sq_before(unsigned long long ka, unsigned long long ta, unsigned long long kb,
-                                          unsigned long long tb) {
-    return ka > kb || (ka == kb && ta > tb);
-}
 
 template <int DT>
 __device__ __forceinline__ unsigned long long sq_load_bits(const void* M, long long at) {
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
 
     for (int i = tid; i < wr; i += 256) {
         const long long gr = rbase - (L - 1) + i;
-        lims[i] = (gr < 0 || gr >= a.rows) ? 0 : (int)sq_limit(gr, a.n, a.limit0, a.limit_step);
+        lims[i] = (gr < 0 || gr >= a.rows) ? 0 : (int)dlc::row_limit(gr, a.n, a.limit0, a.limit_step);
     }
     if (STAGED)
         for (int i = tid; i < a.V * L; i += 256) dtab[i] = (i % L) * wc + (int)offs.o[i];
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
     // columns this block's rows may offer: limits are linear in the row, so the largest sits at an end.  The dense output
     // wants every column of the matrix (what is not offered is written as such).
     const long long rlast = (rbase + rb < a.rows ? rbase + rb : a.rows) - 1;
-    const long long la = sq_limit(rbase, a.n, a.limit0, a.limit_step), lb = sq_limit(rlast, a.n, a.limit0, a.limit_step);
+    const long long la = dlc::row_limit(rbase, a.n, a.limit0, a.limit_step), lb = dlc::row_limit(rlast, a.n, a.limit0, a.limit_step);
     const long long colend = (a.seq_out || poisoned) ? (a.seq_out ? a.n : 0) : (la > lb ? la : lb);
     const long long slab0 = g * a.tiles_per_slab * SQ_SLAB_UNIT;
     const long long slab1 = slab0 + a.tiles_per_slab * SQ_SLAB_UNIT < colend ? slab0 + a.tiles_per_slab * SQ_SLAB_UNIT : colend;
@@ -113,16 +101,11 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
         for (int lr = w; lr < rb; lr += 4) {
             const long long r = rbase + lr;
             if (r >= a.rows) break;
-            unsigned long long e0k = 0, e0t = 0, e1k = 0, e1t = 0, kthk = 0, ktht = 0;
-            const int kl = (k - 1) & 63;
+            WaveList<TlPair> wl;
+            wl.clear();
             // lane s holds what element s of a line needs (read back with v_readlane: no memory access per element)
             const int lv = (STAGED && IS_INT && lane < L) ? lims[lr + L - 1 - lane] : 0;
-            if (a.part) {
-                if (lane < k) { e0k = lkey[lr * k + lane]; e0t = ltag[lr * k + lane]; }
-                if (lane + 64 < k) { e1k = lkey[lr * k + lane + 64]; e1t = ltag[lr * k + lane + 64]; }
-                kthk = k <= 64 ? __shfl(e0k, kl) : __shfl(e1k, kl);
-                ktht = k <= 64 ? __shfl(e0t, kl) : __shfl(e1t, kl);
-            }
+            if (a.part) wl.load(k, lane, [&](int i) { return TlPair{lkey[lr * k + i], ltag[lr * k + i]}; });
             for (int ch = 0; ch < ct && j0 + ch < slab1; ch += 64) {
                 const int jl = ch + lane;
                 const long long j = j0 + jl;
@@ -187,29 +170,14 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
                     else ((double*)a.seq_out)[at] = have ? dlc_f64_unkey(k2) : __longlong_as_double(SQ_NAN_BITS);
                 }
                 if (a.part) {
-                    const unsigned long long tag = ((unsigned long long)(~(unsigned)j) << 32) | (unsigned)bv;
-                    for (unsigned long long todo = __ballot(have && sq_before(bk, tag, kthk, ktht)); todo; todo &= todo - 1) {
-                        const int src = __ffsll((long long)todo) - 1;
-                        const unsigned long long xk = __shfl(bk, src), xt = __shfl(tag, src);
-                        if (!sq_before(xk, xt, kthk, ktht)) continue;     // (the k-th has moved up since the ballot)
-                        // E'[i] = E[i] before x ? E[i] : (E[i-1] before x ? x : E[i-1]), E[i] = lane i's e0, E[64+i] its e1
-                        unsigned long long p0k = __shfl_up(e0k, 1), p0t = __shfl_up(e0t, 1);
-                        unsigned long long p1k = __shfl_up(e1k, 1), p1t = __shfl_up(e1t, 1);
-                        const unsigned long long l0k = __shfl(e0k, 63), l0t = __shfl(e0t, 63);
-                        if (lane == 0) { p1k = l0k; p1t = l0t; }
-                        const bool lo0 = lane == 0 || sq_before(p0k, p0t, xk, xt);
-                        const bool lo1 = sq_before(p1k, p1t, xk, xt);
-                        if (!sq_before(e1k, e1t, xk, xt)) { e1k = lo1 ? xk : p1k; e1t = lo1 ? xt : p1t; }
-                        if (!sq_before(e0k, e0t, xk, xt)) { e0k = lo0 ? xk : p0k; e0t = lo0 ? xt : p0t; }
-                        kthk = k <= 64 ? __shfl(e0k, kl) : __shfl(e1k, kl);
-                        ktht = k <= 64 ? __shfl(e0t, kl) : __shfl(e1t, kl);
+                    const TlPair cand = {bk, ((unsigned long long)(~(unsigned)j) << 32) | (unsigned)bv};
+                    for (unsigned long long todo = __ballot(have && cand.before(wl.kth)); todo; todo &= todo - 1) {
+                        const TlPair x = cand.shfl(__ffsll((long long)todo) - 1);
+                        if (x.before(wl.kth)) wl.insert(x, k, lane);      // (the k-th may have moved up since the ballot)
                     }
                 }
             }
-            if (a.part) {
-                if (lane < k) { lkey[lr * k + lane] = e0k; ltag[lr * k + lane] = e0t; }
-                if (lane + 64 < k) { lkey[lr * k + lane + 64] = e1k; ltag[lr * k + lane + 64] = e1t; }
-            }
+            if (a.part) wl.store(k, lane, [&](int i, TlPair e) { lkey[lr * k + i] = e.key; ltag[lr * k + i] = e.tag; });
         }
     }
     if (a.part)                                                   // (a wave writes the rows it owns: no barrier)
@@ -221,76 +189,28 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
         }
 }
 
-__device__ __forceinline__ unsigned long long sq_shfl_xor_u64(unsigned long long v, int o) {
-    return ((unsigned long long)(unsigned)__shfl_xor((int)(v >> 32), o) << 32) | (unsigned)__shfl_xor((int)v, o);
-}
-
-// One workgroup per output row: k rounds of "best head of the G sorted lists".  Entries are distinct, so exactly one
-// thread holds the round's winner and advances that list.
+// One workgroup per output row: the k best of its G sorted lists, decoded.
 template <bool IS_INT>
 __global__ __launch_bounds__(256) void sequence_merge_kernel(const unsigned long long* __restrict__ part, int G, int k, int lower,
                                                              void* __restrict__ out_scores, long long* __restrict__ out_idx,
                                                              int* __restrict__ out_slope, const long long* __restrict__ poison) {
-    __shared__ int head[SQ_TARGET_WG];
-    __shared__ unsigned long long wk[4], wt[4];
-    const int tid = threadIdx.x;
     const long long q = blockIdx.x;
     if (poison && *poison != 0) {
-        for (int t = tid; t < k; t += 256) {
+        for (int t = threadIdx.x; t < k; t += 256) {
             ((double*)out_scores)[q * k + t] = __longlong_as_double(SQ_NAN_BITS);
             out_idx[q * k + t] = -1;
             if (out_slope) out_slope[q * k + t] = -1;
         }
         return;
     }
-    const unsigned long long* P = part + (size_t)q * G * k * 2;
-    for (int g = tid; g < G; g += 256) head[g] = 0;
-    __syncthreads();
-    unsigned long long bk, bt;
-    int bg;
-    auto local_best = [&]() {
-        bk = 0ull; bt = 0ull; bg = -1;
-        for (int g = tid; g < G; g += 256) {
-            const int h = head[g];
-            if (h < k) {
-                const unsigned long long vk = P[((size_t)g * k + h) * 2], vt = P[((size_t)g * k + h) * 2 + 1];
-                if (sq_before(vk, vt, bk, bt)) { bk = vk; bt = vt; bg = g; }
-            }
-        }
-    };
-    local_best();
-    for (int i = 0; i < k; ++i) {
-        unsigned long long mk = bk, mt = bt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok = sq_shfl_xor_u64(mk, o), ot = sq_shfl_xor_u64(mt, o);
-            if (sq_before(ok, ot, mk, mt)) { mk = ok; mt = ot; }
-        }
-        if ((tid & 63) == 0) { wk[tid >> 6] = mk; wt[tid >> 6] = mt; }
-        __syncthreads();
-        mk = wk[0]; mt = wt[0];
-        for (int ww = 1; ww < 4; ++ww)
-            if (sq_before(wk[ww], wt[ww], mk, mt)) { mk = wk[ww]; mt = wt[ww]; }
-        __syncthreads();
-        const bool none = mt == 0ull;
-        if (tid == 0) {
-            const unsigned long long k2 = lower ? ~mk : mk;
-            if (IS_INT) ((long long*)out_scores)[q * k + i] = none ? -1ll : (long long)(k2 ^ SQ_SIGN);
-            else ((double*)out_scores)[q * k + i] = none ? (lower ? INFINITY : -INFINITY) : dlc_f64_unkey(k2);
-            out_idx[q * k + i] = none ? -1ll : (long long)(~(unsigned)(mt >> 32));
-            if (out_slope) out_slope[q * k + i] = none ? -1 : (int)(mt & 0xffffffffull);
-        }
-        if (!none && bg >= 0 && bk == mk && bt == mt) {
-            ++head[bg];
-            local_best();
-        }
-    }
-}
-
-int64_t sq_slabs_cap(int64_t rows, int64_t cols) {
-    const int64_t cap = dlc::cdiv(SQ_TARGET_WG, dlc::cdiv(rows, SQ_MAX_RB));
-    const int64_t tiles = dlc::cdiv(cols, SQ_SLAB_UNIT);
-    return tiles < cap ? tiles : cap;
+    tl_merge_slabs<TlPair>(part + (size_t)q * G * k * 2, G, k, [&](int i, TlPair m) {
+        const bool none = m.is_empty();
+        const unsigned long long k2 = lower ? ~m.key : m.key;
+        if (IS_INT) ((long long*)out_scores)[q * k + i] = none ? -1ll : (long long)(k2 ^ SQ_SIGN);
+        else ((double*)out_scores)[q * k + i] = none ? (lower ? INFINITY : -INFINITY) : dlc_f64_unkey(k2);
+        out_idx[q * k + i] = none ? -1ll : (long long)(~(unsigned)(m.tag >> 32));
+        if (out_slope) out_slope[q * k + i] = none ? -1 : (int)(m.tag & 0xffffffffull);
+    });
 }
 
 // The scan's shape for a table: rows per block, columns per tile, staged or not, LDS bytes.
@@ -322,7 +242,8 @@ extern "C" size_t dlc_sequence_topk_workspace_bytes(int64_t rows, int64_t n, int
     if (rows < 1 || n < 1 || n > 0x7fffffffll || L < 1 || L > SQ_MAX_L || n_slopes < 1 || n_slopes > SQ_MAX_SLOPES || k < 1 ||
         k > DLC_MAX_K)
         return 0;
-    return dlc::align_up((size_t)rows * (size_t)sq_slabs_cap(rows, n) * (size_t)k * 16, 256);
+    const int64_t slabs = dlc::max_slabs(dlc::cdiv(rows, SQ_MAX_RB), dlc::cdiv(n, SQ_SLAB_UNIT), TL_MAX_SLABS);
+    return dlc::align_up((size_t)rows * (size_t)slabs * (size_t)k * 16, 256);
 }
 
 extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
@@ -374,15 +295,11 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
     hipStream_t st = (hipStream_t)stream;
 
     // columns any output row offers (limits are linear in the row); the dense output covers the matrix's n columns
-    const int64_t l0 = sq_limit(row0, n, limit0, limit_step), l1 = sq_limit(rows - 1, n, limit0, limit_step);
+    const int64_t l0 = dlc::row_limit(row0, n, limit0, limit_step), l1 = dlc::row_limit(rows - 1, n, limit0, limit_step);
     const int64_t cols = seq_out ? n : (l0 > l1 ? l0 : l1);
-    int64_t G = 1, tps = 1;
-    if (cols > 0) {
-        const int64_t tiles = dlc::cdiv(cols, SQ_SLAB_UNIT);
-        G = sq_slabs_cap(rows, cols);
-        tps = dlc::cdiv(tiles, G);
-        G = dlc::cdiv(tiles, tps);
-    }
+    dlc::SlabSplit slabs = {1, 1};
+    if (cols > 0) slabs = dlc::split_slabs(dlc::cdiv(rows, SQ_MAX_RB), dlc::cdiv(cols, SQ_SLAB_UNIT), TL_MAX_SLABS);
+    const int64_t G = slabs.G;
     // a few rows (a streamed batch): smaller row blocks, down to a row per wave, until the chip has a workgroup per CU --
     // the window's extra rows then come from L2, and a wave's serial chain of additions is what the call takes
     int rb_cap = SQ_MAX_RB;
@@ -390,7 +307,7 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
     const SqPlan p = sq_plan(rows_out, L, n_slopes, maxoff, lists ? k : 1, lists, rb_cap);
     SqArgs a;
     a.M = scores; a.rows = rows; a.row0 = row0; a.n = n; a.ld = ld; a.limit0 = limit0; a.limit_step = limit_step;
-    a.tiles_per_slab = tps; a.ld_out = ld_out; a.part = lists ? (unsigned long long*)workspace : nullptr; a.seq_out = seq_out;
+    a.tiles_per_slab = slabs.tiles_per_slab; a.ld_out = ld_out; a.part = lists ? (unsigned long long*)workspace : nullptr; a.seq_out = seq_out;
     a.poison = (const long long*)poison; a.L = L; a.V = n_slopes; a.maxoff = maxoff; a.lower = lower_is_better ? 1 : 0; a.k = lists ? k : 1;
     a.rb = p.rb; a.ct = p.ct; a.wc = p.ct + maxoff;
     const int64_t blocks = dlc::cdiv(rows_out, p.rb);

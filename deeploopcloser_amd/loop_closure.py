@@ -44,6 +44,12 @@ def first_k_eligible(scores, idx, limit, k):
     return s, i
 
 
+def _nothing_older(b, k, fill, dtype, device):
+    """(scores, ids) [b, k] of b frames none of which has a frame old enough yet: (fill, -1) in every slot."""
+    return (torch.full((b, k), fill, dtype=dtype, device=device),
+            torch.full((b, k), -1, dtype=torch.int64, device=device))
+
+
 class LoopClosureDetector:
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
                  device=None):
@@ -75,9 +81,7 @@ class LoopClosureDetector:
             out_s.append(s)
             out_i.append(i)
         if not out_s:
-            dev = self.db.engine.device
-            return (torch.empty((0, self.k), dtype=torch.float32, device=dev),
-                    torch.empty((0, self.k), dtype=torch.int64, device=dev))
+            return _nothing_older(0, self.k, float("-inf"), torch.float32, self.db.engine.device)
         if len(out_s) == 1:                                  # (torch.cat of one tensor is a copy: two launches per batch)
             return out_s[0], out_i[0]
         return torch.cat(out_s), torch.cat(out_i)
@@ -89,10 +93,8 @@ class LoopClosureDetector:
         g0 -= db.row_offset
         q = db.rows[g0:g0 + b]
         n_search = g0 + b - 1 - self.exclusion             # what the newest frame of the batch may see
-        dev = db.engine.device
         if n_search <= 0:
-            return (torch.full((b, k), float("-inf"), dtype=torch.float32, device=dev),
-                    torch.full((b, k), -1, dtype=torch.int64, device=dev))
+            return _nothing_older(b, k, float("-inf"), torch.float32, db.engine.device)
         # one score pass over what the newest frame may see; frame j of the batch keeps to the rows below g0 - exclusion + j
         # (dlc_cosine_topk_older -- the lists of a k + b - 1 match followed by dlc_topk_keep_older / first_k_eligible)
         return db.engine.match_topk(q, db.rows[:n_search], k, older_than=g0 - self.exclusion)
@@ -111,10 +113,20 @@ class LoopClosureDetector:
 class _SequenceRows:
     """The resident score rows of a detector with sequence=L: a [L - 1 + batch, ld] buffer of `dtype` whose first L - 1
     rows are the context -- the score rows of the L - 1 frames before the batch -- and whose next rows receive the
-    batch's.  ld is the store's capacity, so a row never moves while the store does not grow."""
+    batch's.  ld is the store's capacity, so a row never moves while the store does not grow.  It also holds what the
+    sequence search of those rows takes, checked: `slopes`, an int32 table [1..16, L] (default sequence.slope_offsets(L)),
+    and a k within the search's range."""
 
-    def __init__(self, length, dtype):
-        self.context, self.dtype, self.buf = int(length) - 1, dtype, None
+    def __init__(self, length, slopes, k, dtype):
+        from .sequence import slope_offsets
+        if not 1 <= length <= 64:
+            raise ValueError("sequence=%d outside 1..64" % length)
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        self.slopes = slope_offsets(length) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
+        if self.slopes.ndim != 2 or self.slopes.shape[1] != length or not 1 <= self.slopes.shape[0] <= 16:
+            raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
+        self.context, self.dtype, self.buf = length - 1, dtype, None
 
     def batch_rows(self, b, capacity, device):
         """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b (the buffer is re-laid, the context kept, when
@@ -164,19 +176,12 @@ class SdavLoopClosureDetector:
             raise ValueError("exclusion must be >= 0")
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
         self.sequence = None if sequence is None else int(sequence)
-        if self.sequence is None:
-            if slopes is not None:
-                raise ValueError("slopes needs sequence=L")
-        else:
-            from .sequence import slope_offsets
-            if not 1 <= self.sequence <= 64:
-                raise ValueError("sequence=%d outside 1..64" % self.sequence)
-            if not 1 <= k <= L.DLC_MAX_K:
-                raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-            self.slopes = slope_offsets(self.sequence) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
-            if self.slopes.ndim != 2 or self.slopes.shape[1] != self.sequence or not 1 <= self.slopes.shape[0] <= 16:
-                raise ValueError("slopes must be an int32 table [1..16, %d]" % self.sequence)
-            self._seq = _SequenceRows(self.sequence, torch.float64)   # the last L - 1 score rows, then the batch's
+        if self.sequence is not None:
+            self._seq = _SequenceRows(self.sequence, slopes, k, torch.float64)   # the last L - 1 score rows, then the batch's
+            self.slopes = self._seq.slopes
+        elif slopes is not None:
+            raise ValueError("slopes needs sequence=L")
+        self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
 
@@ -201,15 +206,18 @@ class SdavLoopClosureDetector:
                 eng.sdav_stream_query_batch(st.state, st.desc, first, b, st.score, st.a, st.b, out=self._seq_rows(b), stats=st.stats)
             return self._seq_rank(first, b)
         if first + b - 1 == 0:                                        # the very first frame alone: nothing older
-            none = torch.full((b, self.k), float("-inf"), dtype=torch.float64, device=eng.device)
-            return (torch.where(self.poisoned != 0, float("nan"), none),
-                    torch.full((b, self.k), -1, dtype=torch.int64, device=eng.device))
+            return self._nothing_older(b)
         # frame first + r against every older frame, all B of them in one pair of launches (dlc_sdav_stream_query_batch):
         # rows[r, :first + r]
         rows = st.query_batch(first, b)
         # the k best of the frames old enough -- one launch for the batch (dlc_topk_rows_f64: score descending, ties ->
         # the older frame; the kernel reads the stream's poison word and answers (NaN, -1) everywhere when it is set)
         return eng.topk_rows_f64(rows, first - self.exclusion, 1, self.k, poison=self.poisoned)
+
+    def _nothing_older(self, b):
+        """(-inf, -1) in every slot of b frames' lists; (NaN, -1) once the stream is poisoned."""
+        s, i = _nothing_older(b, self.k, float("-inf"), torch.float64, self.stream.engine.device)
+        return torch.where(self.poisoned != 0, float("nan"), s), i
 
     # ---- two batches in flight ------------------------------------------------------------------------------------------
     # query_and_insert runs a batch's six launches one behind the other: copy, quantisation, the strip's product kernel (200
@@ -232,8 +240,6 @@ class SdavLoopClosureDetector:
         if x.dim() != 3 or x.shape[1] != st.p or x.shape[2] != st.h:       # (before a ticket is spent on it)
             raise ValueError("frames must be [B, %d, %d]" % (st.p, st.h))
         b, first = x.shape[0], len(st)
-        if not hasattr(self, "_slots"):
-            self._slots, self._pending, self._tickets = [{}, {}], None, 0
         t = self._tickets
         self._tickets += 1
         main, side = torch.cuda.current_stream(eng.device), eng.side_stream
@@ -265,7 +271,7 @@ class SdavLoopClosureDetector:
     def _flush(self):
         """The second half of the batch whose products are in flight -- resolution + scores + ranking, on the caller's stream
         behind that batch's product kernel."""
-        if getattr(self, "_pending", None) is None:
+        if self._pending is None:
             return
         st, eng = self.stream, self.stream.engine
         slot = self._slots[self._pending % 2]
@@ -296,15 +302,13 @@ class SdavLoopClosureDetector:
             s, i, _, _ = eng.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b - 1,
                                            limit0=first - seq.context - self.exclusion, limit_step=1, poison=self.poisoned)
         else:                                                         # the very first frame alone: nothing older
-            none = torch.full((b, self.k), float("-inf"), dtype=torch.float64, device=eng.device)
-            s = torch.where(self.poisoned != 0, float("nan"), none)
-            i = torch.full((b, self.k), -1, dtype=torch.int64, device=eng.device)
+            s, i = self._nothing_older(b)
         seq.advance(b)
         return s, i
 
     def result(self, ticket):
         """(scores [B, k] float64, ids [B, k] int64) of a submitted batch, in the current stream's order."""
-        if not hasattr(self, "_slots") or not self._tickets - 2 <= ticket < self._tickets:
+        if not self._tickets - 2 <= ticket < self._tickets:
             raise ValueError("SdavLoopClosureDetector.result: ticket %r is not in flight" % (ticket,))
         if self._pending == ticket:
             self._flush()
@@ -363,17 +367,11 @@ class CnnVtlLoopClosureDetector:
         self.k, self.exclusion = int(k), int(exclusion)
         self.max_distance = None if max_distance is None else int(max_distance)
         self.sequence = None if sequence is None else int(sequence)
-        if self.sequence is None:
-            if slopes is not None:
-                raise ValueError("slopes needs sequence=L")
-        else:
-            from .sequence import slope_offsets
-            if not 1 <= self.sequence <= 64:
-                raise ValueError("sequence=%d outside 1..64" % self.sequence)
-            self.slopes = slope_offsets(self.sequence) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
-            if self.slopes.ndim != 2 or self.slopes.shape[1] != self.sequence or not 1 <= self.slopes.shape[0] <= 16:
-                raise ValueError("slopes must be an int32 table [1..16, %d]" % self.sequence)
-            self._seq = _SequenceRows(self.sequence, torch.int64)    # the last L - 1 distance rows, then the batch's
+        if self.sequence is not None:
+            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64)   # the last L - 1 distance rows, then the batch's
+            self.slopes = self._seq.slopes
+        elif slopes is not None:
+            raise ValueError("slopes needs sequence=L")
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -394,8 +392,7 @@ class CnnVtlLoopClosureDetector:
             return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
                                                   limit0=first - self.exclusion, limit_step=1)
         if b == 0:
-            none = torch.empty((0, self.k), dtype=torch.int64, device=db.engine.device)
-            return none, none.clone()
+            return _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
         # frame first + r against the frames below first + r - exclusion, as rows behind the L - 1 rows before them; matrix
         # row m is frame first - (L - 1) + m (rows of frames before the stream began offer nothing and are never read)
         seq = self._seq

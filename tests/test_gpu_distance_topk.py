@@ -60,10 +60,13 @@ def test_topk_equals_the_reference_matrix(dlc, golden, name):
         assert np.array_equal(d, ed) and np.array_equal(i, ei), (name, k)
 
 
-# every value of each axis at least once: D, N (1, k - 1, k, 1 000, 70 001), Q (1, 7, 256, 300), k (1, 20, 128)
+# every value of each axis at least once: D, N (1, k - 1, k, 1 000, 70 001), Q (1, 7, 256, 300), k (1, 20, 128); then
+# k = 63, 64, 65, where a list's last entry moves from a lane's first register to its second (the 16 x 256 tile, four
+# slabs: the merge sees several lists)
 SWEEP = [(1, 70001, 7, 20), (3, 1, 300, 128), (4, 19, 256, 20), (15, 128, 7, 128), (16, 1000, 300, 1), (63, 1000, 1, 128),
          (64, 70001, 1, 20), (65, 127, 300, 128), (2243, 1000, 256, 20), (2463, 20, 300, 20), (2463, 1000, 7, 1),
-         (15, 70001, 256, 128), (2243, 127, 1, 128), (64, 1, 1, 1), (3, 1000, 256, 1)]
+         (15, 70001, 256, 128), (2243, 127, 1, 128), (64, 1, 1, 1), (3, 1000, 256, 1),
+         (17, 1000, 7, 63), (17, 1000, 7, 64), (17, 1000, 7, 65)]
 
 
 @pytest.mark.parametrize("d,n,q,k", SWEEP)

@@ -71,7 +71,8 @@ def data(rng, dtype, rows, n):
 
 # (dtype, L, slopes, rows, row0, n, k, limit0, limit_step, lower): every value of each axis at least once -- dtype, L (1, 2,
 # 10, 33, 64), slopes (1, 5, 16), rows (1, L-1, L, 300), row0 (0, L-1), n (1, 7, 1000, 70 001), k (1, 20, 128), limit_step
-# (0, 1) with negative and over-large limit0, both senses
+# (0, 1) with negative and over-large limit0, both senses; then k = 63, 64, 65, where a list's last entry moves from a
+# lane's first register to its second
 SWEEP = [
     ("f64", 1, 1, 1, 0, 1, 1, None, 0, False),
     ("f32", 2, 5, 1, 0, 7, 20, -3, 1, True),                      # rows = L - 1: nothing is offered
@@ -89,6 +90,15 @@ SWEEP = [
     ("f64", 33, 5, 33, 32, 70001, 1, 69000, 1, False),
     ("i64", 1, 1, 1, 0, 1000, MAX_K, -5, 1, True),
     ("f32", 64, 16, 63, 0, 1000, MAX_K, None, 0, True),           # rows = L - 1
+    ("f64", 2, 5, 40, 1, 1000, 63, None, 0, False),
+    ("f64", 2, 5, 40, 1, 1000, 64, None, 0, False),
+    ("f64", 2, 5, 40, 1, 1000, 65, None, 0, False),
+    ("i64", 2, 5, 40, 1, 1000, 63, -3, 1, True),
+    ("i64", 2, 5, 40, 1, 1000, 64, -3, 1, True),
+    ("i64", 2, 5, 40, 1, 1000, 65, -3, 1, True),
+    ("i64", 2, 5, 40, 1, 1000, 63, None, 0, True),                # (the limits above keep those lists short of k: these fill)
+    ("i64", 2, 5, 40, 1, 1000, 64, None, 0, True),
+    ("i64", 2, 5, 40, 1, 1000, 65, None, 0, True),
 ]
 
 
