@@ -86,6 +86,13 @@ const char* dlc_status_string(int status);
  * (src/cnn_vtl/network/cnn_vtl.py:33-93).
  * dtype: DLC_F64 (the reference's arithmetic; v_mfma_f64_16x16x4_f64) or
  * DLC_F32 (v_mfma_f32_16x16x4_f32).  bias may be NULL.  Any M,N,K >= 1.
+ * Operands: A is M rows of pitch lda >= K; B is K rows of pitch ldb >= N (DLC_B_KN) or N rows of pitch
+ * ldb >= K (DLC_B_NK); C is M rows of pitch ldc >= N; pitches in elements.  Any such pitch is accepted, and the
+ * bases and pitches need only the alignment of an element.  What lies between a row's end and the next row (and
+ * around the operands) is never read into a result -- it may hold NaNs -- and never written.  Even lda / ldb, even
+ * K (and N for DLC_B_KN) and 16-byte-aligned bases of A and B only select a faster route (the LDS-DMA kernel) for
+ * DLC_F64; in one pass every route sums k in the same order and returns the same bits
+ * (tests/test_gpu_gemm_f64_operands.py).
  */
 int dlc_gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act,
                       int64_t M, int64_t N, int64_t K,

@@ -4,7 +4,7 @@
     (rows non-zero in one 32-deep k-slice: the case that catches a stale ring slot or a product dropped in one slice),
     chains with the bound propagated layer by layer, and the input contract of include/dlc.h;
   * fp32: gemm_bias_act on every plan (one pass, split-K under latency_mode, both B layouts, every activation, bias or
-    none, leading dimensions wider than the row), dlc_bias_act in fp32 and fp64, and their callers SDAV(dtype="float32")
+    none, leading dimensions of A, B and C wider than the row), dlc_bias_act in fp32 and fp64, and their callers SDAV(dtype="float32")
     and TensorWrapper.
 Every case prints its worst err / bound and asserts it is <= 1.  The bounds are derived, not fitted
 (tests/test_precision_bounds_cpu.py shows they hold for an emulation and break for each modelled defect)."""
@@ -220,7 +220,8 @@ def test_gemm_bias_act_f32_every_plan(eng, blayout):
 
 @pytest.mark.parametrize("m,n,k,blayout", [(300, 2500, 2500, 0), (37, 53, 29, 1), (60, 300, 1695, 1), (129, 98, 5000, 0)])
 def test_gemm_bias_act_f32_wide_leading_dimensions(eng, m, n, k, blayout):
-    """lda > K and ldc > N through the C ABI: A's padding is NaN (never read), C's padding a sentinel (never written)."""
+    """lda > K, ldb > B's row width and ldc > N through the C ABI: A's and B's padding is NaN (never read), C's padding a
+    sentinel (never written).  B both tight and wide, in the layout of the case."""
     from deeploopcloser_amd import _lib as L
     rng = np.random.RandomState(m + n + k)
     a = rng.standard_normal((m, k)).astype(np.float32)
@@ -229,25 +230,29 @@ def test_gemm_bias_act_f32_wide_leading_dimensions(eng, m, n, k, blayout):
     lda, ldc = k + 5, n + 3
     wide = torch.full((m, lda), float("nan"), dtype=torch.float32, device="cuda")
     wide[:, :k] = dev(a, torch.float32)
-    tb = dev(b if blayout == 0 else b.T, torch.float32)
+    tight_b = dev(b if blayout == 0 else b.T, torch.float32)
+    wide_b = torch.full((tight_b.shape[0], tight_b.shape[1] + 7), float("nan"), dtype=torch.float32, device="cuda")
+    wide_b[:, :tight_b.shape[1]] = tight_b
     tbias = dev(bias, torch.float32)
     z = dev(a) @ dev(b) + dev(bias)
-    for scratch in (False, True):
-        for act in (L.DLC_ACT_NONE, L.DLC_ACT_SIGMOID, L.DLC_ACT_RELU):
-            out = torch.full((m, ldc), 12345.0, dtype=torch.float32, device="cuda")
-            if scratch:
-                eng.set_scratch()
-            try:
-                eng._check(eng.lib.dlc_gemm_bias_act(eng.ctx, L.DLC_F32, blayout, act, m, n, k, wide.data_ptr(), lda,
-                                                      tb.data_ptr(), tb.stride(0), tbias.data_ptr(), out.data_ptr(), ldc, None))
-                torch.cuda.synchronize()
-            finally:
+    for tb in (tight_b, wide_b):
+        assert tb.stride(0) == tight_b.shape[1] + (7 if tb is wide_b else 0)
+        for scratch in (False, True):
+            for act in (L.DLC_ACT_NONE, L.DLC_ACT_SIGMOID, L.DLC_ACT_RELU):
+                out = torch.full((m, ldc), 12345.0, dtype=torch.float32, device="cuda")
                 if scratch:
-                    eng.set_scratch(0)
-            assert torch.all(out[:, n:] == 12345.0)
-            bound = pb.act_bound(act, z, pb.gemm_dz(dev(a).abs() @ dev(b).abs(), k, pb.latency_chunks_max(k) if scratch else 1, dev(bias)))
-            report("fp32 gemm lda %d ldc %d, %dx%dx%d, act %d, latency %s" % (lda, ldc, m, n, k, act, scratch),
-                   pb.ratio(out[:, :n].double() - _act_ref(act, z), bound))
+                    eng.set_scratch()
+                try:
+                    eng._check(eng.lib.dlc_gemm_bias_act(eng.ctx, L.DLC_F32, blayout, act, m, n, k, wide.data_ptr(), lda,
+                                                          tb.data_ptr(), tb.stride(0), tbias.data_ptr(), out.data_ptr(), ldc, None))
+                    torch.cuda.synchronize()
+                finally:
+                    if scratch:
+                        eng.set_scratch(0)
+                assert torch.all(out[:, n:] == 12345.0)
+                bound = pb.act_bound(act, z, pb.gemm_dz(dev(a).abs() @ dev(b).abs(), k, pb.latency_chunks_max(k) if scratch else 1, dev(bias)))
+                report("fp32 gemm lda %d ldb %d ldc %d, %dx%dx%d, act %d, latency %s" % (lda, tb.stride(0), ldc, m, n, k, act, scratch),
+                       pb.ratio(out[:, :n].double() - _act_ref(act, z), bound))
 
 
 # --------------------------------------------------------------------------------------------------- g. bias_act
