@@ -14,7 +14,7 @@ include/dlc.h, with the reference's Python call surface on top:
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
     sequence_topk / sequence_scores / slope_offsets   (sequence-consistent search over a score matrix; new)
-    LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; the last two take sequence=L)
+    LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; all three take sequence=L)
 
 Importing the package is cheap and works without a GPU; constructing any of
 the classes needs libdlc_hip.so and a visible MI355X and raises otherwise.

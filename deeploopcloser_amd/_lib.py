@@ -16,7 +16,7 @@ DLC_BF16, DLC_F16, DLC_F32, DLC_F64, DLC_I8, DLC_U8, DLC_I64 = 0, 1, 2, 3, 4, 5,
 DLC_ACT_NONE, DLC_ACT_SIGMOID, DLC_ACT_RELU = 0, 1, 2
 DLC_B_KN, DLC_B_NK = 0, 1
 DLC_MAX_K = 128
-DLC_ABI_VERSION = 14         # include/dlc.h; load() refuses a library built from another header
+DLC_ABI_VERSION = 15         # include/dlc.h; load() refuses a library built from another header
 DLC_SELECT_COOP = 1
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 
@@ -116,6 +116,7 @@ SIGNATURES = {
     "dlc_topk_keep_older": (_int, [_vp, _vp, _vp, _i64, _int, _i64, _int, _vp, _vp, _vp]),
     "dlc_cosine_scores_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dlc_cosine_scores": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "dlc_cosine_score_rows": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "dlc_host_to_device": (_int, [_vp, _vp, _vp, _sz, _vp]),
     "dlc_device_to_host": (_int, [_vp, _vp, _vp, _sz, _vp]),
     "dlc_set_host_threads": (_int, [_vp, _int]),

@@ -551,15 +551,7 @@ __device__ __forceinline__ unsigned long long pack_key(float score, unsigned id)
 }
 __device__ __forceinline__ unsigned key_id(unsigned long long key) { return ~(unsigned)key; }
 
-// Ordering key of an fp64 score: quantised to 2^-40 (oracle/cosine.py: order_key), so that two rows whose exact
-// scores are equal but whose fp64 sums differ in the last bits (the same products in another order) still tie.
-constexpr long long KEY64_EMPTY = (long long)0x8000000000000000ull;
-__device__ __forceinline__ long long f64_key(double s) {
-    const double x = s * 1099511627776.0;                 // 2^40
-    if (!(x > -4.0e18)) return KEY64_EMPTY + 1;           // -inf, NaN, absurdly negative: last
-    if (x > 4.0e18) return 0x7fffffffffffffffll;
-    return __double2ll_rn(x);                             // round half to even, as np.round
-}
+// (f64_key, the ordering key of an fp64 score, and KEY64_EMPTY: dlc_internal.h -- cosine_rows.hip writes the same keys)
 
 // wave-wide unsigned max through DPP (row_shr 1,2,4,8 + row_bcast 15 / 31), result in every lane
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {

@@ -142,6 +142,17 @@ __device__ __forceinline__ float dlc_f16_bits_to_f32(unsigned short h) {
     return (float)v;
 }
 
+// Ordering key of an fp64 score: quantised to 2^-40 (oracle/cosine.py: order_key), so that two rows whose exact
+// scores are equal but whose fp64 sums differ in the last bits (the same products in another order) still tie.
+// The integer the whole cosine path ranks by (cosine_topk.hip) and the one cosine_rows.hip writes as rows.
+constexpr long long KEY64_EMPTY = (long long)0x8000000000000000ull;
+__device__ __forceinline__ long long f64_key(double s) {
+    const double x = s * 1099511627776.0;                 // 2^40
+    if (!(x > -4.0e18)) return KEY64_EMPTY + 1;           // -inf, NaN, absurdly negative: last
+    if (x > 4.0e18) return 0x7fffffffffffffffll;
+    return __double2ll_rn(x);                             // round half to even, as np.round
+}
+
 // Order-preserving 64-bit key of a double (atomicMin / atomicMax on unsigned long long): per-frame minima / maxima of
 // the CnnVtl descriptor are folded this way by several kernels (cnnvtl.hip, the convolution epilogue of gemm_dma_f64.hip).
 // keys[2 f] = key of the minimum of frame f (initially ~0), keys[2 f + 1] = key of its maximum (initially 0).

@@ -1299,6 +1299,59 @@ class Engine:
                                                 need, self._stream()))
         return s
 
+    def cosine_score_rows(self, q, db, limit0=None, limit_step=0, out=None, keys=False, out_keys=None):
+        """The cosine path's score as rows (dlc_cosine_score_rows, include/dlc.h): float64 [Q, N], the fp64 score of every
+        stored query row of q [Q, d] against the stored rows of db [N, d] (bf16 / fp16, one dtype, one width: a multiple
+        of 8) -- bit for bit the number match_topk(details=True) reports for that pair -- and / or its ordering keys,
+        int64 [Q, N] = round-half-even(score * 2^40), the integer the cosine path ranks by.  Query r is written in its
+        first clamp(limit0 + r * limit_step, 0, N) cells (limit0 None = N: all of them); the other cells keep what the
+        caller's tensor held, and hold NaN (scores) / INT64_MIN (keys) -- "not offered" -- where the engine allocates.
+        out / out_keys: caller-kept float64 / int64 [Q, N] tensors, which may be views whose rows lie further apart than
+        N, both with one row stride (their columns past N are left alone too).  Returns the scores; with keys=True (or
+        out_keys given) the keys -- (scores, keys) when `out` is given as well."""
+        if q.dim() != 2 or db.dim() != 2 or q.dtype != db.dtype or q.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError("cosine_score_rows: q and db must be 2-D, both bf16 or both fp16")
+        if q.device != self.device or db.device != self.device:
+            raise ValueError("cosine_score_rows: q and db must be on %s" % self.device)
+        if q.shape[1] != db.shape[1]:
+            raise ValueError("cosine_score_rows: q and db widths differ (%d, %d)" % (q.shape[1], db.shape[1]))
+        if q.stride(1) != 1 or db.stride(1) != 1:
+            raise ValueError("cosine_score_rows: stored descriptor rows must be contiguous")
+        nq, d = q.shape
+        n = db.shape[0]
+        want_keys = bool(keys) or out_keys is not None
+        want_scores = out is not None or not want_keys
+
+        def result(t, dtype, name, fill):
+            if t is None:
+                t = torch.empty((nq, n), dtype=dtype, device=self.device)
+                if limit0 is not None:
+                    t.fill_(fill)
+            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != (nq, n) or t.dtype != dtype or \
+                    t.device != self.device or (n > 1 and t.stride(1) != 1) or (nq > 1 and t.stride(0) < n):
+                raise ValueError("cosine_score_rows: %s must be a %s tensor of shape (%d, %d) on %s with unit column "
+                                 "stride and rows at least %d apart" % (name, dtype, nq, n, self.device, n))
+            return t
+
+        o_s = result(out, torch.float64, "out", float("nan")) if want_scores else None
+        o_k = result(out_keys, torch.int64, "out_keys", -(1 << 63)) if want_keys else None
+        both = o_s is not None and o_k is not None
+        ret = (o_s, o_k) if both else (o_k if o_k is not None else o_s)
+        if nq == 0 or n == 0:
+            return ret
+        if d == 0:
+            raise ValueError("cosine_score_rows: empty descriptors")
+        ld_out = (o_s if o_s is not None else o_k).stride(0) if nq > 1 else n
+        if both and nq > 1 and o_k.stride(0) != ld_out:
+            raise ValueError("cosine_score_rows: out and out_keys must have one row stride (%d, %d)" % (ld_out, o_k.stride(0)))
+        self._check(self.lib.dlc_cosine_score_rows(self.ctx, _TORCH_TO_DLC[q.dtype], _ptr(q), nq, q.stride(0), _ptr(db), n,
+                                                    db.stride(0), d, n if limit0 is None else int(limit0), int(limit_step),
+                                                    _ptr(o_s), _ptr(o_k), ld_out, self._stream()))
+        for t in (o_s, o_k):
+            if t is not None:
+                self._wrote(t)
+        return ret
+
     # ---- profiling hooks for bench.py ---------------------------------------------------
     def set_profiling(self, enabled):
         self._check(self.lib.dlc_set_profiling(self.ctx, 1 if enabled else 0))

@@ -51,13 +51,34 @@ def _nothing_older(b, k, fill, dtype, device):
 
 
 class LoopClosureDetector:
+    """The cosine detector: every new frame against the key-frames more than `exclusion` frames older, the k best by the
+    cosine path's fp64 score (dlc_cosine_topk_older), candidates at or above `threshold`.
+
+    sequence = L (None: off, every path as it is without it -- the fused top-k, no score rows are formed) asks whether
+    the match holds over the last L frames, as the other two detectors do: a pair (frame t, older frame j) is scored by
+    the SUM of the L frame scores along a line through (t, j) of the score matrix, the best of the lines of `slopes` (an
+    int32 table [1..16, L]; default sequence.slope_offsets(L)), and the k best sums are the candidates.  The rows summed
+    are the scores' ordering KEYS -- int64, round-half-even(score * 2^40), the integer the top-k itself ranks by
+    (dlc_cosine_score_rows into a resident int64 buffer that keeps the last L - 1 rows, then dlc_sequence_topk on int64):
+    the sums are exact and free of summation order, the ranking (sum, then the older frame) is the top-k's own rule, and
+    sequence=1 returns the ids of sequence=None index for index.  The lists do not depend on the batching; a frame with
+    fewer than L - 1 predecessors gets (-inf, -1).  Scores are then float64, key sum * 2^-40 (exact), and `threshold` is
+    compared with that SUM of L scores, not with one score, as the SDAV detector's is: a mean of 0.9 is threshold=0.9 * L.
+    (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)"""
+
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None):
+                 device=None, sequence=None, slopes=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
             raise ValueError("exclusion must be >= 0")
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
+        self.sequence = None if sequence is None else int(sequence)
+        if self.sequence is not None:
+            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64)   # the last L - 1 key rows, then the batch's
+            self.slopes = self._seq.slopes
+        elif slopes is not None:
+            raise ValueError("slopes needs sequence=L")
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     def __len__(self):
@@ -71,7 +92,8 @@ class LoopClosureDetector:
     def query_and_insert(self, descriptors):
         """The next B frames' descriptors [B, dim] (ids len(self) .. len(self)+B-1) ->
         (scores [B,k] float32, ids [B,k] int64) on the device, best first, (-inf, -1) where fewer
-        than k key-frames are old enough; the frames are then key-frames themselves."""
+        than k key-frames are old enough; the frames are then key-frames themselves.  With sequence=L the
+        scores are float64: the sum of the L scores along the best line."""
         x = self.db._as_float(descriptors)
         if x.dim() != 2:
             raise ValueError("descriptors must be [B, dim]")
@@ -81,7 +103,8 @@ class LoopClosureDetector:
             out_s.append(s)
             out_i.append(i)
         if not out_s:
-            return _nothing_older(0, self.k, float("-inf"), torch.float32, self.db.engine.device)
+            return _nothing_older(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
+                                  self.db.engine.device)
         if len(out_s) == 1:                                  # (torch.cat of one tensor is a copy: two launches per batch)
             return out_s[0], out_i[0]
         return torch.cat(out_s), torch.cat(out_i)
@@ -92,6 +115,8 @@ class LoopClosureDetector:
         g0, _ = db.append(x)                               # normalised once, used as query and as key-frame
         g0 -= db.row_offset
         q = db.rows[g0:g0 + b]
+        if self.sequence is not None:
+            return self._seq_step(q, g0, b)
         n_search = g0 + b - 1 - self.exclusion             # what the newest frame of the batch may see
         if n_search <= 0:
             return _nothing_older(b, k, float("-inf"), torch.float32, db.engine.device)
@@ -99,8 +124,23 @@ class LoopClosureDetector:
         # (dlc_cosine_topk_older -- the lists of a k + b - 1 match followed by dlc_topk_keep_older / first_k_eligible)
         return db.engine.match_topk(q, db.rows[:n_search], k, older_than=g0 - self.exclusion)
 
+    def _seq_step(self, q, g0, b):
+        """The lists of frames g0 .. g0 + b - 1 (already key-frames) by the sequence search: their key rows against the
+        frames below g0 + r - exclusion go behind the L - 1 rows before them; matrix row m is frame g0 - (L - 1) + m (rows
+        of frames before the stream began offer nothing and are never read).  Then the last L - 1 rows become the next
+        batch's context."""
+        db, seq = self.db, self._seq
+        db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1,
+                      out=seq.batch_rows(b, db.capacity, db.engine.device)[:, :g0 + b])
+        s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=g0 + b,
+                                             limit0=g0 - seq.context - self.exclusion, limit_step=1)
+        seq.advance(b)
+        # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
+        return torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i
+
     def loops(self, scores, ids, first_id):
-        """[(frame id, matched key-frame id, score)] of the candidates at or above the threshold."""
+        """[(frame id, matched key-frame id, score)] of the candidates at or above the threshold (with sequence=L: the sum
+        of the L scores along the candidate's line)."""
         s, i = scores.cpu().numpy(), ids.cpu().numpy()
         out = []
         for r in range(s.shape[0]):

@@ -160,6 +160,20 @@ class KeyframeDatabase:
     def match(self, queries):
         return self.engine.cosine_scores(self.prepare_queries(queries), self.rows)
 
+    def scores_f64(self, queries, limit0=None, limit_step=0, out=None):
+        """float64 [Q, len(db)]: the fp64 score of every query against the key-frames as rows (dlc_cosine_score_rows) --
+        the numbers match_topk(details=True) reports, bit for bit.  queries: [Q, dim] floats, or stored rows (bf16 / fp16)
+        such as a slice of `rows`.  Query r is written in its first clamp(limit0 + r * limit_step, 0, len(db)) cells
+        (local rows; limit0 None: all); the others are NaN, or keep what `out` held."""
+        return self.engine.cosine_score_rows(self.prepare_queries(queries), self.rows, limit0=limit0, limit_step=limit_step,
+                                             out=out)
+
+    def score_keys(self, queries, limit0=None, limit_step=0, out=None):
+        """int64 [Q, len(db)]: the ordering keys of those scores, round-half-even(score * 2^40) -- the integer the top-k
+        ranks by, and what the sequence search sums exactly.  Cells not offered are INT64_MIN, or keep what `out` held."""
+        return self.engine.cosine_score_rows(self.prepare_queries(queries), self.rows, limit0=limit0, limit_step=limit_step,
+                                             keys=True, out_keys=out)
+
 
 class MatchPipeline:
     """Two-stream pipelined top-k match against one resident shard.  Meant for the sharded case: on a

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 14
+#define DLC_ABI_VERSION 15
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -796,6 +796,34 @@ size_t dlc_cosine_scores_workspace_bytes(int64_t q, int64_t n, int64_t d);
 int dlc_cosine_scores(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t ldq,
                       const void* DB, int64_t n, int64_t lddb, int64_t d,
                       float* S, int64_t lds, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The cosine path's score as rows (cosine_rows.hip): out_scores[r * ld_out + j] = THE score of query row r and
+ * database row j -- the ONE number of the cosine path, the fp64 sum of the exact products in the order of rescore8_f64
+ * (cosine_topk.hip): lane l of a wave takes the 16-byte pieces l, l + 64, ... of the two rows in ascending order, one
+ * fp64 fma chain over each piece's eight elements in ascending order, from +0.0 (a lane with no piece contributes +0.0);
+ * the 64 chains are combined by the xor 32, 16, ..., 1 butterfly.  It is a function of (query row, database row, d)
+ * alone -- not of the tile shape, the limits or the other queries of the call -- and it is, bit for bit, what
+ * dlc_cosine_topk* write to out_scores_f64 for that pair.  out_keys[r * ld_out + j] = the integer the whole cosine path
+ * ranks by: round-half-even(score * 2^40), clamped (NaN, -inf and anything below -4e18 -> INT64_MIN + 1; above 4e18 ->
+ * INT64_MAX).  Either output may be NULL, not both.  int64 key rows are what dlc_sequence_topk(DLC_I64) takes: sums of
+ * keys are exact and free of summation order, and its ranking (value, then the lower column) is then the cosine path's
+ * own rule.
+ * Row r is written for 0 <= j < lim(r), lim(r) = clamp(limit0 + r * limit_step, 0, n) -- the limit convention of
+ * dlc_cnnvtl_distance_rows, dlc_topk_rows_f64 and dlc_sequence_topk; any limit_step, negative included.
+ * EVERY OTHER WORD OF THE OUTPUTS KEEPS ITS BITS: the cells at or past lim(r) and the columns n .. ld_out-1.  When
+ * every lim(r) is 0 nothing is launched and the call returns DLC_OK.
+ * Operands as in dlc_cosine_topk -- rows as stored, bases 16-byte aligned -- except that d need only be a multiple of 8
+ * (and the strides, >= d); Q may be rows of DB (both are only read); the outputs (8-byte aligned, ld_out >= n) must
+ * not overlap the operands.  Any argument error is DLC_ERR_BAD_ARG and leaves the outputs untouched.
+ * No workspace, no memset, no atomics; one launch on `stream` (a wave per 4 x 4 block of pairs, 1 x 8 for a single
+ * query; the operands come straight from L2); never synchronises.
+ */
+int dlc_cosine_score_rows(dlc_ctx* ctx, int dtype /* DLC_BF16 | DLC_F16 */,
+                          const void* Q, int64_t q, int64_t ldq,
+                          const void* DB, int64_t n, int64_t lddb, int64_t d,
+                          int64_t limit0, int64_t limit_step,
+                          double* out_scores, int64_t* out_keys, int64_t ld_out, void* stream);
 
 /* ---- host arrays in, host arrays out (the reference's NumPy contract) ----------- */
 /*
