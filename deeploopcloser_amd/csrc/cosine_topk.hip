@@ -1496,6 +1496,19 @@ __global__ __launch_bounds__(FIN_THREADS) void merge_topk_kernel(const double* _
 }
 
 
+// fp64 -> fp32 as a rounding of its own.  The stored value is the fp64 result rounded to fp32 and THEN to bf16 / fp16 (what a
+// host reference does with .astype(float32) and a cast), but the compiler folds (__bf16)(float)v and (_Float16)(float)v into
+// ONE rounding fp64 -> 16 bit (bf16: through a round-to-odd fp32; fp16: an integer sequence), which gives the other
+// neighbour wherever the fp32 value is a tie of the stored format -- a few elements in 10^5.  The empty asm keeps the fp32
+// value a value of its own; it costs nothing (the folded forms are the longer ones).  What guards the barrier against removal:
+// tests/test_row_prep_cpu.py::test_single_rounding_differs_on_a_built_element states the difference, and
+// tests/test_gpu_row_prep.py::test_normalize_rows_vs_oracle fails on every route without it.
+__device__ __forceinline__ float f64_to_f32_once(double v) {
+    float f = (float)v;
+    asm volatile("" : "+v"(f));
+    return f;
+}
+
 // Row L2 normalisation into the stored descriptor format.
 template <typename Src, typename Tag>
 __global__ __launch_bounds__(256) void l2_normalize_kernel(const Src* __restrict__ src, long long lds, int d,
@@ -1548,11 +1561,11 @@ __global__ __launch_bounds__(256) void l2_normalize_kernel(const Src* __restrict
     const double nrm = sqrt(red[4] + red[5] + red[6] + red[7]);
     const double inv = nrm > 0.0 ? 1.0 / nrm : 1.0;
     auto to16 = [&](double v) -> unsigned {
-        const float f = (float)((v - mean) * inv);
+        const float f = f64_to_f32_once((v - mean) * inv);
         if constexpr (__is_same(Tag, dlc_bf16_tag)) return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)f);
         else return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f);
     };
-    unsigned short* o = dst + row * ldd;                  // ldd is a multiple of 64: rows of dst are 128-byte aligned
+    unsigned short* o = dst + row * ldd;                  // dst is 4-byte aligned and ldd even: so is every pair below
     // pairs of outputs as one 32-bit store (ldd is even); elements past d are zero padding
     for (int e = tid * 2; e < (int)ldd; e += 512) {
         const unsigned lo = e < d ? to16((double)x[e]) : 0u;
@@ -1625,7 +1638,7 @@ __global__ __launch_bounds__(256) void l2_normalize_regs_kernel(const Src* __res
         for (int i = 0; i < VW; ++i) {
             bits[i] = 0;
             if (e0 + i < d) {
-                const float f = (float)(((double)v[j][i] - mean) * inv);
+                const float f = f64_to_f32_once(((double)v[j][i] - mean) * inv);
                 if constexpr (__is_same(Tag, dlc_bf16_tag)) bits[i] = __builtin_bit_cast(unsigned short, (__bf16)f);
                 else bits[i] = __builtin_bit_cast(unsigned short, (_Float16)f);
             }
@@ -2345,6 +2358,7 @@ extern "C" int dlc_l2_normalize_rows(dlc_ctx* ctx, int src_dtype, const void* sr
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "l2_normalize_rows: bad argument");
     if (ldd % BK) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: ldd=%lld must be a multiple of %d", (long long)ldd, BK);
     if (ldd > 0x7fffffff) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: ldd too large");
+    if ((uintptr_t)dst & 3) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: dst must be 4-byte aligned");
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;

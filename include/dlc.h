@@ -605,6 +605,21 @@ int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows,
  * DLC_F64, row stride lds) into the stored descriptor format dst[n, ldd]
  * (DLC_BF16 or DLC_F16), columns d..ldd-1 zero-filled.  ldd must be a multiple
  * of 64 (the GEMM's K step).
+ * Each element is (x - mean) * (1 / norm) evaluated in fp64 and rounded fp64 ->
+ * fp32 -> the stored type, both to nearest even; a row's bits depend on the
+ * row, d, ldd, the types and the alignment of its operands, never on the other
+ * rows of the call.  A row of zeros (or, centred, of one repeated value whose
+ * mean is exact) is stored as zeros; a row holding a NaN or an infinity is
+ * stored with at least one NaN.
+ * ALIGNMENT.  dst must be 4-byte aligned (outputs are stored in pairs;
+ * DLC_ERR_BAD_SHAPE otherwise); src needs its type's alignment only.  The
+ * one-pass forms additionally want src 16-byte aligned, lds a multiple of 16
+ * bytes and dst 8-byte aligned -- any other call is served by the multi-pass
+ * kernel, same values up to the summation order.
+ * RANGE.  Sums of squares are formed in fp64 without scaling: every fp32 source
+ * is in range; an fp64 source must keep |x - mean| within [1e-154, 1e154] (or
+ * zero) -- beyond it the squares under- or overflow and the row is not
+ * normalised.
  */
 int dlc_l2_normalize_rows(dlc_ctx* ctx, int src_dtype, const void* src, int64_t n, int64_t d, int64_t lds,
                           int center, int dst_dtype, void* dst, int64_t ldd, void* stream);
@@ -667,6 +682,13 @@ int dlc_cosine_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t l
  *                         Call it once per shard at load time and again for appended rows; sharded: all-reduce(MAX).
  *   dlc_cosine_tau_scale  tau_scale[i] = max(1, |Q_i| * R / 1.01), R = *db_max_norm (a device float; NULL = 1.005: the
  *                         database is dlc_l2_normalize_rows' output and only the queries are foreign).
+ * Both never under-report: the norm is an fp32 sum of squares (one chain per lane of a wave) times 1.001, which covers the
+ * chain's rounding for rows of up to 2^20 elements (d <= 1048576: the worst row loses 1e-3 of its sum of squares there);
+ * longer rows are outside the guarantee, and so are rows whose elements are so small (|x| < 1.1e-19) that their squares
+ * are not normal fp32 numbers.  Neither over-reports by more than 1 %, by the same count: a lane's chain of d / 64 fp32
+ * fmas and the butterfly can also err UPWARDS by 1e-3 of the sum of squares at 2^20 elements (5e-4 of the norm); with the
+ * 1.001, the roundings of the square root and the products, the scale's 1.000001 and its rounded 1 / 1.01 the factor stays
+ * below 1.002.  The padding ld > d is never read.
  */
 int dlc_max_row_norm(dlc_ctx* ctx, int dtype, const void* rows, int64_t n, int64_t ld, int64_t d, float* max_norm,
                      void* stream);

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import row_prep_oracle as rp
+
 pytestmark = pytest.mark.gpu
 
 
@@ -533,7 +535,12 @@ def test_normalize_rows(eng):
         ref = y / np.linalg.norm(y, axis=1, keepdims=True)
         ref_bf = torch.from_numpy(ref.astype(np.float32)).to(torch.bfloat16).float().numpy()
         assert np.abs(got[:, :100] - ref_bf).max() <= 2.0 ** -8 * np.abs(ref).max() and np.all(got[:, 100:] == 0)
-        assert (got[:, :100] == ref_bf).mean() > 0.999
+        # every element inside the interval of tests/row_prep_oracle.py: bit equality wherever its two ends agree
+        lo, hi = rp.interval(x, center, "bf16")
+        bits = rp.f32_to_bits(got[:, :100], "bf16")                         # exact: the values are bf16
+        outside, amb = rp.verdict(bits, lo, hi, "bf16")
+        assert not outside.any(), (center, rp.first_outside(outside, lo, hi, bits, "bf16"))
+        assert center or not amb.any()
 
 
 # --------------------------------------------------------------------------- dense layers / SDAV
@@ -1762,7 +1769,13 @@ def test_normalize_one_pass_forms_vs_reference_rounding(eng, dlc):
                     g = got.float().cpu().numpy()
                     assert np.all(g[:, d:] == 0)
                     ulp = 2.0 ** -8 if dt == "bf16" else 2.0 ** -11
-                    assert np.abs(g[:, :d] - ref).max() <= ulp * np.abs(ref).max() and (g[:, :d] == ref).mean() > 0.99, (d, src, center, dt)
+                    assert np.abs(g[:, :d] - ref).max() <= ulp * np.abs(ref).max(), (d, src, center, dt)
+                    # every element inside the interval of tests/row_prep_oracle.py: bit equality wherever its ends agree
+                    lo, hi = rp.interval(x, center, dt)
+                    bits = got[:, :d].contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
+                    outside, amb = rp.verdict(bits, lo, hi, dt)
+                    assert not outside.any(), (d, src, center, dt, rp.first_outside(outside, lo, hi, bits, dt))
+                    assert center or not amb.any(), (d, src, center, dt)
     # a strided (unaligned) source view takes the multi-pass kernel: same values as the aligned copy
     x = torch.from_numpy(rng.standard_normal((5, 1001)).astype(np.float32)).to(eng.device)
     a = eng.normalize(x[:, 1:].contiguous(), "bf16")
