@@ -13,7 +13,7 @@ include/dlc.h, with the reference's Python call surface on top:
     MathUtils                     (src/utils/MathUtils.py)
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
-    sequence_topk / sequence_scores / slope_offsets   (sequence-consistent search over a score matrix; new)
+    sequence_topk / sequence_scores / slope_offsets / contrast_normalize   (sequence-consistent search over a score matrix; new)
     LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; all three take sequence=L)
 
 Importing the package is cheap and works without a GPU; constructing any of
@@ -32,10 +32,10 @@ from .dist import ShardedKeyframeDatabase, shard_bounds, merge_topk_torch
 from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, read_ppm
 from . import tensor_wrapper
 from . import sequence
-from .sequence import slope_offsets, sequence_topk, sequence_scores
+from .sequence import slope_offsets, sequence_topk, sequence_scores, contrast_normalize
 from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector
 
-__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "contrast_normalize", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

@@ -1014,6 +1014,44 @@ class Engine:
             ws.numel() if ws is not None else 0, self._stream()))
         return o_s, o_i, o_v, seq
 
+    def contrast_rows(self, scores, radius, n=None, limit0=None, limit_step=0, out=None):
+        """SeqSLAM's local contrast normalisation of score rows (dlc_contrast_rows, include/dlc.h): fp64 [rows, n], cell
+        (r, j) = (x - mean) / sample std over the cells j - radius .. j + radius of row r, clipped to the row's first
+        clamp(limit0 + r * limit_step, 0, n) cells (limit0 None = n), 0.0 where the window holds fewer than two cells or is
+        constant; each window summed on its own in fp64, left to right, so a row does not depend on its batch.  scores
+        [rows, >= n]: fp64, fp32 or int64 on the device (a row-strided view is taken as it is).  Cells that are not
+        offered keep what `out` held, and hold NaN -- "not offered", as sequence_scores writes it -- when the engine
+        allocates the result.  out: a caller-kept fp64 tensor whose first n columns are written (out[:, :n] is returned);
+        its rows may lie further apart than its width (a row-strided view is taken as it is)."""
+        if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype not in self._SEQ_DTYPES:
+            raise ValueError("contrast_rows: scores must be a 2-D float64, float32 or int64 tensor")
+        if scores.device != self.device:
+            raise ValueError("contrast_rows: scores must be on %s" % self.device)
+        if not 1 <= int(radius) <= 32:
+            raise ValueError("contrast_rows: radius=%d outside 1..32" % int(radius))
+        rows = scores.shape[0]
+        n = scores.shape[1] if n is None else int(n)
+        if rows < 1 or n < 1 or n > scores.shape[1]:
+            raise ValueError("contrast_rows: scores [%d, %d] with n=%d: nothing to normalise" % (rows, scores.shape[1], n))
+        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
+            scores = scores.contiguous()
+        ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+        if out is None:
+            out = torch.empty((rows, n), dtype=torch.float64, device=self.device)
+            if limit0 is not None or limit_step != 0:
+                out.fill_(float("nan"))
+        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < n or \
+                out.dtype != torch.float64 or out.device != self.device or (out.shape[1] > 1 and out.stride(1) != 1) or \
+                (rows > 1 and out.stride(0) < n):
+            raise ValueError("contrast_rows: out must be a float64 tensor of shape (%d, >= %d) on %s with unit column stride "
+                             "and rows at least %d apart" % (rows, n, self.device, n))
+        ld_out = out.stride(0) if rows > 1 else n
+        self._check(self.lib.dlc_contrast_rows(self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld,
+                                                n if limit0 is None else int(limit0), int(limit_step), int(radius), _ptr(out),
+                                                ld_out, self._stream()))
+        self._wrote(out)
+        return out[:, :n]
+
     # ---- cosine + top-k -----------------------------------------------------------------
     @staticmethod
     def stored_width(d):

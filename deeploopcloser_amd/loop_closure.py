@@ -64,21 +64,33 @@ class LoopClosureDetector:
     sequence=1 returns the ids of sequence=None index for index.  The lists do not depend on the batching; a frame with
     fewer than L - 1 predecessors gets (-inf, -1).  Scores are then float64, key sum * 2^-40 (exact), and `threshold` is
     compared with that SUM of L scores, not with one score, as the SDAV detector's is: a mean of 0.9 is threshold=0.9 * L.
-    (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)"""
+    (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)
+
+    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
+    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
+    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
+    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
+    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
+    the lists still do not depend on the batching.  Scores are the float64 sums of L normalised values (no 2^-40 rescale: the
+    keys' scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1)."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None, sequence=None, slopes=None):
+                 device=None, sequence=None, slopes=None, contrast=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
             raise ValueError("exclusion must be >= 0")
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
         self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
         if self.sequence is not None:
-            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64)   # the last L - 1 key rows, then the batch's
+            # the last L - 1 key rows, then the batch's
+            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64, self.contrast)
             self.slopes = self._seq.slopes
         elif slopes is not None:
             raise ValueError("slopes needs sequence=L")
+        elif contrast is not None:
+            raise ValueError("contrast needs sequence=L")
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     def __len__(self):
@@ -130,11 +142,13 @@ class LoopClosureDetector:
         of frames before the stream began offer nothing and are never read).  Then the last L - 1 rows become the next
         batch's context."""
         db, seq = self.db, self._seq
-        db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1,
-                      out=seq.batch_rows(b, db.capacity, db.engine.device)[:, :g0 + b])
+        db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1, out=seq.raw_rows(b, db.capacity, db.engine)[:, :g0 + b])
+        seq.normalise(db.engine, g0 + b, g0 - self.exclusion)
         s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=g0 + b,
                                              limit0=g0 - seq.context - self.exclusion, limit_step=1)
         seq.advance(b)
+        if self.contrast is not None:                        # fp64 sums of normalised values as they are
+            return s, i
         # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
         return torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i
 
@@ -155,9 +169,13 @@ class _SequenceRows:
     rows are the context -- the score rows of the L - 1 frames before the batch -- and whose next rows receive the
     batch's.  ld is the store's capacity, so a row never moves while the store does not grow.  It also holds what the
     sequence search of those rows takes, checked: `slopes`, an int32 table [1..16, L] (default sequence.slope_offsets(L)),
-    and a k within the search's range."""
+    and a k within the search's range.
 
-    def __init__(self, length, slopes, k, dtype):
+    contrast = R (1..32): the detector's rows are normalised on their way in (dlc_contrast_rows) -- the batch's raw rows,
+    of `dtype`, go into an engine workspace (raw_rows), normalise() writes them behind the context rows, and the buffer
+    is float64.  A row's normalisation depends on that row alone, so the context rows stay valid."""
+
+    def __init__(self, length, slopes, k, dtype, contrast=None):
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
             raise ValueError("sequence=%d outside 1..64" % length)
@@ -166,7 +184,11 @@ class _SequenceRows:
         self.slopes = slope_offsets(length) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
         if self.slopes.ndim != 2 or self.slopes.shape[1] != length or not 1 <= self.slopes.shape[0] <= 16:
             raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
-        self.context, self.dtype, self.buf = length - 1, dtype, None
+        if contrast is not None and not 1 <= contrast <= 32:
+            raise ValueError("contrast=%d outside 1..32" % contrast)
+        self.contrast, self.raw_dtype, self._raw = contrast, dtype, None
+        self._raw_item = torch.empty((), dtype=dtype).element_size()
+        self.context, self.dtype, self.buf = length - 1, dtype if contrast is None else torch.float64, None
 
     def batch_rows(self, b, capacity, device):
         """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b (the buffer is re-laid, the context kept, when
@@ -179,6 +201,23 @@ class _SequenceRows:
                 new[:ctx, :buf.shape[1]] = buf[:ctx]
             self.buf = buf = new
         return buf[ctx:ctx + b]
+
+    def raw_rows(self, b, capacity, engine):
+        """Where the detector's kernels write the next batch's b rows, [b, capacity]: the buffer's own rows, or with
+        contrast=R a workspace of the raw type (the current stream's, as the rows' consumers are)."""
+        if self.contrast is None:
+            return self.batch_rows(b, capacity, engine.device)
+        size = b * capacity * self._raw_item
+        self._raw = engine.workspace("contrast_raw", size)[:size].view(self.raw_dtype).view(b, capacity)
+        return self._raw
+
+    def normalise(self, engine, n, limit0):
+        """contrast=R: the raw rows' first n columns, row r offering limit0 + r of them, normalised into the buffer's
+        batch rows (one launch on the current stream).  Without contrast the rows are already there."""
+        if self.contrast is not None:
+            raw = self._raw
+            engine.contrast_rows(raw[:, :n], self.contrast, limit0=limit0, limit_step=1,
+                                 out=self.batch_rows(raw.shape[0], raw.shape[1], engine.device)[:, :n])
 
     def window(self, b):
         """The context rows and the batch's b rows behind them: what the sequence search reads."""
@@ -205,10 +244,19 @@ class SdavLoopClosureDetector:
     the candidates (dlc_sequence_topk, include/dlc.h; Milford & Wyeth, ICRA 2012).  The detector keeps the last L - 1 score
     rows resident in front of each batch's rows, so the lists do not depend on how the frames were batched; frame t's
     line may only touch scores of frames old enough for the frame that produced them (row t - s offers the frames below
-    t - s - exclusion), and a frame with fewer than L - 1 predecessors gets (-inf, -1)."""
+    t - s - exclusion), and a frame with fewer than L - 1 predecessors gets (-inf, -1).
+
+    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
+    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
+    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
+    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
+    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
+    the lists still do not depend on the batching.  Scores are the float64 sums of L normalised values, `threshold` is compared
+    with that sum, and an empty slot is (-inf, -1); submit() / result() launch the normalisation on the stream of the
+    rows' consumers, and a poisoned stream answers (NaN, -1) as before."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, sequence=None, slopes=None, **stream_args):
+                 device=None, sequence=None, slopes=None, contrast=None, **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
@@ -216,11 +264,15 @@ class SdavLoopClosureDetector:
             raise ValueError("exclusion must be >= 0")
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
         self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
         if self.sequence is not None:
-            self._seq = _SequenceRows(self.sequence, slopes, k, torch.float64)   # the last L - 1 score rows, then the batch's
+            # the last L - 1 score rows, then the batch's
+            self._seq = _SequenceRows(self.sequence, slopes, k, torch.float64, self.contrast)
             self.slopes = self._seq.slopes
         elif slopes is not None:
             raise ValueError("slopes needs sequence=L")
+        elif contrast is not None:
+            raise ValueError("contrast needs sequence=L")
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
@@ -328,8 +380,8 @@ class SdavLoopClosureDetector:
     # ---- sequence=L: the last L - 1 score rows stay resident ---------------------------------------------------------------
     def _seq_rows(self, b):
         """Where the next batch's b score rows go: behind the context rows (_SequenceRows; the leading dimension is the
-        stream's capacity)."""
-        return self._seq.batch_rows(b, self.stream.capacity, self.stream.engine.device)
+        stream's capacity), or with contrast=R into the workspace they are normalised from."""
+        return self._seq.raw_rows(b, self.stream.capacity, self.stream.engine)
 
     def _seq_rank(self, first, b):
         """The lists of stream frames first .. first + b - 1, whose score rows sit behind the context rows; then the last
@@ -337,8 +389,9 @@ class SdavLoopClosureDetector:
         below that minus the exclusion (rows of frames before the stream began offer nothing and are never read)."""
         eng, seq = self.stream.engine, self._seq
         if seq.buf is None:
-            self._seq_rows(b)
+            seq.batch_rows(b, self.stream.capacity, eng.device)
         if first + b - 1 > 0:
+            seq.normalise(eng, first + b - 1, first - self.exclusion)
             s, i, _, _ = eng.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b - 1,
                                            limit0=first - seq.context - self.exclusion, limit_step=1, poison=self.poisoned)
         else:                                                         # the very first frame alone: nothing older
@@ -393,25 +446,39 @@ class CnnVtlLoopClosureDetector:
     k smallest sums are the candidates (dlc_cnnvtl_distance_rows into a resident int64 buffer that keeps the last L - 1
     rows, then dlc_sequence_topk with lower_is_better).  The lists do not depend on the batching; a frame with fewer than
     L - 1 predecessors gets (-1, -1).  max_distance is then compared with the sequence sum -- L distances, not one -- as the
-    SDAV detector's threshold is with its sum of scores."""
+    SDAV detector's threshold is with its sum of scores.
 
-    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None):
+    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
+    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
+    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
+    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
+    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
+    the lists still do not depend on the batching.  Distances stay lower-is-better (the standard deviation is positive); dist is
+    then the float64 sum of L normalised values, max_distance is compared with that sum (it may be negative), and an
+    empty slot is (+inf, -1)."""
+
+    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
+                 contrast=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
             raise ValueError("exclusion must be >= 0")
-        if max_distance is not None and max_distance < 0:
+        if max_distance is not None and max_distance < 0 and contrast is None:
             raise ValueError("max_distance must be >= 0 (or None)")
         if dim < 1 or capacity < 1:
             raise ValueError("dim and capacity must be positive")
         self.k, self.exclusion = int(k), int(exclusion)
-        self.max_distance = None if max_distance is None else int(max_distance)
+        self.max_distance = max_distance if max_distance is None else (int if contrast is None else float)(max_distance)
         self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
         if self.sequence is not None:
-            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64)   # the last L - 1 distance rows, then the batch's
+            # the last L - 1 distance rows, then the batch's
+            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64, self.contrast)
             self.slopes = self._seq.slopes
         elif slopes is not None:
             raise ValueError("slopes needs sequence=L")
+        elif contrast is not None:
+            raise ValueError("contrast needs sequence=L")
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -432,12 +499,15 @@ class CnnVtlLoopClosureDetector:
             return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
                                                   limit0=first - self.exclusion, limit_step=1)
         if b == 0:
+            if self.contrast is not None:
+                return _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
             return _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
         # frame first + r against the frames below first + r - exclusion, as rows behind the L - 1 rows before them; matrix
         # row m is frame first - (L - 1) + m (rows of frames before the stream began offer nothing and are never read)
         seq = self._seq
         db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
-                     out=seq.batch_rows(b, db.capacity, db.engine.device)[:, :first + b])
+                     out=seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
+        seq.normalise(db.engine, first + b, first - self.exclusion)
         s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b,
                                              limit0=first - seq.context - self.exclusion, limit_step=1, lower_is_better=True)
         seq.advance(b)
@@ -448,7 +518,7 @@ class CnnVtlLoopClosureDetector:
         sum of the L distances along the candidate's line)."""
         d, i = dist.cpu().numpy(), ids.cpu().numpy()
         lim = self.max_distance
-        return [(first_id + r, int(i[r, c]), int(d[r, c])) for r in range(d.shape[0]) for c in range(d.shape[1])
+        return [(first_id + r, int(i[r, c]), d[r, c].item()) for r in range(d.shape[0]) for c in range(d.shape[1])
                 if i[r, c] >= 0 and (lim is None or d[r, c] <= lim)]
 
 
@@ -508,6 +578,9 @@ def main(argv=None):
                          "reference's SDAV similarity (needs --network sdav; the distinctive score comes from the first batch)")
     ap.add_argument("--sequence", type=int, default=None, metavar="L",
                     help="--metric similarity: rank by the sum of the scores along a line of L frames (sequence search)")
+    ap.add_argument("--contrast", type=int, default=None, metavar="R",
+                    help="with --sequence: normalise every score against the R key-frames on either side of it first "
+                         "(SeqSLAM's local contrast normalisation), R in 1..32")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
@@ -527,6 +600,10 @@ def main(argv=None):
         ap.error("--sequence needs --metric similarity")
     if args.sequence is not None and not 1 <= args.sequence <= 64:
         ap.error("--sequence must be 1..64")
+    if args.contrast is not None and args.sequence is None:
+        ap.error("--contrast needs --sequence")
+    if args.contrast is not None and not 1 <= args.contrast <= 32:
+        ap.error("--contrast must be 1..32")
     if args.threshold is None:
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
@@ -565,7 +642,8 @@ def _stream(args, files):
             # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
-                                          exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence)
+                                          exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
+                                          contrast=args.contrast)
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))

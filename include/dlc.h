@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 15
+#define DLC_ABI_VERSION 16
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -598,6 +598,37 @@ int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows,
                       int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_slope,
                       void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/*
+ * SeqSLAM's local contrast normalisation of score rows (Milford & Wyeth, ICRA 2012, III-B): every cell against its
+ * neighbourhood within its own row, (x - local mean) / local std, before dlc_sequence_topk sums along lines -- a stretch
+ * of key-frames that resembles everything goes flat, a true revisit stands out from its neighbours.
+ * INPUT.  M = scores [rows, ld], n <= ld columns in use, dtype DLC_F64, DLC_F32 or DLC_I64.  Row r offers its first
+ * lim(r) = clamp(limit0 + r * limit_step, 0, n) entries (the convention of dlc_cnnvtl_distance_rows and
+ * dlc_sequence_topk; any limit_step, negative included).  radius: 1..32 (SeqSLAM's R_window = 10 is radius 5).
+ * For a cell (r, j) with j < lim(r): a = max(0, j - radius), b = min(lim(r), j + radius + 1), cnt = b - a and
+ * x_c = (double) M[r][c] (exact from fp32; from int64 rounded to nearest even, exact below 2^53).  All arithmetic is
+ * fp64, every operation rounded on its own (no fma contraction), division and sqrt the IEEE correctly rounded ones:
+ *     s    = x_a;  s = s + x_{a+1};  ...  s = s + x_{b-1}          (left to right; starts FROM x_a, not from 0)
+ *     mean = s / (double)cnt
+ *     q    = (x_a - mean) * (x_a - mean);  q = q + (x_c - mean) * (x_c - mean) for c = a+1 .. b-1 (left to right)
+ *     sd   = sqrt(q / (double)(cnt - 1))                           (the sample standard deviation, as MATLAB's std)
+ *     out[r][j] = 0.0 if cnt < 2 or sd == 0.0, else (x_j - mean) / sd
+ * Each cell's window is summed on its own (no running sum across cells), so a row's result depends on that row and its
+ * limit alone: not on the tiling, the batching or the plan.  An infinity or a NaN in the window yields what IEEE
+ * arithmetic gives, NaN (a cell dlc_sequence_topk does not offer).  sd > 0 keeps the order of merit within a
+ * neighbourhood: lower_is_better passes through unchanged.
+ * OUTPUT.  out is fp64 [rows, ld_out], ld_out >= n.  EVERY OTHER WORD OF out KEEPS ITS VALUE: the cells at or past
+ * lim(r) and the columns n .. ld_out-1.  No element at or past lim(r) of its row is read.  out must not overlap scores.
+ * When every lim(r) is 0 nothing is launched and the call returns DLC_OK.
+ * scores rows need only their element's alignment (8 bytes, 4 for DLC_F32) and any ld; out 8 bytes.  No workspace; one
+ * launch on `stream` (no memset, no atomics); never synchronises.  Any rows >= 1, 1 <= n < 2^31.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, an unknown dtype, rows < 1, n < 1, radius outside 1..32, ld < n or
+ * ld_out < n; DLC_ERR_BAD_SHAPE for n >= 2^31.  Nothing is written then.
+ */
+int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t n, int64_t ld,
+                      int64_t limit0, int64_t limit_step, int radius,
+                      double* out, int64_t ld_out, void* stream);
 
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
