@@ -795,6 +795,38 @@ int dlc_cosine_select_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, in
  *                               (taking, per query, the new list where status == 2) gives the exact
  *                               global top-k.  dlc_cosine_topk / dlc_cosine_select_topk run it
  *                               themselves; a sharded caller runs it when any status is 1.
+ *
+ * What each stage hands out, exactly (tests/shard_protocol_oracle.py restates it on the host; tests/
+ * test_gpu_shard_protocol.py holds the library to it).  tau_shard = dlc_cosine_score_error_bound of the shard's
+ * shape, tau_any = dlc_cosine_score_error_bound_any_plan(d), both times tau_scale[q] where the caller supplies one:
+ *   group_ids / group_max  The min(kg, groups of the shard) groups with the largest fp32 maxima, ordered by (maximum
+ *                          descending, group index ascending) -- among groups of equal maxima the lower index is
+ *                          listed first, and is the one listed at all where the list ends inside a tie; each group
+ *                          once; the -1 / -inf padding only at the end.  group_max[e] is within tau_shard of the
+ *                          fp64 maximum of group e's rows (rows past n do not count), no unlisted row of the shard
+ *                          scores above group_max[kg] + tau_shard in fp64, group_max[kg] <= every listed maximum,
+ *                          and it is -inf exactly when every group of the shard is listed.
+ *   the filter             "Strictly larger" is the comparison of the fp32 values (equal maxima never drop one
+ *                          another; -inf entries count for nothing), over the kg listed columns of all `parts`
+ *                          shards, the shard's own included.  parts = 0 keeps every listed group.
+ *   the part               The k best rows of the surviving groups by (f64 key descending, row ascending), their fp64
+ *                          scores THE scores; (-inf, -1) past the rows found -- all of it where no group survives.
+ *                          The group list is only read.
+ *   out_bound              max(column kg of every shard, every listed maximum the filter drops on any shard), -inf
+ *                          when there is neither: a function of all_group_max alone, so bit-equal on every shard.
+ *                          (parts = 0: the shard's own column kg.)  No row outside the surviving groups of all shards
+ *                          scores above out_bound + tau_any in fp64.
+ *   the merge              Orders the parts' entries by (f64 key descending, global row ascending), whatever order the
+ *                          parts were gathered in; entries with idx < 0 are empty.  out_status[q] = 0 when bound[q]
+ *                          is -inf (nothing was left behind -- also when fewer than k rows exist at all) or when k rows
+ *                          were found and the k-th fp64 score > (double)bound[q] + tau * (double)tau_scale[q]; 1
+ *                          otherwise.  A query with status 0 holds the exact global top-k already.
+ *   the exhaustive round   Touches the queries with status 1 only: their lists are replaced and their status becomes
+ *                          2; every other query's status, scores and rows are left as they are.  lower_stride = 0
+ *                          reads one number for every query.  tau must be >= 0 (NaN is refused), lower_stride >= 0.
+ * Refusals write nothing: dlc_cosine_rescore_topk with parts < 0 or parts > 0 and no all_group_max
+ * (DLC_ERR_BAD_ARG); dlc_topk_merge_strided with parts < 1, a part stride below q * k, tau < 0 or NaN
+ * (DLC_ERR_BAD_ARG) or parts * k > 2048 (DLC_ERR_BAD_SHAPE).
  */
 int dlc_cosine_groups_per_query(int k);
 int dlc_cosine_select_groups(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t ldq,
