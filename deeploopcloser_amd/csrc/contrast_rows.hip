@@ -162,8 +162,7 @@ extern "C" int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, in
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: scores and out must be aligned to their element");
     if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "contrast_rows: n must be below 2^31");
     // columns any row offers (limits are linear in the row, so the largest sits at an end)
-    const int64_t l0 = dlc::row_limit(0, n, limit0, limit_step), l1 = dlc::row_limit(rows - 1, n, limit0, limit_step);
-    const int64_t cols = l0 > l1 ? l0 : l1;
+    const int64_t cols = dlc::max_row_limit(0, rows - 1, n, limit0, limit_step);
     if (cols == 0) return DLC_OK;
     CrArgs a;
     a.M = scores; a.out = out; a.ld = ld; a.ld_out = ld_out; a.limit0 = limit0; a.limit_step = limit_step;

@@ -149,8 +149,7 @@ extern "C" int dlc_cosine_score_rows(dlc_ctx* ctx, int dtype, const void* Q, int
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cosine_score_rows: outputs must be 8-byte aligned");
     if (q > 0x7fffff00ll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cosine_score_rows: q too large");
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t l0 = dlc::row_limit(0, n, limit0, limit_step), l1 = dlc::row_limit(q - 1, n, limit0, limit_step);
-    const int64_t lmax = l0 > l1 ? l0 : l1;
+    const int64_t lmax = dlc::max_row_limit(0, q - 1, n, limit0, limit_step);
     if (lmax == 0) return DLC_OK;
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);

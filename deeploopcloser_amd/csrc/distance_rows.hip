@@ -131,8 +131,7 @@ extern "C" int dlc_cnnvtl_distance_rows(dlc_ctx* ctx, const int8_t* queries, int
     const int64_t qtiles = dlc::cdiv(Q, p.qt());
     if (qtiles > 65535) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_rows: Q must not exceed 2^20");
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t l0 = dlc::row_limit(0, N, limit0, limit_step), l1 = dlc::row_limit(Q - 1, N, limit0, limit_step);
-    const int64_t lmax = l0 > l1 ? l0 : l1;
+    const int64_t lmax = dlc::max_row_limit(0, Q - 1, N, limit0, limit_step);
     if (lmax == 0) return DLC_OK;
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);

@@ -208,8 +208,7 @@ extern "C" int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int
     hipStream_t st = (hipStream_t)stream;
 
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t l0 = dlc::row_limit(0, N, limit0, limit_step), l1 = dlc::row_limit(Q - 1, N, limit0, limit_step);
-    const int64_t lmax = l0 > l1 ? l0 : l1;
+    const int64_t lmax = dlc::max_row_limit(0, Q - 1, N, limit0, limit_step);
     const TkPlan p = tk_plan(Q);
     int64_t G = 0;
     if (lmax > 0) {

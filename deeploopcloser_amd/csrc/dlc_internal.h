@@ -97,6 +97,11 @@ __host__ __device__ __forceinline__ int64_t row_limit(int64_t r, int64_t n, int6
     const int64_t l = limit0 + r * limit_step;
     return l < 0 ? 0 : (l > n ? n : l);
 }
+// The largest row_limit of rows r_first .. r_last: at one end of the range (host entry points size their launches by it).
+inline int64_t max_row_limit(int64_t r_first, int64_t r_last, int64_t n, int64_t limit0, int64_t limit_step) {
+    const int64_t la = row_limit(r_first, n, limit0, limit_step), lb = row_limit(r_last, n, limit0, limit_step);
+    return la > lb ? la : lb;
+}
 
 // A scan's column tiles shared out among G slabs so that row_tiles x G comes to about max_wg workgroups.  max_slabs
 // bounds G for every smaller col_tiles too (the split's own G is not monotonic in col_tiles): it sizes the workspace.

@@ -295,8 +295,7 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
     hipStream_t st = (hipStream_t)stream;
 
     // columns any output row offers (limits are linear in the row); the dense output covers the matrix's n columns
-    const int64_t l0 = dlc::row_limit(row0, n, limit0, limit_step), l1 = dlc::row_limit(rows - 1, n, limit0, limit_step);
-    const int64_t cols = seq_out ? n : (l0 > l1 ? l0 : l1);
+    const int64_t cols = seq_out ? n : dlc::max_row_limit(row0, rows - 1, n, limit0, limit_step);
     dlc::SlabSplit slabs = {1, 1};
     if (cols > 0) slabs = dlc::split_slabs(dlc::cdiv(rows, SQ_MAX_RB), dlc::cdiv(cols, SQ_SLAB_UNIT), TL_MAX_SLABS);
     const int64_t G = slabs.G;

@@ -879,22 +879,43 @@ class Engine:
         padded[:, :d] = x[:, :d]
         return padded
 
+    def _int8_pair(self, who, q, db, d):
+        """The checks of the distance calls' operands q [Q, >= d], db [N, >= d] (int8, on the device) -> d (None: the
+        rows' one width)."""
+        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
+            raise ValueError("%s: q and db must be 2-D int8" % who)
+        if q.device != self.device or db.device != self.device:
+            raise ValueError("%s: q and db must be on %s" % (who, self.device))
+        if d is None:
+            if q.shape[1] != db.shape[1]:
+                raise ValueError("%s: q and db widths differ (%d, %d)" % (who, q.shape[1], db.shape[1]))
+            d = q.shape[1]
+        d = int(d)
+        if d > q.shape[1] or d > db.shape[1]:
+            raise ValueError("%s: d=%d exceeds the rows' width" % (who, d))
+        return d
+
+    def _rows_out(self, what, t, rows, n, dtype, kind, fill=None, wider=False):
+        """The [rows, n] result of a call that writes each row's offered cells only: allocated (and filled with `fill`,
+        "not offered", unless None) when t is None, else the caller-kept t, checked -- `what` and `kind` name it in the
+        error ("cosine_score_rows: out", "a float64"); wider: t may have more than n columns."""
+        if t is None:
+            t = torch.empty((rows, n), dtype=dtype, device=self.device)
+            if fill is not None:
+                t.fill_(fill)
+        elif not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or \
+                (t.shape[1] < n if wider else t.shape[1] != n) or t.dtype != dtype or t.device != self.device or \
+                (t.shape[1] > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n):
+            raise ValueError("%s must be %s tensor of shape (%d, %s%d) on %s with unit column stride and rows at least %d "
+                             "apart" % (what, kind, rows, ">= " if wider else "", n, self.device, n))
+        return t
+
     def cnnvtl_distance_topk(self, q, db, k, d=None, limit0=None, limit_step=0, out=None):
         """(dist [Q, k] int64, idx [Q, k] int64): the k rows of db [N, D] int8 nearest to each query row of q [Q, D] int8 by
         the cnn_vtl distance, distance ascending, ties -> the lower row; query r sees the first min(N, limit0 + r *
         limit_step) rows (limit0 None = N); (-1, -1) where it sees fewer than k.  d: the descriptor length when the rows are
         padded (the bytes past d are ignored); out: a caller-kept (dist, idx) pair."""
-        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
-            raise ValueError("cnnvtl_distance_topk: q and db must be 2-D int8")
-        if q.device != self.device or db.device != self.device:
-            raise ValueError("cnnvtl_distance_topk: q and db must be on %s" % self.device)
-        if d is None:
-            if q.shape[1] != db.shape[1]:
-                raise ValueError("cnnvtl_distance_topk: q and db widths differ (%d, %d)" % (q.shape[1], db.shape[1]))
-            d = q.shape[1]
-        d = int(d)
-        if d > q.shape[1] or d > db.shape[1]:
-            raise ValueError("cnnvtl_distance_topk: d=%d exceeds the rows' width" % d)
+        d = self._int8_pair("cnnvtl_distance_topk", q, db, d)
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("cnnvtl_distance_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         nq, n = q.shape[0], db.shape[0]
@@ -926,26 +947,10 @@ class Engine:
         as sequence_scores writes it -- when the engine allocates the result.  d: the descriptor length when the rows
         are padded (the bytes past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows
         lie further apart than N (its columns past N are left alone too)."""
-        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
-            raise ValueError("cnnvtl_distance_rows: q and db must be 2-D int8")
-        if q.device != self.device or db.device != self.device:
-            raise ValueError("cnnvtl_distance_rows: q and db must be on %s" % self.device)
-        if d is None:
-            if q.shape[1] != db.shape[1]:
-                raise ValueError("cnnvtl_distance_rows: q and db widths differ (%d, %d)" % (q.shape[1], db.shape[1]))
-            d = q.shape[1]
-        d = int(d)
-        if d > q.shape[1] or d > db.shape[1]:
-            raise ValueError("cnnvtl_distance_rows: d=%d exceeds the rows' width" % d)
+        d = self._int8_pair("cnnvtl_distance_rows", q, db, d)
         nq, n = q.shape[0], db.shape[0]
-        if out is None:
-            out = torch.empty((nq, n), dtype=torch.int64, device=self.device)
-            if limit0 is not None:
-                out.fill_(-1)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (nq, n) or out.dtype != torch.int64 or \
-                out.device != self.device or (n > 1 and out.stride(1) != 1) or (nq > 1 and out.stride(0) < n):
-            raise ValueError("cnnvtl_distance_rows: out must be an int64 tensor of shape (%d, %d) on %s with unit column "
-                             "stride and rows at least %d apart" % (nq, n, self.device, n))
+        out = self._rows_out("cnnvtl_distance_rows: out", out, nq, n, torch.int64, "an int64",
+                             None if limit0 is None else -1)
         if nq == 0 or n == 0:
             return out
         if d == 0:                                               # empty descriptors: every distance is 0
@@ -963,6 +968,21 @@ class Engine:
 
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
 
+    def _score_matrix(self, who, scores, n, nothing):
+        """The checks of a score-matrix operand [rows, >= n] (fp64, fp32 or int64 on the device) -> (scores, rows, n, ld):
+        a row-strided view is taken as it is, anything else made contiguous."""
+        if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype not in self._SEQ_DTYPES:
+            raise ValueError("%s: scores must be a 2-D float64, float32 or int64 tensor" % who)
+        if scores.device != self.device:
+            raise ValueError("%s: scores must be on %s" % (who, self.device))
+        rows = scores.shape[0]
+        n = scores.shape[1] if n is None else int(n)
+        if rows < 1 or n < 1 or n > scores.shape[1]:
+            raise ValueError("%s: scores [%d, %d] with n=%d: nothing to %s" % (who, rows, scores.shape[1], n, nothing))
+        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
+            scores = scores.contiguous()
+        return scores, rows, n, scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+
     def sequence_topk(self, scores, length, offsets, k=None, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,
                       dense=False, poison=None):
         """The sequence search of dlc_sequence_topk (include/dlc.h) over scores [rows, >= n] (fp64, fp32 or int64 on the
@@ -972,17 +992,7 @@ class Engine:
         idx int64, slope int32, dense): fp64 scores (int64 for int64 input); k None -> no lists (None three times);
         dense: the [rows - row0, n] cell scores as well (NaN / -1 where a cell is not offered), else None.
         poison: a device int64 [1] read by the kernels; non-zero -> every fp64 slot NaN, idx and slope -1."""
-        if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype not in self._SEQ_DTYPES:
-            raise ValueError("sequence_topk: scores must be a 2-D float64, float32 or int64 tensor")
-        if scores.device != self.device:
-            raise ValueError("sequence_topk: scores must be on %s" % self.device)
-        rows = scores.shape[0]
-        n = scores.shape[1] if n is None else int(n)
-        if rows < 1 or n < 1 or n > scores.shape[1]:
-            raise ValueError("sequence_topk: scores [%d, %d] with n=%d: nothing to search" % (rows, scores.shape[1], n))
-        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
-            scores = scores.contiguous()
-        ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+        scores, rows, n, ld = self._score_matrix("sequence_topk", scores, n, "search")
         off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
         if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
             raise ValueError("sequence_topk: offsets must be an integer table [n_slopes, L=%d]" % int(length))
@@ -1023,28 +1033,11 @@ class Engine:
         offered keep what `out` held, and hold NaN -- "not offered", as sequence_scores writes it -- when the engine
         allocates the result.  out: a caller-kept fp64 tensor whose first n columns are written (out[:, :n] is returned);
         its rows may lie further apart than its width (a row-strided view is taken as it is)."""
-        if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype not in self._SEQ_DTYPES:
-            raise ValueError("contrast_rows: scores must be a 2-D float64, float32 or int64 tensor")
-        if scores.device != self.device:
-            raise ValueError("contrast_rows: scores must be on %s" % self.device)
+        scores, rows, n, ld = self._score_matrix("contrast_rows", scores, n, "normalise")
         if not 1 <= int(radius) <= 32:
             raise ValueError("contrast_rows: radius=%d outside 1..32" % int(radius))
-        rows = scores.shape[0]
-        n = scores.shape[1] if n is None else int(n)
-        if rows < 1 or n < 1 or n > scores.shape[1]:
-            raise ValueError("contrast_rows: scores [%d, %d] with n=%d: nothing to normalise" % (rows, scores.shape[1], n))
-        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
-            scores = scores.contiguous()
-        ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
-        if out is None:
-            out = torch.empty((rows, n), dtype=torch.float64, device=self.device)
-            if limit0 is not None or limit_step != 0:
-                out.fill_(float("nan"))
-        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < n or \
-                out.dtype != torch.float64 or out.device != self.device or (out.shape[1] > 1 and out.stride(1) != 1) or \
-                (rows > 1 and out.stride(0) < n):
-            raise ValueError("contrast_rows: out must be a float64 tensor of shape (%d, >= %d) on %s with unit column stride "
-                             "and rows at least %d apart" % (rows, n, self.device, n))
+        out = self._rows_out("contrast_rows: out", out, rows, n, torch.float64, "a float64",
+                             float("nan") if limit0 is not None or limit_step != 0 else None, wider=True)
         ld_out = out.stride(0) if rows > 1 else n
         self._check(self.lib.dlc_contrast_rows(self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld,
                                                 n if limit0 is None else int(limit0), int(limit_step), int(radius), _ptr(out),
@@ -1361,15 +1354,8 @@ class Engine:
         want_scores = out is not None or not want_keys
 
         def result(t, dtype, name, fill):
-            if t is None:
-                t = torch.empty((nq, n), dtype=dtype, device=self.device)
-                if limit0 is not None:
-                    t.fill_(fill)
-            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != (nq, n) or t.dtype != dtype or \
-                    t.device != self.device or (n > 1 and t.stride(1) != 1) or (nq > 1 and t.stride(0) < n):
-                raise ValueError("cosine_score_rows: %s must be a %s tensor of shape (%d, %d) on %s with unit column "
-                                 "stride and rows at least %d apart" % (name, dtype, nq, n, self.device, n))
-            return t
+            return self._rows_out("cosine_score_rows: " + name, t, nq, n, dtype, "a %s" % dtype,
+                                  None if limit0 is None else fill)
 
         o_s = result(out, torch.float64, "out", float("nan")) if want_scores else None
         o_k = result(out_keys, torch.int64, "out_keys", -(1 << 63)) if want_keys else None

@@ -50,6 +50,28 @@ def _nothing_older(b, k, fill, dtype, device):
             torch.full((b, k), -1, dtype=torch.int64, device=device))
 
 
+def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False):
+    """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
+    if sequence is not None:
+        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better)
+    if slopes is not None:
+        raise ValueError("slopes needs sequence=L")
+    if contrast is not None:
+        raise ValueError("contrast needs sequence=L")
+    return None
+
+
+def _loops(values, ids, first_id, limit, lower_is_better=False):
+    """[(frame id, matched frame id, value)] of the candidates whose value is at or above `limit` (at or below it with
+    lower_is_better; None: every candidate), row by row, best first.  The value is a Python int where the values are
+    integers, else a float."""
+    v, i = values.cpu().numpy(), ids.cpu().numpy()
+    ok = i >= 0
+    if limit is not None:
+        ok &= (v <= limit) if lower_is_better else (v >= limit)
+    return [(first_id + int(r), int(i[r, c]), v[r, c].item()) for r, c in zip(*np.nonzero(ok))]
+
+
 class LoopClosureDetector:
     """The cosine detector: every new frame against the key-frames more than `exclusion` frames older, the k best by the
     cosine path's fp64 score (dlc_cosine_topk_older), candidates at or above `threshold`.
@@ -66,13 +88,9 @@ class LoopClosureDetector:
     compared with that SUM of L scores, not with one score, as the SDAV detector's is: a mean of 0.9 is threshold=0.9 * L.
     (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)
 
-    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
-    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
-    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
-    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
-    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
-    the lists still do not depend on the batching.  Scores are the float64 sums of L normalised values (no 2^-40 rescale: the
-    keys' scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1)."""
+    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the key rows in front of the
+    sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values (no 2^-40 rescale: the keys'
+    scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1)."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
                  device=None, sequence=None, slopes=None, contrast=None):
@@ -83,14 +101,10 @@ class LoopClosureDetector:
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
-        if self.sequence is not None:
-            # the last L - 1 key rows, then the batch's
-            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64, self.contrast)
+        # the last L - 1 key rows, then the batch's
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64)
+        if self._seq is not None:
             self.slopes = self._seq.slopes
-        elif slopes is not None:
-            raise ValueError("slopes needs sequence=L")
-        elif contrast is not None:
-            raise ValueError("contrast needs sequence=L")
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     def __len__(self):
@@ -127,8 +141,15 @@ class LoopClosureDetector:
         g0, _ = db.append(x)                               # normalised once, used as query and as key-frame
         g0 -= db.row_offset
         q = db.rows[g0:g0 + b]
-        if self.sequence is not None:
-            return self._seq_step(q, g0, b)
+        if self._seq is not None:
+            # the frames' key rows against the frames below g0 + r - exclusion, searched behind the L - 1 rows before them
+            db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1,
+                          out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :g0 + b])
+            s, i = self._seq.search(db.engine, b, g0 + b, g0 - self.exclusion)
+            if self.contrast is not None:                    # fp64 sums of normalised values as they are
+                return s, i
+            # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
+            return torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i
         n_search = g0 + b - 1 - self.exclusion             # what the newest frame of the batch may see
         if n_search <= 0:
             return _nothing_older(b, k, float("-inf"), torch.float32, db.engine.device)
@@ -136,32 +157,10 @@ class LoopClosureDetector:
         # (dlc_cosine_topk_older -- the lists of a k + b - 1 match followed by dlc_topk_keep_older / first_k_eligible)
         return db.engine.match_topk(q, db.rows[:n_search], k, older_than=g0 - self.exclusion)
 
-    def _seq_step(self, q, g0, b):
-        """The lists of frames g0 .. g0 + b - 1 (already key-frames) by the sequence search: their key rows against the
-        frames below g0 + r - exclusion go behind the L - 1 rows before them; matrix row m is frame g0 - (L - 1) + m (rows
-        of frames before the stream began offer nothing and are never read).  Then the last L - 1 rows become the next
-        batch's context."""
-        db, seq = self.db, self._seq
-        db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1, out=seq.raw_rows(b, db.capacity, db.engine)[:, :g0 + b])
-        seq.normalise(db.engine, g0 + b, g0 - self.exclusion)
-        s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=g0 + b,
-                                             limit0=g0 - seq.context - self.exclusion, limit_step=1)
-        seq.advance(b)
-        if self.contrast is not None:                        # fp64 sums of normalised values as they are
-            return s, i
-        # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
-        return torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i
-
     def loops(self, scores, ids, first_id):
         """[(frame id, matched key-frame id, score)] of the candidates at or above the threshold (with sequence=L: the sum
         of the L scores along the candidate's line)."""
-        s, i = scores.cpu().numpy(), ids.cpu().numpy()
-        out = []
-        for r in range(s.shape[0]):
-            for c in range(s.shape[1]):
-                if i[r, c] >= 0 and s[r, c] >= self.threshold:
-                    out.append((first_id + r, int(i[r, c]), float(s[r, c])))
-        return out
+        return _loops(scores, ids, first_id, self.threshold)
 
 
 class _SequenceRows:
@@ -169,13 +168,18 @@ class _SequenceRows:
     rows are the context -- the score rows of the L - 1 frames before the batch -- and whose next rows receive the
     batch's.  ld is the store's capacity, so a row never moves while the store does not grow.  It also holds what the
     sequence search of those rows takes, checked: `slopes`, an int32 table [1..16, L] (default sequence.slope_offsets(L)),
-    and a k within the search's range.
+    and a k within the search's range.  A detector gets the batch's rows' destination (raw_rows), fills them with its own
+    kernel and calls search().
 
-    contrast = R (1..32): the detector's rows are normalised on their way in (dlc_contrast_rows) -- the batch's raw rows,
-    of `dtype`, go into an engine workspace (raw_rows), normalise() writes them behind the context rows, and the buffer
-    is float64.  A row's normalisation depends on that row alone, so the context rows stay valid."""
+    contrast = R (1..32) puts SeqSLAM's local contrast normalisation in front of the sequence search: the batch's raw
+    rows, of `dtype`, go into an engine workspace (raw_rows), dlc_contrast_rows (include/dlc.h) writes every cell as
+    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, behind
+    the context rows (normalise) -- the buffer is float64 then -- and the lines are summed over that.  A stretch of
+    key-frames that resembles every frame goes flat; a true revisit stands out from its neighbours.  A row's
+    normalisation depends on that row alone, so the context rows stay valid and the lists still do not depend on the
+    batching."""
 
-    def __init__(self, length, slopes, k, dtype, contrast=None):
+    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False):
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
             raise ValueError("sequence=%d outside 1..64" % length)
@@ -186,6 +190,7 @@ class _SequenceRows:
             raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
         if contrast is not None and not 1 <= contrast <= 32:
             raise ValueError("contrast=%d outside 1..32" % contrast)
+        self.length, self.k, self.lower_is_better = length, k, lower_is_better
         self.contrast, self.raw_dtype, self._raw = contrast, dtype, None
         self._raw_item = torch.empty((), dtype=dtype).element_size()
         self.context, self.dtype, self.buf = length - 1, dtype if contrast is None else torch.float64, None
@@ -230,6 +235,18 @@ class _SequenceRows:
             keep = buf[b:b + ctx]
             buf[:ctx] = keep.clone() if b < ctx else keep             # (source and destination overlap for short batches)
 
+    def search(self, engine, b, n, limit0, poison=None):
+        """(values [b, k], ids [b, k]) of the batch's b frames, whose raw rows are written: over the first n columns, the
+        batch's row r offering limit0 + r of them and every context row one fewer than the row behind it (matrix row m
+        is the frame L - 1 - m before the batch's first; rows of frames before the stream began offer nothing and are never
+        read).  Then the last L - 1 rows become the next batch's context."""
+        self.normalise(engine, n, limit0)
+        s, i, _, _ = engine.sequence_topk(self.window(b), self.length, self.slopes, k=self.k, row0=self.context, n=n,
+                                          limit0=limit0 - self.context, limit_step=1,
+                                          lower_is_better=self.lower_is_better, poison=poison)
+        self.advance(b)
+        return s, i
+
 
 class SdavLoopClosureDetector:
     """The same question asked with the REFERENCE's similarity (SimilarityCalculator.similarity_score,
@@ -246,12 +263,8 @@ class SdavLoopClosureDetector:
     line may only touch scores of frames old enough for the frame that produced them (row t - s offers the frames below
     t - s - exclusion), and a frame with fewer than L - 1 predecessors gets (-inf, -1).
 
-    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
-    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
-    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
-    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
-    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
-    the lists still do not depend on the batching.  Scores are the float64 sums of L normalised values, `threshold` is compared
+    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the score rows in front of
+    the sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values, `threshold` is compared
     with that sum, and an empty slot is (-inf, -1); submit() / result() launch the normalisation on the stream of the
     rows' consumers, and a poisoned stream answers (NaN, -1) as before."""
 
@@ -265,14 +278,10 @@ class SdavLoopClosureDetector:
         self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
-        if self.sequence is not None:
-            # the last L - 1 score rows, then the batch's
-            self._seq = _SequenceRows(self.sequence, slopes, k, torch.float64, self.contrast)
+        # the last L - 1 score rows, then the batch's
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64)
+        if self._seq is not None:
             self.slopes = self._seq.slopes
-        elif slopes is not None:
-            raise ValueError("slopes needs sequence=L")
-        elif contrast is not None:
-            raise ValueError("contrast needs sequence=L")
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
@@ -286,6 +295,8 @@ class SdavLoopClosureDetector:
         outside its fixed range or a NaN was appended, now or earlier: `poisoned`, SimilarityStream.stats[1]) returns
         (NaN, -1) in every slot -- "these scores mean nothing", visible in the tensors themselves without a host read;
         loops() raises."""
+        if self._pending is not None:                                 # a submitted batch's rows are ranked before this one's,
+            self._flush()                                             # and nothing is in flight when the stream grows
         st = self.stream
         eng = st.engine
         x = eng.to_device(frames, torch.float64)
@@ -293,18 +304,28 @@ class SdavLoopClosureDetector:
             x = x.unsqueeze(0)
         b = x.shape[0]
         first = st.append(x)                                          # all B frames become resident: one quantisation launch
-        if self.sequence is not None:
-            if first + b - 1 > 0:
-                eng.sdav_stream_query_batch(st.state, st.desc, first, b, st.score, st.a, st.b, out=self._seq_rows(b), stats=st.stats)
-            return self._seq_rank(first, b)
         if first + b - 1 == 0:                                        # the very first frame alone: nothing older
+            if self._seq is not None:                                 # (its row offers nothing, and is context all the same)
+                self._seq.batch_rows(b, st.capacity, eng.device)
+                self._seq.advance(b)
             return self._nothing_older(b)
         # frame first + r against every older frame, all B of them in one pair of launches (dlc_sdav_stream_query_batch):
         # rows[r, :first + r]
-        rows = st.query_batch(first, b)
-        # the k best of the frames old enough -- one launch for the batch (dlc_topk_rows_f64: score descending, ties ->
-        # the older frame; the kernel reads the stream's poison word and answers (NaN, -1) everywhere when it is set)
-        return eng.topk_rows_f64(rows, first - self.exclusion, 1, self.k, poison=self.poisoned)
+        if self._seq is None:
+            rows = st.query_batch(first, b)
+        else:
+            rows = eng.sdav_stream_query_batch(st.state, st.desc, first, b, st.score, st.a, st.b,
+                                               out=self._seq.raw_rows(b, st.capacity, eng), stats=st.stats)
+        return self._rank(rows, first, b)
+
+    def _rank(self, rows, first, b):
+        """The lists of stream frames first .. first + b - 1 from their score rows -- one launch for the batch, which reads
+        the stream's poison word and answers (NaN, -1) everywhere when it is set.  Without sequence=L the k best of the
+        frames old enough (dlc_topk_rows_f64: score descending, ties -> the older frame); with it the rows sit where
+        the search's raw_rows put them, and the last L - 1 of them become the next batch's context."""
+        if self._seq is None:
+            return self.stream.engine.topk_rows_f64(rows, first - self.exclusion, 1, self.k, poison=self.poisoned)
+        return self._seq.search(self.stream.engine, b, first + b - 1, first - self.exclusion, poison=self.poisoned)
 
     def _nothing_older(self, b):
         """(-inf, -1) in every slot of b frames' lists; (NaN, -1) once the stream is poisoned."""
@@ -368,36 +389,11 @@ class SdavLoopClosureDetector:
         st, eng = self.stream, self.stream.engine
         slot = self._slots[self._pending % 2]
         torch.cuda.current_stream(eng.device).wait_event(slot["products"])
-        rows = slot["rows"][:slot["b"]] if self.sequence is None else self._seq_rows(slot["b"])
+        rows = slot["rows"][:slot["b"]] if self._seq is None else self._seq.raw_rows(slot["b"], st.capacity, eng)
         eng.sdav_stream_query_batch_staged(st.state, st.desc, slot["first"], slot["b"], st.score, 2, rows, slot["ws"], st.a, st.b,
                                            stats=st.stats)
-        if self.sequence is None:
-            slot["out"] = eng.topk_rows_f64(rows, slot["first"] - self.exclusion, 1, self.k, poison=self.poisoned)
-        else:
-            slot["out"] = self._seq_rank(slot["first"], slot["b"])
+        slot["out"] = self._rank(rows, slot["first"], slot["b"])
         self._pending = None
-
-    # ---- sequence=L: the last L - 1 score rows stay resident ---------------------------------------------------------------
-    def _seq_rows(self, b):
-        """Where the next batch's b score rows go: behind the context rows (_SequenceRows; the leading dimension is the
-        stream's capacity), or with contrast=R into the workspace they are normalised from."""
-        return self._seq.raw_rows(b, self.stream.capacity, self.stream.engine)
-
-    def _seq_rank(self, first, b):
-        """The lists of stream frames first .. first + b - 1, whose score rows sit behind the context rows; then the last
-        L - 1 rows become the next batch's context.  Matrix row m is stream frame first - (L - 1) + m: it offers the frames
-        below that minus the exclusion (rows of frames before the stream began offer nothing and are never read)."""
-        eng, seq = self.stream.engine, self._seq
-        if seq.buf is None:
-            seq.batch_rows(b, self.stream.capacity, eng.device)
-        if first + b - 1 > 0:
-            seq.normalise(eng, first + b - 1, first - self.exclusion)
-            s, i, _, _ = eng.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b - 1,
-                                           limit0=first - seq.context - self.exclusion, limit_step=1, poison=self.poisoned)
-        else:                                                         # the very first frame alone: nothing older
-            s, i = self._nothing_older(b)
-        seq.advance(b)
-        return s, i
 
     def result(self, ticket):
         """(scores [B, k] float64, ids [B, k] int64) of a submitted batch, in the current stream's order."""
@@ -425,10 +421,9 @@ class SdavLoopClosureDetector:
     def loops(self, scores, ids, first_id):
         """[(frame id, older frame id, score)] at or above the threshold; raises when the stream has been poisoned (a value
         outside its fixed range: SimilarityStream.stats[1])."""
-        s, i = scores.cpu().numpy(), ids.cpu().numpy()
+        found = _loops(scores, ids, first_id, self.threshold)
         self._check_poison()
-        return [(first_id + r, int(i[r, c]), float(s[r, c])) for r in range(s.shape[0]) for c in range(s.shape[1])
-                if i[r, c] >= 0 and s[r, c] >= self.threshold]
+        return found
 
 
 class CnnVtlLoopClosureDetector:
@@ -448,12 +443,8 @@ class CnnVtlLoopClosureDetector:
     L - 1 predecessors gets (-1, -1).  max_distance is then compared with the sequence sum -- L distances, not one -- as the
     SDAV detector's threshold is with its sum of scores.
 
-    contrast = R (None: off; needs sequence=L, R in 1..32) puts SeqSLAM's local contrast normalisation in front of the
-    sequence search: the batch's raw rows go into a workspace, dlc_contrast_rows (include/dlc.h) writes every cell as
-    (x - mean) / std over the R key-frames on either side of it, within the frame's own row and what it may see, into the
-    resident buffer -- float64 then -- and the lines are summed over that.  A stretch of key-frames that resembles every
-    frame goes flat; a true revisit stands out from its neighbours.  A row's normalisation depends on that row alone, so
-    the lists still do not depend on the batching.  Distances stay lower-is-better (the standard deviation is positive); dist is
+    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the distance rows in front
+    of the sequence search (_SequenceRows).  Distances stay lower-is-better (the standard deviation is positive); dist is
     then the float64 sum of L normalised values, max_distance is compared with that sum (it may be negative), and an
     empty slot is (+inf, -1)."""
 
@@ -471,14 +462,10 @@ class CnnVtlLoopClosureDetector:
         self.max_distance = max_distance if max_distance is None else (int if contrast is None else float)(max_distance)
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
-        if self.sequence is not None:
-            # the last L - 1 distance rows, then the batch's
-            self._seq = _SequenceRows(self.sequence, slopes, self.k, torch.int64, self.contrast)
+        # the last L - 1 distance rows, then the batch's
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True)
+        if self._seq is not None:
             self.slopes = self._seq.slopes
-        elif slopes is not None:
-            raise ValueError("slopes needs sequence=L")
-        elif contrast is not None:
-            raise ValueError("contrast needs sequence=L")
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -502,24 +489,15 @@ class CnnVtlLoopClosureDetector:
             if self.contrast is not None:
                 return _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
             return _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
-        # frame first + r against the frames below first + r - exclusion, as rows behind the L - 1 rows before them; matrix
-        # row m is frame first - (L - 1) + m (rows of frames before the stream began offer nothing and are never read)
-        seq = self._seq
+        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
         db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
-                     out=seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
-        seq.normalise(db.engine, first + b, first - self.exclusion)
-        s, i, _, _ = db.engine.sequence_topk(seq.window(b), self.sequence, self.slopes, k=self.k, row0=seq.context, n=first + b,
-                                             limit0=first - seq.context - self.exclusion, limit_step=1, lower_is_better=True)
-        seq.advance(b)
-        return s, i
+                     out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
+        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
 
     def loops(self, dist, ids, first_id):
         """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance (with sequence=L: the
         sum of the L distances along the candidate's line)."""
-        d, i = dist.cpu().numpy(), ids.cpu().numpy()
-        lim = self.max_distance
-        return [(first_id + r, int(i[r, c]), d[r, c].item()) for r in range(d.shape[0]) for c in range(d.shape[1])
-                if i[r, c] >= 0 and (lim is None or d[r, c] <= lim)]
+        return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True)
 
 
 def _frame_files(dataset_path, pattern):

@@ -41,5 +41,9 @@ inline int64_t row_limit(int64_t r, int64_t n, int64_t limit0, int64_t limit_ste
     const int64_t l = limit0 + r * limit_step;
     return l < 0 ? 0 : (l > n ? n : l);
 }
+inline int64_t max_row_limit(int64_t r_first, int64_t r_last, int64_t n, int64_t limit0, int64_t limit_step) {
+    const int64_t la = row_limit(r_first, n, limit0, limit_step), lb = row_limit(r_last, n, limit0, limit_step);
+    return la > lb ? la : lb;
+}
 struct DeviceGuard { bool ok = true; explicit DeviceGuard(int) {} };
 }

@@ -457,3 +457,41 @@ def test_detector_two_batches_in_flight_equals_batch_by_batch():
         assert torch.equal(torch.nan_to_num(rows[q, :first + q], posinf=1e300), torch.nan_to_num(one[q, :first + q], posinf=1e300))
     with pytest.raises(Exception):
         eng.sdav_stream_query_batch_staged(st.state, st.desc, first, 4, st.score, 1, rows[:4], ws_, st.a, st.b)   # no strip below 8
+
+
+def test_detector_query_and_insert_with_a_ticket_pending():
+    """SdavLoopClosureDetector.query_and_insert behind a submit() whose result has not been fetched: the submitted batch's
+    second half runs first, so its rows are ranked before the later batch's (the sequence search's context rows stay in
+    frame order) and nothing is in flight when the stream grows.  submit / query_and_insert / result in turn give the
+    lists of query_and_insert alone, with and without sequence / contrast, for a stream that holds everything and one
+    that grows inside a query_and_insert with a ticket pending."""
+    import deeploopcloser_amd as dlc
+    eng = dlc.default_engine()
+    g = torch.Generator(device=eng.device)
+    g.manual_seed(31)
+    n, p, h = 64, 30, 300
+    ds = torch.sigmoid(4.0 * torch.randn((n, p, h), generator=g, device=eng.device, dtype=torch.float64))
+    ds[40] = ds[7]
+    ds[41, 3] = ds[8, 11]
+    for opts in ({}, {"sequence": 3}, {"sequence": 3, "contrast": 2}):
+        for capacity in (64, 24):
+            plain = dlc.SdavLoopClosureDetector(ds, patches=p, width=h, k=4, exclusion=2, capacity=capacity, **opts)
+            piped = dlc.SdavLoopClosureDetector(ds, patches=p, width=h, k=4, exclusion=2, capacity=capacity, **opts)
+            want, got, f, pending = [], [], 0, 0
+            for b_submit, b_query in ((8, 3), (9, 12), (16, 5), (8, 3)):
+                t = piped.submit(ds[f:f + b_submit])
+                pending += piped._pending == t                        # (the very first batch is not pipelined)
+                later = piped.query_and_insert(ds[f + b_submit:f + b_submit + b_query])
+                got += [piped.result(t), later]
+                for b in (b_submit, b_query):
+                    want.append(plain.query_and_insert(ds[f:f + b]))
+                    f += b
+            assert f == n and len(piped) == n and pending == 3, (opts, capacity)
+            assert piped.stream.capacity > 24 or capacity == 64
+            ws, wi = torch.cat([w[0] for w in want]), torch.cat([w[1] for w in want])
+            gs, gi = torch.cat([o[0] for o in got]), torch.cat([o[1] for o in got])
+            torch.cuda.synchronize()
+            assert torch.equal(wi, gi), (opts, capacity)
+            assert torch.equal(torch.nan_to_num(ws, posinf=1e300, neginf=-1e300),
+                               torch.nan_to_num(gs, posinf=1e300, neginf=-1e300)), (opts, capacity)
+            assert int(piped.stream.stats[1]) == 0
