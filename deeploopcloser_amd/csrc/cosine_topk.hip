@@ -28,6 +28,7 @@
 // 16 accumulators (4 tiles x 4 regs) one CONTIGUOUS block of 16 database rows
 // (two groups of 8).
 #include "dlc_internal.h"
+#include "lds_dma.h"
 
 #include <algorithm>
 
@@ -74,13 +75,6 @@ template <> struct Mfma16<dlc_f16_tag> {
     }
     static __device__ __forceinline__ float to_f32(unsigned short h) { return dlc_f16_bits_to_f32(h); }
 };
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const char* g, char* l) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0);
-}
 
 // LDS image of an operand tile: 256 rows x 128 B, 16-B chunk `ch` of row `r`
 // lives in slot ch ^ f(r).  f is chosen so that each ds_read_b128 lane group of
@@ -130,10 +124,8 @@ constexpr int GEMM_PARTIAL = 2;  //           this K chunk's partial score tile 
 // each in two 32-wide k-slices: 8 mini-phases of 8 MFMAs per K tile.
 constexpr int HALF_BYTES = 128 * 128;
 
-// Four LDS-DMA wave-instructions (4 x 1 KiB: 32 rows of one half tile).  Issued from inline asm
-// so that hipcc does not count them: it would otherwise put s_waitcnt vmcnt(0) in front of every
-// ds_read and serialise the pipeline.  M0 carries the LDS destination (wave-uniform); saved and
-// restored because the compiler owns it.  s_nop 4 covers an SGPR operand freshly written by a VALU.
+// A wave stages 32 rows of a half tile with four LDS-DMA pieces (4 x 1 KiB), dma_s of lds_dma.h.
+//
 // Cache policy of the DATABASE stream's loads.  The rows are read exactly once, at 4 TB/s through 8 L2s of 4 MiB,
 // while the 2 MiB query block is re-read by every workgroup: with the default policy the stream keeps pushing
 // query lines out.  `nt` (non-temporal) marks the stream's lines for early replacement: 2.06 -> 1.86 ms per
@@ -141,43 +133,8 @@ constexpr int HALF_BYTES = 128 * 128;
 #ifndef DLC_A_CACHE_POLICY
 #define DLC_A_CACHE_POLICY " nt"
 #endif
-#define DLC_DMA4_BODY(POLICY)                                \
-    asm volatile(                                            \
-        "s_nop 4\n\t"                                        \
-        "s_mov_b32 %0, m0\n\t"                               \
-        "s_mov_b32 m0, %6\n\t"                               \
-        "s_nop 0\n\t"                                        \
-        "global_load_lds_dwordx4 %1, %5" POLICY "\n\t"       \
-        "s_add_u32 m0, %6, 0x400\n\t"                        \
-        "s_nop 0\n\t"                                        \
-        "global_load_lds_dwordx4 %2, %5" POLICY "\n\t"       \
-        "s_add_u32 m0, %6, 0x800\n\t"                        \
-        "s_nop 0\n\t"                                        \
-        "global_load_lds_dwordx4 %3, %5" POLICY "\n\t"       \
-        "s_add_u32 m0, %6, 0xc00\n\t"                        \
-        "s_nop 0\n\t"                                        \
-        "global_load_lds_dwordx4 %4, %5" POLICY "\n\t"       \
-        "s_mov_b32 m0, %0"                                   \
-        : "=&s"(keep)                                        \
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(sbase), "s"(lds0) \
-        : "memory", "scc")
-__device__ __forceinline__ void dma4(const unsigned (&voff)[4], const char* sbase, unsigned lds0) {
-    unsigned keep;
-    DLC_DMA4_BODY("");
-}
 // the database operand's form: streamed once, so its cache policy is a separate knob
-__device__ __forceinline__ void dma4_stream(const unsigned (&voff)[4], const char* sbase, unsigned lds0) {
-    unsigned keep;
-    DLC_DMA4_BODY(DLC_A_CACHE_POLICY);
-}
-
-#define DLC_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define DLC_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+DLC_DMA_S_FORM(dma_s_stream, DLC_A_CACHE_POLICY)
 
 // MASKQ: instantiation for a last query block with fewer than 193 queries -- waves whose 64-query
 // column block lies entirely past q skip their fragment reads and MFMAs (they still stage and
@@ -241,8 +198,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
     const int fa = ((i >> 1) & 1) | ((i >> 2) << 1);
     const int fb = (i >> 1) & 7;
     typedef const __attribute__((address_space(3))) u32x4_t* lds_u4p;
-    typedef const __attribute__((address_space(3))) char* lds_cp;
-    const lds_cp lbase = (lds_cp)(lptr_t)smem;
+    const lcptr_t lbase = (lcptr_t)(lptr_t)smem;
     const unsigned rdA0_l = (wr * 64 + 16 * (i >> 2) + (i & 3)) * 128 + (((0 + kq) ^ fa) << 4);   // + tt*512
     const unsigned rdA1_l = (wr * 64 + 16 * (i >> 2) + (i & 3)) * 128 + (((4 + kq) ^ fa) << 4);
     const unsigned rdB0_l = B_RING + (wc * 32 + i) * 128 + (((0 + kq) ^ fb) << 4);                // + c*2048
@@ -283,7 +239,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
     do {                                                                                             \
         if (is_a) {                                                                                  \
             int kk_ = (t2) < nk ? (t2) : nk - 1;                                                     \
-            dma4_stream(voff[H], a_base + (long long)kk_ * 128, lds_stage + (POS) + (H) * HALF_BYTES); \
+            dma_s_stream(voff[H], a_base + (long long)kk_ * 128, lds_stage + (POS) + (H) * HALF_BYTES); \
         }                                                                                            \
     } while (0)
     // wave 4 + j stages exactly the queries of column block j: nobody reads them when that block is idle
@@ -292,7 +248,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
     do {                                                                                             \
         if (!is_a && b_on) {                                                                         \
             int kk_ = (t2) < nk ? (t2) : nk - 1;                                                     \
-            dma4(voff[H], b_base + (long long)kk_ * 128, lds_stage + B_RING + (POS) + (H) * HALF_BYTES); \
+            dma_s(voff[H], b_base + (long long)kk_ * 128, lds_stage + B_RING + (POS) + (H) * HALF_BYTES); \
         }                                                                                            \
     } while (0)
 

@@ -19,7 +19,7 @@
 // odd rows in 32-63, and 8 rows of one parity take 8 different slots) touches every bank once.  (Keyed on r & 7
 // instead, rows r and r + 8 shared their banks: SQ_LDS_BANK_CONFLICT was half of SQ_LDS_IDX_ACTIVE.)  The swizzle is applied to the DMA's per-lane SOURCE address; the LDS destination stays lane-linear.
 // Rows past M / columns past N are clamped to the last valid one (their results are never stored); a K tail reads a
-// page of zeros instead, convolution padding is served as zeros by out-of-range buffer offsets (dma_a4b).
+// page of zeros instead, convolution padding is served as zeros by out-of-range buffer offsets (dma_b).
 // Addresses cost the vector unit nothing per K tile: DMA sources are a scalar base + fixed 32-bit lane offsets, LDS
 // read pointers step once per tile -- every vector / LDS instruction beside an fp64 MFMA costs the SIMD ~7 cycles.
 //
@@ -28,6 +28,7 @@
 // their SIMD partners 4-7 run half a tile behind (k-slices 2-3 of tile t-1, then 0-1 of tile t) -- see the main loop.
 #include <algorithm>
 #include "gemm_internal.h"
+#include "lds_dma.h"
 
 namespace dlc_gemm {
 namespace {
@@ -86,9 +87,6 @@ struct TriWalk {
     }
 };
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) const char* lcptr_t;
-
 // Between the k-slices of a K tile: for the plain operands, a scheduling fence -- the source's order (reads of slice
 // k+1, then the 16 MFMAs of slice k) is the schedule; left alone hipcc pairs B reads of neighbouring slices and moves
 // them up, which measured 1.8 % (SDAV layers) and 2.7 % (Gram) slower.  The convolution form, whose DMA addresses are
@@ -102,168 +100,18 @@ typedef __attribute__((address_space(3))) const char* lcptr_t;
 #define DLC_SLICE_FENCE() do { if constexpr (!CONV) __builtin_amdgcn_sched_barrier(0); } while (0)
 
 
-// LDS-DMA wave-instructions of one K tile: four 1 KiB pieces of the A stage (dma_a4), two of the B stage (dma_b2).
-// Inline asm so that hipcc does not count them in vmcnt (it would wait for vmcnt(0) in front of every LDS read); M0
-// carries the wave-uniform LDS destination and is saved / restored because the compiler owns it.  s_nop 4 covers
-// SGPR operands freshly written by v_readfirstlane.
-__device__ __forceinline__ void dma_a4(const char* a0, const char* a1, const char* a2, const char* a3, unsigned lds_a) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_add_u32 m0, %5, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_add_u32 m0, %5, 0x800\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, off\n\t"
-        "s_add_u32 m0, %5, 0xc00\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "s"(lds_a)
-        : "memory", "scc");
-}
-__device__ __forceinline__ void dma_b2(const char* b0, const char* b1, unsigned lds_b) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_add_u32 m0, %3, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(b0), "v"(b1), "s"(lds_b)
-        : "memory", "scc");
-}
-
-// The same with a wave-uniform 64-bit base in SGPRs and 32-bit per-lane offsets that never change: a K tile's
-// addresses then cost scalar adds only (each vector instruction beside the fp64 MFMAs costs the SIMD ~7 cycles:
-// 20 more of them per K tile measured 1.4 % -- DLC_EXP_DMA_SPLIT_A_READS).
-__device__ __forceinline__ void dma_a4s(unsigned o0, unsigned o1, unsigned o2, unsigned o3, const char* base, unsigned lds_a) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %5\n\t"
-        "s_add_u32 m0, %6, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %5\n\t"
-        "s_add_u32 m0, %6, 0x800\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, %5\n\t"
-        "s_add_u32 m0, %6, 0xc00\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, %5\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(base), "s"(lds_a)
-        : "memory", "scc");
-}
-// The convolution's A operand: buffer addressing -- a wave-uniform descriptor (base stepping with the kernel tap and
-// channel block) + per-lane 32-bit offsets; a lane whose tap falls into the padding carries an offset past
-// num_records and the hardware writes ZEROS to its LDS slot (scripts/micro/buffer_lds_oob.hip: out-of-range dwords of
-// a `buffer_load ... lds` land as 0; an soffset counts in the range check, so the base is stepped instead).
-// "s" operands must BE in SGPRs: hipcc does not move a value it keeps in VGPRs there by itself (a diagnostic build
-// failed to assemble that way), so the wave-uniform bases go through readfirstlane -- a no-op on a value that is
-// already scalar.
-__device__ __forceinline__ const char* uniform_ptr(const char* p) {
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return (const char*)(((unsigned long long)hi << 32) | lo);
-}
-typedef __attribute__((ext_vector_type(4))) unsigned rsrc_t;
-constexpr unsigned DMA_OOB = 0xfffffff0u;       // >= num_records of every descriptor built here
-constexpr unsigned DMA_NUM_RECORDS = 0x80000000u;
-__device__ __forceinline__ rsrc_t make_rsrc(const char* base) {
-    const unsigned long long a = (unsigned long long)base;
-    rsrc_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);       // stride 0: raw buffer
-    r[2] = DMA_NUM_RECORDS;
-    r[3] = 0x00020000u;                         // gfx9 raw-buffer word (32-bit data format)
-    return r;
-}
-__device__ __forceinline__ void dma_a4b(unsigned o0, unsigned o1, unsigned o2, unsigned o3, rsrc_t rsrc, unsigned lds_a) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %5, 0 offen lds\n\t"
-        "s_add_u32 m0, %6, 0x400\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %2, %5, 0 offen lds\n\t"
-        "s_add_u32 m0, %6, 0x800\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %3, %5, 0 offen lds\n\t"
-        "s_add_u32 m0, %6, 0xc00\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %4, %5, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(rsrc), "s"(lds_a)
-        : "memory", "scc");
-}
-// ... and of one (the 64-row tile's A part: 8 rows per wave)
-__device__ __forceinline__ void dma_1(const char* a0, unsigned lds_a) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(a0), "s"(lds_a) : "memory", "scc");
-}
-__device__ __forceinline__ void dma_1s(unsigned o0, const char* base, unsigned lds_a) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(o0), "s"(base), "s"(lds_a) : "memory", "scc");
-}
-__device__ __forceinline__ void dma_1b(unsigned o0, rsrc_t rsrc, unsigned lds_a) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(o0), "s"(rsrc), "s"(lds_a) : "memory", "scc");
-}
-__device__ __forceinline__ void dma_a2b(unsigned o0, unsigned o1, rsrc_t rsrc, unsigned lds_a) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
-        "s_add_u32 m0, %4, 0x400\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %2, %3, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(o0), "v"(o1), "s"(rsrc), "s"(lds_a)
-        : "memory", "scc");
-}
-__device__ __forceinline__ void dma_b2s(unsigned o0, unsigned o1, const char* base, unsigned lds_b) {
-    unsigned keep;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\t"
-        "s_add_u32 m0, %4, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %3\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(o0), "v"(o1), "s"(base), "s"(lds_b)
-        : "memory", "scc");
-}
+// The LDS-DMA wave-instructions of one K tile (lds_dma.h has the statements and their protocol): MI 1 KiB pieces of
+// the A stage (4, 2, or 1 -- the 64-row tile's A part: 8 rows per wave) and two of the B stage per wave, in three
+// addressing forms.
+//   dma_s  plain operands: a wave-uniform 64-bit base in SGPRs and 32-bit per-lane offsets that never change -- a K
+//          tile's addresses then cost scalar adds only (each vector instruction beside the fp64 MFMAs costs the SIMD ~7
+//          cycles: 20 more of them per K tile measured 1.4 % -- DLC_EXP_DMA_SPLIT_A_READS).
+//   dma_v  64-bit per-lane addresses: a K-tail tile only, whose pieces past K come from the page of zeros.
+//   dma_b  the convolution's A operand: buffer addressing -- a wave-uniform descriptor (base stepping with the kernel
+//          tap and channel block) + per-lane 32-bit offsets; a lane whose tap falls into the padding carries an offset
+//          past num_records (DMA_OOB) and the hardware writes ZEROS to its LDS slot (scripts/micro/buffer_lds_oob.hip:
+//          out-of-range dwords of a `buffer_load ... lds` land as 0; an soffset counts in the range check, so the base
+//          is stepped instead).
 
 __device__ __forceinline__ double act_f64(double z, int act) {
     if (act == DLC_ACT_SIGMOID) return 1.0 / (1.0 + exp(-z));
@@ -461,9 +309,7 @@ __global__ __launch_bounds__(NT3, 2) void gemm_dma_f64_kernel(DmaArgs p) {
                     if (++cv_kx == p.cv.KW) { cv_kx = 0; ++cv_ky; }
                 }
             }
-            if constexpr (MI == 4) dma_a4b(a_eff[0], a_eff[1], a_eff[2], a_eff[3], rs, lds_a);
-            else if constexpr (MI == 2) dma_a2b(a_eff[0], a_eff[1], rs, lds_a);
-            else dma_1b(a_eff[0], rs, lds_a);
+            dma_b(a_eff, rs, lds_a);
         } else {
             const char* base = uniform_ptr(a_base + (long long)tt * (TK3 * 8));
             if (a_tail && tt == nkt - 1) {
@@ -471,13 +317,9 @@ __global__ __launch_bounds__(NT3, 2) void gemm_dma_f64_kernel(DmaArgs p) {
                 const char* sa[MI];
 #pragma unroll
                 for (int j = 0; j < MI; ++j) sa[j] = a_piece[j] * 2 >= klim ? zsrc : base + a_off[j];
-                if constexpr (MI == 4) dma_a4(sa[0], sa[1], sa[2], sa[3], lds_a);
-                else if constexpr (MI == 2) dma_b2(sa[0], sa[1], lds_a);
-                else dma_1(sa[0], lds_a);
+                dma_v(sa, lds_a);
             } else {
-                if constexpr (MI == 4) dma_a4s(a_off[0], a_off[1], a_off[2], a_off[3], base, lds_a);
-                else if constexpr (MI == 2) dma_b2s(a_off[0], a_off[1], base, lds_a);
-                else dma_1s(a_off[0], base, lds_a);
+                dma_s(a_off, base, lds_a);
             }
         }
     };
@@ -494,9 +336,9 @@ __global__ __launch_bounds__(NT3, 2) void gemm_dma_f64_kernel(DmaArgs p) {
                 if constexpr (BLAYOUT == DLC_B_NK) sb[j] = b_piece[j] * 2 >= klim ? zsrc : base + b_off[j];
                 else sb[j] = b_piece[j] >= klim ? zsrc : base + b_off[j];
             }
-            dma_b2(sb[0], sb[1], lds_b);
+            dma_v(sb, lds_b);
         } else {
-            dma_b2s(b_off[0], b_off[1], base, lds_b);
+            dma_s(b_off, base, lds_b);
         }
     };
 
@@ -557,8 +399,8 @@ __global__ __launch_bounds__(NT3, 2) void gemm_dma_f64_kernel(DmaArgs p) {
     // wait for this wave's DMA pieces (all that are in flight belong to the tile about to become readable), then the
     // workgroup barrier: behind it that tile is visible to every wave and the stage of the tile two back is free
     auto arrive = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        DLC_WAIT_VMCNT(0);
+        __builtin_amdgcn_s_barrier();                                    // (wg_barrier() without its leading fence, which the wait is)
         asm volatile("" ::: "memory");
     };
     auto issue = [&](int t, int stage) {
@@ -617,7 +459,7 @@ __global__ __launch_bounds__(NT3, 2) void gemm_dma_f64_kernel(DmaArgs p) {
         rd(3, 1); mm(0);
         mm(1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // no DMA may outlive the workgroup's LDS
+    DLC_WAIT_VMCNT(0);                                                   // no DMA may outlive the workgroup's LDS
 
     // ---- epilogue: bias + activation, C/D layout of v_mfma_f64_16x16x4_f64: row = (lane >> 4) + 4 * reg, col = lane & 15
     // CONV with mm_keys: the minimum / maximum of every image's outputs is folded into ordered keys on the way out

@@ -52,6 +52,7 @@
 // The same k loop serves CnnVtl's tolerance mode (dlc_cnnvtl_encode_split) through a third epilogue, MODE SP_CONV: the
 // second half of this file.
 #include "gemm_internal.h"
+#include "lds_dma.h"
 
 namespace dlc_gemm {
 namespace {
@@ -72,8 +73,6 @@ typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 constexpr int SP_X_SHIFT = 11;                 // activations are carried as h * 2^11
 constexpr int SP_SUPER = 4;                    // activation row tiles per super-row of the tile order
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 struct SplitArgs {
     const char* W[2];           // weight pieces, K32-major: [K/32][Np rows (permuted inside 64s)][32] fp16 (rows >= N, k >= K: zeros)
     const char* X[2];           // activation pieces, K32-major: [slices][Mp rows][32] fp16
@@ -92,33 +91,11 @@ struct SplitArgs {
     long long per_xcd, extra;   // tiles per XCD: per_xcd (+ 1 for the first `extra` XCDs), in the order of the file header
 };
 
-// LDS-DMA wave-instructions of 1 KiB each: inline asm so that hipcc does not count them in vmcnt, M0 saved and restored
-// (cosine_topk.hip: dma4).  The instruction's immediate offset is
-// added to the global address AND to the LDS address (M0 + offset + 16 * lane), and a run is laid out alike on both
-// sides: one address register and one M0 value serve every piece of it.
-// Four pieces (a 4 KiB run) in one statement, SKIPPED by a wave whose `on` is 0: the jump is inside the statement, so that
-// the compiler sees straight-line code (a C-level `if` around the statement -- basic blocks inside the k loop -- cost the
-// register allocator its footing at 252 of 256 registers: spills).
-__device__ __forceinline__ void sp_dma4(unsigned on, unsigned voff, const char* sbase, unsigned lds0) {
-    unsigned keep;
-    asm volatile(
-        "s_cmp_eq_u32 %4, 0\n\t"
-        "s_cbranch_scc1 .Lsp_skip_%=\n\t"
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-        "s_mov_b32 m0, %0\n"
-        ".Lsp_skip_%=:"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds0), "s"(on)
-        : "memory", "scc");
-}
-// s_waitcnt vmcnt(N0) for a wave whose `sel` is 0, vmcnt(N1) otherwise -- the choice inside the statement (see sp_dma4)
+// The operands reach LDS by dma_run4_if (lds_dma.h): four pieces (a 4 KiB run) in one statement, SKIPPED by a wave whose
+// `on` is 0.  The jump is inside the statement, so that the compiler sees straight-line code (a C-level `if` around the
+// statement -- basic blocks inside the k loop -- cost the register allocator its footing at 252 of 256 registers: spills).
+
+// s_waitcnt vmcnt(N0) for a wave whose `sel` is 0, vmcnt(N1) otherwise -- the choice inside the statement (as in dma_run4_if)
 template <int N0, int N1>
 __device__ __forceinline__ void sp_wait_vmcnt_by(unsigned sel) {
     asm volatile(
@@ -133,20 +110,6 @@ __device__ __forceinline__ void sp_wait_vmcnt_by(unsigned sel) {
         : "s"(sel), "n"(N0), "n"(N1)
         : "memory", "scc");
 }
-__device__ __forceinline__ const char* sp_uniform_ptr(const char* p) {
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return (const char*)(((unsigned long long)hi << 32) | lo);
-}
-
-#define SP_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define SP_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-__device__ __forceinline__ void sp_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // SplitArgs + what the convolution epilogue of the CnnVtl tolerance mode needs (O, C, ldc, oslice_b are unused there)
 struct ConvSplitArgs : SplitArgs {
     float* Cf;                  // [M, N] fp32: the layer's NHWC output
@@ -211,7 +174,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
     const long long slice_b = lw < 2 ? p.wslice_b : p.xslice_b;
     const long long tile_off = (lw < 2 ? (long long)tile_n * SP_BM * SP_ROWB : tile_m * SP_BN * SP_ROWB) + (lw & 1) * (SP_OP / 2);
     const int piece_sel = late ? 0 : 1;                     // late waves stage the first pieces (W1 / h1), early ones the second
-    const char* src = sp_uniform_ptr((lw < 2 ? p.W[piece_sel] : p.X[piece_sel]) + tile_off);
+    const char* src = uniform_ptr((lw < 2 ? p.W[piece_sel] : p.X[piece_sel]) + tile_off);
     const unsigned lds_mine = lds_base + (late ? (unsigned)SP_RING_A : (unsigned)SP_RING_B) + (unsigned)(lw >> 1) * SP_OP +
                               (unsigned)(lw & 1) * (SP_OP / 2);                // inside slot 0 of this wave's ring
     const int ns = p.ns;
@@ -220,8 +183,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
     const int i = lane & 15;
     const int kq = lane >> 4;
     typedef const __attribute__((address_space(3))) u32x4_t* lds_u4p;
-    typedef const __attribute__((address_space(3))) char* lds_cp;
-    const lds_cp lbase = (lds_cp)(lptr_t)smem_sp;
+    const lcptr_t lbase = (lcptr_t)(lptr_t)smem_sp;
     const unsigned rd_l = (unsigned)(i * SP_ROWB + ((kq ^ (((i >> 3) & 1) << 1)) << 4));
     const unsigned rdW = rd_l + (unsigned)wr * (SP_OP / 2);                      // weight fragment T at + T KiB inside a slot
     const unsigned rdH = rd_l + (unsigned)SP_OP + (unsigned)wc * (SP_OP / 4);    // activation fragment c at + c KiB
@@ -255,7 +217,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
 #define SP_ISSUE4(ON, SLOT, S2, Q)                                                                               \
     do {                                                                                                         \
         const int ss_ = (S2) < ns ? (S2) : ns - 1;                                                               \
-        sp_dma4(ON, voff, src + (long long)ss_ * slice_b + (Q) * 4096, lds_mine + (SLOT) + (Q) * 4096);          \
+        dma_run4_if(ON, voff, src + (long long)ss_ * slice_b + (Q) * 4096, lds_mine + (SLOT) + (Q) * 4096);      \
     } while (0)
 
     // One slice, entered with W1 and HCUR = h1 of it in registers; leaves W1 and HNXT = h1 of the next.
@@ -267,8 +229,8 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
         SP_PAIR(12); SP_ONLY_MFMA(20);                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         sp_wait_vmcnt_by<0, 8>(late);                              /* early: (W2, h2) of s + 1 landed; late: all but its youngest (W1, h1) pair */ \
-        SP_WAIT_LGKM0();                                           /* this wave's reads of slice s are done */     \
-        sp_barrier();                                              /* slice s is dead; slice s + 1 is visible */  \
+        DLC_WAIT_LGKM0();                                          /* this wave's reads of slice s are done */     \
+        wg_barrier();                                              /* slice s is dead; slice s + 1 is visible */  \
         SP_ISSUE4(early, sb, (S) + 2, 0);                          /* (W2, h2) of s + 2: wanted in one period */  \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         SP_MFMA(fW1, HNXT, 0, 4);                                  /* P2 = h2 . W1 */                            \
@@ -309,15 +271,15 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
     SP_ISSUE4(late, SP_PAIR_B, 1, 0); SP_ISSUE4(late, SP_PAIR_B, 1, 1);
     SP_ISSUE4(late, 2 * SP_PAIR_B, 2, 0); SP_ISSUE4(late, 2 * SP_PAIR_B, 2, 1);
     sp_wait_vmcnt_by<8, 16>(late);                             // slice 0 landed (this wave's share)
-    sp_barrier();
+    wg_barrier();
     SP_READ_W(fW1, SP_RING_A + 0);
     SP_READ_H(fhA, SP_RING_A + 0);
     for (int s = 0; s < ns; s += 2) {
         SP_STEP(s, fhA, fhB);
         if (s + 1 < ns) SP_STEP(s + 1, fhB, fhA);
     }
-    SP_WAIT_VMCNT(0);    // the clamped tail DMAs must not outlive the workgroup's LDS
-    SP_WAIT_LGKM0();
+    DLC_WAIT_VMCNT(0);   // the clamped tail DMAs must not outlive the workgroup's LDS
+    DLC_WAIT_LGKM0();
 #undef SP_STEP
 #undef SP_ISSUE4
 #undef SP_PAIR
@@ -339,7 +301,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
     // the tile's 256 biases through LDS (the ring is dead): ONE global load per thread; a lane's sixteen then come as four
     // 16-byte LDS reads (read straight from memory they were 32 dependent 8-byte loads per lane: a tenth of a tile's time)
     {
-        sp_barrier();                                          // every wave is past its last fragment read
+        wg_barrier();                                          // every wave is past its last fragment read
         float* bl = (float*)smem_sp;
         if (tid < SP_BM) bl[tid] = bias_l;
         __syncthreads();
@@ -454,7 +416,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
             // fp64 out, a ROW at a time: the wave's 64 rows x 64 columns come back from LDS with 32 lanes on one row's 512
             // bytes, two rows per store instruction.  (Stored from the accumulators' layout every lane wrote 16 bytes of a
             // different cache line: 64 lines per instruction, 0.14 ms of this layer's 0.99.)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            DLC_WAIT_LGKM0();
             __builtin_amdgcn_wave_barrier();
             const int nb = tile_n * SP_BM + wr * 128 + th * 64, cj = 2 * (lane & 31);
             const bool pairs = (p.ldc & 1) == 0 && ((unsigned long long)p.C & 15) == 0;
@@ -471,7 +433,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void gemm_split_f16_kernel(typename 
                     if (nb + cj + 1 < p.N) dst[1] = (double)v.y;
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the next half's rows overwrite the block
+            DLC_WAIT_LGKM0();                                      // the next half's rows overwrite the block
             __builtin_amdgcn_wave_barrier();
         }
     }

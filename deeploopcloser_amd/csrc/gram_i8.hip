@@ -38,12 +38,12 @@
 // 240 k-steps of 32 MFMAs per wave instead of 40 of 96, every slice streamed again per class (18.6 GB over the fabric
 // for 0.49 GB of panels, profiles/r02i), 12 LDS fragment reads per 32 MFMAs instead of 24 per 96.
 #include "gemm_internal.h"
+#include "lds_dma.h"
 
 namespace dlc_gemm {
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int v4i;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int GI_T = 128;                 // tile: 128 row patches x 128 column patches, 4 waves of 64 x 64
 constexpr int GI_KS = 64;                 // bytes of K (per slice) per LDS stage = one MFMA k-step
@@ -144,25 +144,10 @@ template <int B> __device__ __forceinline__ v4i gi_acc_read() {
 }
 #define GI_ACC(C, J, I) ((((C) * 4 + (J)) * 4 + (I)) * 4)
 
-// One 1 KiB LDS-DMA piece: lane l fetches bytes l * 16 .. + 15 behind the wave-uniform base `src` (+ voff, which carries
-// the k-step) into LDS at `lds` + l * 16.  Inline asm so that hipcc does not count it in vmcnt (it would wait for
-// vmcnt(0) in front of every LDS read).  M0 carries the LDS destination and is declared CLOBBERED, not saved and restored
-// (two more instructions per piece, twelve pieces per k-step of a wave that has nothing else to hide them behind): hipcc
-// warns that M0 is a reserved register it may not preserve across the statement, so the BUILD checks what the claim rests
-// on -- `make` runs csrc/check_m0.py, which disassembles this kernel and fails if any instruction outside these asm
-// statements reads or writes M0.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma1(unsigned voff, const char* src, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(src), "s"(lds) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-__device__ __forceinline__ const char* uniform_ptr(const char* p) {
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return (const char*)(((unsigned long long)hi << 32) | lo);
-}
+// One 1 KiB LDS-DMA piece, dma1_s_m0clobber(voff, src, lds) of lds_dma.h: lane l fetches bytes l * 16 .. + 15 behind the
+// wave-uniform base `src` (+ voff, which carries the k-step) into LDS at `lds` + l * 16.  M0 is declared CLOBBERED, not
+// saved and restored (two more instructions per piece, twelve pieces per k-step of a wave that has nothing else to hide
+// them behind); `make` runs csrc/check_m0.py on this kernel, which is what that form rests on.
 
 // LDS stage (48 KiB): the row panel's 8 groups of 16 rows x 3 slices, a 1 KiB block each in MFMA operand order -- block
 // (g * 3 + s), lane l of a block holds row l % 16, bytes (l / 16) * 16 .. + 15 of the k-step of slice s -- then the
@@ -229,8 +214,8 @@ __global__ __launch_bounds__(256) void gram_i8_kernel(const GramI8Args p) {
     int is_slot = 0;                                // ... and the slot it goes to
     auto issue_piece = [&](int b) {
         const unsigned lds = lds_w + is_slot * GI_STAGE + (b / 6) * GI_HALF + (b % 6) * 1024;
-        if (b < 6) dma1(voff_issue, src[b], lds);
-        else dma1(yoff[(b - 6) / 3] + (unsigned)((b - 6) % 3) * slice_bytes + kbytes, xbase, lds);
+        if (b < 6) dma1_s_m0clobber(voff_issue, src[b], lds);
+        else dma1_s_m0clobber(yoff[(b - 6) / 3] + (unsigned)((b - 6) % 3) * slice_bytes + kbytes, xbase, lds);
     };
     auto issue_done = [&]() {
         voff_issue += 1024;
@@ -324,7 +309,7 @@ __global__ __launch_bounds__(256) void gram_i8_kernel(const GramI8Args p) {
         for (int b = 0; b < 12; ++b) issue_piece(b);
         issue_done();
     }
-    asm volatile("s_waitcnt vmcnt(24)" ::: "memory");                    // stage 0 (12 pieces per stage and wave)
+    DLC_WAIT_VMCNT(24);                                                  // stage 0 (12 pieces per stage and wave)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     GI_RDX(0, 0); GI_RDX(2, 0); GI_RDYB(0, 0, 0); GI_RDYB(0, 1, 0); GI_RDY2(0);
@@ -351,7 +336,7 @@ __global__ __launch_bounds__(256) void gram_i8_kernel(const GramI8Args p) {
 #undef GI_RDX
 #undef GI_RDY2
 #undef GI_RDYB
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    DLC_WAIT_VMCNT(0);
 
     // ---- epilogue: the patch arg-min of every (row patch, column frame) of the tile, decided here -- the products never
     // leave the chip (r02 / early r03 wrote them out, 2 GB, for a second kernel to read back).

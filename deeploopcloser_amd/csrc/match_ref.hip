@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "gemm_internal.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -246,14 +247,6 @@ __global__ __launch_bounds__(256) void distinctive_score_kernel(const double* __
 #define DLC_DSD_COLS 16
 #endif
 constexpr int DSD_RB = 384, DSD_NB = 3;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dsd_dma(unsigned voff, const char* sbase, unsigned lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-#pragma clang diagnostic pop
 template <int DSD_C>
 __global__ __launch_bounds__(256) void distinctive_score_dma_kernel(const double* __restrict__ desc, long long rows, int H,
                                                                     double mu, double sigma, double* __restrict__ score,
@@ -263,28 +256,25 @@ __global__ __launch_bounds__(256) void distinctive_score_dma_kernel(const double
     constexpr int PPR = DSD_C / 2, RPI = 64 / PPR;             // 16-byte pieces per row; rows per DMA instruction
     constexpr int IPW = DSD_RB / RPI / 3;                      // DMA instructions per loader wave and batch
     constexpr int NQ = 192 / DSD_C;                            // threads of waves 1-3 per column (the extremes)
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     const int groups = (H + DSD_C - 1) / DSD_C, per = (groups + 7) / 8;
     const int grp = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);      // XCD x: the x-th contiguous eighth of the groups
     if (grp >= groups) return;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col0 = grp * DSD_C;
     const long long rowb = (long long)H * 8, nb = (rows + DSD_RB - 1) / DSD_RB;
-    const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)dsd_smem;
+    const unsigned lds_base = (unsigned)(unsigned long long)(lptr_t)dsd_smem;
     // loader lanes: piece (16 bytes = two columns) lane & 7 of row lane >> 3 of an instruction's eight rows; a piece past
     // the last column fetches piece 0 again (nobody reads it)
     const unsigned pc16 = (unsigned)((col0 + (lane % PPR) * 2 < H ? (lane % PPR) : 0) * 16);
     auto issue = [&](long long t, int slot) {                  // batch t (past the end: the last one again, into a dead slot)
         const long long tc = t < nb ? t : nb - 1, r0 = tc * DSD_RB;
         const long long last = rows - 1 - r0;                  // rows past the end re-read the last one
-        const unsigned long long a = (unsigned long long)(desc + r0 * H + col0);
-        const unsigned a_lo = __builtin_amdgcn_readfirstlane((unsigned)a), a_hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        const char* base = (const char*)(((unsigned long long)a_hi << 32) | a_lo);      // (unsigned halves: the builtin returns int)
+        const char* base = uniform_ptr((const char*)(desc + r0 * H + col0));
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)slot * DSD_BB + (unsigned)(w - 1) * IPW * 1024);
 #pragma unroll
         for (int j = 0; j < IPW; ++j) {
             const long long ri = ((w - 1) * IPW + j) * RPI + lane / PPR;
-            dsd_dma((unsigned)((ri < last ? ri : last) * rowb) + pc16, base, dst + j * 1024);
+            dma1_s_nopad((unsigned)((ri < last ? ri : last) * rowb) + pc16, base, dst + j * 1024);
         }
     };
     // extremes: thread (c, q) of waves 1-3 sees rows q, q + 12, .. of column c of every batch
@@ -296,7 +286,7 @@ __global__ __launch_bounds__(256) void distinctive_score_dma_kernel(const double
         for (int t = 0; t < DSD_NB - 1; ++t) issue(t, t);
     int slot = 0, free_slot = DSD_NB - 1;
     for (long long t = 0; t < nb; ++t) {
-        if (w > 0) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(IPW * (DSD_NB - 2)) : "memory");    // this wave's pieces of batch t
+        if (w > 0) DLC_WAIT_VMCNT(IPW * (DSD_NB - 2));         // this wave's pieces of batch t
         __syncthreads();                                       // batch t is whole; batch t - 1 is consumed
         const double* b = (const double*)(dsd_smem + slot * DSD_BB);
         const long long r0 = t * DSD_RB;
@@ -349,7 +339,7 @@ __global__ __launch_bounds__(256) void distinctive_score_dma_kernel(const double
         free_slot = slot;
         slot = slot == DSD_NB - 1 ? 0 : slot + 1;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the redundant tail DMAs must not outlive the workgroup's LDS
+    DLC_WAIT_VMCNT(0);                                         // the redundant tail DMAs must not outlive the workgroup's LDS
     __syncthreads();
     if (w == 0 && lane < DSD_C && col0 + lane < H) {
         const double avg = s / (double)rows;
