@@ -365,6 +365,7 @@ __device__ __forceinline__ long long f64_to_i64_trunc(double v) {
     if (!(fabs(v) < 9.2233720368547758e18)) return (long long)0x8000000000000000ull;   // inf / nan / overflow
     return (long long)v;   // truncation toward zero
 }
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // |dot(score, m_a - m_b)| (SimilarityCalculator.py:42-43) from the two rows' double-double projections (gram_i8.hip:
 // sim_rows_kernel): good to 1e-20 of the projections however close the rows lie -- bit-identical rows (a frame seen twice,
@@ -543,23 +544,98 @@ __device__ __forceinline__ int direct_argmin_wave(const double* __restrict__ xa,
     return ebi;
 }
 
+// ---- The tie rule of the similarity, stated once: the first minimum, copies never taken, near-ties decided as NumPy
+// decides them.  Every kernel that answers "which patch of the other frame is nearest" -- the two Gram pair kernels, the
+// filter's pair kernel, the streaming arg-min and the strip's resolution -- goes through these, so the streaming rows
+// equal the matrix call's columns by construction.  (sim_sample_kernel has one lane per patch and tests copies
+// lane-parallel: the same rule in another shape.)
+__device__ __forceinline__ int first_bit(unsigned m) { return __ffs((int)m) - 1; }
+__device__ __forceinline__ int first_bit(unsigned long long m) { return __ffsll((long long)m) - 1; }
+
+// This wave's 8 value stacks for direct_argmin_wave out of a workgroup's PF_STACK_BYTES of LDS (static or dynamic).
+__device__ __forceinline__ double* wave_stacks(double* base, int w) { return base + (size_t)w * 8 * PF_STACK_DEPTH; }
+
+// The candidate set without the copies of an earlier member: a copy (equal content hashes, sim_mix64; hb: the two hash
+// words per patch of the candidates' frame) has that member's distance and a later index, np.argmin never takes it.
+template <typename M>
+__device__ __forceinline__ M drop_copies(M cand, const unsigned long long* __restrict__ hb) {
+    M kept = 0;
+    for (M m = cand; m; m &= m - 1) {
+        const int b = first_bit(m);
+        bool copy = false;
+        for (M k2 = kept; k2; k2 &= k2 - 1) {
+            const int e = first_bit(k2);
+            copy |= hb[2 * e] == hb[2 * b] && hb[2 * e + 1] == hb[2 * b + 1];
+        }
+        if (!copy) kept |= (M)1 << b;
+    }
+    return kept;
+}
+
+// At most one member left: decided.  (An empty set keeps bi: only the general Gram kernel can meet one -- a NaN distance
+// is inside no window -- everywhere else the set is non-empty by construction and the guard does nothing.)
+template <typename M>
+__device__ __forceinline__ void decided(M& cand, int& bi) {
+    if (!(cand & (cand - 1))) { bi = cand ? first_bit(cand) : bi; cand = 0; }
+}
+
+// The undecided arg-mins of a wave (lanes with active and a set of two or more), one after the other, each by the whole
+// wave: where(src, xa, xj) gives the row and the other frame's first row for source lane src; that lane's bi takes the
+// verdict.  Returns the number of direct evaluations (wave-uniform).
+template <typename M, typename Where>
+__device__ __forceinline__ unsigned long long resolve_undecided(M cand, bool active, int& bi, int P, int H, int lane,
+                                                                const int2* __restrict__ prog, int prog_len, double* stacks,
+                                                                Where where) {
+    unsigned long long n = 0;
+    for (unsigned long long todo = __ballot(cand != 0 && active); todo; todo &= todo - 1) {
+        const int src = first_bit(todo);
+        unsigned long long cm = (unsigned long long)(unsigned)__shfl((int)cand, src);
+        if constexpr (sizeof(M) == 8) cm |= (unsigned long long)(unsigned)__shfl((int)(cand >> 32), src) << 32;
+        const double *xa, *xj;
+        where(src, xa, xj);
+        const int ebi = direct_argmin_wave(xa, xj, cm, P, H, lane, prog, prog_len, stacks);
+        if (lane == src) bi = ebi;
+        ++n;
+    }
+    return n;
+}
+
+// The pair's tail: the term ca + cb log |dot(score, m_a - m_b*)| of every live lane (SimilarityCalculator.py:42-43, :48;
+// row ra against its nearest row rb) and their sum over the pair's LANES lanes -- this xor tree IS the summation order.
+template <int LANES>
+__device__ __forceinline__ double pair_terms(bool live, const double* __restrict__ proj, long long ra, long long rb, double ca,
+                                             double cb) {
+    double term = 0.0, wd = 1.0;
+    if (live) wd = proj_diff(proj, ra, rb);
+    if (live) term = ca + cb * log(wd);
+    for (int o = LANES / 2; o > 0; o >>= 1) term += __shfl_xor(term, o);
+    return term;
+}
+__device__ __forceinline__ void store_pair(double* __restrict__ out_f64, long long* __restrict__ out_i64, long long N, long long i,
+                                           long long j, double term) {
+    out_f64[i * N + j] = term;
+    out_f64[j * N + i] = term;
+    if (out_i64) {
+        const long long t = f64_to_i64_trunc(term);
+        out_i64[i * N + j] = t;
+        out_i64[j * N + i] = t;
+    }
+}
+
 // One wave per frame pair (i, j), i in [i_lo, i_hi), j in (i, N).  G is the Gram
 // block  desc[i_lo*P .. i_hi*P) . desc[col0 ..)^T  with leading dimension ldg.
 __global__ __launch_bounds__(256) void pair_score_kernel(const double* __restrict__ desc, const double* __restrict__ G,
                                                          long long ldg, long long col0, const double* __restrict__ nrm2,
-                                                         const double* __restrict__ proj,
-                                                         const double* __restrict__ score, long long N, int P, int H,
+                                                         const double* __restrict__ proj, long long N, int P, int H,
                                                          long long i_lo, long long i_hi, double ca, double cb,
                                                          double* __restrict__ out_f64, long long* __restrict__ out_i64,
                                                          const int2* __restrict__ prog, const unsigned long long* __restrict__ prog_len,
                                                          const unsigned long long* __restrict__ rowhash) {
-    __shared__ double stacks[4][8 * PF_STACK_DEPTH];
+    __shared__ double stacks[PF_STACK_BYTES / 8];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long j = (long long)blockIdx.x * 4 + w;
     const long long i = i_lo + blockIdx.y;
     if (i >= i_hi || j >= N || j <= i) return;
-    double term = 0.0, wd = 1.0;
-    long long rb = 0;
     int bi = 0;
     unsigned long long cand = 0;
     const long long ra = i * P + (lane < P ? lane : 0);
@@ -577,38 +653,15 @@ __global__ __launch_bounds__(256) void pair_score_kernel(const double* __restric
         const double win = gram_window(H, na, nbmax, best);
         for (int b = 0; b < P; ++b) {
             const double d2 = fmax(na + nrm2[j * P + b] - 2.0 * grow[b], 0.0);
-            if (!(d2 - best <= win)) continue;
-            bool copy = false;                                  // a copy of an earlier candidate: np.argmin never takes it
-            for (unsigned long long m = cand; m; m &= m - 1) {
-                const long long e = j * P + (__ffsll((long long)m) - 1);
-                copy |= rowhash[2 * e] == rowhash[2 * (j * P + b)] && rowhash[2 * e + 1] == rowhash[2 * (j * P + b) + 1];
-            }
-            if (!copy) cand |= 1ull << b;
+            if (d2 - best <= win) cand |= 1ull << b;
         }
-        if (!(cand & (cand - 1))) { bi = cand ? __ffsll((long long)cand) - 1 : bi; cand = 0; }
+        cand = drop_copies(cand, rowhash + 2 * (j * P));
+        decided(cand, bi);
     }
-    for (unsigned long long todo = __ballot(cand != 0); todo; todo &= todo - 1) {
-        const int src = __ffsll((long long)todo) - 1;
-        const unsigned long long cm = ((unsigned long long)(unsigned)__shfl((int)(cand >> 32), src) << 32) |
-                                      (unsigned long long)(unsigned)__shfl((int)cand, src);
-        const int ebi = direct_argmin_wave(desc + (i * P + src) * H, desc + j * P * H, cm, P, H, lane, prog, (int)*prog_len, stacks[w]);
-        if (lane == src) bi = ebi;
-    }
-    if (lane < P) {
-        rb = j * P + bi;
-        wd = proj_diff(proj, ra, rb);                           // |dot(score, m_i - m_j*)|, :42-43
-    }
-    if (lane < P) term = ca + cb * log(wd);                     // :48
-    for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o);
-    if (lane == 0) {
-        out_f64[i * N + j] = term;
-        out_f64[j * N + i] = term;
-        if (out_i64) {
-            const long long t = f64_to_i64_trunc(term);
-            out_i64[i * N + j] = t;
-            out_i64[j * N + i] = t;
-        }
-    }
+    resolve_undecided(cand, true, bi, P, H, lane, prog, (int)*prog_len, wave_stacks(stacks, w),
+                      [&](int src, const double*& xa, const double*& xj) { xa = desc + (i * P + src) * H; xj = desc + j * P * H; });
+    const double term = pair_terms<64>(lane < P, proj, ra, j * P + bi, ca, cb);
+    if (lane == 0) store_pair(out_f64, out_i64, N, i, j, term);
 }
 
 // The same for P <= 32 patches per frame (the reference: 30) with the Gram rows read as long contiguous runs: a workgroup takes frame i against PS_JT consecutive
@@ -620,8 +673,7 @@ constexpr int PS_JT = 8;
 constexpr int PS_GX = 8;        // workgroups per frame i: each walks every PS_GX-th run of PS_JT frames
 __global__ __launch_bounds__(256) void pair_score_tile_kernel(const double* __restrict__ desc, const double* __restrict__ G,
                                                               long long ldg, long long col0, const double* __restrict__ nrm2,
-                                                              const double* __restrict__ proj,
-                                                              const double* __restrict__ score, long long N, int P, int H,
+                                                              const double* __restrict__ proj, long long N, int P, int H,
                                                               long long i_lo, long long i_hi, double ca, double cb,
                                                               double* __restrict__ out_f64, long long* __restrict__ out_i64,
                                                               const int2* __restrict__ prog,
@@ -671,7 +723,6 @@ __global__ __launch_bounds__(256) void pair_score_tile_kernel(const double* __re
         const long long jn = j0 + (long long)PS_GX * PS_JT;
         if (jn < N) fetch(jn);
         const long long j = j0 + jj;
-        double term = 0.0, wd = 1.0;
         const bool pair_ok = j > i && j < N;
         int bi = 0;
         unsigned cand = 0;
@@ -701,39 +752,19 @@ __global__ __launch_bounds__(256) void pair_score_tile_kernel(const double* __re
             }
             const double win = gram_window(H, na, nbmax, best);
             if (second - best <= win) {
-                const unsigned long long* hbj = rowhash + 2 * (j * P);
-                for (int b = 0; b < P; ++b) {
-                    if (!(fmax(na + nbj[b] - 2.0 * grow[b], 0.0) - best <= win)) continue;
-                    bool copy = false;
-                    for (unsigned m = cand; m; m &= m - 1) {
-                        const int e = __ffs((int)m) - 1;
-                        copy |= hbj[2 * e] == hbj[2 * b] && hbj[2 * e + 1] == hbj[2 * b + 1];
-                    }
-                    if (!copy) cand |= 1u << b;
-                }
-                if (!(cand & (cand - 1))) { bi = __ffs((int)cand) - 1; cand = 0; }       // one patch left: decided
+                for (int b = 0; b < P; ++b)
+                    if (fmax(na + nbj[b] - 2.0 * grow[b], 0.0) - best <= win) cand |= 1u << b;
+                cand = drop_copies(cand, rowhash + 2 * (j * P));
+                decided(cand, bi);
             }
         }
-        for (unsigned long long todo = __ballot(cand != 0); todo; todo &= todo - 1) {    // this wave's undecided arg-mins
-            const int src = __ffsll((long long)todo) - 1;
-            const unsigned cm = (unsigned)__shfl((int)cand, src);
-            const long long j_s = j0 + w * 2 + (src >> 5);
-            const int ebi = direct_argmin_wave(desc + (i * P + (src & 31)) * H, desc + j_s * P * H, (unsigned long long)cm, P, H, lane,
-                                               prog, (int)*prog_len, ps_lds_raw + (size_t)w * 8 * PF_STACK_DEPTH);
-            if (lane == src) bi = ebi;
-        }
-        if (pair_ok && a < P) wd = proj_diff(proj, ra, j * P + bi);     // |dot(score, m_i - m_j*)|, :42-43
-        if (pair_ok && a < P) term = ca + cb * log(wd);         // :48
-        for (int o = 16; o > 0; o >>= 1) term += __shfl_xor(term, o);      // the 32 lanes of this pair (lanes >= P hold 0)
-        if (pair_ok && a == 0) {
-            out_f64[i * N + j] = term;
-            out_f64[j * N + i] = term;
-            if (out_i64) {
-                const long long t = f64_to_i64_trunc(term);
-                out_i64[i * N + j] = t;
-                out_i64[j * N + i] = t;
-            }
-        }
+        resolve_undecided(cand, true, bi, P, H, lane, prog, (int)*prog_len, wave_stacks(ps_lds_raw, w),
+                          [&](int src, const double*& xa, const double*& xj) {       // lane = (frame jj of this wave's two, patch a)
+                              xa = desc + (i * P + (src & 31)) * H;
+                              xj = desc + (j0 + w * 2 + (src >> 5)) * P * H;
+                          });
+        const double term = pair_terms<32>(pair_ok && a < P, proj, ra, j * P + bi, ca, cb);     // (lanes >= P hold 0)
+        if (pair_ok && a == 0) store_pair(out_f64, out_i64, N, i, j, term);
         __syncthreads();                                         // g / nb are rewritten for the next run
     }
 }
@@ -750,7 +781,7 @@ __global__ __launch_bounds__(256) void pair_score_tile_kernel(const double* __re
 __global__ __launch_bounds__(256) void pair_score_amin_kernel(const double* __restrict__ desc,
                                                               const unsigned char* __restrict__ abi,
                                                               const unsigned* __restrict__ acand, long long rp,
-                                                              const double* __restrict__ proj, const double* __restrict__ score,
+                                                              const double* __restrict__ proj,
                                                               unsigned long long* __restrict__ keys, long long N, int P, int H,
                                                               double ca, double cb, double* __restrict__ out_f64,
                                                               long long* __restrict__ out_i64, const int2* __restrict__ prog,
@@ -779,52 +810,19 @@ __global__ __launch_bounds__(256) void pair_score_amin_kernel(const double* __re
             bi = abi[j * rp + ra];
             cand = acand[j * rp + ra];
             if (cand) {
-                // a copy of an earlier candidate (equal content hashes: sim_mix64) has that candidate's distance and a
-                // later index: np.argmin never takes it
-                const unsigned long long* hbj = rowhash + 2 * (j * P);
-                unsigned kept = 0;
-                for (unsigned m = cand; m; m &= m - 1) {
-                    const int b = __ffs((int)m) - 1;
-                    bool copy = false;
-                    for (unsigned k2 = kept; k2; k2 &= k2 - 1) {
-                        const int e = __ffs((int)k2) - 1;
-                        copy |= hbj[2 * e] == hbj[2 * b] && hbj[2 * e + 1] == hbj[2 * b + 1];
-                    }
-                    if (!copy) kept |= 1u << b;
-                }
-                cand = kept;
-                if (!(cand & (cand - 1))) { bi = __ffs((int)cand) - 1; cand = 0; }       // one patch left: decided
+                cand = drop_copies(cand, rowhash + 2 * (j * P));
+                decided(cand, bi);
             }
         }
-        // the undecided arg-mins of this wave, one after the other
-        unsigned long long todo = __ballot(cand != 0);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const unsigned cm = (unsigned)__shfl((int)cand, src);
-            const int a_s = src & 31;
-            const long long j_s = j0 + (src >> 5);
-            const int ebi = direct_argmin_wave(desc + (i * P + a_s) * H, desc + j_s * P * H, (unsigned long long)cm, P, H, lane,
-                                               prog, prog_len, ps_lds_all + (size_t)w * 8 * PF_STACK_DEPTH);
-            if (lane == src) bi = ebi;
-            if (lane == 0) {
-                ++fallbacks;
-                if (direct_map) direct_map[i * N + j_s] = 1;
-            }
-        }
-        double term = 0.0, wd = 1.0;
-        if (live) wd = proj_diff(proj, ra, j * P + bi);         // |dot(score, m_i - m_j*)|, :42-43
-        if (live) term = ca + cb * log(wd);                     // :48
-        for (int o = 16; o > 0; o >>= 1) term += __shfl_xor(term, o);
-        if (pair_ok && a == 0) {
-            out_f64[i * N + j] = term;
-            out_f64[j * N + i] = term;
-            if (out_i64) {
-                const long long t = f64_to_i64_trunc(term);
-                out_i64[i * N + j] = t;
-                out_i64[j * N + i] = t;
-            }
-        }
+        fallbacks += resolve_undecided(cand, true, bi, P, H, lane, prog, prog_len, wave_stacks(ps_lds_all, w),
+                                       [&](int src, const double*& xa, const double*& xj) {
+                                           const long long j_s = j0 + (src >> 5);
+                                           xa = desc + (i * P + (src & 31)) * H;
+                                           xj = desc + j_s * P * H;
+                                           if (lane == 0 && direct_map) direct_map[i * N + j_s] = 1;
+                                       });
+        const double term = pair_terms<32>(live, proj, ra, j * P + bi, ca, cb);
+        if (pair_ok && a == 0) store_pair(out_f64, out_i64, N, i, j, term);
     }
     if (lane == 0 && fallbacks) atomicAdd(n_fallback, fallbacks);
 }
@@ -872,7 +870,7 @@ __global__ __launch_bounds__(256) void sim_sample_kernel(const double* __restric
     double d = lane < P ? d2s[lane] * inv * inv : INFINITY;       // in the filter's units (|v_b - v_a|^2)
     if (lane < P) {
         const unsigned long long* hb = rowhash + 2 * (j * P);
-        bool copy = false;
+        bool copy = false;                                        // (drop_copies' rule, one lane per patch)
         for (int e = 0; e < lane; ++e) copy |= hb[2 * e] == hb[2 * lane] && hb[2 * e + 1] == hb[2 * lane + 1];
         if (copy) d = INFINITY;
     }
@@ -948,7 +946,7 @@ __global__ __launch_bounds__(256) void stream_argmin_kernel(const char* __restri
                                                             const int2* __restrict__ prog) {
     constexpr int NG = 2 * NQ + 1;                                 // query-side groups: NQ * P + 15 patches at most
     constexpr int DEPTH = NQ == 1 ? 4 : 2;                         // k-steps in flight (registers: rings of DEPTH buffers)
-    __shared__ double stacks[4][8 * PF_STACK_DEPTH];
+    __shared__ double stacks[PF_STACK_BYTES / 8];
     f += (long long)blockIdx.y * NQ;                               // the pass's first query frame
     bi_out += (long long)blockIdx.y * NQ * bi_pitch;
     const int nv = (int)(f_end - f < NQ ? f_end - f : NQ);         // query frames of this pass (>= 1)
@@ -1054,30 +1052,14 @@ __global__ __launch_bounds__(256) void stream_argmin_kernel(const char* __restri
             cand |= (unsigned)__shfl_xor((int)cand, 16);
             cand |= (unsigned)__shfl_xor((int)cand, 32);
             if (cand & (cand - 1)) {
-                // a copy of an earlier candidate (equal content hashes) has that candidate's distance and a later index
-                const unsigned long long* hb = rowhash + 2 * rows_old;
-                unsigned kept = 0;
-                for (unsigned m = cand; m; m &= m - 1) {
-                    const int b = __ffs((int)m) - 1;
-                    bool copy = false;
-                    for (unsigned k2 = kept; k2; k2 &= k2 - 1) {
-                        const int e = __ffs((int)k2) - 1;
-                        copy |= hb[2 * e] == hb[2 * b] && hb[2 * e + 1] == hb[2 * b + 1];
-                    }
-                    if (!copy) kept |= 1u << b;
-                }
-                cand = kept;
-                if (!(cand & (cand - 1))) { bi = __ffs((int)cand) - 1; cand = 0; }
+                cand = drop_copies(cand, rowhash + 2 * rows_old);
+                decided(cand, bi);
             } else cand = 0;
-            for (unsigned long long todo = __ballot(cand != 0 && quad == 0 && a_ok); todo; todo &= todo - 1) {
-                const int src = __ffsll((long long)todo) - 1;
-                const unsigned cm = (unsigned)__shfl((int)cand, src);
-                const long long a_s = (gd0 + ig) * 16 + (src & 15);
-                const int ebi = direct_argmin_wave(desc + a_s * H, desc + rows_old * H, (unsigned long long)cm, P, H, lane, prog,
-                                                   prog_len, stacks[w]);
-                if (lane == src) bi = ebi;
-                if (lane == 0) ++directs;
-            }
+            directs += resolve_undecided(cand, quad == 0 && a_ok, bi, P, H, lane, prog, prog_len, wave_stacks(stacks, w),
+                                         [&](int src, const double*& xa, const double*& xj) {
+                                             xa = desc + ((gd0 + ig) * 16 + (src & 15)) * H;
+                                             xj = desc + rows_old * H;
+                                         });
             if (quad == 0 && a_ok) bi_out[(long long)y * bi_pitch + a] = (unsigned char)bi;
         }
     }
@@ -1088,7 +1070,6 @@ __global__ __launch_bounds__(256) void stream_argmin_kernel(const char* __restri
 // b* = bi[j P + a] the patch of frame f nearest to a: the tail of the pair kernels, term for term and in their summation
 // order (32-lane xor tree), so the row equals the matrix call's column f bit for bit.
 __global__ __launch_bounds__(256) void stream_score_kernel(const double* __restrict__ desc, const double* __restrict__ proj,
-                                                           const double* __restrict__ score,
                                                            const unsigned char* __restrict__ bi_in, long long bi_pitch,
                                                            unsigned long long* __restrict__ keys, long long f, int P, int H,
                                                            double ca, double cb, double* __restrict__ row, long long ld_row,
@@ -1103,14 +1084,9 @@ __global__ __launch_bounds__(256) void stream_score_kernel(const double* __restr
         keys[4] = 0ull;                                         // reset for the next query (no memset launch in front of it)
     }
     const bool pair_ok = j < f, live = pair_ok && a < P;
-    double term = 0.0, wd = 1.0;
-    if (live) {
-        const long long ra = j * P + a;
-        wd = proj_diff(proj, ra, f * P + bi_in[ra]);            // |dot(score, m_i - m_j*)|, :42-43
-    }
-    if (live) term = ca + cb * log(wd);                         // :48
-    for (int o = 16; o > 0; o >>= 1) term += __shfl_xor(term, o);
-    if (pair_ok && a == 0) row[j] = keys[2] ? __longlong_as_double(0x7ff8000000000000ll) : term;
+    const long long ra = j * P + a;
+    const double term = pair_terms<32>(live, proj, ra, f * P + (live ? bi_in[ra] : 0), ca, cb);
+    if (pair_ok && a == 0) row[j] = keys[2] ? quiet_nan() : term;
 }
 
 // The batched query through the matrix call's product kernel (gram_argmin_i8_strip: the batch's frames are a strip of
@@ -1140,31 +1116,16 @@ __global__ __launch_bounds__(256) void strip_resolve_kernel(const double* __rest
         bi = abi[(fj - fj_base) * rp + ra];
         cand = acand[(fj - fj_base) * rp + ra];
         if (cand) {
-            const unsigned long long* hbj = rowhash + 2 * (fj * P);
-            unsigned kept = 0;
-            for (unsigned m = cand; m; m &= m - 1) {
-                const int b = __ffs((int)m) - 1;
-                bool copy = false;
-                for (unsigned k2 = kept; k2; k2 &= k2 - 1) {
-                    const int e = __ffs((int)k2) - 1;
-                    copy |= hbj[2 * e] == hbj[2 * b] && hbj[2 * e + 1] == hbj[2 * b + 1];
-                }
-                if (!copy) kept |= 1u << b;
-            }
-            cand = kept;
-            if (!(cand & (cand - 1))) { bi = __ffs((int)cand) - 1; cand = 0; }           // one patch left: decided
+            cand = drop_copies(cand, rowhash + 2 * (fj * P));
+            decided(cand, bi);
         }
     }
-    unsigned long long directs = 0;
-    for (unsigned long long todo = __ballot(cand != 0); todo; todo &= todo - 1) {
-        const int src = __ffsll((long long)todo) - 1;
-        const unsigned cm = (unsigned)__shfl((int)cand, src);
-        const long long ra_s = (long long)blockIdx.x * 256 + w * 64 + src;
-        const int ebi = direct_argmin_wave(desc + ra_s * H, desc + fj * P * H, (unsigned long long)cm, P, H, lane, prog, prog_len,
-                                           rs_lds_all + (size_t)w * 8 * PF_STACK_DEPTH);
-        if (lane == src) bi = ebi;
-        if (lane == 0) ++directs;
-    }
+    const unsigned long long directs =
+        resolve_undecided(cand, true, bi, P, H, lane, prog, prog_len, wave_stacks(rs_lds_all, w),
+                          [&](int src, const double*& xa, const double*& xj) {
+                              xa = desc + ((long long)blockIdx.x * 256 + w * 64 + src) * H;
+                              xj = desc + fj * P * H;
+                          });
     if (live) bi_out[(long long)blockIdx.y * bi_pitch + ra] = (unsigned char)bi;
     if (lane == 0 && directs) atomicAdd(&keys[4], directs);
 }
@@ -1182,7 +1143,7 @@ __global__ __launch_bounds__(256) void topk_rows_f64_kernel(const double* __rest
     const long long r = blockIdx.x;
     if (poison && *poison != 0) {                                // the caller's "these scores mean nothing" word: say so in the
         for (int t = threadIdx.x; t < k; t += 256) {             // output itself (NaN, -1), not with an empty list
-            out_s[r * k + t] = __longlong_as_double(0x7ff8000000000000ll);
+            out_s[r * k + t] = quiet_nan();
             out_i[r * k + t] = -1;
         }
         return;
@@ -1275,7 +1236,7 @@ __global__ __launch_bounds__(256) void sim_finish_kernel(const unsigned long lon
     if (stats && blockIdx.x == 0 && threadIdx.x == 0) { stats[0] = (long long)keys[4]; stats[1] = (long long)keys[2]; }
     if (!poison || !bad) return;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nn; e += (long long)gridDim.x * 256) {
-        out_f64[e] = __longlong_as_double(0x7ff8000000000000ll);
+        out_f64[e] = quiet_nan();
         if (out_i64) out_i64[e] = (long long)0x8000000000000000ull;
     }
 }
@@ -1491,7 +1452,7 @@ extern "C" int dlc_sdav_similarity_matrix(dlc_ctx* ctx, const double* desc, int6
             rc = dlc_gemm::gram_argmin_i8(ctx, N, P, H, qx, nbp, keys, abi, acand, ws + w.blk, st);
             if (rc != DLC_OK) return rc;
             hipLaunchKernelGGL(pair_score_amin_kernel, dim3(PS_GX, (unsigned)(N - 1)), dim3(256), PF_STACK_BYTES, st, desc,
-                               (const unsigned char*)abi, (const unsigned*)acand, (long long)dlc_gemm::sim_argmin_pitch(N, P), proj, score, keys,
+                               (const unsigned char*)abi, (const unsigned*)acand, (long long)dlc_gemm::sim_argmin_pitch(N, P), proj, keys,
                                (long long)N, (int)P, (int)H, a, b, out_f64, (long long*)out_i64, prog, rowhash, direct_pairs);
             DLC_LAUNCH_CHECK(ctx, "pair_score_amin_kernel");
         }
@@ -1540,7 +1501,13 @@ extern "C" int dlc_sdav_similarity_matrix(dlc_ctx* ctx, const double* desc, int6
                        : dlc_gemm::gram_upper_f64(ctx, DLC_B_NK, mrows, ncols, H, desc + i_lo * P * H, H, desc + col0 * H, H, gram,
                                                   ncols, (int)P, i_lo * P, col0, st);
         if (rc != DLC_OK) return rc;
-        dim3 grid((unsigned)dlc::cdiv(N, 4), (unsigned)(i_hi - i_lo));
+        // (the general and the tiled kernel take the same arguments)
+        auto launch_pairs = [&](auto kernel, dim3 grid, size_t lds) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, desc, (const double*)gram, ncols, col0, (const double*)nrm2,
+                               (const double*)proj, (long long)N, (int)P, (int)H, i_lo, i_hi, a, b, out_f64, (long long*)out_i64,
+                               (const int2*)(ws + w.prog), (const unsigned long long*)(ws + w.keys) + 5,
+                               (const unsigned long long*)(ws + w.rowhash));
+        };
         const size_t tile_lds = PF_STACK_BYTES + ((size_t)P * ((PS_JT * P) | 1) + (size_t)PS_JT * P) * sizeof(double);
         const bool tiled = P <= 32;
         if (tiled) {
@@ -1548,15 +1515,9 @@ extern "C" int dlc_sdav_similarity_matrix(dlc_ctx* ctx, const double* desc, int6
                 DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)pair_score_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 76 * 1024));
                 ctx->func_attr_set |= 1ull << DLC_ATTR_PAIR_TILE;
             }
-            hipLaunchKernelGGL(pair_score_tile_kernel, dim3(PS_GX, (unsigned)(i_hi - i_lo)), dim3(256), tile_lds,
-                               st, desc, gram, ncols, col0, nrm2, proj, score, (long long)N, (int)P, (int)H, i_lo, i_hi, a, b,
-                               out_f64, (long long*)out_i64, (const int2*)(ws + w.prog),
-                               (const unsigned long long*)(ws + w.keys) + 5, (const unsigned long long*)(ws + w.rowhash));
+            launch_pairs(pair_score_tile_kernel, dim3(PS_GX, (unsigned)(i_hi - i_lo)), tile_lds);
         } else
-            hipLaunchKernelGGL(pair_score_kernel, grid, dim3(256), 0, st, desc, gram, ncols, col0, nrm2, proj, score,
-                               (long long)N, (int)P, (int)H, i_lo, i_hi, a, b, out_f64, (long long*)out_i64,
-                               (const int2*)(ws + w.prog), (const unsigned long long*)(ws + w.keys) + 5,
-                               (const unsigned long long*)(ws + w.rowhash));
+            launch_pairs(pair_score_kernel, dim3((unsigned)dlc::cdiv(N, 4), (unsigned)(i_hi - i_lo)), 0);
         DLC_LAUNCH_CHECK(ctx, "pair_score_kernel");
     }
     return DLC_OK;
@@ -1626,9 +1587,10 @@ static BatchWs batch_ws(int64_t capacity, int64_t P, int64_t nq) {
     return w;
 }
 
-static int stream_query_impl(dlc_ctx* ctx, const char* what, void* state, size_t state_bytes, int64_t capacity, int64_t P, int64_t H,
-                             const double* desc, int64_t f, int64_t nq, const double* score, double a, double b, double* rows_out,
-                             int64_t ld_rows, int64_t* stats, unsigned char* bi, int64_t bi_pitch, void* stream,
+// (the distinctive score is not an argument: it went into the resident projections when the frames were appended)
+static int stream_query_impl(dlc_ctx* ctx, void* state, int64_t capacity, int64_t P, int64_t H, const double* desc, int64_t f,
+                             int64_t nq, double a, double b, double* rows_out, int64_t ld_rows, int64_t* stats, unsigned char* bi,
+                             int64_t bi_pitch, void* stream,
                              char* batch_base = nullptr, const BatchWs* bw = nullptr, int stage = 0) {
     hipStream_t st = (hipStream_t)stream;
     const StreamWs w = stream_ws(capacity, P, H);
@@ -1659,27 +1621,20 @@ static int stream_query_impl(dlc_ctx* ctx, const char* what, void* state, size_t
                            (const unsigned long long*)(ws + w.rowhash), keys, (long long)f, (int)P, (int)H, (const int2*)(ws + w.prog), bi,
                            (long long)bi_pitch);
         DLC_LAUNCH_CHECK(ctx, "strip_resolve_kernel");
-        hipLaunchKernelGGL(stream_score_kernel, dim3((unsigned)dlc::cdiv(f_last, (int64_t)8), (unsigned)nq), dim3(256), 0, st, desc,
-                           (const double*)(ws + w.proj), score, (const unsigned char*)bi, (long long)bi_pitch, keys, (long long)f, (int)P,
-                           (int)H, a, b, rows_out, (long long)ld_rows, (long long*)stats);
-        DLC_LAUNCH_CHECK(ctx, what);
-        return DLC_OK;
+    } else {
+        const long long groups = dlc::cdiv(f_last * P, (int64_t)16);      // of the newest query; an older one's extra blocks leave at once
+        const dim3 agrid((unsigned)dlc::cdiv(groups, (long long)(4 * SR_G)), (unsigned)(nq == 1 ? 1 : dlc::cdiv(nq, (int64_t)2)));
+        // (a batch: two query frames per pass over the panel)
+        const auto argmin_kernel = nq == 1 ? stream_argmin_kernel<1> : stream_argmin_kernel<2>;
+        hipLaunchKernelGGL(argmin_kernel, agrid, dim3(256), 0, st, (const char*)(ws + w.panel), gpitch, (int)(kp / 64), desc,
+                           (const double*)(ws + w.nu2), (const unsigned long long*)(ws + w.rowhash), keys, (long long)f,
+                           (long long)(f + nq), (int)P, (int)H, bi, (long long)bi_pitch, (const int2*)(ws + w.prog));
+        DLC_LAUNCH_CHECK(ctx, "stream_argmin_kernel");
     }
-    const long long groups = dlc::cdiv(f_last * P, (int64_t)16);          // of the newest query; an older one's extra blocks leave at once
-    const dim3 agrid((unsigned)dlc::cdiv(groups, (long long)(4 * SR_G)), (unsigned)(nq == 1 ? 1 : dlc::cdiv(nq, (int64_t)2)));
-    if (nq == 1)
-        hipLaunchKernelGGL(stream_argmin_kernel<1>, agrid, dim3(256), 0, st, (const char*)(ws + w.panel), gpitch, (int)(kp / 64), desc,
-                           (const double*)(ws + w.nu2), (const unsigned long long*)(ws + w.rowhash), keys, (long long)f,
-                           (long long)(f + nq), (int)P, (int)H, bi, (long long)bi_pitch, (const int2*)(ws + w.prog));
-    else                                                        // a batch: two query frames per pass over the panel
-        hipLaunchKernelGGL(stream_argmin_kernel<2>, agrid, dim3(256), 0, st, (const char*)(ws + w.panel), gpitch, (int)(kp / 64), desc,
-                           (const double*)(ws + w.nu2), (const unsigned long long*)(ws + w.rowhash), keys, (long long)f,
-                           (long long)(f + nq), (int)P, (int)H, bi, (long long)bi_pitch, (const int2*)(ws + w.prog));
-    DLC_LAUNCH_CHECK(ctx, "stream_argmin_kernel");
     hipLaunchKernelGGL(stream_score_kernel, dim3((unsigned)dlc::cdiv(f_last, (int64_t)8), (unsigned)nq), dim3(256), 0, st, desc,
-                       (const double*)(ws + w.proj), score, (const unsigned char*)bi, (long long)bi_pitch, keys, (long long)f, (int)P,
+                       (const double*)(ws + w.proj), (const unsigned char*)bi, (long long)bi_pitch, keys, (long long)f, (int)P,
                        (int)H, a, b, rows_out, (long long)ld_rows, (long long*)stats);
-    DLC_LAUNCH_CHECK(ctx, what);
+    DLC_LAUNCH_CHECK(ctx, "stream_score_kernel");
     return DLC_OK;
 }
 
@@ -1693,7 +1648,7 @@ extern "C" int dlc_sdav_stream_query(dlc_ctx* ctx, void* state, size_t state_byt
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     const StreamWs w = stream_ws(capacity, P, H);
-    return stream_query_impl(ctx, "stream_score_kernel", state, state_bytes, capacity, P, H, desc, f, 1, score, a, b, row_out, 0, stats,
+    return stream_query_impl(ctx, state, capacity, P, H, desc, f, 1, a, b, row_out, 0, stats,
                              (unsigned char*)((char*)state + w.bi), 0, stream);
 }
 
@@ -1702,51 +1657,49 @@ extern "C" size_t dlc_sdav_stream_query_batch_workspace_bytes(int64_t capacity, 
     return batch_ws(capacity, P, n_queries).total;
 }
 
+// Both batched entry points: the argument, workspace and alignment checks in the order their callers are promised (the
+// device guard sits between the workspace's size and its alignment, so the checks and the launch share this one
+// function), then the query.  stage 0: the one-call form; 1 / 2: the staged form, which takes the strip's shapes only;
+// < 0: the staged form called with a stage that is neither.
+static int batch_query(dlc_ctx* ctx, const char* what, void* state, size_t state_bytes, int64_t capacity, int64_t P, int64_t H,
+                       const double* desc, int64_t f_first, int64_t n_queries, const double* score, double a, double b,
+                       double* rows_out, int64_t ld_rows, int64_t* stats, void* workspace, size_t workspace_bytes, int stage,
+                       void* stream) {
+    const bool staged = stage != 0;
+    int rc = stream_check(ctx, what, state, state_bytes, capacity, P, H);
+    if (rc != DLC_OK) return rc;
+    if (stage < 0) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: stage must be 1 or 2", what);
+    if (!desc || !score || !rows_out || f_first < 0 || n_queries < 1 || n_queries > 65535 || f_first + n_queries > capacity ||
+        ld_rows < f_first + n_queries - 1)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: bad argument (frames [%lld, %lld) of capacity %lld, ld_rows %lld)", what,
+                         (long long)f_first, (long long)(f_first + n_queries), (long long)capacity, (long long)ld_rows);
+    if (staged && (n_queries < STRIP_MIN_QUERIES || !dlc_gemm::sim_filter_fits(capacity, P, H)))
+        return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "%s: only the strip form (batches of %lld frames and more) has two stages", what,
+                         (long long)STRIP_MIN_QUERIES);
+    const BatchWs bw = batch_ws(capacity, P, n_queries);
+    if (!workspace || workspace_bytes < bw.total)
+        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, bw.total);
+    dlc::DeviceGuard guard(ctx->device);
+    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    if ((uintptr_t)workspace & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: workspace must be 256-byte aligned", what);
+    return stream_query_impl(ctx, state, capacity, P, H, desc, f_first, n_queries, a, b, rows_out, ld_rows, stats,
+                             (unsigned char*)workspace + bw.bi, bw.pitch, stream, (char*)workspace, &bw, stage);
+}
+
 extern "C" int dlc_sdav_stream_query_batch(dlc_ctx* ctx, void* state, size_t state_bytes, int64_t capacity, int64_t P, int64_t H,
                                            const double* desc, int64_t f_first, int64_t n_queries, const double* score, double a,
                                            double b, double* rows_out, int64_t ld_rows, int64_t* stats, void* workspace,
                                            size_t workspace_bytes, void* stream) {
-    int rc = stream_check(ctx, "sdav_stream_query_batch", state, state_bytes, capacity, P, H);
-    if (rc != DLC_OK) return rc;
-    if (!desc || !score || !rows_out || f_first < 0 || n_queries < 1 || n_queries > 65535 || f_first + n_queries > capacity ||
-        ld_rows < f_first + n_queries - 1)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query_batch: bad argument (frames [%lld, %lld) of capacity %lld, ld_rows %lld)",
-                         (long long)f_first, (long long)(f_first + n_queries), (long long)capacity, (long long)ld_rows);
-    const size_t need = dlc_sdav_stream_query_batch_workspace_bytes(capacity, P, n_queries);
-    if (!workspace || workspace_bytes < need)
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sdav_stream_query_batch: workspace %zu < %zu bytes", workspace_bytes, need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    if ((uintptr_t)workspace & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query_batch: workspace must be 256-byte aligned");
-    const BatchWs bw = batch_ws(capacity, P, n_queries);
-    return stream_query_impl(ctx, "stream_score_kernel", state, state_bytes, capacity, P, H, desc, f_first, n_queries, score, a, b, rows_out,
-                             ld_rows, stats, (unsigned char*)workspace + bw.bi, bw.pitch, stream, (char*)workspace, &bw);
+    return batch_query(ctx, "sdav_stream_query_batch", state, state_bytes, capacity, P, H, desc, f_first, n_queries, score, a, b,
+                       rows_out, ld_rows, stats, workspace, workspace_bytes, 0, stream);
 }
 
 extern "C" int dlc_sdav_stream_query_batch_staged(dlc_ctx* ctx, void* state, size_t state_bytes, int64_t capacity, int64_t P, int64_t H,
                                                   const double* desc, int64_t f_first, int64_t n_queries, const double* score, double a,
                                                   double b, double* rows_out, int64_t ld_rows, int64_t* stats, void* workspace,
                                                   size_t workspace_bytes, int stage, void* stream) {
-    int rc = stream_check(ctx, "sdav_stream_query_batch_staged", state, state_bytes, capacity, P, H);
-    if (rc != DLC_OK) return rc;
-    if (stage != 1 && stage != 2) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query_batch_staged: stage must be 1 or 2");
-    if (!desc || !score || !rows_out || f_first < 0 || n_queries < 1 || n_queries > 65535 || f_first + n_queries > capacity ||
-        ld_rows < f_first + n_queries - 1)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query_batch_staged: bad argument (frames [%lld, %lld) of capacity %lld, ld_rows %lld)",
-                         (long long)f_first, (long long)(f_first + n_queries), (long long)capacity, (long long)ld_rows);
-    if (n_queries < STRIP_MIN_QUERIES || !dlc_gemm::sim_filter_fits(capacity, P, H))
-        return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "sdav_stream_query_batch_staged: only the strip form (batches of %lld frames and more) "
-                         "has two stages", (long long)STRIP_MIN_QUERIES);
-    const size_t need = dlc_sdav_stream_query_batch_workspace_bytes(capacity, P, n_queries);
-    if (!workspace || workspace_bytes < need)
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sdav_stream_query_batch_staged: workspace %zu < %zu bytes", workspace_bytes, need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    if ((uintptr_t)workspace & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query_batch_staged: workspace must be 256-byte aligned");
-    if (f_first + n_queries - 1 == 0) return DLC_OK;              // (frame 0 alone cannot be a strip; kept for symmetry)
-    const BatchWs bw = batch_ws(capacity, P, n_queries);
-    return stream_query_impl(ctx, "stream_score_kernel", state, state_bytes, capacity, P, H, desc, f_first, n_queries, score, a, b, rows_out,
-                             ld_rows, stats, (unsigned char*)workspace + bw.bi, bw.pitch, stream, (char*)workspace, &bw, stage);
+    return batch_query(ctx, "sdav_stream_query_batch_staged", state, state_bytes, capacity, P, H, desc, f_first, n_queries, score, a, b,
+                       rows_out, ld_rows, stats, workspace, workspace_bytes, stage == 1 || stage == 2 ? stage : -1, stream);
 }
 
 extern "C" int dlc_topk_rows_f64(dlc_ctx* ctx, const double* scores, int64_t rows, int64_t ld, int64_t limit0, int64_t limit_step,

@@ -10,7 +10,8 @@ import deeploopcloser_amd as dlc
 
 eng = dlc.default_engine()
 g = torch.Generator(device=eng.device); g.manual_seed(3)
-n, p, h = 1063, 30, 2500
+n, p, h = int(os.environ.get("DLC_PROF_N", "1063")), int(os.environ.get("DLC_PROF_P", "30")), 2500
+force_f64 = os.environ.get("DLC_PROF_FORCE_F64", "0") == "1"   # the fp64 Gram route (its pair kernels on the clock)
 kind = sys.argv[1] if len(sys.argv) > 1 else "saturated"
 if kind == "saturated":
     ds = torch.sigmoid(35.0 * torch.randn((n, p, h), generator=g, device=eng.device, dtype=torch.float64))
@@ -40,7 +41,7 @@ warm, calls = int(os.environ.get("DLC_PROF_WARM", "3")), int(os.environ.get("DLC
 def call():
     score, rng = eng.distinctive_score(ds, 0.5, 0.2, with_range=True)      # as SimilarityCalculator(dataset).similarity_matrix()
     stats = torch.zeros((2,), dtype=torch.int64, device=eng.device)
-    eng.sdav_similarity_matrix(ds, score, 10.0, -10.0, range=rng, stats=stats)
+    eng.sdav_similarity_matrix(ds, score, 10.0, -10.0, range=rng, stats=stats, force_f64=force_f64)
     return stats
 for _ in range(warm):
     stats = call()
@@ -51,5 +52,5 @@ for _ in range(calls):
     stats = call()
 e1.record()
 torch.cuda.synchronize()
-print("%s: %.3f ms per call (HIP events, %d calls back to back after %d warm-up calls), stats %s"
-      % (kind, e0.elapsed_time(e1) / calls, calls, warm, stats.tolist()), flush=True)
+print("%s%s: %.3f ms per call (HIP events, %d calls back to back after %d warm-up calls), stats %s"
+      % (kind, " (N = %d, P = %d, fp64 route)" % (n, p) if force_f64 else "", e0.elapsed_time(e1) / calls, calls, warm, stats.tolist()), flush=True)

@@ -1036,6 +1036,44 @@ def test_similarity_tiny_descriptors_follow_the_reference(dlc, monkeypatch):
         assert np.abs(got[fin] - ref[fin]).max() <= 1e-9 * max(1.0, np.abs(ref[fin]).max()), (n, p, h)
 
 
+def _general_pair_kernel_cases():
+    """(shape, kind, descriptors) for 33..64 patches per frame.  33: the first patch count that leaves the tiled kernel;
+    64 fills the candidate mask; widths of one, two and several leaves of the pairwise summation."""
+    rng = np.random.RandomState(43)
+    for n, p, h in [(5, 33, 17), (4, 64, 64), (6, 40, 129), (3, 47, 300)]:
+        x = 1.0 / (1.0 + np.exp(-35.0 * rng.standard_normal((n * p, h))))
+        x[1::2] = x[0::2][: x[1::2].shape[0]]
+        x[1::2, 0] += 1e-7                                # near-ties, as test_similarity_near_ties_follow_the_reference
+        binary = (rng.uniform(size=(n, p, h)) < 0.5).astype(np.float64)     # integer branch (1a) of the direct evaluation
+        for kind, ds in (("near_ties", x.reshape(n, p, h)), ("binary", binary)):
+            ds[1, p - 1] = ds[1, p - 2]                   # an exact copy at the two highest bits of the mask: only the hashes part them
+            if n > 2:
+                ds[2] = ds[0]                             # a frame seen twice: +inf scores
+            yield (n, p, h), kind, ds
+
+
+def test_similarity_general_pair_kernel_follows_the_reference(eng):
+    """More than 32 patches per frame: the fp64 Gram route's general kernel (one wave per frame pair, 64-bit candidate
+    mask) against the oracle -- near-ties that only the direct evaluation orders, exact copies among the highest patch
+    indices, a repeated frame, purely binary descriptors."""
+    from oracle import similarity as osim
+    for shape, kind, ds in _general_pair_kernel_cases():
+        ref = osim.similarity_matrix_f64(ds)
+        assert not np.isnan(ref).any() and np.isposinf(ref).sum() == 2, (shape, kind)
+        dev = torch.from_numpy(ds).to(eng.device)
+        score = eng.distinctive_score(dev, 0.5, 0.2)
+        mf, mi = eng.sdav_similarity_matrix(dev, score, 10.0, -10.0)
+        got, got_i = mf.cpu().numpy(), mi.cpu().numpy()
+        fin = np.isfinite(ref)
+        assert not np.isnan(got).any(), (shape, kind)
+        assert np.array_equal(np.isposinf(got), np.isposinf(ref)), (shape, kind)
+        assert np.array_equal(np.isfinite(got), fin), (shape, kind)
+        assert np.abs(got[fin] - ref[fin]).max() <= 1e-9 * max(1.0, np.abs(ref[fin]).max()), (shape, kind)
+        assert np.array_equal(got, got.T) and np.all(np.diag(got) == -1.0), (shape, kind)
+        assert np.array_equal(got_i, osim.truncate_to_int64(got)), (shape, kind)
+        assert np.array_equal(got_i, got_i.T) and np.all(np.diag(got_i) == -1), (shape, kind)
+
+
 def test_similarity_filter_equals_fp64_gram_route(eng, monkeypatch):
     """The two routes of dlc_sdav_similarity_matrix -- exact integer products of column-centred 24-bit fixed-point descriptors that
     decide the arg-min (with a direct fp64 evaluation where their error bound cannot), and the fp64 Gram matrix --
