@@ -16,7 +16,7 @@ DLC_BF16, DLC_F16, DLC_F32, DLC_F64, DLC_I8, DLC_U8, DLC_I64 = 0, 1, 2, 3, 4, 5,
 DLC_ACT_NONE, DLC_ACT_SIGMOID, DLC_ACT_RELU = 0, 1, 2
 DLC_B_KN, DLC_B_NK = 0, 1
 DLC_MAX_K = 128
-DLC_ABI_VERSION = 16         # include/dlc.h; load() refuses a library built from another header
+DLC_ABI_VERSION = 17         # include/dlc.h; load() refuses a library built from another header
 DLC_SELECT_COOP = 1
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 
@@ -92,6 +92,9 @@ SIGNATURES = {
     "dlc_sequence_topk": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(C.c_int32), _int, _int,
                                  _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "dlc_contrast_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
+    "dlc_peak_topk_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "dlc_peak_topk_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _i64, _int, _i64, _int, _vp, _vp, _vp,
+                                  _vp, _sz, _vp]),
     "dlc_l2_normalize_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp]),
     "dlc_cosine_topk_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "dlc_cosine_topk": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

@@ -1045,6 +1045,40 @@ class Engine:
         self._wrote(out)
         return out[:, :n]
 
+    def peak_topk_rows(self, scores, k, suppress, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None,
+                       poison=None):
+        """(scores [rows, k], idx [rows, k] int64): distinct-place candidates, the windowed peak top-k of
+        dlc_peak_topk_rows (include/dlc.h).  Per row of scores [rows, >= n] (fp64, fp32 or int64 on the device; a
+        row-strided view is taken as it is) the best cell among its first clamp(limit0 + r * limit_step, 0, n) (limit0
+        None = n), then the best one more than `suppress` columns from it, and so on: k picks, best first, ties -> the
+        lower column.  A NaN is never taken; absent (int64 rows only): a value that marks a cell as not there (the -1 of
+        sequence_scores).  Scores are fp64 (int64 for int64 rows); empty slots (-inf or +inf, -1), (-1, -1) for int64.
+        poison: a device int64 [1] read by the kernels; non-zero -> every fp64 slot (NaN, -1)."""
+        scores, rows, n, ld = self._score_matrix("peak_topk_rows", scores, n, "pick from")
+        k, suppress = int(k), int(suppress)
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("peak_topk_rows: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if not 0 <= suppress < 1 << 63:
+            raise ValueError("peak_topk_rows: suppress=%d outside 0..2^63-1" % suppress)
+        is_int = scores.dtype == torch.int64
+        if absent is not None and not is_int:
+            raise ValueError("peak_topk_rows: absent is for int64 rows (a float row marks absence with NaN)")
+        if poison is not None:
+            if is_int:
+                raise ValueError("peak_topk_rows: the poison word marks fp64 outputs; int64 rows have none")
+            self._check_out("poison", poison, (1,), torch.int64)
+        o_s = torch.empty((rows, k), dtype=torch.int64 if is_int else torch.float64, device=self.device)
+        o_i = torch.empty((rows, k), dtype=torch.int64, device=self.device)
+        need = self.lib.dlc_peak_topk_rows_workspace_bytes(rows, n, k)
+        if need == 0:
+            raise ValueError("peak_topk_rows: rows=%d, n=%d outside the supported sizes" % (rows, n))
+        ws = self.workspace("peak_topk_rows", need)
+        self._check(self.lib.dlc_peak_topk_rows(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(bool(lower_is_better)), suppress, int(absent is not None), 0 if absent is None else int(absent),
+            k, _ptr(o_s), _ptr(o_i), _ptr(poison), _ptr(ws), ws.numel(), self._stream()))
+        return o_s, o_i
+
     # ---- cosine + top-k -----------------------------------------------------------------
     @staticmethod
     def stored_width(d):

@@ -50,14 +50,16 @@ def _nothing_older(b, k, fill, dtype, device):
             torch.full((b, k), -1, dtype=torch.int64, device=device))
 
 
-def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False):
+def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None):
     """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
     if sequence is not None:
-        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better)
+        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress)
     if slopes is not None:
         raise ValueError("slopes needs sequence=L")
     if contrast is not None:
         raise ValueError("contrast needs sequence=L")
+    if suppress is not None:
+        raise ValueError("suppress needs sequence=L (L = 1 ranks by the frame scores themselves)")
     return None
 
 
@@ -90,10 +92,14 @@ class LoopClosureDetector:
 
     contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the key rows in front of the
     sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values (no 2^-40 rescale: the keys'
-    scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1)."""
+    scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1).
+
+    suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best key-frame, then
+    the best one more than W key-frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.
+    Scores, dtypes and empty slots are as without it."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None, sequence=None, slopes=None, contrast=None):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -102,7 +108,8 @@ class LoopClosureDetector:
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 key rows, then the batch's
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64)
+        self.suppress = None if suppress is None else int(suppress)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress)
         if self._seq is not None:
             self.slopes = self._seq.slopes
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
@@ -177,9 +184,14 @@ class _SequenceRows:
     the context rows (normalise) -- the buffer is float64 then -- and the lines are summed over that.  A stretch of
     key-frames that resembles every frame goes flat; a true revisit stands out from its neighbours.  A row's
     normalisation depends on that row alone, so the context rows stay valid and the lists still do not depend on the
-    batching."""
+    batching.
 
-    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False):
+    suppress = W (>= 0) makes the k candidates distinct places: the sequence search writes the batch's dense cell scores
+    and dlc_peak_topk_rows (include/dlc.h) picks from them -- the best cell, then the best one more than W key-frames
+    from every earlier pick -- under the same limits, order of merit and poison word.  A dense score depends on the rows
+    behind it alone, so these lists do not depend on the batching either."""
+
+    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None):
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
             raise ValueError("sequence=%d outside 1..64" % length)
@@ -190,7 +202,9 @@ class _SequenceRows:
             raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
         if contrast is not None and not 1 <= contrast <= 32:
             raise ValueError("contrast=%d outside 1..32" % contrast)
-        self.length, self.k, self.lower_is_better = length, k, lower_is_better
+        if suppress is not None and not 0 <= suppress < 1 << 63:
+            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
+        self.length, self.k, self.lower_is_better, self.suppress = length, k, lower_is_better, suppress
         self.contrast, self.raw_dtype, self._raw = contrast, dtype, None
         self._raw_item = torch.empty((), dtype=dtype).element_size()
         self.context, self.dtype, self.buf = length - 1, dtype if contrast is None else torch.float64, None
@@ -241,9 +255,15 @@ class _SequenceRows:
         is the frame L - 1 - m before the batch's first; rows of frames before the stream began offer nothing and are never
         read).  Then the last L - 1 rows become the next batch's context."""
         self.normalise(engine, n, limit0)
-        s, i, _, _ = engine.sequence_topk(self.window(b), self.length, self.slopes, k=self.k, row0=self.context, n=n,
-                                          limit0=limit0 - self.context, limit_step=1,
-                                          lower_is_better=self.lower_is_better, poison=poison)
+        s, i, _, dense = engine.sequence_topk(self.window(b), self.length, self.slopes,
+                                              k=self.k if self.suppress is None else None, row0=self.context, n=n,
+                                              limit0=limit0 - self.context, limit_step=1,
+                                              lower_is_better=self.lower_is_better, dense=self.suppress is not None,
+                                              poison=poison)
+        if self.suppress is not None:                              # k places: picks more than `suppress` key-frames apart
+            s, i = engine.peak_topk_rows(dense, self.k, self.suppress, limit0=limit0, limit_step=1,
+                                         lower_is_better=self.lower_is_better,
+                                         absent=-1 if dense.dtype == torch.int64 else None, poison=poison)
         self.advance(b)
         return s, i
 
@@ -266,10 +286,14 @@ class SdavLoopClosureDetector:
     contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the score rows in front of
     the sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values, `threshold` is compared
     with that sum, and an empty slot is (-inf, -1); submit() / result() launch the normalisation on the stream of the
-    rows' consumers, and a poisoned stream answers (NaN, -1) as before."""
+    rows' consumers, and a poisoned stream answers (NaN, -1) as before.
+
+    suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best frame, then the
+    best one more than W frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.  Scores,
+    dtypes, empty slots and the poisoned answer are as without it."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, sequence=None, slopes=None, contrast=None, **stream_args):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
@@ -279,7 +303,8 @@ class SdavLoopClosureDetector:
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 score rows, then the batch's
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64)
+        self.suppress = None if suppress is None else int(suppress)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress)
         if self._seq is not None:
             self.slopes = self._seq.slopes
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
@@ -446,10 +471,15 @@ class CnnVtlLoopClosureDetector:
     contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the distance rows in front
     of the sequence search (_SequenceRows).  Distances stay lower-is-better (the standard deviation is positive); dist is
     then the float64 sum of L normalised values, max_distance is compared with that sum (it may be negative), and an
-    empty slot is (+inf, -1)."""
+    empty slot is (+inf, -1).
+
+    suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the nearest key-frame,
+    then the nearest one more than W key-frames from it, and so on (_SequenceRows) -- instead of one minimum and its
+    neighbours; with k = 2 and W = R_window / 2 the two distances are OpenSeqSLAM's min_value and min_value_2nd
+    (sequence.uniqueness_ratio).  Distances, dtypes and empty slots are as without it."""
 
     def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None):
+                 contrast=None, suppress=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -463,7 +493,9 @@ class CnnVtlLoopClosureDetector:
         self.sequence = None if sequence is None else int(sequence)
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 distance rows, then the batch's
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True)
+        self.suppress = None if suppress is None else int(suppress)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
+                                     suppress=self.suppress)
         if self._seq is not None:
             self.slopes = self._seq.slopes
         from .distance import CnnVtlKeyframeDatabase
@@ -559,6 +591,9 @@ def main(argv=None):
     ap.add_argument("--contrast", type=int, default=None, metavar="R",
                     help="with --sequence: normalise every score against the R key-frames on either side of it first "
                          "(SeqSLAM's local contrast normalisation), R in 1..32")
+    ap.add_argument("--suppress", type=int, default=None, metavar="W",
+                    help="with --sequence: report distinct places -- every candidate more than W frames from the better "
+                         "ones of its frame (the windowed peak selection)")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
@@ -582,6 +617,10 @@ def main(argv=None):
         ap.error("--contrast needs --sequence")
     if args.contrast is not None and not 1 <= args.contrast <= 32:
         ap.error("--contrast must be 1..32")
+    if args.suppress is not None and args.sequence is None:
+        ap.error("--suppress needs --sequence")
+    if args.suppress is not None and args.suppress < 0:
+        ap.error("--suppress must be >= 0")
     if args.threshold is None:
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
@@ -621,7 +660,7 @@ def _stream(args, files):
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
                                           exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
-                                          contrast=args.contrast)
+                                          contrast=args.contrast, suppress=args.suppress)
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))

@@ -8,6 +8,11 @@ The matrices are the reference's as they come: SimilarityCalculator.similarity_m
 and DistanceCalculator.distance_matrix (int64, lower_is_better=True).  NumPy in -> NumPy out, device tensors in -> device
 tensors out.
 
+Distinct places.  The k best cells of a row are mostly ONE place: a revisit of key-frame j scores almost as well against
+j - 1, j + 1, ...  peak_topk / sequence_peaks pick the best cell, then the best one more than `suppress` key-frames from
+it, and so on (dlc_peak_topk_rows, include/dlc.h) -- SeqSLAM's "best trajectory, then the best one outside a window
+around it" -- and uniqueness_ratio is the quotient of the first two.
+
 contrast = R (None: off) first scores every cell against its neighbourhood within its row, (x - local mean) / local std
 over the R key-frames on either side -- SeqSLAM's local contrast normalisation (III-B of the paper; dlc_contrast_rows,
 include/dlc.h) -- so that a stretch of key-frames that resembles everything goes flat before the lines are summed.
@@ -15,6 +20,7 @@ include/dlc.h) -- so that a stretch of key-frames that resembles everything goes
 import numpy as np
 import torch
 
+from ._lib import DLC_MAX_K
 from .engine import default_engine
 
 
@@ -67,14 +73,19 @@ def contrast_normalize(matrix, radius, limit0=None, limit_step=0):
     return out.cpu().numpy() if as_numpy else out
 
 
-def _run(matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast=None):
-    e = default_engine()
-    matrix, as_numpy = _on_device(e, matrix)
+def _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast, poison=None):
+    """Engine.sequence_topk of a device matrix behind the optional contrast normalisation: device tensors."""
     if contrast is not None:
         matrix = contrast_normalize(matrix, contrast, limit0, limit_step)
     offsets = slope_offsets(L) if offsets is None else offsets
-    out = e.sequence_topk(matrix, L, offsets, k=k, limit0=limit0, limit_step=limit_step, lower_is_better=lower_is_better,
-                          dense=dense)
+    return e.sequence_topk(matrix, L, offsets, k=k, limit0=limit0, limit_step=limit_step, lower_is_better=lower_is_better,
+                           dense=dense, poison=poison)
+
+
+def _run(matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast=None):
+    e = default_engine()
+    matrix, as_numpy = _on_device(e, matrix)
+    out = _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast)
     return tuple(None if t is None else (t.cpu().numpy() if as_numpy else t) for t in out)
 
 
@@ -92,3 +103,60 @@ def sequence_scores(matrix, L, offsets=None, limit0=None, limit_step=0, lower_is
     """The dense [rows, n] sequence scores themselves (fp64, or int64 for int64 matrices): NaN / -1 where a cell has no
     valid line.  contrast = R: of contrast_normalize(matrix, R, limit0, limit_step), fp64."""
     return _run(matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast)[3]
+
+
+def _peaks(e, matrix, k, suppress, limit0, limit_step, lower_is_better, absent):
+    """Engine.peak_topk_rows of a device matrix; a matrix without rows or columns gives the empty lists."""
+    if matrix.shape[0] and matrix.shape[1]:
+        return e.peak_topk_rows(matrix, k, suppress, limit0=limit0, limit_step=limit_step, lower_is_better=lower_is_better,
+                                absent=absent)
+    if not 1 <= int(k) <= DLC_MAX_K or int(suppress) < 0:
+        raise ValueError("peak_topk: k=%d outside 1..%d or suppress=%d negative" % (int(k), DLC_MAX_K, int(suppress)))
+    is_int = matrix.dtype == torch.int64
+    fill = -1 if is_int else float("inf" if lower_is_better else "-inf")
+    shape = (matrix.shape[0], int(k))
+    return (torch.full(shape, fill, dtype=torch.int64 if is_int else torch.float64, device=e.device),
+            torch.full(shape, -1, dtype=torch.int64, device=e.device))
+
+
+def peak_topk(matrix, k, suppress, limit0=None, limit_step=0, lower_is_better=False, absent=None):
+    """(scores [rows, k], idx [rows, k] int64): distinct-place candidates of any score matrix [rows, n] (fp64, fp32 or
+    int64).  Per row the best cell among its first clamp(limit0 + r * limit_step, 0, n) columns (limit0 None: all), then
+    the best one more than `suppress` columns from it, then the best one more than `suppress` from both, ...: k picks,
+    best first, ties -> the lower column (dlc_peak_topk_rows, include/dlc.h).  A NaN is never picked; absent: for int64
+    matrices, a value that marks a cell as not there.  Scores are fp64 (int64 for int64 matrices); empty slots are
+    (-inf or +inf, -1), or (-1, -1) for int64.  suppress = 0 is the plain top-k."""
+    e = default_engine()
+    matrix, as_numpy = _on_device(e, matrix)
+    out = _peaks(e, matrix, k, suppress, limit0, limit_step, lower_is_better, absent)
+    return tuple(t.cpu().numpy() if as_numpy else t for t in out)
+
+
+def sequence_peaks(matrix, k, L, suppress, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None):
+    """(scores [rows, k], idx [rows, k] int64): the distinct-place candidates by the sequence score -- sequence_scores
+    (same L, offsets, limits and contrast), then peak_topk over those dense scores with the same limits: the best
+    trajectory, then the best one whose end lies more than `suppress` key-frames from it, ...  With k = 2,
+    lower_is_better and suppress = R_window / 2 the two slots are OpenSeqSLAM's min_value and min_value_2nd
+    (uniqueness_ratio).  int64 matrices: the dense scores mark "no valid line" with -1, which is passed on as the absent
+    value, so a genuine sequence sum of -1 is not offered either -- the convention (and the collision) of
+    dlc_sequence_topk's int64 seq_out."""
+    e = default_engine()
+    matrix, as_numpy = _on_device(e, matrix)
+    dense = _search(e, matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast)[3]
+    out = _peaks(e, dense, k, suppress, limit0, limit_step, lower_is_better, -1 if dense.dtype == torch.int64 else None)
+    return tuple(t.cpu().numpy() if as_numpy else t for t in out)
+
+
+def uniqueness_ratio(scores):
+    """float64 [rows]: scores[:, 0] / scores[:, 1] of lists with k >= 2 from peak_topk / sequence_peaks -- SeqSLAM's
+    uniqueness ratio, the best score over the best score outside the window around it.  It is meaningful for positive
+    lower-is-better scores (sums of distances): near 0 for a match that stands alone, near 1 for one that does not.  NaN
+    where slot 1 is empty (an infinity, or -1 in int64 lists).  NumPy in -> NumPy out, tensors in -> tensors out."""
+    as_numpy = not isinstance(scores, torch.Tensor)
+    s = torch.as_tensor(np.asarray(scores)) if as_numpy else scores
+    if s.dim() != 2 or s.shape[1] < 2:
+        raise ValueError("uniqueness_ratio: scores must be [rows, k >= 2]")
+    empty = (s[:, 1] == -1) if not s.dtype.is_floating_point else torch.isinf(s[:, 1])
+    ratio = s[:, 0].to(torch.float64) / s[:, 1].to(torch.float64)
+    ratio = torch.where(empty, torch.full_like(ratio, float("nan")), ratio)
+    return ratio.numpy() if as_numpy else ratio

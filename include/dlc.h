@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 16
+#define DLC_ABI_VERSION 17
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -629,6 +629,49 @@ int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows,
 int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t n, int64_t ld,
                       int64_t limit0, int64_t limit_step, int radius,
                       double* out, int64_t ld_out, void* stream);
+
+/*
+ * Distinct-place candidates: the windowed peak top-k of score rows -- the last step of SeqSLAM's matcher (Milford &
+ * Wyeth, ICRA 2012, III-D: the best trajectory, then the best one outside a window of key-frames around it).  A revisit
+ * of key-frame j scores almost as well against j - 1, j + 1, ...: a plain top-k fills up with the neighbours of one peak.
+ * Here a pick keeps every cell within `suppress` columns of it out of the later picks, so k picks are k places.
+ * INPUT.  M = scores [rows, ld], n <= ld columns in use, dtype DLC_F64, DLC_F32 or DLC_I64 -- rows of
+ * dlc_sdav_stream_query_batch, dlc_cnnvtl_distance_rows, dlc_cosine_score_rows, or dlc_sequence_topk's seq_out.
+ * OFFERED CELLS.  Row r offers the cells j < lim(r) = clamp(limit0 + r * limit_step, 0, n) (the convention of
+ * dlc_topk_rows_f64 and dlc_sequence_topk; any limit_step, negative included) that are present: for DLC_F64 / DLC_F32 a
+ * NaN is never offered (+inf and -inf are ordinary values); for DLC_I64 a cell equal to `absent` is not offered when
+ * has_absent != 0 (how the -1 of dlc_sequence_topk's int64 seq_out is passed).  has_absent != 0 with a float dtype is
+ * DLC_ERR_BAD_ARG.
+ * ORDER OF MERIT.  Exactly dlc_topk_rows_f64's and dlc_sequence_topk's: the order of the numbers, -0.0 below +0.0,
+ * descending, or ascending with lower_is_better; ties -> the lower j.
+ * PICKS.  p_1 is the best offered cell; p_i is the best offered cell with |j - p_m| > suppress for every m < i; the
+ * picking stops after k picks or when no cell is left.  suppress >= 0, any value up to INT64_MAX; 1 <= k <= DLC_MAX_K;
+ * n < 2^31; any rows >= 1; ld >= n; rows need only their element's alignment (8 bytes, 4 for DLC_F32).
+ * OUTPUT.  out_scores [rows, k]: fp64 for DLC_F64 / DLC_F32 (the conversion is exact), int64 for DLC_I64; out_idx
+ * [rows, k] int64; best first.  Empty slots hold (-inf, or +inf if lower_is_better, -1) in fp64 and (-1, -1) for DLC_I64.
+ * poison (device, may be NULL; DLC_ERR_BAD_ARG with DLC_I64): the word of dlc_topk_rows_f64 -- non-zero turns every
+ * slot into (NaN, -1).
+ * READS.  No cell at or past lim(r), and no column n .. ld-1, is read or has any influence.
+ * CONSEQUENCES.  With suppress = 0 the lists equal dlc_topk_rows_f64 on the same fp64 rows, bit for bit.  With k = 2,
+ * lower_is_better and suppress = R_window / 2, slots 0 and 1 are OpenSeqSLAM's min_value and min_value_2nd (their
+ * quotient is its uniqueness ratio).  A row's result depends on that row and its limit alone: not on the batching or
+ * the plan.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, an unknown dtype, rows < 1, n < 1, ld < n, suppress < 0, k outside
+ * 1..DLC_MAX_K, has_absent with a float dtype, poison with DLC_I64 or a misaligned pointer; DLC_ERR_BAD_SHAPE for
+ * n >= 2^31; DLC_ERR_WORKSPACE for a workspace that is missing, too small or not 16-byte aligned.  Nothing is written
+ * then.  When every lim(r) is 0 the outputs are the empty fill and the call returns DLC_OK.
+ * Workspace: dlc_peak_topk_rows_workspace_bytes(rows, n, k) bytes (0 = bad arguments): 16 bytes per 256 columns of
+ * every row.  The outputs and the workspace must not overlap the matrix or each other.
+ * At most two launches on `stream` (the best offered cell of every 256-column chunk into the workspace -- the one pass
+ * over the rows -- then one workgroup per row: k rounds of "best chunk", each of which forms again only the chunks the
+ * pick's window cuts); no atomics, no memset; never synchronises.
+ */
+size_t dlc_peak_topk_rows_workspace_bytes(int64_t rows, int64_t n, int k);
+int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */, const void* scores,
+                       int64_t rows, int64_t n, int64_t ld, int64_t limit0, int64_t limit_step,
+                       int lower_is_better, int64_t suppress, int has_absent, int64_t absent, int k,
+                       void* out_scores, int64_t* out_idx, const int64_t* poison,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
