@@ -14,6 +14,7 @@ include/dlc.h, with the reference's Python call surface on top:
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
     sequence_topk / sequence_scores / slope_offsets / contrast_normalize   (sequence-consistent search over a score matrix; new)
+        steps=(d_min, d_max) on them and on the detectors: the elastic search, a chain that steps back d_min..d_max key-frames per frame
     peak_topk / sequence_peaks / uniqueness_ratio   (distinct-place candidates: picks more than `suppress` columns apart; new)
     LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; all three take sequence=L, suppress=W)
 

@@ -19,7 +19,7 @@
 // sum, or the biased int64 sum, complemented when lower is better) and a TAG (~column << 32 | slope; larger = lower
 // column).  Entries of a row are distinct (the column is in them), so the result does not depend on the plan.  (0, 0) is
 // the empty slot: below every entry, since a column < 2^31 leaves the tag's top bit set.
-#include "topk_list.h"
+#include "sequence_merge.h"
 
 namespace {
 
@@ -27,8 +27,6 @@ constexpr int SQ_MAX_L = 64, SQ_MAX_SLOPES = 16;
 constexpr int SQ_SLAB_UNIT = 256;          // columns a slab is counted in
 constexpr int SQ_MAX_RB = 32;              // output rows per workgroup, at most
 constexpr size_t SQ_LDS_SMALL = 64 * 1024, SQ_LDS_LARGE = 150 * 1024;
-constexpr unsigned long long SQ_SIGN = 0x8000000000000000ull;
-constexpr long long SQ_NAN_BITS = 0x7ff8000000000000ll;
 
 struct SqOffsets { short o[SQ_MAX_SLOPES * SQ_MAX_L]; };          // [slope][L], by value (2 KB of the kernel's arguments)
 
@@ -40,13 +38,6 @@ struct SqArgs {
     const long long* poison;
     int L, V, maxoff, lower, k, rb, ct, wc;
 };
-
-template <int DT>
-__device__ __forceinline__ unsigned long long sq_load_bits(const void* M, long long at) {
-    if (DT == DLC_F64) return (unsigned long long)__double_as_longlong(((const double*)M)[at]);
-    if (DT == DLC_F32) return (unsigned long long)__double_as_longlong((double)((const float*)M)[at]);
-    return (unsigned long long)((const long long*)M)[at];
-}
 
 template <int DT, bool STAGED>
 __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, const SqOffsets offs) {
@@ -187,30 +178,6 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
             unsigned long long* P = a.part + (((size_t)(r - a.row0) * G + g) * k) * 2;
             for (int i = lane; i < k; i += 64) { P[2 * i] = lkey[lr * k + i]; P[2 * i + 1] = ltag[lr * k + i]; }
         }
-}
-
-// One workgroup per output row: the k best of its G sorted lists, decoded.
-template <bool IS_INT>
-__global__ __launch_bounds__(256) void sequence_merge_kernel(const unsigned long long* __restrict__ part, int G, int k, int lower,
-                                                             void* __restrict__ out_scores, long long* __restrict__ out_idx,
-                                                             int* __restrict__ out_slope, const long long* __restrict__ poison) {
-    const long long q = blockIdx.x;
-    if (poison && *poison != 0) {
-        for (int t = threadIdx.x; t < k; t += 256) {
-            ((double*)out_scores)[q * k + t] = __longlong_as_double(SQ_NAN_BITS);
-            out_idx[q * k + t] = -1;
-            if (out_slope) out_slope[q * k + t] = -1;
-        }
-        return;
-    }
-    tl_merge_slabs<TlPair>(part + (size_t)q * G * k * 2, G, k, [&](int i, TlPair m) {
-        const bool none = m.is_empty();
-        const unsigned long long k2 = lower ? ~m.key : m.key;
-        if (IS_INT) ((long long*)out_scores)[q * k + i] = none ? -1ll : (long long)(k2 ^ SQ_SIGN);
-        else ((double*)out_scores)[q * k + i] = none ? (lower ? INFINITY : -INFINITY) : dlc_f64_unkey(k2);
-        out_idx[q * k + i] = none ? -1ll : (long long)(~(unsigned)(m.tag >> 32));
-        if (out_slope) out_slope[q * k + i] = none ? -1 : (int)(m.tag & 0xffffffffull);
-    });
 }
 
 // The scan's shape for a table: rows per block, columns per tile, staged or not, LDS bytes.

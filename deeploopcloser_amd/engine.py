@@ -42,6 +42,18 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def check_steps(steps):
+    """(d_min, d_max) of an elastic sequence search's steps, checked: two integers, 0 <= d_min <= d_max <= 8."""
+    try:
+        d_min, d_max = steps
+        ok = int(d_min) == d_min and int(d_max) == d_max and 0 <= d_min <= d_max <= L.DLC_MAX_STEP
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("steps=%r: need (d_min, d_max) with 0 <= d_min <= d_max <= %d" % (steps, L.DLC_MAX_STEP))
+    return int(d_min), int(d_max)
+
+
 class Engine:
     """One engine per device / rank (wraps a dlc_ctx)."""
 
@@ -1022,6 +1034,45 @@ class Engine:
             int(limit_step), int(length), off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(lower_is_better)),
             1 if k is None else int(k), _ptr(o_s), _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws),
             ws.numel() if ws is not None else 0, self._stream()))
+        return o_s, o_i, o_v, seq
+
+    def sequence_elastic_topk(self, scores, length, steps, k=None, row0=0, n=None, limit0=None, limit_step=0,
+                              lower_is_better=False, dense=False, poison=None):
+        """The elastic sequence search of dlc_sequence_elastic_topk (include/dlc.h) over scores [rows, >= n] (fp64, fp32 or
+        int64 on the device; a row-strided view is taken as it is): the best chain of L frame scores that ends in each
+        cell and steps back steps = (d_min, d_max) key-frames per frame, 0 <= d_min <= d_max <= 8, and per row r >= row0
+        the k best cells among its first clamp(limit0 + r * limit_step, 0, n) (limit0 None = n).  Returns (scores
+        [rows - row0, k], idx int64, span int32, dense) as sequence_topk does, the span -- the key-frames the chosen chain
+        covers -- in the slope's place.  poison: as in sequence_topk."""
+        scores, rows, n, ld = self._score_matrix("sequence_elastic_topk", scores, n, "search")
+        d_min, d_max = check_steps(steps)
+        if not 1 <= int(length) <= 64:
+            raise ValueError("sequence_elastic_topk: L=%d outside 1..64" % int(length))
+        if not 0 <= int(row0) < rows:
+            raise ValueError("sequence_elastic_topk: row0=%d outside 0..%d" % (row0, rows - 1))
+        if k is None and not dense:
+            raise ValueError("sequence_elastic_topk: neither lists (k) nor the dense scores were asked for")
+        if k is not None and not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("sequence_elastic_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if poison is not None:
+            self._check_out("poison", poison, (1,), torch.int64)
+        out_dtype = torch.int64 if scores.dtype == torch.int64 else torch.float64
+        ro = rows - int(row0)
+        o_s = o_i = o_v = seq = ws = None
+        if k is not None:
+            o_s = torch.empty((ro, k), dtype=out_dtype, device=self.device)
+            o_i = torch.empty((ro, k), dtype=torch.int64, device=self.device)
+            o_v = torch.empty((ro, k), dtype=torch.int32, device=self.device)
+            need = self.lib.dlc_sequence_elastic_topk_workspace_bytes(rows, n, int(length), d_min, d_max, int(k))
+            if need == 0:
+                raise ValueError("sequence_elastic_topk: L=%d, k=%d, n=%d outside the supported sizes" % (length, k, n))
+            ws = self.workspace("sequence_elastic_topk", need)
+        if dense:
+            seq = torch.empty((ro, n), dtype=out_dtype, device=self.device)
+        self._check(self.lib.dlc_sequence_elastic_topk(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(length), d_min, d_max, int(bool(lower_is_better)), 1 if k is None else int(k), _ptr(o_s),
+            _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
         return o_s, o_i, o_v, seq
 
     def contrast_rows(self, scores, radius, n=None, limit0=None, limit_step=0, out=None):

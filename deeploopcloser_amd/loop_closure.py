@@ -50,12 +50,14 @@ def _nothing_older(b, k, fill, dtype, device):
             torch.full((b, k), -1, dtype=torch.int64, device=device))
 
 
-def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None):
+def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None):
     """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
     if sequence is not None:
-        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress)
+        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps)
     if slopes is not None:
         raise ValueError("slopes needs sequence=L")
+    if steps is not None:
+        raise ValueError("steps needs sequence=L")
     if contrast is not None:
         raise ValueError("contrast needs sequence=L")
     if suppress is not None:
@@ -96,10 +98,15 @@ class LoopClosureDetector:
 
     suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best key-frame, then
     the best one more than W key-frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.
-    Scores, dtypes and empty slots are as without it."""
+    Scores, dtypes and empty slots are as without it.
+
+    steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
+    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
+    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
+    dtypes, empty slots, contrast and suppress are as with the lines."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -109,9 +116,10 @@ class LoopClosureDetector:
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 key rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress,
+                                     steps=steps)
         if self._seq is not None:
-            self.slopes = self._seq.slopes
+            self.slopes, self.steps = self._seq.slopes, self._seq.steps
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     def __len__(self):
@@ -186,20 +194,30 @@ class _SequenceRows:
     normalisation depends on that row alone, so the context rows stay valid and the lists still do not depend on the
     batching.
 
+    steps = (d_min, d_max) (0 <= d_min <= d_max <= 8; excludes `slopes`) makes the search elastic: the best chain of L
+    cells that steps back d_min .. d_max key-frames per frame instead of the best straight line
+    (dlc_sequence_elastic_topk, include/dlc.h) -- the same window, limits, first output row, dense scores and poison
+    word, and a cell still depends on the L rows behind it alone.
+
     suppress = W (>= 0) makes the k candidates distinct places: the sequence search writes the batch's dense cell scores
     and dlc_peak_topk_rows (include/dlc.h) picks from them -- the best cell, then the best one more than W key-frames
     from every earlier pick -- under the same limits, order of merit and poison word.  A dense score depends on the rows
     behind it alone, so these lists do not depend on the batching either."""
 
-    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None):
+    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None, steps=None):
+        from .engine import check_steps
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
             raise ValueError("sequence=%d outside 1..64" % length)
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        self.slopes = slope_offsets(length) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
-        if self.slopes.ndim != 2 or self.slopes.shape[1] != length or not 1 <= self.slopes.shape[0] <= 16:
-            raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
+        if steps is not None and slopes is not None:
+            raise ValueError("steps and slopes exclude each other")
+        self.steps, self.slopes = None if steps is None else check_steps(steps), None
+        if self.steps is None:
+            self.slopes = slope_offsets(length) if slopes is None else np.ascontiguousarray(slopes, dtype=np.int32)
+            if self.slopes.ndim != 2 or self.slopes.shape[1] != length or not 1 <= self.slopes.shape[0] <= 16:
+                raise ValueError("slopes must be an int32 table [1..16, %d]" % length)
         if contrast is not None and not 1 <= contrast <= 32:
             raise ValueError("contrast=%d outside 1..32" % contrast)
         if suppress is not None and not 0 <= suppress < 1 << 63:
@@ -255,11 +273,11 @@ class _SequenceRows:
         is the frame L - 1 - m before the batch's first; rows of frames before the stream began offer nothing and are never
         read).  Then the last L - 1 rows become the next batch's context."""
         self.normalise(engine, n, limit0)
-        s, i, _, dense = engine.sequence_topk(self.window(b), self.length, self.slopes,
-                                              k=self.k if self.suppress is None else None, row0=self.context, n=n,
-                                              limit0=limit0 - self.context, limit_step=1,
-                                              lower_is_better=self.lower_is_better, dense=self.suppress is not None,
-                                              poison=poison)
+        search = engine.sequence_topk if self.steps is None else engine.sequence_elastic_topk
+        s, i, _, dense = search(self.window(b), self.length, self.slopes if self.steps is None else self.steps,
+                                k=self.k if self.suppress is None else None, row0=self.context, n=n,
+                                limit0=limit0 - self.context, limit_step=1, lower_is_better=self.lower_is_better,
+                                dense=self.suppress is not None, poison=poison)
         if self.suppress is not None:                              # k places: picks more than `suppress` key-frames apart
             s, i = engine.peak_topk_rows(dense, self.k, self.suppress, limit0=limit0, limit_step=1,
                                          lower_is_better=self.lower_is_better,
@@ -290,10 +308,15 @@ class SdavLoopClosureDetector:
 
     suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best frame, then the
     best one more than W frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.  Scores,
-    dtypes, empty slots and the poisoned answer are as without it."""
+    dtypes, empty slots and the poisoned answer are as without it.
+
+    steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
+    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
+    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
+    dtypes, empty slots, contrast and suppress are as with the lines."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, **stream_args):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
@@ -304,9 +327,10 @@ class SdavLoopClosureDetector:
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 score rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress,
+                                     steps=steps)
         if self._seq is not None:
-            self.slopes = self._seq.slopes
+            self.slopes, self.steps = self._seq.slopes, self._seq.steps
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
@@ -476,10 +500,15 @@ class CnnVtlLoopClosureDetector:
     suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the nearest key-frame,
     then the nearest one more than W key-frames from it, and so on (_SequenceRows) -- instead of one minimum and its
     neighbours; with k = 2 and W = R_window / 2 the two distances are OpenSeqSLAM's min_value and min_value_2nd
-    (sequence.uniqueness_ratio).  Distances, dtypes and empty slots are as without it."""
+    (sequence.uniqueness_ratio).  Distances, dtypes and empty slots are as without it.
+
+    steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
+    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
+    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
+    dtypes, empty slots, contrast and suppress are as with the lines."""
 
     def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None):
+                 contrast=None, suppress=None, steps=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -495,9 +524,9 @@ class CnnVtlLoopClosureDetector:
         # the last L - 1 distance rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=self.suppress)
+                                     suppress=self.suppress, steps=steps)
         if self._seq is not None:
-            self.slopes = self._seq.slopes
+            self.slopes, self.steps = self._seq.slopes, self._seq.steps
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -594,6 +623,9 @@ def main(argv=None):
     ap.add_argument("--suppress", type=int, default=None, metavar="W",
                     help="with --sequence: report distinct places -- every candidate more than W frames from the better "
                          "ones of its frame (the windowed peak selection)")
+    ap.add_argument("--steps", default=None, metavar="DMIN:DMAX",
+                    help="with --sequence: the elastic search -- from frame to frame the matched key-frame steps back "
+                         "DMIN..DMAX key-frames (0 <= DMIN <= DMAX <= 8) instead of following a straight line")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
@@ -621,6 +653,16 @@ def main(argv=None):
         ap.error("--suppress needs --sequence")
     if args.suppress is not None and args.suppress < 0:
         ap.error("--suppress must be >= 0")
+    if args.steps is not None:
+        if args.sequence is None:
+            ap.error("--steps needs --sequence")
+        try:
+            d_min, d_max = (int(x) for x in args.steps.split(":"))
+        except ValueError:
+            ap.error("--steps must be DMIN:DMAX")
+        if not 0 <= d_min <= d_max <= L.DLC_MAX_STEP:
+            ap.error("--steps must be DMIN:DMAX with 0 <= DMIN <= DMAX <= %d" % L.DLC_MAX_STEP)
+        args.steps = (d_min, d_max)
     if args.threshold is None:
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
@@ -660,7 +702,7 @@ def _stream(args, files):
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
                                           exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
-                                          contrast=args.contrast, suppress=args.suppress)
+                                          contrast=args.contrast, suppress=args.suppress, steps=args.steps)
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))

@@ -8,6 +8,13 @@ The matrices are the reference's as they come: SimilarityCalculator.similarity_m
 and DistanceCalculator.distance_matrix (int64, lower_is_better=True).  NumPy in -> NumPy out, device tensors in -> device
 tensors out.
 
+Elastic search.  A straight line is a revisit at one speed.  steps = (d_min, d_max) on sequence_topk, sequence_scores and
+sequence_peaks replaces the lines by chains: from frame to frame the chain steps back any d_min .. d_max key-frames (a
+stop, a slow corner, unevenly spaced key-frames), the best chain found by dynamic programming, one addition per cell and
+level, oldest row first (dlc_sequence_elastic_topk, include/dlc.h: the recursion is the definition; the lowest step wins
+ties).  In place of the winning slope the lists carry the chain's span, the key-frames it covers.  contrast runs in front
+of it and suppress behind it as with the lines; steps=None is every path as it was.
+
 Distinct places.  The k best cells of a row are mostly ONE place: a revisit of key-frame j scores almost as well against
 j - 1, j + 1, ...  peak_topk / sequence_peaks pick the best cell, then the best one more than `suppress` key-frames from
 it, and so on (dlc_peak_topk_rows, include/dlc.h) -- SeqSLAM's "best trajectory, then the best one outside a window
@@ -21,7 +28,7 @@ import numpy as np
 import torch
 
 from ._lib import DLC_MAX_K
-from .engine import default_engine
+from .engine import check_steps, default_engine
 
 
 def slope_offsets(L, v_min=0.8, v_max=1.2, v_step=0.1):
@@ -73,36 +80,48 @@ def contrast_normalize(matrix, radius, limit0=None, limit_step=0):
     return out.cpu().numpy() if as_numpy else out
 
 
-def _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast, poison=None):
-    """Engine.sequence_topk of a device matrix behind the optional contrast normalisation: device tensors."""
+def _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast, poison=None, steps=None):
+    """Engine.sequence_topk -- with steps, Engine.sequence_elastic_topk -- of a device matrix behind the optional contrast
+    normalisation: device tensors."""
+    if steps is not None:
+        if offsets is not None:
+            raise ValueError("sequence search: steps and offsets exclude each other")
+        steps = check_steps(steps)
     if contrast is not None:
         matrix = contrast_normalize(matrix, contrast, limit0, limit_step)
+    if steps is not None:
+        return e.sequence_elastic_topk(matrix, L, steps, k=k, limit0=limit0, limit_step=limit_step,
+                                       lower_is_better=lower_is_better, dense=dense, poison=poison)
     offsets = slope_offsets(L) if offsets is None else offsets
     return e.sequence_topk(matrix, L, offsets, k=k, limit0=limit0, limit_step=limit_step, lower_is_better=lower_is_better,
                            dense=dense, poison=poison)
 
 
-def _run(matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast=None):
+def _run(matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast=None, steps=None):
     e = default_engine()
     matrix, as_numpy = _on_device(e, matrix)
-    out = _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast)
+    out = _search(e, matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, contrast, steps=steps)
     return tuple(None if t is None else (t.cpu().numpy() if as_numpy else t) for t in out)
 
 
-def sequence_topk(matrix, k, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None):
+def sequence_topk(matrix, k, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None, steps=None):
     """(scores [rows, k], idx [rows, k] int64, slope [rows, k] int32): per row r of matrix [rows, n] the k best cells by the
     sequence score over L rows, among the row's first clamp(limit0 + r * limit_step, 0, n) columns (limit0 None: all),
     best first, ties -> the lower column.  offsets: an int32 table [V, L] (default slope_offsets(L)); slope: the row of it
     that won.  Empty slots: (-inf or +inf, -1, -1) in fp64, (-1, -1, -1) for int64 matrices; the first L - 1 rows are empty.
     contrast = R: the search runs on contrast_normalize(matrix, R, limit0, limit_step); scores are then fp64 for int64
-    matrices too."""
-    return _run(matrix, L, offsets, int(k), False, limit0, limit_step, lower_is_better, contrast)[:3]
+    matrices too.
+    steps = (d_min, d_max) (None: the lines above; with offsets: ValueError): the ELASTIC search -- the best chain of L
+    cells that ends in (r, j) and steps back d_min .. d_max columns per row (dlc_sequence_elastic_topk); the third
+    result is then span [rows, k] int32, the columns the chosen chain covers."""
+    return _run(matrix, L, offsets, int(k), False, limit0, limit_step, lower_is_better, contrast, steps)[:3]
 
 
-def sequence_scores(matrix, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None):
+def sequence_scores(matrix, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None, steps=None):
     """The dense [rows, n] sequence scores themselves (fp64, or int64 for int64 matrices): NaN / -1 where a cell has no
-    valid line.  contrast = R: of contrast_normalize(matrix, R, limit0, limit_step), fp64."""
-    return _run(matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast)[3]
+    valid line.  contrast = R: of contrast_normalize(matrix, R, limit0, limit_step), fp64.  steps = (d_min, d_max): the
+    elastic search's (no valid chain), as in sequence_topk."""
+    return _run(matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast, steps)[3]
 
 
 def _peaks(e, matrix, k, suppress, limit0, limit_step, lower_is_better, absent):
@@ -132,9 +151,10 @@ def peak_topk(matrix, k, suppress, limit0=None, limit_step=0, lower_is_better=Fa
     return tuple(t.cpu().numpy() if as_numpy else t for t in out)
 
 
-def sequence_peaks(matrix, k, L, suppress, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None):
+def sequence_peaks(matrix, k, L, suppress, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None,
+                   steps=None):
     """(scores [rows, k], idx [rows, k] int64): the distinct-place candidates by the sequence score -- sequence_scores
-    (same L, offsets, limits and contrast), then peak_topk over those dense scores with the same limits: the best
+    (same L, offsets or steps, limits and contrast), then peak_topk over those dense scores with the same limits: the best
     trajectory, then the best one whose end lies more than `suppress` key-frames from it, ...  With k = 2,
     lower_is_better and suppress = R_window / 2 the two slots are OpenSeqSLAM's min_value and min_value_2nd
     (uniqueness_ratio).  int64 matrices: the dense scores mark "no valid line" with -1, which is passed on as the absent
@@ -142,7 +162,7 @@ def sequence_peaks(matrix, k, L, suppress, offsets=None, limit0=None, limit_step
     dlc_sequence_topk's int64 seq_out."""
     e = default_engine()
     matrix, as_numpy = _on_device(e, matrix)
-    dense = _search(e, matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast)[3]
+    dense = _search(e, matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast, steps=steps)[3]
     out = _peaks(e, dense, k, suppress, limit0, limit_step, lower_is_better, -1 if dense.dtype == torch.int64 else None)
     return tuple(t.cpu().numpy() if as_numpy else t for t in out)
 

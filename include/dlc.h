@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 17
+#define DLC_ABI_VERSION 18
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -598,6 +598,61 @@ int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows,
                       int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_slope,
                       void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/*
+ * The ELASTIC sequence search: dlc_sequence_topk's question with a chain in place of a straight line.  A revisit whose
+ * speed changes inside the L frames -- a stop at a junction, a slow corner before a fast straight, key-frames inserted
+ * at an uneven rate -- lies on none of the lines of an offset table; here every frame of the chain may step back by any
+ * d_min <= d <= d_max key-frames from the frame after it (dynamic time warping with bounded steps, by dynamic
+ * programming).  Arguments as dlc_sequence_topk (dtype, M = scores [rows, ld] with n columns in use, row0, lim(r) =
+ * clamp(limit0 + r * limit_step, 0, n), lower_is_better, k, the outputs, poison, workspace, stream); d_min, d_max take the
+ * place of the offset table and out_span that of out_slope.
+ * DEFINITION -- the recursion itself.  For an output row r with r - (L-1) >= 0 let rho(t) = r - (L-1) + t, t = 0 .. L-1
+ * (the chain's rows, oldest first):
+ *     A_0(c) = M[rho(0)][c]                         valid iff 0 <= c < lim(rho(0)) and the element is not NaN
+ *     A_t(c) = P_t(c) + M[rho(t)][c],  t = 1 .. L-1   one addition: fp64 for DLC_F64 / DLC_F32 (the conversion is exact),
+ *                                                   wrapping int64 for DLC_I64
+ *     P_t(c) = the best VALID A_{t-1}(c - d) over d = d_min .. d_max, the LOWEST d among equals
+ *              A_t(c) is valid iff P_t(c) exists, 0 <= c < lim(rho(t)) and the sum is not NaN
+ *     E(r, j)    = A_{L-1}(j)                       (so j < lim(r) is implied)
+ *     span(r, j) = j - (the column the chosen chain started in at t = 0),   0 <= span <= (L-1) * d_max.
+ * "Best" is dlc_sequence_topk's: the maximum, or the minimum when lower_is_better is set, in the order of the numbers with
+ * -0.0 below +0.0.  A cell that is not valid is not offered; a row with r - (L-1) < 0 offers nothing.
+ * OUTPUT for rows row0 <= r < rows (rows below row0 are context only): the k best offered cells of the row by E, best
+ * first, ties -> the lower j.  out_scores [rows - row0, k] fp64 (int64 for DLC_I64), out_idx int64, out_span int32 (may be
+ * NULL); the slots past the offered count hold index -1, span -1 and the score -inf (+inf if lower_is_better) / -1 for
+ * DLC_I64.  seq_out [rows - row0, ld_out] (may be NULL; same type as out_scores; ld_out >= n) receives E in its first n
+ * columns, NaN / -1 where a cell is not offered; columns n .. ld_out - 1 keep their bits.  At least one of (out_scores +
+ * out_idx) and seq_out must be given; without the lists k, workspace and out_span are not used.  poison: as
+ * dlc_sequence_topk (non-zero: every fp64 slot (NaN, -1, span -1), seq_out NaN; DLC_ERR_BAD_ARG with DLC_I64).
+ * Nothing at or past a row's limit, and no column n .. ld - 1, is read.
+ * CONSEQUENCES.  IEEE addition is monotone (x <= y implies x + m <= y + m when neither sum is NaN), so whenever no
+ * partial sum is NaN -- always for finite data; for DLC_I64 while nothing wraps -- E(r, j) is the best PATH SUM over all
+ * paths j = j_0 >= j_1 >= ... >= j_{L-1} with j_s - j_{s+1} in [d_min, d_max] and column j_s < lim(r - s) of row r - s,
+ * added OLDEST row first: ((M[r-L+1][j_{L-1}] + M[r-L+2][j_{L-2}]) + ...) + M[r][j_0].  With opposite infinities inside a
+ * window the recursion decides (a chain whose partial sum is NaN ends there; another may go on).  Every sum is formed in
+ * one fixed order, integer rows stay exact, and a cell is a function of the L rows behind it alone: the result does not
+ * depend on how rows are batched or on the launch plan.
+ *   - With L = 1 the lists equal dlc_topk_rows_f64's on the same rows bit for bit (every span is 0).
+ *   - With d_min = d_max = d on DLC_I64, scores and indices equal dlc_sequence_topk's with the one slope off[s] = s * d,
+ *     and every span is (L-1) * d: integer sums do not depend on the order.
+ *   - For fp64 the same holds whenever the sums are exact: this search adds the OLDEST row first, dlc_sequence_topk the
+ *     newest first, and inexact sums may differ in the last place.
+ * Limits: 1 <= L <= 64, 0 <= d_min <= d_max <= DLC_MAX_STEP, 1 <= k <= DLC_MAX_K, any rows, 0 <= row0 < rows, n < 2^31.
+ * Errors: DLC_ERR_BAD_ARG (a limit above, a missing pointer, ld < n, ld_out < n), DLC_ERR_BAD_SHAPE (more rows than one
+ * launch takes), DLC_ERR_WORKSPACE (NULL, not 16-byte aligned, or too small); nothing is written then.
+ * Two launches on `stream` (a scan, one wave per output row and column slab that carries the L levels over a column tile
+ * and its halo of (L-1) * d_max columns, then dlc_sequence_topk's merge); never synchronises.  Workspace:
+ * dlc_sequence_elastic_topk_workspace_bytes(rows, n, L, d_min, d_max, k) bytes (0 = bad arguments).  The outputs and the
+ * workspace must not overlap the matrix or each other.
+ */
+#define DLC_MAX_STEP 8
+size_t dlc_sequence_elastic_topk_workspace_bytes(int64_t rows, int64_t n, int L, int d_min, int d_max, int k);
+int dlc_sequence_elastic_topk(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
+                              int64_t limit0, int64_t limit_step, int L, int d_min, int d_max,
+                              int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_span,
+                              void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /*
  * SeqSLAM's local contrast normalisation of score rows (Milford & Wyeth, ICRA 2012, III-B): every cell against its
