@@ -15,6 +15,7 @@ include/dlc.h, with the reference's Python call surface on top:
     encode / match / match_topk   (BASELINE.json north_star; new)
     sequence_topk / sequence_scores / slope_offsets / contrast_normalize   (sequence-consistent search over a score matrix; new)
         steps=(d_min, d_max) on them and on the detectors: the elastic search, a chain that steps back d_min..d_max key-frames per frame
+    sequence_chains (and chains=True on sequence_topk / sequence_peaks / the detectors): the L matched key-frames behind a candidate; new
     peak_topk / sequence_peaks / uniqueness_ratio   (distinct-place candidates: picks more than `suppress` columns apart; new)
     LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; all three take sequence=L, suppress=W)
 
@@ -34,10 +35,10 @@ from .dist import ShardedKeyframeDatabase, shard_bounds, merge_topk_torch
 from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, read_ppm
 from . import tensor_wrapper
 from . import sequence
-from .sequence import slope_offsets, sequence_topk, sequence_scores, contrast_normalize, peak_topk, sequence_peaks, uniqueness_ratio
+from .sequence import slope_offsets, sequence_topk, sequence_scores, sequence_chains, contrast_normalize, peak_topk, sequence_peaks, uniqueness_ratio
 from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector
 
-__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

@@ -23,12 +23,9 @@
 
 namespace {
 
-constexpr int SQ_MAX_L = 64, SQ_MAX_SLOPES = 16;
 constexpr int SQ_SLAB_UNIT = 256;          // columns a slab is counted in
 constexpr int SQ_MAX_RB = 32;              // output rows per workgroup, at most
 constexpr size_t SQ_LDS_SMALL = 64 * 1024, SQ_LDS_LARGE = 150 * 1024;
-
-struct SqOffsets { short o[SQ_MAX_SLOPES * SQ_MAX_L]; };          // [slope][L], by value (2 KB of the kernel's arguments)
 
 struct SqArgs {
     const void* M;
@@ -237,18 +234,9 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
     if (poison && dtype == DLC_I64)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: the poison word marks fp64 outputs; DLC_I64 has none");
     SqOffsets offs;
-    memset(&offs, 0, sizeof(offs));
     int maxoff = 0;
-    for (int v = 0; v < n_slopes; ++v)
-        for (int s = 0; s < L; ++s) {
-            const int32_t o = offsets[(size_t)v * L + s];
-            if (o < 0 || o > 32767 || (s == 0 && o != 0) || (s > 0 && o < offsets[(size_t)v * L + s - 1]))
-                return dlc::fail(ctx, DLC_ERR_BAD_ARG,
-                                 "sequence_topk: offsets[%d][%d]=%d (rows start at 0, never decrease, stay within 0..32767)", v, s,
-                                 (int)o);
-            offs.o[v * L + s] = (short)o;
-            if (o > maxoff) maxoff = o;
-        }
+    const int bad = sq_pack_offsets(ctx, "sequence_topk", offsets, n_slopes, L, &offs, &maxoff);
+    if (bad != DLC_OK) return bad;
     const int64_t rows_out = rows - row0;
     size_t need = 0;
     if (lists) {

@@ -25,7 +25,6 @@
 
 namespace {
 
-constexpr int EL_MAX_L = 64;
 constexpr int EL_ROWS = 4;                 // output rows per workgroup: one per wave
 constexpr int EL_CT = 512, EL_CT_WIDE = 1024, EL_WIDE_HALO = 256;   // columns per tile; the wide tile past this halo
 constexpr int EL_CT_MIN = 128, EL_WANT_WG = 256;   // a small call: narrower tiles, down to this, until this many workgroups
@@ -98,6 +97,8 @@ __global__ __launch_bounds__(256) void sequence_elastic_scan_kernel(const ElArgs
                     }
                     ok = ok && in;
                 }
+                // (el_level_key of sequence_merge.h, spelled out: through the function the same arithmetic is scheduled
+                // differently and this kernel measured 8-17 % slower, docs/LAB.md 19)
                 if (IS_INT) {
                     const unsigned long long sum = t > 0 ? ((key ^ flip) ^ SQ_SIGN) + bits : bits;
                     key = (sum ^ SQ_SIGN) ^ flip;

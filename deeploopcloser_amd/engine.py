@@ -1075,6 +1075,69 @@ class Engine:
             _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
         return o_s, o_i, o_v, seq
 
+    def _chain_args(self, who, scores, length, idx, row0, n, poison):
+        """The checks the two chain calls share -> (scores, rows, n, ld, idx [rows - row0, k] int64 contiguous, k)."""
+        scores, rows, n, ld = self._score_matrix(who, scores, n, "search")
+        if not 1 <= int(length) <= 64:
+            raise ValueError("%s: L=%d outside 1..64" % (who, int(length)))
+        if not 0 <= int(row0) < rows:
+            raise ValueError("%s: row0=%d outside 0..%d" % (who, row0, rows - 1))
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64 or idx.device != self.device:
+            raise ValueError("%s: idx must be an int64 tensor [rows - row0, k] on %s" % (who, self.device))
+        if idx.shape[0] != rows - int(row0) or not 1 <= idx.shape[1] <= L.DLC_MAX_K:
+            raise ValueError("%s: idx [%d, %d]: need [%d, 1..%d]" % (who, idx.shape[0], idx.shape[1], rows - int(row0), L.DLC_MAX_K))
+        if poison is not None:
+            if scores.dtype == torch.int64:
+                raise ValueError("%s: the poison word marks fp64 outputs; int64 rows have none" % who)
+            self._check_out("poison", poison, (1,), torch.int64)
+        return scores, rows, n, ld, idx.contiguous(), idx.shape[1]
+
+    def sequence_elastic_chains(self, scores, length, steps, idx, row0=0, n=None, limit0=None, limit_step=0,
+                                lower_is_better=False, cells=False, poison=None):
+        """The chains of dlc_sequence_elastic_chains (include/dlc.h): for every candidate end column idx[r - row0, i] (the
+        idx of sequence_elastic_topk or of peak_topk_rows over its dense scores; -1: an empty slot) of the elastic
+        search over scores with the same length, steps, row0, n, limits and order, the L matched columns, oldest frame
+        first.  Returns (chain int32 [rows - row0, k, L], cells or None): cells=True adds the matrix cells along the chain
+        (fp64, int64 for int64 scores), which summed oldest first give the candidate's score bit for bit.  A slot that
+        is no chain (empty, past the row's limit, no valid chain, poisoned) holds -1 and NaN / -1."""
+        scores, rows, n, ld, idx, k = self._chain_args("sequence_elastic_chains", scores, length, idx, row0, n, poison)
+        d_min, d_max = check_steps(steps)
+        ro = rows - int(row0)
+        chain = torch.empty((ro, k, int(length)), dtype=torch.int32, device=self.device)
+        o_c = None
+        if cells:
+            o_c = torch.empty((ro, k, int(length)), dtype=torch.int64 if scores.dtype == torch.int64 else torch.float64,
+                              device=self.device)
+        self._check(self.lib.dlc_sequence_elastic_chains(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(length), d_min, d_max, int(bool(lower_is_better)), k, _ptr(idx), _ptr(chain), _ptr(o_c),
+            _ptr(poison), self._stream()))
+        return chain, o_c
+
+    def sequence_chains(self, scores, length, offsets, idx, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,
+                        cells=False, poison=None):
+        """The chains of dlc_sequence_chains (include/dlc.h): for every candidate end column idx[r - row0, i] of the line
+        search over scores with the same length, HOST table offsets [V, L], row0, n, limits and order, the L columns of
+        its winning line, oldest frame first.  Returns (chain int32 [rows - row0, k, L], cells or None, slope int32
+        [rows - row0, k]): the cells summed NEWEST first give the candidate's score bit for bit; slope is the row of the
+        table that won.  A slot that is no chain holds -1 (cells NaN / -1, slope -1)."""
+        scores, rows, n, ld, idx, k = self._chain_args("sequence_chains", scores, length, idx, row0, n, poison)
+        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
+        if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
+            raise ValueError("sequence_chains: offsets must be an integer table [n_slopes, L=%d]" % int(length))
+        ro = rows - int(row0)
+        chain = torch.empty((ro, k, int(length)), dtype=torch.int32, device=self.device)
+        slope = torch.empty((ro, k), dtype=torch.int32, device=self.device)
+        o_c = None
+        if cells:
+            o_c = torch.empty((ro, k, int(length)), dtype=torch.int64 if scores.dtype == torch.int64 else torch.float64,
+                              device=self.device)
+        self._check(self.lib.dlc_sequence_chains(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(length), off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(lower_is_better)), k,
+            _ptr(idx), _ptr(chain), _ptr(o_c), _ptr(slope), _ptr(poison), self._stream()))
+        return chain, o_c, slope
+
     def contrast_rows(self, scores, radius, n=None, limit0=None, limit_step=0, out=None):
         """SeqSLAM's local contrast normalisation of score rows (dlc_contrast_rows, include/dlc.h): fp64 [rows, n], cell
         (r, j) = (x - mean) / sample std over the cells j - radius .. j + radius of row r, clipped to the row's first

@@ -9,6 +9,10 @@ top-k path and reports the candidates whose cosine score reaches `threshold`.
 
     python -m deeploopcloser_amd.loop_closure DATASET_DIR --network cnn_vtl --k 5 --threshold 0.9
 
+With --sequence L --chains every candidate line is followed by one line `chain<TAB>frame:key-frame<TAB>...`: the L pairs
+the candidate was matched along, oldest frame first (the detectors' chains=True; dlc_sequence_chains /
+dlc_sequence_elastic_chains, include/dlc.h).
+
 Batching never changes a result: a batch of B frames is matched in one call against the longest
 prefix any of its frames may see, each frame keeping to the key-frames old enough for IT inside the
 selection (dlc_cosine_topk_older).  The same lists come from a match with k+B-1 candidates per frame
@@ -50,10 +54,12 @@ def _nothing_older(b, k, fill, dtype, device):
             torch.full((b, k), -1, dtype=torch.int64, device=device))
 
 
-def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None):
+def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None, chains=False):
     """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
     if sequence is not None:
-        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps)
+        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps, chains)
+    if chains:
+        raise ValueError("chains needs sequence=L")
     if slopes is not None:
         raise ValueError("slopes needs sequence=L")
     if steps is not None:
@@ -65,15 +71,27 @@ def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False
     return None
 
 
-def _loops(values, ids, first_id, limit, lower_is_better=False):
+def _loops(values, ids, first_id, limit, lower_is_better=False, chains=None):
     """[(frame id, matched frame id, value)] of the candidates whose value is at or above `limit` (at or below it with
     lower_is_better; None: every candidate), row by row, best first.  The value is a Python int where the values are
-    integers, else a float."""
+    integers, else a float.  chains [B, k, L] (a detector's third result with chains=True): every entry gains a fourth
+    element, the candidate's L (frame id, key-frame id) pairs, oldest frame first -- the last pair is the entry's own."""
     v, i = values.cpu().numpy(), ids.cpu().numpy()
     ok = i >= 0
     if limit is not None:
         ok &= (v <= limit) if lower_is_better else (v >= limit)
-    return [(first_id + int(r), int(i[r, c]), v[r, c].item()) for r, c in zip(*np.nonzero(ok))]
+    found = [(first_id + int(r), int(i[r, c]), v[r, c].item()) for r, c in zip(*np.nonzero(ok))]
+    if chains is None:
+        return found
+    ch = chains.cpu().numpy()
+    length = ch.shape[2]
+    return [f + ([(f[0] - (length - 1) + t, int(ch[r, c, t])) for t in range(length)],)
+            for f, (r, c) in zip(found, zip(*np.nonzero(ok)))]
+
+
+def _no_chains(b, k, length, device):
+    """chain [b, k, L] of b frames none of which has a candidate: -1 everywhere."""
+    return torch.full((b, k, length), -1, dtype=torch.int32, device=device)
 
 
 class LoopClosureDetector:
@@ -103,10 +121,14 @@ class LoopClosureDetector:
     steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
     the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
     straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
-    dtypes, empty slots, contrast and suppress are as with the lines."""
+    dtypes, empty slots, contrast and suppress are as with the lines.
+
+    chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert returns a third
+    tensor, chain int32 [B, k, L] -- for every candidate the key-frame id each of the last L frames was matched to, oldest
+    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -116,8 +138,9 @@ class LoopClosureDetector:
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 key rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress,
-                                     steps=steps)
+                                     steps=steps, chains=self.chains)
         if self._seq is not None:
             self.slopes, self.steps = self._seq.slopes, self._seq.steps
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
@@ -134,21 +157,19 @@ class LoopClosureDetector:
         """The next B frames' descriptors [B, dim] (ids len(self) .. len(self)+B-1) ->
         (scores [B,k] float32, ids [B,k] int64) on the device, best first, (-inf, -1) where fewer
         than k key-frames are old enough; the frames are then key-frames themselves.  With sequence=L the
-        scores are float64: the sum of the L scores along the best line."""
+        scores are float64: the sum of the L scores along the best line.  With chains=True a third tensor, chain
+        [B, k, L] int32."""
         x = self.db._as_float(descriptors)
         if x.dim() != 2:
             raise ValueError("descriptors must be [B, dim]")
-        out_s, out_i = [], []
-        for lo in range(0, x.shape[0], self.max_batch):
-            s, i = self._step(x[lo:lo + self.max_batch])
-            out_s.append(s)
-            out_i.append(i)
-        if not out_s:
-            return _nothing_older(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
-                                  self.db.engine.device)
-        if len(out_s) == 1:                                  # (torch.cat of one tensor is a copy: two launches per batch)
-            return out_s[0], out_i[0]
-        return torch.cat(out_s), torch.cat(out_i)
+        outs = [self._step(x[lo:lo + self.max_batch]) for lo in range(0, x.shape[0], self.max_batch)]
+        if not outs:
+            out = _nothing_older(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
+                                 self.db.engine.device)
+            return out + (_no_chains(0, self.k, self.sequence, self.db.engine.device),) if self.chains else out
+        if len(outs) == 1:                                   # (torch.cat of one tensor is a copy: two launches per batch)
+            return outs[0]
+        return tuple(torch.cat(t) for t in zip(*outs))
 
     def _step(self, x):
         db, k = self.db, self.k
@@ -160,11 +181,11 @@ class LoopClosureDetector:
             # the frames' key rows against the frames below g0 + r - exclusion, searched behind the L - 1 rows before them
             db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1,
                           out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :g0 + b])
-            s, i = self._seq.search(db.engine, b, g0 + b, g0 - self.exclusion)
+            s, i, *chain = self._seq.search(db.engine, b, g0 + b, g0 - self.exclusion)
             if self.contrast is not None:                    # fp64 sums of normalised values as they are
-                return s, i
+                return (s, i, *chain)
             # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
-            return torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i
+            return (torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i, *chain)
         n_search = g0 + b - 1 - self.exclusion             # what the newest frame of the batch may see
         if n_search <= 0:
             return _nothing_older(b, k, float("-inf"), torch.float32, db.engine.device)
@@ -172,10 +193,11 @@ class LoopClosureDetector:
         # (dlc_cosine_topk_older -- the lists of a k + b - 1 match followed by dlc_topk_keep_older / first_k_eligible)
         return db.engine.match_topk(q, db.rows[:n_search], k, older_than=g0 - self.exclusion)
 
-    def loops(self, scores, ids, first_id):
+    def loops(self, scores, ids, first_id, chains=None):
         """[(frame id, matched key-frame id, score)] of the candidates at or above the threshold (with sequence=L: the sum
-        of the L scores along the candidate's line)."""
-        return _loops(scores, ids, first_id, self.threshold)
+        of the L scores along the candidate's line).  chains: the third result of query_and_insert with chains=True --
+        every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
+        return _loops(scores, ids, first_id, self.threshold, chains=chains)
 
 
 class _SequenceRows:
@@ -202,9 +224,14 @@ class _SequenceRows:
     suppress = W (>= 0) makes the k candidates distinct places: the sequence search writes the batch's dense cell scores
     and dlc_peak_topk_rows (include/dlc.h) picks from them -- the best cell, then the best one more than W key-frames
     from every earlier pick -- under the same limits, order of merit and poison word.  A dense score depends on the rows
-    behind it alone, so these lists do not depend on the batching either."""
+    behind it alone, so these lists do not depend on the batching either.
 
-    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None, steps=None):
+    chains = True adds the candidates' chains: after the picks, over the same window, limits and order, the column each
+    of the L frames of a candidate was matched to, oldest frame first (dlc_sequence_chains, with steps
+    dlc_sequence_elastic_chains, include/dlc.h: one more launch, formed again for the k cells of every row alone, so the
+    picks of `suppress` are served too).  A chain depends on the L rows behind its cell alone."""
+
+    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None, steps=None, chains=False):
         from .engine import check_steps
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
@@ -223,6 +250,7 @@ class _SequenceRows:
         if suppress is not None and not 0 <= suppress < 1 << 63:
             raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
         self.length, self.k, self.lower_is_better, self.suppress = length, k, lower_is_better, suppress
+        self.chains = bool(chains)
         self.contrast, self.raw_dtype, self._raw = contrast, dtype, None
         self._raw_item = torch.empty((), dtype=dtype).element_size()
         self.context, self.dtype, self.buf = length - 1, dtype if contrast is None else torch.float64, None
@@ -271,7 +299,8 @@ class _SequenceRows:
         """(values [b, k], ids [b, k]) of the batch's b frames, whose raw rows are written: over the first n columns, the
         batch's row r offering limit0 + r of them and every context row one fewer than the row behind it (matrix row m
         is the frame L - 1 - m before the batch's first; rows of frames before the stream began offer nothing and are never
-        read).  Then the last L - 1 rows become the next batch's context."""
+        read).  With chains a third tensor, chain [b, k, L] int32.  Then the last L - 1 rows become the next batch's
+        context."""
         self.normalise(engine, n, limit0)
         search = engine.sequence_topk if self.steps is None else engine.sequence_elastic_topk
         s, i, _, dense = search(self.window(b), self.length, self.slopes if self.steps is None else self.steps,
@@ -282,8 +311,14 @@ class _SequenceRows:
             s, i = engine.peak_topk_rows(dense, self.k, self.suppress, limit0=limit0, limit_step=1,
                                          lower_is_better=self.lower_is_better,
                                          absent=-1 if dense.dtype == torch.int64 else None, poison=poison)
+        chain = ()
+        if self.chains:                                            # the alignment behind every pick, over the same window
+            form = engine.sequence_chains if self.steps is None else engine.sequence_elastic_chains
+            chain = form(self.window(b), self.length, self.slopes if self.steps is None else self.steps, i, row0=self.context,
+                         n=n, limit0=limit0 - self.context, limit_step=1, lower_is_better=self.lower_is_better,
+                         poison=poison)[:1]
         self.advance(b)
-        return s, i
+        return (s, i, *chain)
 
 
 class SdavLoopClosureDetector:
@@ -313,10 +348,15 @@ class SdavLoopClosureDetector:
     steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
     the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
     straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
-    dtypes, empty slots, contrast and suppress are as with the lines."""
+    dtypes, empty slots, contrast and suppress are as with the lines.
+
+    chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert and result() return
+    a third tensor, chain int32 [B, k, L] -- for every candidate the frame id each of the last L frames was matched to,
+    oldest frame first (_SequenceRows); -1 where the slot is empty or the stream poisoned.  loops(..., chains=chain)
+    lists them as pairs."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, **stream_args):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
@@ -327,8 +367,9 @@ class SdavLoopClosureDetector:
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 score rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress,
-                                     steps=steps)
+                                     steps=steps, chains=self.chains)
         if self._seq is not None:
             self.slopes, self.steps = self._seq.slopes, self._seq.steps
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
@@ -343,7 +384,7 @@ class SdavLoopClosureDetector:
         (-inf, -1) where fewer than k frames are old enough; the frames are resident afterwards.  A POISONED stream (a value
         outside its fixed range or a NaN was appended, now or earlier: `poisoned`, SimilarityStream.stats[1]) returns
         (NaN, -1) in every slot -- "these scores mean nothing", visible in the tensors themselves without a host read;
-        loops() raises."""
+        loops() raises.  With chains=True a third tensor, chain [B, k, L] int32."""
         if self._pending is not None:                                 # a submitted batch's rows are ranked before this one's,
             self._flush()                                             # and nothing is in flight when the stream grows
         st = self.stream
@@ -379,7 +420,8 @@ class SdavLoopClosureDetector:
     def _nothing_older(self, b):
         """(-inf, -1) in every slot of b frames' lists; (NaN, -1) once the stream is poisoned."""
         s, i = _nothing_older(b, self.k, float("-inf"), torch.float64, self.stream.engine.device)
-        return torch.where(self.poisoned != 0, float("nan"), s), i
+        out = (torch.where(self.poisoned != 0, float("nan"), s), i)
+        return out + (_no_chains(b, self.k, self.sequence, i.device),) if self.chains else out
 
     # ---- two batches in flight ------------------------------------------------------------------------------------------
     # query_and_insert runs a batch's six launches one behind the other: copy, quantisation, the strip's product kernel (200
@@ -445,7 +487,8 @@ class SdavLoopClosureDetector:
         self._pending = None
 
     def result(self, ticket):
-        """(scores [B, k] float64, ids [B, k] int64) of a submitted batch, in the current stream's order."""
+        """(scores [B, k] float64, ids [B, k] int64) of a submitted batch, in the current stream's order; with chains=True
+        (scores, ids, chain [B, k, L] int32)."""
         if not self._tickets - 2 <= ticket < self._tickets:
             raise ValueError("SdavLoopClosureDetector.result: ticket %r is not in flight" % (ticket,))
         if self._pending == ticket:
@@ -467,10 +510,11 @@ class SdavLoopClosureDetector:
                                "infinity) was appended -- the filter's error bound does not hold, every later row is NaN; "
                                "create the stream with a value_range / column_centre that covers the data")
 
-    def loops(self, scores, ids, first_id):
+    def loops(self, scores, ids, first_id, chains=None):
         """[(frame id, older frame id, score)] at or above the threshold; raises when the stream has been poisoned (a value
-        outside its fixed range: SimilarityStream.stats[1])."""
-        found = _loops(scores, ids, first_id, self.threshold)
+        outside its fixed range: SimilarityStream.stats[1]).  chains: the third result of query_and_insert / result with
+        chains=True -- every entry then ends in the candidate's L (frame id, older frame id) pairs, oldest first."""
+        found = _loops(scores, ids, first_id, self.threshold, chains=chains)
         self._check_poison()
         return found
 
@@ -505,10 +549,14 @@ class CnnVtlLoopClosureDetector:
     steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
     the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
     straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
-    dtypes, empty slots, contrast and suppress are as with the lines."""
+    dtypes, empty slots, contrast and suppress are as with the lines.
+
+    chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert returns a third
+    tensor, chain int32 [B, k, L] -- for every candidate the key-frame id each of the last L frames was matched to, oldest
+    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs."""
 
     def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None, steps=None):
+                 contrast=None, suppress=None, steps=None, chains=False):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -523,8 +571,9 @@ class CnnVtlLoopClosureDetector:
         self.contrast = None if contrast is None else int(contrast)
         # the last L - 1 distance rows, then the batch's
         self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=self.suppress, steps=steps)
+                                     suppress=self.suppress, steps=steps, chains=self.chains)
         if self._seq is not None:
             self.slopes, self.steps = self._seq.slopes, self._seq.steps
         from .distance import CnnVtlKeyframeDatabase
@@ -536,7 +585,8 @@ class CnnVtlLoopClosureDetector:
     def query_and_insert(self, descriptors):
         """The next B frames' int8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (dist [B, k] int64,
         ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
-        key-frames afterwards.  With sequence=L dist is the sum of the L distances along the best line."""
+        key-frames afterwards.  With sequence=L dist is the sum of the L distances along the best line.  With chains=True
+        a third tensor, chain [B, k, L] int32."""
         db = self.db
         x = db.engine.to_device(descriptors)
         if x.dim() == 1:
@@ -548,17 +598,20 @@ class CnnVtlLoopClosureDetector:
                                                   limit0=first - self.exclusion, limit_step=1)
         if b == 0:
             if self.contrast is not None:
-                return _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
-            return _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
+                out = _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
+            else:
+                out = _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
+            return out + (_no_chains(0, self.k, self.sequence, db.engine.device),) if self.chains else out
         # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
         db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
                      out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
         return self._seq.search(db.engine, b, first + b, first - self.exclusion)
 
-    def loops(self, dist, ids, first_id):
+    def loops(self, dist, ids, first_id, chains=None):
         """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance (with sequence=L: the
-        sum of the L distances along the candidate's line)."""
-        return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True)
+        sum of the L distances along the candidate's line).  chains: the third result of query_and_insert with
+        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
+        return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True, chains=chains)
 
 
 def _frame_files(dataset_path, pattern):
@@ -603,6 +656,11 @@ def describe_cnn_vtl(files, network=None, as_int8=False):
     return desc if as_int8 else desc.to(torch.float32)
 
 
+def chain_line(pairs):
+    """The CLI's line under a candidate: `chain`, then the L frame:key-frame pairs, oldest frame first, tab-separated."""
+    return "chain\t" + "\t".join("%d:%d" % p for p in pairs)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="stream the frames of a dataset through the loop-closure detector")
     ap.add_argument("dataset_path")
@@ -626,6 +684,9 @@ def main(argv=None):
     ap.add_argument("--steps", default=None, metavar="DMIN:DMAX",
                     help="with --sequence: the elastic search -- from frame to frame the matched key-frame steps back "
                          "DMIN..DMAX key-frames (0 <= DMIN <= DMAX <= 8) instead of following a straight line")
+    ap.add_argument("--chains", action="store_true",
+                    help="with --sequence: under every candidate a line `chain` with the L frame:key-frame pairs it was "
+                         "matched along, oldest frame first")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
     ap.add_argument("--exclusion", type=int, default=30)
@@ -663,6 +724,8 @@ def main(argv=None):
         if not 0 <= d_min <= d_max <= L.DLC_MAX_STEP:
             ap.error("--steps must be DMIN:DMAX with 0 <= DMIN <= DMAX <= %d" % L.DLC_MAX_STEP)
         args.steps = (d_min, d_max)
+    if args.chains and args.sequence is None:
+        ap.error("--chains needs --sequence")
     if args.threshold is None:
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
@@ -702,19 +765,22 @@ def _stream(args, files):
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
                                           exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
-                                          contrast=args.contrast, suppress=args.suppress, steps=args.steps)
+                                          contrast=args.contrast, suppress=args.suppress, steps=args.steps,
+                                          chains=args.chains)
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))
         elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))
-        s, i = det.query_and_insert(desc)
-        found = det.loops(s, i, lo)                              # (the one host read of the step)
+        s, i, *chain = det.query_and_insert(desc)
+        found = det.loops(s, i, lo, *chain)                      # (the one host read of the step)
         lat.append(((time.perf_counter() - t0) * 1e3, len(chunk)))
-        for frame, match, score in found:
+        for frame, match, score, *pairs in found:
             print(("loop\t%d\t%s\t%d\t%s\t" + ("%d" if args.metric == "distance" else "%.4f"))
                   % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
+            if pairs:
+                print(chain_line(pairs[0]))
     print("frames\t%d\tkey-frames\t%d" % (len(files), len(det)), file=sys.stderr)
     # the first step pays one-time costs (the library's first launches, workspaces, the database's reservation): reported apart
     steady = lat[1:] if len(lat) > 1 else lat

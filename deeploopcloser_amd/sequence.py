@@ -15,6 +15,12 @@ level, oldest row first (dlc_sequence_elastic_topk, include/dlc.h: the recursion
 ties).  In place of the winning slope the lists carry the chain's span, the key-frames it covers.  contrast runs in front
 of it and suppress behind it as with the lines; steps=None is every path as it was.
 
+Chains.  A candidate's score is a sum over L frames; sequence_chains (and chains=True on sequence_topk / sequence_peaks)
+returns the alignment behind it: for each of the L frames, oldest first, the column it was matched to, and on request
+the matrix cells along them (dlc_sequence_elastic_chains / dlc_sequence_chains, include/dlc.h) -- L frame-to-key-frame
+pairs per loop closure, the weakest frame's score, per-frame correspondences.  With steps it is the chain the recursion
+chose, otherwise the winning line.
+
 Distinct places.  The k best cells of a row are mostly ONE place: a revisit of key-frame j scores almost as well against
 j - 1, j + 1, ...  peak_topk / sequence_peaks pick the best cell, then the best one more than `suppress` key-frames from
 it, and so on (dlc_peak_topk_rows, include/dlc.h) -- SeqSLAM's "best trajectory, then the best one outside a window
@@ -104,7 +110,37 @@ def _run(matrix, L, offsets, k, dense, limit0, limit_step, lower_is_better, cont
     return tuple(None if t is None else (t.cpu().numpy() if as_numpy else t) for t in out)
 
 
-def sequence_topk(matrix, k, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None, steps=None):
+def _chains(e, matrix, idx, L, offsets, steps, limit0, limit_step, lower_is_better, cells):
+    """(chain, cells or None) of a device matrix that the search saw (behind the contrast front already) and a device idx."""
+    if steps is not None:
+        if offsets is not None:
+            raise ValueError("sequence search: steps and offsets exclude each other")
+        return e.sequence_elastic_chains(matrix, L, check_steps(steps), idx, limit0=limit0, limit_step=limit_step,
+                                         lower_is_better=lower_is_better, cells=cells)
+    return e.sequence_chains(matrix, L, slope_offsets(L) if offsets is None else offsets, idx, limit0=limit0,
+                             limit_step=limit_step, lower_is_better=lower_is_better, cells=cells)[:2]
+
+
+def sequence_chains(matrix, idx, L, offsets=None, steps=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None,
+                    cells=False):
+    """chain int32 [rows, k, L] -- with cells=True (chain, cells [rows, k, L]) -- of the candidates idx [rows, k] (int64
+    end columns from sequence_topk or sequence_peaks with the same L, offsets or steps, limits, order and contrast; -1: an
+    empty slot): the column each of the L frames of the candidate's chain was matched to, oldest frame first, chain[...,
+    L-1] = idx.  With steps the chain the elastic recursion chose (its cells summed oldest first are the candidate's score
+    bit for bit), otherwise the winning line (summed newest first).  A slot that is no candidate of its row holds -1, and
+    NaN / -1 in cells.  contrast = R: of contrast_normalize(matrix, R, limit0, limit_step), the matrix the search saw."""
+    e = default_engine()
+    matrix, as_numpy = _on_device(e, matrix)
+    idx = e.to_device(np.ascontiguousarray(idx, dtype=np.int64)) if not isinstance(idx, torch.Tensor) else idx
+    if contrast is not None:
+        matrix = contrast_normalize(matrix, contrast, limit0, limit_step)
+    out = _chains(e, matrix, idx, L, offsets, steps, limit0, limit_step, lower_is_better, cells)
+    out = tuple(t.cpu().numpy() if as_numpy else t for t in out if t is not None)
+    return out if cells else out[0]
+
+
+def sequence_topk(matrix, k, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None, steps=None,
+                  chains=False):
     """(scores [rows, k], idx [rows, k] int64, slope [rows, k] int32): per row r of matrix [rows, n] the k best cells by the
     sequence score over L rows, among the row's first clamp(limit0 + r * limit_step, 0, n) columns (limit0 None: all),
     best first, ties -> the lower column.  offsets: an int32 table [V, L] (default slope_offsets(L)); slope: the row of it
@@ -113,8 +149,18 @@ def sequence_topk(matrix, k, L, offsets=None, limit0=None, limit_step=0, lower_i
     matrices too.
     steps = (d_min, d_max) (None: the lines above; with offsets: ValueError): the ELASTIC search -- the best chain of L
     cells that ends in (r, j) and steps back d_min .. d_max columns per row (dlc_sequence_elastic_topk); the third
-    result is then span [rows, k] int32, the columns the chosen chain covers."""
-    return _run(matrix, L, offsets, int(k), False, limit0, limit_step, lower_is_better, contrast, steps)[:3]
+    result is then span [rows, k] int32, the columns the chosen chain covers.
+    chains=True: a fourth result, chain [rows, k, L] int32 -- the column each of the L frames of a candidate was matched
+    to, oldest first (sequence_chains)."""
+    if not chains:
+        return _run(matrix, L, offsets, int(k), False, limit0, limit_step, lower_is_better, contrast, steps)[:3]
+    e = default_engine()
+    matrix, as_numpy = _on_device(e, matrix)
+    if contrast is not None:
+        matrix = contrast_normalize(matrix, contrast, limit0, limit_step)
+    out = _search(e, matrix, L, offsets, int(k), False, limit0, limit_step, lower_is_better, None, steps=steps)[:3]
+    out += (_chains(e, matrix, out[1], L, offsets, steps, limit0, limit_step, lower_is_better, False)[0],)
+    return tuple(t.cpu().numpy() if as_numpy else t for t in out)
 
 
 def sequence_scores(matrix, L, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None, steps=None):
@@ -152,18 +198,23 @@ def peak_topk(matrix, k, suppress, limit0=None, limit_step=0, lower_is_better=Fa
 
 
 def sequence_peaks(matrix, k, L, suppress, offsets=None, limit0=None, limit_step=0, lower_is_better=False, contrast=None,
-                   steps=None):
+                   steps=None, chains=False):
     """(scores [rows, k], idx [rows, k] int64): the distinct-place candidates by the sequence score -- sequence_scores
     (same L, offsets or steps, limits and contrast), then peak_topk over those dense scores with the same limits: the best
     trajectory, then the best one whose end lies more than `suppress` key-frames from it, ...  With k = 2,
     lower_is_better and suppress = R_window / 2 the two slots are OpenSeqSLAM's min_value and min_value_2nd
     (uniqueness_ratio).  int64 matrices: the dense scores mark "no valid line" with -1, which is passed on as the absent
     value, so a genuine sequence sum of -1 is not offered either -- the convention (and the collision) of
-    dlc_sequence_topk's int64 seq_out."""
+    dlc_sequence_topk's int64 seq_out.
+    chains=True: a third result, chain [rows, k, L] int32, the picks' chains over the same input (sequence_chains)."""
     e = default_engine()
     matrix, as_numpy = _on_device(e, matrix)
-    dense = _search(e, matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, contrast, steps=steps)[3]
+    if contrast is not None:
+        matrix = contrast_normalize(matrix, contrast, limit0, limit_step)
+    dense = _search(e, matrix, L, offsets, None, True, limit0, limit_step, lower_is_better, None, steps=steps)[3]
     out = _peaks(e, dense, k, suppress, limit0, limit_step, lower_is_better, -1 if dense.dtype == torch.int64 else None)
+    if chains:
+        out += (_chains(e, matrix, out[1], L, offsets, steps, limit0, limit_step, lower_is_better, False)[0],)
     return tuple(t.cpu().numpy() if as_numpy else t for t in out)
 
 

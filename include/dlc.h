@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 18
+#define DLC_ABI_VERSION 19
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -653,6 +653,49 @@ int dlc_sequence_elastic_topk(dlc_ctx* ctx, int dtype, const void* scores, int64
                               int lower_is_better, int k, void* out_scores, int64_t* out_idx, int32_t* out_span,
                               void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/*
+ * The CHAIN of a candidate: the alignment behind a score of dlc_sequence_elastic_topk or dlc_sequence_topk -- for each of
+ * the L frames of the chain the key-frame it was matched to, and the matrix cells along it.  The searches keep one
+ * scalar of it (the span, the slope); a pose graph wants the L frame-to-key-frame pairs, a gate the weakest frame's score.
+ * Arguments as the searches' (dtype, M = scores [rows, ld] with n columns in use, row0, lim(r), L, the steps or the HOST
+ * offset table, lower_is_better, poison, stream).  idx [rows - row0, k] (device int64) holds the candidates' end columns
+ * j: the out_idx of either search or of dlc_peak_topk_rows over its seq_out, -1 for an empty slot.  The alignment is
+ * formed again for those cells alone, by the recursion / the sums defined above, so the same call serves the fused lists
+ * and picks from the dense scores (which carry neither slope nor span).
+ * OUTPUT.  out_chain int32 [rows - row0, k, L]: the matched columns, OLDEST frame first -- chain[t] is the column in row
+ * rho(t) = r - (L-1) + t, chain[L-1] = j.  out_cells [rows - row0, k, L] (may be NULL): cells[t] = M[rho(t)][chain[t]],
+ * fp64 for DLC_F64 / DLC_F32 (the conversion is exact), int64 for DLC_I64.
+ * ELASTIC (dlc_sequence_elastic_chains), for E(r, j) valid: chain[t-1] = chain[t] - d*, d* the step P_t(chain[t]) chose
+ * (the best valid A_{t-1}(c - d), the lowest d among equals, in the order of merit above, -0.0 below +0.0).  Hence
+ *   - chain[0] == j - span(r, j); every step chain[t] - chain[t-1] lies in [d_min, d_max]; every chain[t] < lim(rho(t));
+ *   - ((cells[0] + cells[1]) + ...) + cells[L-1] equals E(r, j) bit for bit (wrapping for DLC_I64);
+ *   - a chain depends on the L rows behind its cell alone: not on the batching, row0 or the launch plan;
+ *   - with L = 1 the chain is [j].
+ * LINES (dlc_sequence_chains), for S(r, j) offered: v* is dlc_sequence_topk's winning slope (the lowest v attaining the
+ * best valid Z_v), chain[t] = j - off[v*][L-1-t], and out_slope [rows - row0, k] (may be NULL) receives v*.  Summed
+ * newest first, as Z_v is defined -- cells[L-1] + cells[L-2] + ... + cells[0] -- the cells give S(r, j) bit for bit.
+ * NOT A CHAIN: an idx of -1 (any value outside -1 .. n-1 is taken as -1 and never read from), idx >= lim(r), a cell that
+ * is not valid (r - (L-1) < 0 included) or a non-zero poison word give chain = -1 in all L places, slope -1 and cells
+ * NaN (-1 for DLC_I64).
+ * Nothing at or past a row's limit, and no column n .. ld - 1, is read.
+ * Limits: the searches' own -- 1 <= L <= 64, 0 <= d_min <= d_max <= DLC_MAX_STEP, 1 <= n_slopes <= 16 and the table as
+ * dlc_sequence_topk takes it, 1 <= k <= DLC_MAX_K, 0 <= row0 < rows, n < 2^31; (rows - row0) * k < 2^31.
+ * Errors: DLC_ERR_BAD_ARG (a limit above, a missing pointer, ld < n, poison with DLC_I64), DLC_ERR_BAD_SHAPE (more
+ * candidates than one launch takes); nothing is written then.
+ * Each entry point is ONE launch on `stream` (elastic: one wave per candidate runs the forward recursion over the
+ * trapezoid of columns that can reach (r, j) -- at level t the columns j - (L-1-t) * d_max .. j - (L-1-t) * d_min, at most
+ * 505 -- keeping the chosen step of every (level, column) in LDS, then walks back); no workspace; never synchronises.
+ * The outputs must not overlap the matrix, idx or each other.
+ */
+int dlc_sequence_elastic_chains(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
+                                int64_t limit0, int64_t limit_step, int L, int d_min, int d_max,
+                                int lower_is_better, int k, const int64_t* idx, int32_t* out_chain, void* out_cells,
+                                const int64_t* poison, void* stream);
+int dlc_sequence_chains(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
+                        int64_t limit0, int64_t limit_step, int L, int n_slopes, const int32_t* offsets,
+                        int lower_is_better, int k, const int64_t* idx, int32_t* out_chain, void* out_cells,
+                        int32_t* out_slope, const int64_t* poison, void* stream);
 
 /*
  * SeqSLAM's local contrast normalisation of score rows (Milford & Wyeth, ICRA 2012, III-B): every cell against its
