@@ -10,6 +10,8 @@ include/dlc.h, with the reference's Python call surface on top:
     SimilarityCalculator          (src/sdav/similarity; + SimilarityStream: one new frame against the resident ones)
     DistanceCalculator            (src/cnn_vtl/similarity; + distance_rows: a rectangular set of pairs in one call;
                                    + CnnVtlKeyframeDatabase: k nearest by that distance, or the distance rows themselves)
+    SeqSlam, DifferenceCalculator, SadKeyframeDatabase   (SeqSLAM's own front-end: patch-normalised grey thumbnails compared
+                                   by the sum of absolute differences -- no weights; new)
     MathUtils                     (src/utils/MathUtils.py)
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
@@ -17,7 +19,7 @@ include/dlc.h, with the reference's Python call surface on top:
         steps=(d_min, d_max) on them and on the detectors: the elastic search, a chain that steps back d_min..d_max key-frames per frame
     sequence_chains (and chains=True on sequence_topk / sequence_peaks / the detectors): the L matched key-frames behind a candidate; new
     peak_topk / sequence_peaks / uniqueness_ratio   (distinct-place candidates: picks more than `suppress` columns apart; new)
-    LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector   (streaming; all three take sequence=L, suppress=W)
+    LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector   (streaming; all take sequence=L, suppress=W)
 
 Importing the package is cheap and works without a GPU; constructing any of
 the classes needs libdlc_hip.so and a visible MI355X and raises otherwise.
@@ -30,15 +32,16 @@ from .sda import SDA
 from .cnn_vtl import CnnVtl
 from .similarity import SimilarityCalculator, SimilarityStream
 from .distance import DistanceCalculator, CnnVtlKeyframeDatabase
+from .seqslam import SeqSlam, DifferenceCalculator, SadKeyframeDatabase
 from .matching import encode, match, match_topk, KeyframeDatabase, MatchPipeline, flatten_frame_descriptors
 from .dist import ShardedKeyframeDatabase, shard_bounds, merge_topk_torch
 from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, read_ppm
 from . import tensor_wrapper
 from . import sequence
 from .sequence import slope_offsets, sequence_topk, sequence_scores, sequence_chains, contrast_normalize, peak_topk, sequence_peaks, uniqueness_ratio
-from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector
+from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector
 
-__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

@@ -1,5 +1,6 @@
 // What the two cnn_vtl distance kernels over (query tile x db tile) share: distance_topk.hip (the fused k-nearest scan)
-// and distance_rows.hip (the rectangular distance rows).  The tile shapes and the masked 16-byte load.
+// and distance_rows.hip (the rectangular distance rows) -- and sad_rows.hip, the same rows for SeqSLAM's sum of absolute
+// differences on unsigned bytes.  The tile shapes and the masked 16-byte load.
 #pragma once
 #include "gemm_internal.h"
 
@@ -41,6 +42,10 @@ __device__ __forceinline__ u32x4_t tk_load16(const int8_t* row, long long k, lon
         }
     }
     return v;
+}
+// The same block of a row of unsigned bytes (sad_rows.hip): the words are the same, only the operand's type differs.
+__device__ __forceinline__ u32x4_t tk_load16(const uint8_t* row, long long k, long long D) {
+    return tk_load16((const int8_t*)row, k, D);
 }
 
 }  // namespace

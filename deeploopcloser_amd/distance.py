@@ -69,32 +69,32 @@ class DistanceCalculator:
         return e.cnnvtl_distance_rows(e.to_device(q, torch.int8), e.to_device(x, torch.int8)).cpu().numpy()
 
 
-class CnnVtlKeyframeDatabase:
-    """cnn_vtl key-frame descriptors (int8 [n, dim]) resident in HBM, searched by the reference's distance.
+class _ByteRowStore:
+    """What the resident byte-descriptor stores share (CnnVtlKeyframeDatabase here, seqslam.SadKeyframeDatabase): rows of
+    `DTYPE` bytes zero-padded to a multiple of 16 (the row kernels' alignment) in a capacity-reserved buffer that doubles
+    when an append() outgrows it; `rows` is the view of the first len(db) rows.  KIND names the descriptors in errors."""
 
-    Rows are stored zero-padded to a multiple of 16 bytes (the top-k kernel's row alignment) in a capacity-reserved
-    buffer that doubles when an append() outgrows it; `rows` is the view of the first len(db) rows.  nearest() is
-    dlc_cnnvtl_distance_topk: distance ascending, ties -> the lower id, (-1, -1) past the rows there are; distances() is
-    dlc_cnnvtl_distance_rows: the [Q, len(db)] distances themselves, for callers that rank them another way (the
-    sequence search)."""
-
-    FORMAT = "dlc-cnnvtl-keyframes-v1"
+    DTYPE, KIND = None, None
 
     def __init__(self, descriptors, capacity=None, device=None):
         self.engine = default_engine(device)
         x = self.engine.to_device(descriptors)
-        if x.dim() != 2 or x.dtype != torch.int8:
-            raise ValueError("cnn_vtl descriptors must be [n, dim] int8")
+        if x.dim() != 2 or x.dtype != self.DTYPE:
+            raise ValueError("%s descriptors must be [n, dim] %s" % (self.KIND, self._dtype_name()))
         if x.shape[1] < 1:
-            raise ValueError("cnn_vtl descriptors must have dim >= 1")
+            raise ValueError("%s descriptors must have dim >= 1" % self.KIND)
         self.dim = int(x.shape[1])
         self._n = 0
         n = int(x.shape[0])
         cap = max(n, 1 if capacity is None else int(capacity))
-        self._store = torch.zeros((cap, self.stored_width(self.dim)), dtype=torch.int8, device=self.engine.device)
+        self._store = torch.zeros((cap, self.stored_width(self.dim)), dtype=self.DTYPE, device=self.engine.device)
         if n:
             self._store[:n, :self.dim] = x
             self._n = n
+
+    @classmethod
+    def _dtype_name(cls):
+        return str(cls.DTYPE).split(".")[-1]
 
     @staticmethod
     def stored_width(dim):
@@ -104,13 +104,13 @@ class CnnVtlKeyframeDatabase:
     def empty(cls, dim, capacity=4096, device=None):
         """A database of `dim`-byte descriptors with no key-frames yet and room for `capacity`."""
         if dim < 1 or capacity < 1:
-            raise ValueError("CnnVtlKeyframeDatabase.empty: dim and capacity must be positive")
+            raise ValueError("%s.empty: dim and capacity must be positive" % cls.__name__)
         eng = default_engine(device)
-        return cls(torch.empty((0, int(dim)), dtype=torch.int8, device=eng.device), capacity=capacity, device=device)
+        return cls(torch.empty((0, int(dim)), dtype=cls.DTYPE, device=eng.device), capacity=capacity, device=device)
 
     @property
     def rows(self):
-        """[len, stored_width(dim)] int8: the stored rows, padding bytes included."""
+        """[len, stored_width(dim)]: the stored rows, padding bytes included."""
         return self._store[:self._n]
 
     @property
@@ -123,16 +123,15 @@ class CnnVtlKeyframeDatabase:
     def reserve(self, capacity):
         """Room for at least `capacity` key-frames (one device-to-device copy when it grows)."""
         if capacity > self.capacity:
-            grown = torch.zeros((int(capacity), self._store.shape[1]), dtype=torch.int8, device=self.engine.device)
+            grown = torch.zeros((int(capacity), self._store.shape[1]), dtype=self.DTYPE, device=self.engine.device)
             grown[:self._n] = self._store[:self._n]
             self._store = grown
 
     def append(self, descriptors):
-        """Store further key-frames [B, dim] int8; returns their ids (first, last+1).  Stream-ordered on the current
-        stream."""
+        """Store further key-frames [B, dim]; returns their ids (first, last+1).  Stream-ordered on the current stream."""
         x = self.engine.to_device(descriptors)
-        if x.dim() != 2 or x.dtype != torch.int8 or x.shape[1] != self.dim:
-            raise ValueError("append: descriptors must be [B, %d] int8" % self.dim)
+        if x.dim() != 2 or x.dtype != self.DTYPE or x.shape[1] != self.dim:
+            raise ValueError("append: descriptors must be [B, %d] %s" % (self.dim, self._dtype_name()))
         b = int(x.shape[0])
         if self._n + b > self.capacity:
             self.reserve(max(2 * self.capacity, self._n + b))
@@ -140,6 +139,28 @@ class CnnVtlKeyframeDatabase:
         first = self._n
         self._n += b
         return first, first + b
+
+    def _queries(self, who, queries):
+        """Query rows for the row kernels: [Q, dim], or stored rows [Q, stored_width(dim)] (the padding is ignored)."""
+        q = self.engine.to_device(queries)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.dtype != self.DTYPE or q.shape[1] not in (self.dim, self._store.shape[1]):
+            raise ValueError("%s: queries must be [Q, %d] %s" % (who, self.dim, self._dtype_name()))
+        return q
+
+
+class CnnVtlKeyframeDatabase(_ByteRowStore):
+    """cnn_vtl key-frame descriptors (int8 [n, dim]) resident in HBM, searched by the reference's distance.
+
+    Rows are stored zero-padded to a multiple of 16 bytes (the top-k kernel's row alignment) in a capacity-reserved
+    buffer that doubles when an append() outgrows it; `rows` is the view of the first len(db) rows.  nearest() is
+    dlc_cnnvtl_distance_topk: distance ascending, ties -> the lower id, (-1, -1) past the rows there are; distances() is
+    dlc_cnnvtl_distance_rows: the [Q, len(db)] distances themselves, for callers that rank them another way (the
+    sequence search)."""
+
+    FORMAT = "dlc-cnnvtl-keyframes-v1"
+    DTYPE, KIND = torch.int8, "cnn_vtl"
 
     def prefix(self, n):
         """The first n key-frames as a database of their own (a copy: a database owns its reservation)."""
@@ -165,11 +186,7 @@ class CnnVtlKeyframeDatabase:
         of `rows` (the padding is ignored).  limit0 / limit_step: query r is written in its first limit0 + r * limit_step cells only (default: all); the others
         keep what `out` held (a caller-kept int64 [Q, len(self)] tensor or row-strided view), or hold -1 when the result
         is allocated here."""
-        q = self.engine.to_device(queries)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.dim() != 2 or q.dtype != torch.int8 or q.shape[1] not in (self.dim, self._store.shape[1]):
-            raise ValueError("distances: queries must be [Q, %d] int8" % self.dim)
+        q = self._queries("distances", queries)
         return self.engine.cnnvtl_distance_rows(q, self.rows, d=self.dim, limit0=limit0, limit_step=limit_step, out=out)
 
     # ---- on-disk format: one .npz ------------------------------------------------------------------------------------

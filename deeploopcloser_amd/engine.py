@@ -891,11 +891,12 @@ class Engine:
         padded[:, :d] = x[:, :d]
         return padded
 
-    def _int8_pair(self, who, q, db, d):
-        """The checks of the distance calls' operands q [Q, >= d], db [N, >= d] (int8, on the device) -> d (None: the
-        rows' one width)."""
-        if q.dim() != 2 or db.dim() != 2 or q.dtype != torch.int8 or db.dtype != torch.int8:
-            raise ValueError("%s: q and db must be 2-D int8" % who)
+    def _int8_pair(self, who, q, db, d, dtype=torch.int8):
+        """The checks of the distance calls' operands q [Q, >= d], db [N, >= d] (int8 -- or `dtype`, the other byte type
+        -- on the device) -> d (None: the rows' one width)."""
+        if not isinstance(q, torch.Tensor) or not isinstance(db, torch.Tensor) or q.dim() != 2 or db.dim() != 2 or \
+                q.dtype != dtype or db.dtype != dtype:
+            raise ValueError("%s: q and db must be 2-D %s" % (who, str(dtype).split(".")[-1]))
         if q.device != self.device or db.device != self.device:
             raise ValueError("%s: q and db must be on %s" % (who, self.device))
         if d is None:
@@ -975,6 +976,57 @@ class Engine:
         self._check(self.lib.dlc_cnnvtl_distance_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
                                                        n if limit0 is None else int(limit0), int(limit_step), _ptr(out),
                                                        ld_out, self._stream()))
+        self._wrote(out)
+        return out
+
+    # ---- SeqSLAM front-end: patch-normalised thumbnails, SAD difference rows ------------------------------------------
+    def seqslam_describe(self, gray, size, patch, strength, out=None):
+        """uint8 [F, h * w]: SeqSLAM's descriptor of every frame of gray (uint8 [F, H, W] on the device) -- the frame
+        area-resized to size = (h, w), then patch-normalised over patch x patch tiles to 128 + strength * z-score
+        (dlc_seqslam_describe_u8, include/dlc.h), exact.  out: a caller-kept uint8 [F, >= h * w] tensor or row-strided view
+        (a database's rows: the bytes past h * w of a row keep their value); the result is its first h * w columns."""
+        if not isinstance(gray, torch.Tensor) or gray.dtype != torch.uint8 or gray.dim() != 3 or gray.device != self.device:
+            raise ValueError("seqslam_describe: uint8 [F, H, W] on %s expected" % self.device)
+        gray = gray.contiguous()
+        h, w = (int(v) for v in size)
+        f, hh, ww = gray.shape
+        if h < 1 or w < 1:
+            raise ValueError("seqslam_describe: size=%r must be positive" % (size,))
+        out = self._rows_out("seqslam_describe: out", out, f, h * w, torch.uint8, "a uint8", wider=True)
+        if f == 0:
+            return out[:, :h * w]
+        ld_out = out.stride(0) if f > 1 else out.shape[1]
+        self._check(self.lib.dlc_seqslam_describe_u8(self.ctx, _ptr(gray), f, hh, ww, h, w, int(patch), int(strength),
+                                                      _ptr(out), ld_out, self._stream()))
+        self._wrote(out)
+        return out[:, :h * w]
+
+    def _rows16_u8(self, x, d):
+        """_rows16 for uint8 rows."""
+        return self._rows16(x.view(torch.int8), d).view(torch.uint8)
+
+    def sad_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
+        """int64 [Q, N]: the sum of absolute differences of every query row of q [Q, D] uint8 to the rows of db [N, D]
+        uint8 (dlc_sad_u8_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r * limit_step,
+        0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1, "not offered",
+        when the engine allocates the result.  d: the descriptor length when the rows are padded (the bytes past d are
+        ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows lie further apart than N (its
+        columns past N are left alone too)."""
+        d = self._int8_pair("sad_rows", q, db, d, dtype=torch.uint8)
+        nq, n = q.shape[0], db.shape[0]
+        out = self._rows_out("sad_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
+        if nq == 0 or n == 0:
+            return out
+        if d == 0:                                               # empty descriptors: every difference is 0
+            lim = (n if limit0 is None else int(limit0)) + int(limit_step) * torch.arange(nq, device=self.device)
+            out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
+            return out
+        q = self._rows16_u8(q, d)
+        db = self._rows16_u8(db, d)
+        ld_out = out.stride(0) if nq > 1 else n
+        self._check(self.lib.dlc_sad_u8_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
+                                              n if limit0 is None else int(limit0), int(limit_step), _ptr(out), ld_out,
+                                              self._stream()))
         self._wrote(out)
         return out
 

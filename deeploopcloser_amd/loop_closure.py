@@ -8,6 +8,10 @@ matches each new frame against the key-frames more than `exclusion` frames older
 top-k path and reports the candidates whose cosine score reaches `threshold`.
 
     python -m deeploopcloser_amd.loop_closure DATASET_DIR --network cnn_vtl --k 5 --threshold 0.9
+    python -m deeploopcloser_amd.loop_closure DATASET_DIR --network seqslam --metric sad --sequence 10 --contrast 5
+
+--network seqslam --metric sad is SeqSLAM itself, front to back and without weights: patch-normalised grey thumbnails
+(--size, --patch, --strength), their sums of absolute differences, then the sequence search (SeqSlamLoopClosureDetector).
 
 With --sequence L --chains every candidate line is followed by one line `chain<TAB>frame:key-frame<TAB>...`: the L pairs
 the candidate was matched along, oldest frame first (the detectors' chains=True; dlc_sequence_chains /
@@ -614,6 +618,93 @@ class CnnVtlLoopClosureDetector:
         return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True, chains=chains)
 
 
+class SeqSlamLoopClosureDetector:
+    """The streaming question asked the way SeqSLAM asks it (Milford & Wyeth, ICRA 2012): every new frame's descriptor -- a
+    patch-normalised grey thumbnail, uint8 [dim] (seqslam.SeqSlam) -- is compared with all resident frames more than
+    `exclusion` frames older by the sum of absolute differences, and the k with the smallest difference (ties -> the older
+    frame) at or below `max_difference` (all of them when None) are the loop candidates.  No weights are involved.
+
+    Without `sequence` a batch's difference rows go into a resident int64 buffer (dlc_sad_u8_rows, frame first + r seeing
+    the frames below first + r - exclusion) and dlc_peak_topk_rows picks from them, lower is better; suppress = W (default
+    0: a plain top-k) keeps the picks more than W key-frames apart.  (-1, -1) where fewer than k frames are old enough.
+
+    sequence = L is CnnVtlLoopClosureDetector(sequence=L) with these rows in place of the cnn_vtl distance rows: a pair
+    (frame t, older frame j) is scored by the SUM of the L differences along a line through (t, j), the smallest over the
+    lines of `slopes`; the detector keeps the last L - 1 rows resident (_SequenceRows: int64, lower_is_better), and
+    contrast = R, suppress = W, steps = (d_min, d_max) and chains = True mean what they mean there -- with contrast the
+    sums are float64 and an empty slot is (+inf, -1).  max_difference is then compared with the sequence sum.
+
+    In both forms the lists do not depend on how the frames are batched."""
+
+    def __init__(self, dim, k=5, max_difference=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
+                 contrast=None, suppress=None, steps=None, chains=False):
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if exclusion < 0:
+            raise ValueError("exclusion must be >= 0")
+        if max_difference is not None and max_difference < 0 and contrast is None:
+            raise ValueError("max_difference must be >= 0 (or None)")
+        if dim < 1 or capacity < 1:
+            raise ValueError("dim and capacity must be positive")
+        if suppress is not None and not 0 <= suppress < 1 << 63:
+            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
+        self.k, self.exclusion = int(k), int(exclusion)
+        self.max_difference = max_difference if max_difference is None else (int if contrast is None else float)(max_difference)
+        self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
+        self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
+        # (without sequence=L `suppress` is served here, by the peak selection over the frame rows themselves)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
+                                     suppress=None if self.sequence is None else self.suppress, steps=steps,
+                                     chains=self.chains)
+        if self._seq is not None:
+            self.slopes, self.steps = self._seq.slopes, self._seq.steps
+        self._rows = None                                    # without sequence: the batch's difference rows [b, capacity]
+        from .seqslam import SadKeyframeDatabase
+        self.db = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+
+    def __len__(self):
+        return len(self.db)
+
+    def query_and_insert(self, descriptors):
+        """The next B frames' uint8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (diff [B, k] int64,
+        ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
+        key-frames afterwards.  With sequence=L diff is the sum of the L differences along the best line.  With
+        chains=True a third tensor, chain [B, k, L] int32."""
+        db = self.db
+        x = db.engine.to_device(descriptors)
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        first, _ = db.append(x)
+        b = x.shape[0]
+        if b == 0:
+            if self.contrast is not None:
+                out = _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
+            else:
+                out = _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
+            return out + (_no_chains(0, self.k, self.sequence, db.engine.device),) if self.chains else out
+        q = db.rows[first:first + b]
+        if self._seq is None:
+            if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
+                self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
+                                         dtype=torch.int64, device=db.engine.device)
+            rows = self._rows[:b, :first + b]
+            db.differences(q, limit0=first - self.exclusion, limit_step=1, out=rows)
+            return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
+                                            lower_is_better=True)
+        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
+        db.differences(q, limit0=first - self.exclusion, limit_step=1,
+                       out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
+        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
+
+    def loops(self, diff, ids, first_id, chains=None):
+        """[(frame id, matched key-frame id, difference)] of the candidates at or below max_difference (with sequence=L:
+        the sum of the L differences along the candidate's line).  chains: the third result of query_and_insert with
+        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
+        return _loops(diff, ids, first_id, self.max_difference, lower_is_better=True, chains=chains)
+
+
 def _frame_files(dataset_path, pattern):
     files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
     if not files:
@@ -665,16 +756,19 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="stream the frames of a dataset through the loop-closure detector")
     ap.add_argument("dataset_path")
     ap.add_argument("--pattern", default="*.ppm")
-    ap.add_argument("--network", choices=["sdav", "cnn_vtl"], default="cnn_vtl")
+    ap.add_argument("--network", choices=["sdav", "cnn_vtl", "seqslam"], default="cnn_vtl",
+                    help="the descriptor: SDAV, CnnVtl, or SeqSLAM's patch-normalised grey thumbnail (needs no weights; "
+                         "goes with --metric sad)")
     ap.add_argument("--weights", help=".npz written by SDAV.save_weights (sdav) / AlexNet .npy blob (cnn_vtl)")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--threshold", type=float, default=None,
                     help="report candidates at or above this score (default: 0.9 for cosine, all k for similarity)")
-    ap.add_argument("--metric", choices=["cosine", "distance", "similarity"], default="cosine",
-                    help="cosine of the descriptors, the reference's cnn_vtl distance (needs --network cnn_vtl) or the "
-                         "reference's SDAV similarity (needs --network sdav; the distinctive score comes from the first batch)")
+    ap.add_argument("--metric", choices=["cosine", "distance", "similarity", "sad"], default="cosine",
+                    help="cosine of the descriptors, the reference's cnn_vtl distance (needs --network cnn_vtl), the "
+                         "reference's SDAV similarity (needs --network sdav; the distinctive score comes from the first batch) "
+                         "or SeqSLAM's sum of absolute differences (needs --network seqslam)")
     ap.add_argument("--sequence", type=int, default=None, metavar="L",
-                    help="--metric similarity: rank by the sum of the scores along a line of L frames (sequence search)")
+                    help="--metric similarity or sad: rank by the sum of the scores along a line of L frames (sequence search)")
     ap.add_argument("--contrast", type=int, default=None, metavar="R",
                     help="with --sequence: normalise every score against the R key-frames on either side of it first "
                          "(SeqSLAM's local contrast normalisation), R in 1..32")
@@ -689,6 +783,13 @@ def main(argv=None):
                          "matched along, oldest frame first")
     ap.add_argument("--max-distance", type=int, default=None,
                     help="--metric distance: report candidates at or below this distance (default: all k)")
+    ap.add_argument("--max-difference", type=float, default=None,
+                    help="--metric sad: report candidates at or below this difference (with --sequence: the sum along the "
+                         "line; default: all k)")
+    ap.add_argument("--size", default="32x64", metavar="HxW", help="--network seqslam: the thumbnail's rows x columns")
+    ap.add_argument("--patch", type=int, default=8, help="--network seqslam: side of the normalisation tiles, 1..64")
+    ap.add_argument("--strength", type=int, default=32,
+                    help="--network seqslam: descriptor byte = 128 + strength * z-score, 1..127")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -702,8 +803,25 @@ def main(argv=None):
         ap.error("--metric distance needs --network cnn_vtl")
     if args.metric == "similarity" and args.network != "sdav":
         ap.error("--metric similarity needs --network sdav")
-    if args.sequence is not None and args.metric != "similarity":
-        ap.error("--sequence needs --metric similarity")
+    if (args.network == "seqslam") != (args.metric == "sad"):
+        ap.error("--network seqslam and --metric sad need each other")
+    if args.network == "seqslam":
+        try:
+            args.size = tuple(int(v) for v in args.size.lower().split("x"))
+        except ValueError:
+            args.size = ()
+        if len(args.size) != 2 or min(args.size) < 1 or args.size[0] * args.size[1] > 65536:
+            ap.error("--size must be HxW, two positive integers with H * W <= 65536")
+        if not 1 <= args.patch <= 64:
+            ap.error("--patch must be 1..64")
+        if not 1 <= args.strength <= 127:
+            ap.error("--strength must be 1..127")
+        if args.max_difference is not None and args.contrast is None:
+            if args.max_difference < 0 or args.max_difference != int(args.max_difference):
+                ap.error("--max-difference must be a non-negative integer (any number with --contrast)")
+            args.max_difference = int(args.max_difference)
+    if args.sequence is not None and args.metric not in ("similarity", "sad"):
+        ap.error("--sequence needs --metric similarity or sad")
     if args.sequence is not None and not 1 <= args.sequence <= 64:
         ap.error("--sequence must be 1..64")
     if args.contrast is not None and args.sequence is None:
@@ -744,6 +862,12 @@ def _stream(args, files):
         if args.weights:
             net.load_weights(args.weights)
         describe = lambda fs: describe_sdav(fs, net)
+    elif args.network == "seqslam":
+        from . import pipeline
+        from .input import read_ppm
+        from .seqslam import SeqSlam
+        net = SeqSlam(size=args.size, patch=args.patch, strength=args.strength)
+        describe = lambda fs: pipeline.seqslam_descriptors_from_frames(np.stack([read_ppm(f) for f in fs]), net)
     else:
         from .cnn_vtl import CnnVtl
         from .input import read_ppm
@@ -770,6 +894,11 @@ def _stream(args, files):
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))
+        elif det is None and args.metric == "sad":
+            det = SeqSlamLoopClosureDetector(desc.shape[1], k=args.k, max_difference=args.max_difference,
+                                             exclusion=args.exclusion, capacity=max(4096, len(files)), sequence=args.sequence,
+                                             contrast=args.contrast, suppress=args.suppress, steps=args.steps,
+                                             chains=args.chains)
         elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))
@@ -777,7 +906,7 @@ def _stream(args, files):
         found = det.loops(s, i, lo, *chain)                      # (the one host read of the step)
         lat.append(((time.perf_counter() - t0) * 1e3, len(chunk)))
         for frame, match, score, *pairs in found:
-            print(("loop\t%d\t%s\t%d\t%s\t" + ("%d" if args.metric == "distance" else "%.4f"))
+            print(("loop\t%d\t%s\t%d\t%s\t" + ("%d" if isinstance(score, int) else "%.4f"))
                   % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
             if pairs:
                 print(chain_line(pairs[0]))

@@ -173,3 +173,50 @@ def cnn_vtl_distance_matrix_from_frames(frames, network, chunk_frames=None, devi
     res = eng.download(dm)
     _done(timings, m, cur)
     return res
+
+
+def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None, timings=None):
+    """frames: uint8 [N, H, W, 3] RGB (or [N, H, W] grey), a host ndarray or a device tensor -> SeqSLAM descriptors uint8
+    [N, h * w] ON THE DEVICE (seqslam.SeqSlam: grey, area resize, patch normalisation).  A host array is uploaded in chunks
+    of `chunk_frames` frames whose transfer overlaps the previous chunk's kernels; a frame's descriptor does not depend on
+    its chunk.  out: a caller-kept uint8 [N, >= h * w] tensor or row view (a database's rows)."""
+    eng = network.engine
+    n = int(frames.shape[0])
+    if out is None:
+        out = torch.empty((n, network.dim), dtype=torch.uint8, device=eng.device)
+    cur = torch.cuda.current_stream(eng.device)
+
+    def consume(dev, lo, hi):
+        m = _mark(timings, "SeqSlam.transform", cur)
+        network.transform_tensor(dev, out=out[lo:hi])
+        _done(timings, m, cur)
+
+    if n == 0:
+        return out[:, :network.dim]
+    if isinstance(frames, torch.Tensor):
+        for lo in range(0, n, RESIDENT_CHUNK_FRAMES):          # (chunks only bound the grey frames' footprint)
+            consume(frames[lo:lo + RESIDENT_CHUNK_FRAMES], lo, min(n, lo + RESIDENT_CHUNK_FRAMES))
+    else:
+        a = np.asarray(frames)
+        if a.dtype != np.uint8:
+            raise ValueError("seqslam_descriptors_from_frames: frames must be uint8")
+        n_chunks = max(1, -(-n // max(1, int(chunk_frames))))
+        eng.for_each_chunk(a, -(-n // n_chunks), consume, first=FIRST_CHUNK_FRAMES)
+    return out[:, :network.dim]
+
+
+def seqslam_difference_matrix_from_frames(frames, network, chunk_frames=256, device_result=False, timings=None):
+    """Frames -> SeqSLAM descriptors -> the full N x N int64 matrix of their sums of absolute differences (the matrix
+    SeqSLAM's matcher starts from).  One upload, one download (device_result=True: none)."""
+    eng = network.engine
+    cur = torch.cuda.current_stream(eng.device)
+    d8 = seqslam_descriptors_from_frames(frames, network, chunk_frames, timings=timings)
+    m = _mark(timings, "difference matrix", cur)
+    dm = eng.sad_rows(d8, d8)
+    _done(timings, m, cur)
+    if device_result:
+        return dm
+    m = _mark(timings, "download of the matrix", cur)
+    res = eng.download(dm)
+    _done(timings, m, cur)
+    return res

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DLC_ABI_VERSION 19
+#define DLC_ABI_VERSION 20
 
 typedef struct dlc_ctx dlc_ctx;
 
@@ -245,6 +245,40 @@ size_t dlc_harris_keypoints_workspace_bytes(int64_t frames, int H, int W);
 int dlc_harris_keypoints_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int n,
                             int32_t* points, int64_t* responses, int32_t* counts, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ---- encode: SeqSLAM's image descriptor (not in the reference; needs no weights) ------------ */
+/*
+ * SeqSLAM's descriptor of a frame (Milford & Wyeth, ICRA 2012, III-A): the grey frame down-sampled to a thumbnail and
+ * patch-normalised; two descriptors are compared by their sum of absolute differences (dlc_sad_u8_rows), and the
+ * difference rows feed dlc_contrast_rows / dlc_sequence_topk / dlc_peak_topk_rows, the rest of the method.
+ * INPUT.  gray is uint8 [frames, H, W] (what dlc_rgb_to_gray_u8 writes).  The result is exact: a function of the pixels
+ * alone, the same for every launch plan.
+ * AREA RESIZE to T [h, w], integers only.  Source row i covers [i h, (i + 1) h) and thumbnail row y covers
+ * [y H, (y + 1) H) of a common axis of h H units:
+ *     wy(y, i) = max(0, min((i + 1) h, (y + 1) H) - max(i h, y H))         (these sum to H over i; wx(x, j) alike with w, W)
+ *     T(y, x)  = floor((2 * sum_{i, j} wy(y, i) wx(x, j) gray[i][j] + H W) / (2 H W))
+ * -- the area-weighted mean, rounded half up.  h == H and w == W is the identity.
+ * PATCH NORMALISATION over the tiles [y0, min(y0 + patch, h)) x [x0, min(x0 + patch, w)), y0 and x0 multiples of patch
+ * (tiles at the lower and right edge are clipped).  Per tile of c cells: s = sum T, t = sum T * T, Qv = c t - s s, all
+ * exact integers.  If c < 2 or Qv == 0 every cell of the tile is 128.  Otherwise, per cell, in fp64 with division and
+ * sqrt the IEEE correctly rounded ones and no fma contraction:
+ *     u   = (double)(c T - s)
+ *     v   = sqrt((double)(c - 1) / ((double)c * (double)Qv))             (one multiply, one divide, one sqrt)
+ *     z   = rint(((double)strength * u) * v)                             (the first product is exact, the second rounded
+ *                                                                         once; rint rounds to nearest even)
+ *     out = clamp(128 + z, 0, 255)
+ * -- that is 128 + strength * (T - mean) / sample std (MATLAB's std, as OpenSeqSLAM normalises) with every input an exact
+ * integer: no summation order is involved.  (OpenSeqSLAM's own byte format, 127 + round(z), is not this one.)
+ * OUTPUT.  out is uint8 [frames, ld_out], ld_out >= h * w: the thumbnail row-major in the first h * w bytes of a row.
+ * Bytes h * w .. ld_out-1 KEEP THEIR VALUE.  out must not overlap gray.  A row pitch that is a multiple of 16 on a
+ * 16-byte aligned base is what dlc_sad_u8_rows takes.
+ * Limits: frames >= 1, 1 <= h <= H, 1 <= w <= W, h * w <= 65536, H * W < 2^23, 1 <= patch <= 64, 1 <= strength <= 127.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, frames < 1, patch or strength outside its range or ld_out < h * w;
+ * DLC_ERR_BAD_SHAPE for h, w, H, W outside the limits.  Nothing is written then.
+ * No workspace; one launch on `stream` (one workgroup per frame, the thumbnail in LDS); never synchronises.
+ */
+int dlc_seqslam_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int h, int w,
+                            int patch, int strength, uint8_t* out, int64_t ld_out, void* stream);
 
 /* ---- encode: CnnVtl pieces (src/cnn_vtl/network/cnn_vtl.py:28-133) ------ */
 /*
@@ -557,6 +591,28 @@ int dlc_cnnvtl_distance_rows(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int
                              const int8_t* db, int64_t N, int64_t ldd, int64_t D,
                              int64_t limit0, int64_t limit_step,
                              int64_t* out, int64_t ld_out, void* stream);
+
+/*
+ * SeqSLAM's image difference as rows: out[r * ld_out + j] = sum_{p < D} |q_r[p] - db_j[p]| on UNSIGNED bytes (the sum
+ * of absolute differences of two dlc_seqslam_describe_u8 descriptors; Milford & Wyeth, ICRA 2012, III-A), of query row r
+ * of queries [Q, D] (row stride ldq) against row j of db [N, D] (row stride ldd).  The contract is
+ * dlc_cnnvtl_distance_rows' word for word: written for 0 <= j < lim(r) = clamp(limit0 + r * limit_step, 0, N), any
+ * limit_step, negative included (limit_step = 0, limit0 = N: the full [Q, N] block -- the difference matrix is this call
+ * with queries = db); EVERY OTHER WORD OF out KEEPS ITS VALUE, the cells at or past lim(r) and the columns
+ * N .. ld_out-1; when every lim(r) is 0 nothing is launched and the call returns DLC_OK.
+ * out is int64 [Q, ld_out], ld_out >= N.  Both bases 16-byte aligned, ldq and ldd multiples of 16 bytes (>= D); bytes
+ * D .. ld-1 of a row may hold anything and change nothing; queries may be rows of db itself (both are only read); out
+ * must not overlap the operands.  D <= 2^24 (255 * D fits the 32-bit accumulator), N < 2^32, Q <= 2^20.
+ * No workspace; one launch on `stream` (the tiles of dlc_cnnvtl_distance_rows, v_sad_u8 on the staged words, plain
+ * 8-byte stores: no memset, no atomics); never synchronises.  Integers throughout: the result is exact and does not
+ * depend on the plan, nor on how the queries are batched.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, Q, N or D < 1, ldq or ldd < D, ld_out < N or a misaligned base or pitch;
+ * DLC_ERR_BAD_SHAPE for D > 2^24, N >= 2^32 or Q > 2^20 (checked as stated: Q = 2^20 is taken).  Nothing is written then.
+ */
+int dlc_sad_u8_rows(dlc_ctx* ctx, const uint8_t* queries, int64_t Q, int64_t ldq,
+                    const uint8_t* db, int64_t N, int64_t ldd, int64_t D,
+                    int64_t limit0, int64_t limit_step,
+                    int64_t* out, int64_t ld_out, void* stream);
 
 /* ---- match: sequence-consistent search over a score matrix (not in the reference) ----------- */
 /*
