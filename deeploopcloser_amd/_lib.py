@@ -18,7 +18,7 @@ DLC_B_KN, DLC_B_NK = 0, 1
 DLC_MAX_K = 128
 DLC_MAX_STEP = 8             # the largest step of the elastic sequence search (d_max)
 DLC_ABI_VERSION = 20         # include/dlc.h; load() refuses a library built from another header
-DLC_SELECT_COOP = 1
+DLC_SELECT_COOP, DLC_SELECT_NO_HINTS = 1, 2
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float

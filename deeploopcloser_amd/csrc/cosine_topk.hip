@@ -84,6 +84,16 @@ template <> struct Mfma16<dlc_f16_tag> {
 __device__ __forceinline__ int swz_a(int r) { return ((r >> 1) & 1) | (((r >> 4) & 3) << 1); }
 __device__ __forceinline__ int swz_b(int r) { return (r >> 1) & 7; }
 
+// One entry per (query, half tile), written by the one-pass MFMA score kernel only (WsLayout::hints): about the half tile's
+// best group G* -- the lowest-index group whose maximum is the half tile's -- which row holds that maximum and how high
+// the other seven can score.  finish_topk_body re-scores that one row instead of the group where r2 rules the others out.
+// Stored half tile major, hint[ht * q + query]: a wave's 16 queries of one half tile are 128 consecutive bytes (the
+// query-major layout of tmax, 8-byte stores 8 * ldt bytes apart, cost the kernel 13 us more per 1 M-row launch).
+struct alignas(8) HintEntry {
+    float r2;           // upper bound of the fp32 scores of G*'s rows other than row (id & 7); +inf = unknown
+    int id;             // (G* << 3) | a*: G* = 0..15 inside the half tile, a* = the lowest row of G* attaining its maximum
+};
+
 struct GemmArgs {
     const char* Q;      // [q, ldq] elements of 2 bytes
     const char* DB;     // [n, lddb]
@@ -96,6 +106,7 @@ struct GemmArgs {
     long long ldg;
     float* tmax;        // [q, ldt]
     long long ldt;
+    HintEntry* hint;    // [ldt, q] (half tile major): GEMM_GROUPS epilogue only
     long long ng;       // ceil(n/16)
     long long nh;       // ceil(n/128)
     float* S;           // dense mode: [q, lds]
@@ -357,7 +368,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int qidx = qblk * BNQ + wc * 64 + c * 16 + i;
-            float hm[2];
+            float hm[2], gm[2][2];
 #pragma unroll
             for (int th = 0; th < 2; ++th) {
                 // this lane's 16 rows of the half are two groups of 8: MFMA tiles {0,1} and {2,3}
@@ -370,6 +381,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
                         m1 = fmaxf(m1, acc[th * 4 + 2 + tt][c][r]);
                     }
                 hm[th] = fmaxf(m0, m1);
+                gm[th][0] = m0; gm[th][1] = m1;
                 const long long g = tile * (BM / GROUP) + wr * 16 + th * 8 + lg * 2;
                 if (qidx < p.q) {
                     float* dst = p.gmax + (long long)qidx * p.ldg + g;
@@ -382,6 +394,45 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
             h = fmaxf(h, __shfl_xor(h, 32));
             const long long ht = tile * 2 + wr;
             if (lg == 0 && qidx < p.q && ht < p.nh) p.tmax[(long long)qidx * p.ldt + ht] = h;
+            // ---- the half tile's hint (HintEntry).  This lane's groups are G = th * 8 + lg * 2 + j of the half tile; the
+            // lowest one attaining h, min-reduced over the four lg lanes of the query, is G*, and the lane that holds it
+            // looks at its 8 scores: a* = the lowest row attaining h, r2 = the largest of the other seven (a running top-2:
+            // second = med3(first, second, v), first = max(first, v) -- a second row AT the maximum leaves r2 = h, which
+            // is what the padded copies of a last row do: conservative, the finish then re-scores the whole group).
+            int rank = 16;                                  // 16 = none (every score of the half tile is NaN)
+            if (gm[1][1] == h) rank = 9 + lg * 2;
+            if (gm[1][0] == h) rank = 8 + lg * 2;
+            if (gm[0][1] == h) rank = 1 + lg * 2;
+            if (gm[0][0] == h) rank = lg * 2;
+            rank = min(rank, __shfl_xor(rank, 16));
+            rank = min(rank, __shfl_xor(rank, 32));
+            const bool hi_th = (rank & 8) != 0, hi_j = (rank & 1) != 0;
+            float v[GROUP];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float lo = hi_j ? acc[2 + tt][c][r] : acc[tt][c][r];
+                    const float hi = hi_j ? acc[6 + tt][c][r] : acc[4 + tt][c][r];
+                    v[tt * 4 + r] = hi_th ? hi : lo;
+                }
+            float first = v[0], second = -INFINITY;
+            int astar = GROUP - 1;
+#pragma unroll
+            for (int r = 1; r < GROUP; ++r) {
+                second = __builtin_amdgcn_fmed3f(first, second, v[r]);
+                first = fmaxf(first, v[r]);
+            }
+#pragma unroll
+            for (int r = GROUP - 2; r >= 0; --r) astar = v[r] == h ? r : astar;
+            const bool none = rank == 16;
+            const bool owner = none ? lg == 0 : ((rank >> 1) & 3) == lg;
+            if (owner && qidx < p.q && ht < p.nh) {
+                HintEntry e;
+                e.r2 = none ? INFINITY : second;
+                e.id = none ? 0 : ((rank << 3) | astar);
+                p.hint[(long long)ht * p.q + qidx] = e;      // 16 lanes x 8 B in a row: whole 128-byte pieces
+            }
         }
     }
 }
@@ -690,6 +741,7 @@ __device__ __forceinline__ double scaled_tau(double tau, const float* __restrict
 enum { FIN_FUSED = 0, FIN_GROUPS = 1, FIN_RESCORE = 2 };
 struct FinishArgs {
     float* tmax; long long ldt; int nh; int tv_in_lds;
+    const HintEntry* hint;        // [ldt, nq] or null: the score pass's half-tile hints (FIN_FUSED, 512 threads, whole database)
     const float* gmax; long long ldg; long long ng;
     int kg;                       // groups kept per query (k + SLACK)
     const char* Q; long long ldq_b; const char* DB; long long lddb_b;
@@ -769,6 +821,7 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     __syncthreads();
     int kg2;
     unsigned bkey = 0u;      // fp32 key of the largest group maximum left behind by the selection; 0 = nothing left behind
+    const bool use_hint = MODE == FIN_FUSED && THREADS == 512 && a.hint != nullptr && !a.dense_S && !a.limited;
     if constexpr (MODE != FIN_RESCORE) {
     // ---- level 1: the kt half tiles with the largest maximum (ties -> lower tile).
     // Each wave extracts the kt best of its slice by repeated wave arg-max (DPP, no barrier);
@@ -882,6 +935,17 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     // has no row with an fp64 score above u' - tau.  Ranks k .. kg-1 are usually such groups (they are there for the crowded
     // case): dropping them saves their 8 rows' gather each.  They join what is left behind -- and cannot fail the
     // certificate (s_k >= u' - tau > their maximum + tau).
+    // CHAMPION GROUPS (use_hint: the stand-alone fused form behind the one-pass score kernel, HintEntry).  A surviving group
+    // that is its half tile's G* and whose runner-up bound r2 is below u' - 2 tau hands in ONE candidate, its row a*:
+    //   * k groups have a maximum >= u' and the row attaining it is re-scored either way (a* of a champion group, all 8 rows
+    //     of any other), so the k-th fp64 score s_k is >= u' - tau;
+    //   * a skipped row has an fp32 score <= r2 < u' - 2 tau, hence an fp64 score < u' - tau <= s_k: it is never in the
+    //     top-k and never ties with the k-th score, so scores, rows and the `lower` of the exhaustive pass are the same;
+    //   * r2 joins what is left behind and cannot fail the certificate: s_k >= u' - tau > r2 + tau.
+    // The comparison is strict and in fp64 as the pruning's: false for a NaN and for tau = +inf.  With fewer than k groups
+    // (no u') nothing is a champion group.
+    int champ = -1;                                         // tid < kg2: row a* of this thread's champion group
+    unsigned champ_r2 = 0u;
     if (tid < kg2) {
         const int c = sel2[tid];
         int g = c < 0 ? -1 : (int)key_id(ckey[c]);
@@ -891,6 +955,15 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
             const double uk = (double)key_f32((unsigned)(ckey[sel2[k - 1]] >> 32));
             if ((double)key_f32((unsigned)(ckey[c] >> 32)) < uk - 2.0 * tau) g = -2;          // pruned (after the reads below)
         }
+        if (use_hint && g >= 0 && k <= kg2 && sel2[k - 1] >= 0) {
+            const double uk = (double)key_f32((unsigned)(ckey[sel2[k - 1]] >> 32));
+            const HintEntry hv = a.hint[(long long)(g >> 4) * a.nq + qi];                     // GROUPS_PER_HALF = 16
+            // (a* is the lowest row attaining the maximum and rows past n are copies of row n - 1, so a* < n; checked anyway)
+            if ((hv.id >> 3) == (g & 15) && (double)hv.r2 < uk - 2.0 * tau && (long long)g * GROUP + (hv.id & 7) < n) {
+                champ = hv.id & 7;
+                champ_r2 = f32_key(hv.r2);
+            }
+        }
         misc[9] = 0u;                                       // (benign: every writer stores the same value)
         crow[tid] = g;                                      // staged: sel2 / ckey are still being read by the other threads
     }
@@ -898,9 +971,13 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     if (tid < kg2) {
         const int g = crow[tid];
         if (g == -2) atomicMax(&misc[9], (unsigned)(ckey[sel2[tid]] >> 32));
+        if (champ >= 0) atomicMax(&misc[9], champ_r2);
     }
     __syncthreads();
-    if (tid < kg2) sel2[tid] = crow[tid] < 0 ? -1 : crow[tid];                                 // -> group index
+    if (tid < kg2) {
+        sel2[tid] = crow[tid] < 0 ? -1 : crow[tid];                                            // -> group index
+        if (use_hint) sel[tid] = champ;                     // (the half-tile list is dead) -> a*, -1 = the whole group
+    }
     bkey = max(bkey, misc[9]);
     __syncthreads();
     } else {
@@ -973,7 +1050,27 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
         for (int e = tid; e < m3; e += FIN_THREADS) {
             const int g = sel2[e / GROUP];
             const long long row = (long long)g * GROUP + (e % GROUP);
-            crow[e] = (g >= 0 && row < n) ? (int)row : -1;
+            const int astar = use_hint ? sel[e / GROUP] : -1;                 // a champion group: its row a* only
+            crow[e] = (g >= 0 && row < n && (astar < 0 || astar == e % GROUP)) ? (int)row : -1;
+        }
+        if (use_hint) {
+            // work lists (in ckey, which is dead here): single rows wl1[0 .. n1) = candidate slots, whole groups
+            // wl8[0 .. n8) = ranks; in rank order, whatever thread writes them
+            int* wl1 = (int*)ckey;
+            int* wl8 = wl1 + kg;
+            if (tid < kg2) {
+                int b1 = 0, b8 = 0, t1 = 0, t8 = 0;
+                for (int j = 0; j < kg2; ++j) {
+                    const bool on = sel2[j] >= 0, one = on && sel[j] >= 0;
+                    t1 += one ? 1 : 0; t8 += (on && !one) ? 1 : 0;
+                    if (j < tid) { b1 += one ? 1 : 0; b8 += (on && !one) ? 1 : 0; }
+                }
+                if (sel2[tid] >= 0) {
+                    if (sel[tid] >= 0) wl1[b1] = tid * GROUP + sel[tid];
+                    else wl8[b8] = tid;
+                }
+                if (tid == 0) { misc[10] = (unsigned)t1; misc[11] = (unsigned)t8; }
+            }
         }
     }
     __syncthreads();
@@ -991,6 +1088,68 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
                 cs64[ci] = id < 0 ? -INFINITY : sc;
                 ck64[ci] = id < 0 ? KEY64_EMPTY : f64_key(sc);
             }
+        }
+    } else if (use_hint) {
+        // single rows first, up to three in flight per wave (one round for k + SLACK rows over 8 waves), dealt in runs of
+        // `per` from the wave behind the last one that has a whole group; then the whole groups, one per wave and round.
+        // A row's value is rescore8_f64's whatever the dealing (rescore_rows_f64); slots nobody scores are empty.
+        const int n1 = __builtin_amdgcn_readfirstlane((int)misc[10]), n8 = __builtin_amdgcn_readfirstlane((int)misc[11]);
+        const int* wl1 = (const int*)ckey;
+        const int* wl8 = wl1 + kg;
+        for (int e = tid; e < m3; e += FIN_THREADS) { cs64[e] = -INFINITY; ck64[e] = KEY64_EMPTY; }
+        // (each slot has one writer after this: the barrier orders the defaults before the scores)
+        __syncthreads();
+        const int per = (n1 + FIN_WAVES - 1) / FIN_WAVES;
+        const int wv = (w + FIN_WAVES - n8 % FIN_WAVES) % FIN_WAVES;
+        const int hi1 = min(n1, (wv + 1) * per);
+        for (int s = wv * per; s < hi1;) {
+            const int cnt = min(3, hi1 - s);
+            int slot[3], ids3[3];
+            const char* rows3[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                slot[r] = __builtin_amdgcn_readfirstlane(wl1[s + (r < cnt ? r : 0)]);
+                ids3[r] = __builtin_amdgcn_readfirstlane(crow[slot[r]]);
+                rows3[r] = a.DB + (long long)(ids3[r] < 0 ? 0 : ids3[r]) * a.lddb_b;
+            }
+            double sc[3];
+            if (cnt == 3) rescore_rows_f64<Tag, 3, 8>(qrow, rows3, a.d, lane, sc);
+            else if (cnt == 2) {
+                const char* const rows2[2] = {rows3[0], rows3[1]};
+                double sc2[2];
+                rescore_rows_f64<Tag, 2, 8>(qrow, rows2, a.d, lane, sc2);
+                sc[0] = sc2[0]; sc[1] = sc2[1]; sc[2] = 0.0;
+            } else {
+                const char* const rows1[1] = {rows3[0]};
+                double sc1[1];
+                rescore_rows_f64<Tag, 1, 8>(qrow, rows1, a.d, lane, sc1);
+                sc[0] = sc1[0]; sc[1] = sc[2] = 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                if (lane == r && r < cnt && ids3[r] >= 0) {
+                    cs64[slot[r]] = sc[r];
+                    ck64[slot[r]] = f64_key(sc[r]);
+                }
+            s += cnt;
+        }
+        for (int s8 = w; s8 < n8; s8 += FIN_WAVES) {
+            const int e0 = __builtin_amdgcn_readfirstlane(wl8[s8]) * GROUP;
+            int ids[GROUP];
+            const char* rows[GROUP];
+#pragma unroll
+            for (int r = 0; r < GROUP; ++r) {
+                ids[r] = __builtin_amdgcn_readfirstlane(crow[e0 + r]);
+                rows[r] = a.DB + (long long)(ids[r] < 0 ? 0 : ids[r]) * a.lddb_b;
+            }
+            double acc[GROUP];
+            rescore8_f64<Tag, RS_UNROLL>(qrow, rows, a.d, lane, acc);
+#pragma unroll
+            for (int r = 0; r < GROUP; ++r)
+                if (lane == r && ids[r] >= 0) {
+                    cs64[e0 + r] = acc[r];
+                    ck64[e0 + r] = f64_key(acc[r]);
+                }
         }
     } else
     for (int s = w; s * GROUP < m3; s += FIN_WAVES) {
@@ -1702,12 +1861,14 @@ SplitPlan split_plan(int64_t q, int64_t n, int64_t d) {
 }
 
 struct WsLayout {
-    size_t gmax, tmax, part, status, s64, rs_ids, rs_max, rs_scores, rs_idx, rs_bound, total;
+    size_t gmax, tmax, hint, part, status, s64, rs_ids, rs_max, rs_scores, rs_idx, rs_bound, total;
     long long ldg, ldt, ldp;
     int kg;
     SplitPlan sp;
     int rparts;     // > 1: dlc_cosine_topk re-scores with this many workgroups per query (few queries, long rows)
     bool dense;     // small database: the score matrix itself is kept (chunk 0 of `part`) and the candidates are ROWS
+    bool hints;     // the score pass fills `hint` (q * ldt HintEntry behind tmax; the room is there on every plan): the
+                    // one-pass MFMA plan only -- not split-K, not the small-database plan, not the bandwidth kernel
     double tau;     // error bound of the score pass against the fp64 re-score (score_error_bound below)
 };
 
@@ -1765,8 +1926,10 @@ WsLayout ws_layout(int64_t q, int64_t n, int64_t d, int k) {
     size_t o = 0;
     w.gmax = o; o += dlc::align_up((size_t)q * w.ldg * 4, 256);
     w.tmax = o; o += dlc::align_up((size_t)q * w.ldt * 4, 256);
+    w.hint = o; o += dlc::align_up((size_t)q * w.ldt * sizeof(HintEntry), 256);
     w.sp = split_plan(q, n, d);
     w.dense = dense_plan(q, n, d);
+    w.hints = !w.dense && w.sp.nsplit == 1 && !gemv_shape(q, d / BK);     // == launch_scores' GEMM_GROUPS branch
     w.tau = score_error_bound(q, d / BK, w.sp, w.dense);
     w.ldp = ntiles * BM;
     w.part = o;
@@ -1928,6 +2091,7 @@ int prepare_match(dlc_ctx* ctx, const char* what, int dtype, const void* Q, int6
     a.q = (int)q; a.n = n; a.nk = (int)(d / BK);
     a.gmax = (float*)(ws + mc->w.gmax); a.ldg = mc->w.ldg;
     a.tmax = (float*)(ws + mc->w.tmax); a.ldt = mc->w.ldt;
+    a.hint = (HintEntry*)(ws + mc->w.hint);
     a.ng = dlc::cdiv(n, GROUP); a.nh = dlc::cdiv(n, HALF);
     a.S = nullptr; a.lds = 0;
     a.nsplit = mc->w.sp.nsplit; a.kchunk = mc->w.sp.kchunk;
@@ -2050,6 +2214,9 @@ int run_finish(dlc_ctx* ctx, int dtype, const MatchCall& mc, int k, int64_t n, i
     } else if (mc.w.rparts <= 1) {
         f.out_s = out_scores; f.out_s64 = s64; f.out_i = (long long*)out_idx; f.status = status;
         if (mc.w.dense) { f.dense_S = mc.a.P; f.ld_s = mc.a.ldp; f.rslack = DENSE_ROW_SLACK; }
+        // half-tile hints: where the plan's score pass wrote them, for the stand-alone form looking at the whole database
+        if (mc.w.hints && !limited && !(flags & (DLC_SELECT_COOP | DLC_SELECT_NO_HINTS)))
+            f.hint = (const HintEntry*)(ws + mc.w.hint);
         rc = run_select<FIN_FUSED>(ctx, dtype, f, q, flags, st);
         if (rc != DLC_OK) return rc;
     } else {

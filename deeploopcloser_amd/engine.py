@@ -1383,8 +1383,9 @@ class Engine:
                                                       ws.numel(), st))
 
     def select_topk(self, q, db, k, ws, scores, idx, row_offset=0, coop=False, stream=None, scores_f64=None, status=None,
-                    tau_scale=None):
-        """Stage 2 of match_topk (selection, fp64 re-score, final top-k, certificate, exhaustive pass) from the workspace."""
+                    tau_scale=None, hints=True):
+        """Stage 2 of match_topk (selection, fp64 re-score, final top-k, certificate, exhaustive pass) from the workspace.
+        hints=False re-scores every selected group whole (DLC_SELECT_NO_HINTS): the same results, more rows gathered."""
         self._check_stored(q, db)
         self._check_ws(ws)
         self._check_out("scores", scores, (q.shape[0], k), torch.float32)
@@ -1398,7 +1399,8 @@ class Engine:
                                                      _ptr(db), db.shape[0], db.stride(0), q.shape[1], k, row_offset,
                                                      _ptr(scores), _ptr(scores_f64), _ptr(idx), _ptr(status),
                                                      _ptr(tau_scale), _ptr(ws), ws.numel(),
-                                                     L.DLC_SELECT_COOP if coop else 0, st))
+                                                     (L.DLC_SELECT_COOP if coop else 0) |
+                                                     (0 if hints else L.DLC_SELECT_NO_HINTS), st))
 
     def _check_ws(self, ws):
         if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != self.device:

@@ -35,6 +35,9 @@
 extern "C" {
 #endif
 
+/* Raised when a prototype, a struct or the meaning of an existing argument value changes.  A new bit in a `flags`
+ * argument (zero keeps the old behaviour) and a larger *_workspace_bytes() answer (callers ask, never compute) change
+ * neither: DLC_SELECT_NO_HINTS and the hint array of dlc_cosine_topk_workspace_bytes came in at 20. */
 #define DLC_ABI_VERSION 20
 
 typedef struct dlc_ctx dlc_ctx;
@@ -955,9 +958,12 @@ double dlc_cosine_score_error_bound_any_plan(int64_t d);
  *                               pass; reads the workspace (and consumes it), Q and DB.
  * Same operand rules, same workspace size (dlc_cosine_topk_workspace_bytes), same results.
  * flags: DLC_SELECT_COOP selects a small-footprint kernel (256 threads, < 96 VGPRs, a few KiB
- * of LDS) whose workgroups can share a CU with a running score GEMM.
+ * of LDS) whose workgroups can share a CU with a running score GEMM.  DLC_SELECT_NO_HINTS makes the
+ * selection ignore the score pass's half-tile hints (below) and re-score every selected group whole: the
+ * same results bit for bit, more rows gathered -- it is there so that tests can hold the two against each other.
  */
 #define DLC_SELECT_COOP 1
+#define DLC_SELECT_NO_HINTS 2
 int dlc_cosine_score_groups(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t ldq,
                             const void* DB, int64_t n, int64_t lddb, int64_t d, int k,
                             void* workspace, size_t workspace_bytes, void* stream);
@@ -1018,6 +1024,21 @@ int dlc_cosine_select_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, in
  *                          is -inf (nothing was left behind -- also when fewer than k rows exist at all) or when k rows
  *                          were found and the k-th fp64 score > (double)bound[q] + tau * (double)tau_scale[q]; 1
  *                          otherwise.  A query with status 0 holds the exact global top-k already.
+ *   the half-tile hints    (inside dlc_cosine_topk / dlc_cosine_select_topk only; the sharded stages never read them.)  On the
+ *                          one-pass MFMA plan -- no split-K, not the <= 16384-row plan, more than 4 queries -- the score pass
+ *                          also writes, per (query, half tile of 128 rows), 8 bytes into the workspace behind the half-tile
+ *                          maxima: for G*, the lowest group holding the half tile's maximum, the lowest row a* of G* that
+ *                          attains it and r2, the largest fp32 score of G*'s other seven rows (rows past n are copies of
+ *                          row n - 1, so r2 may equal the maximum there).  The 512-thread selection, looking at the whole
+ *                          database (not DLC_SELECT_COOP, not dlc_cosine_topk_older), takes ONE candidate, row a*, from a
+ *                          selected group that is its half tile's G* and has (double)r2 < u_k - 2 tau, u_k = the k-th
+ *                          largest group maximum (strict: never with tau = +inf, a NaN, or fewer than k groups), and r2
+ *                          counts as left behind; every other selected group hands in its 8 rows.  Nothing observable
+ *                          changes: k groups have a maximum >= u_k and the row attaining it is re-scored either way,
+ *                          so the k-th fp64 score s_k >= u_k - tau; a skipped row has an fp32 score <= r2 < u_k - 2 tau,
+ *                          hence an fp64 score < u_k - tau <= s_k -- it is never in the top-k, never ties with its k-th
+ *                          score, cannot fail the certificate (s_k > r2 + tau) and does not move the `lower` the
+ *                          exhaustive round starts from.  Scores, rows and status are those of DLC_SELECT_NO_HINTS.
  *   the exhaustive round   Touches the queries with status 1 only: their lists are replaced and their status becomes
  *                          2; every other query's status, scores and rows are left as they are.  lower_stride = 0
  *                          reads one number for every query.  tau must be >= 0 (NaN is refused), lower_stride >= 0.
