@@ -19,6 +19,7 @@ DLC_MAX_K = 128
 DLC_MAX_STEP = 8             # the largest step of the elastic sequence search (d_max)
 DLC_ABI_VERSION = 20         # include/dlc.h; load() refuses a library built from another header
 DLC_SELECT_COOP, DLC_SELECT_NO_HINTS = 1, 2
+DLC_PRUNE_ON, DLC_PRUNE_OFF, DLC_PRUNE_KEEP = 0, 1, 2     # dlc_set_prune_mode
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
@@ -136,6 +137,8 @@ SIGNATURES = {
     "dlc_set_host_threads": (_int, [_vp, _int]),
     "dlc_set_scratch": (_int, [_vp, _vp, _sz]),
     "dlc_set_profiling": (_int, [_vp, _int]),
+    "dlc_set_prune_mode": (_int, [_vp, _int]),
+    "dlc_cosine_topk_prune_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "dlc_profile_gemm_ms": (_int, [_vp, C.POINTER(_flt), _int]),
 }
 

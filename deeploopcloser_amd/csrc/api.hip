@@ -93,6 +93,15 @@ extern "C" int dlc_set_profiling(dlc_ctx* ctx, int enabled) {
     return DLC_OK;
 }
 
+extern "C" int dlc_set_prune_mode(dlc_ctx* ctx, int mode) {
+    if (!ctx) return DLC_ERR_BAD_ARG;
+    if (mode != DLC_PRUNE_ON && mode != DLC_PRUNE_OFF && mode != DLC_PRUNE_KEEP)
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "set_prune_mode: mode %d", mode);
+    ctx->prune_mode = mode;
+    ctx->prune_kept = 0;
+    return DLC_OK;
+}
+
 extern "C" int dlc_profile_gemm_ms(dlc_ctx* ctx, float* out_ms, int capacity) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!out_ms || capacity < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "profile_gemm_ms: bad output");

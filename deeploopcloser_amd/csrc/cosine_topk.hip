@@ -84,6 +84,50 @@ template <> struct Mfma16<dlc_f16_tag> {
 __device__ __forceinline__ int swz_a(int r) { return ((r >> 1) & 1) | (((r >> 4) & 3) << 1); }
 __device__ __forceinline__ int swz_b(int r) { return (r >> 1) & 7; }
 
+__device__ __forceinline__ unsigned f32_key(float x) {   // monotone: larger float -> larger key
+    unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(unsigned k) {   // inverse of f32_key
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// ---- Pruned epilogue stores (dlc_cosine_topk on the one-pass plan; include/dlc.h, "the pruned score pass").
+// The selection reads gmax and hint only for the kt = min(kg, nh) half tiles with the largest maxima (ties: the lower
+// index), so the score pass keeps, per query, a running lower bound `thr` of the kt-th largest half-tile key and stores
+// the 16 group maxima and the hint of a half tile only when its key reaches the bound it saw.  tmax is always stored.
+//   bkt[PRUNE_NB][q]  uint32 keys, 0 = none: the largest half-tile key seen so far in class ht % PRUNE_NB (atomic max);
+//   thr[q]            uint32 key: a lower bound of the kt-th largest of some snapshot of bkt[*][q] (its top PRUNE_THR_BITS
+//                     bits), 0 while fewer than kt classes are non-zero.
+// (class major: a wave's 16 queries of one half tile post to ONE 64-byte piece in one instruction, and a refreshing lane
+// reads its query's classes in 64 coalesced loads.  Device-scope atomics to one 128-byte line are served one after the
+// other: with bkt[q][class] the first dispatch round queued 256 single posts per line and cost more than the pruning
+// saves, docs/LAB.md 22.)
+// SAFETY.  Every value bkt[b][q] ever holds is 0 or the key of a half tile of class b of THIS launch (both are cleared
+// before the launch), and the classes are disjoint: the kt largest entries of any snapshot -- taken at any time, entry by
+// entry at different times, with stale or lost updates -- are keys of kt DISTINCT half tiles, so the snapshot's kt-th
+// largest is <= the launch's true kt-th largest half-tile key T.  Entries only grow, so every published thr is also <=
+// thr_final, the kt-th largest of the final (order-independent) entries.  The selection takes half tiles with key >= T
+// only; such a half tile passed `key >= thr_seen` whatever thr_seen its workgroup loaded, so its gmax and hint were
+// written.  finish_topk_body is unchanged.  A half tile whose maximum is a NaN always passes.
+// (the finish orders half tiles by `v == -inf ? 0 : f32_key(v)`: half_key below is that key)
+constexpr int PRUNE_NB = 64;                // classes per query = lanes of a wave; a call with kg > PRUNE_NB does not prune
+constexpr int PRUNE_REFRESH_TILES = 17;     // workgroups of every 17th database tile recompute thr (docs/LAB.md 22).  ODD: a
+                                            // tile's XCD is tile % 8, and a multiple of 8 puts every refresh on one XCD
+constexpr int PRUNE_THR_BITS = 20;          // a published threshold is rounded down to its top 20 bits: still a lower bound
+__device__ __forceinline__ unsigned half_key(float h) { return h == -INFINITY ? 0u : f32_key(h); }
+// the kt-th largest (1 <= kt <= 64) of a wave's 64 values, 0 when fewer than kt are non-zero; the same in every lane.
+// (bit by bit from the top: the largest T with at least kt values >= T)
+__device__ __forceinline__ unsigned wave_kth_largest_u32(unsigned v, int kt) {
+    unsigned t = 0u;
+#pragma unroll
+    for (int b = 31; b >= 0; --b) {
+        const unsigned c = t | (1u << b);
+        if (__popcll(__ballot(v >= c)) >= kt) t = c;
+    }
+    return t;
+}
+
 // One entry per (query, half tile), written by the one-pass MFMA score kernel only (WsLayout::hints): about the half tile's
 // best group G* -- the lowest-index group whose maximum is the half tile's -- which row holds that maximum and how high
 // the other seven can score.  finish_topk_body re-scores that one row instead of the group where r2 rules the others out.
@@ -119,6 +163,9 @@ struct GemmArgs {
     int kchunk;
     float* P;           // split-K partial scores [nsplit][q][ldp], ldp = ntiles * 256
     long long ldp;
+    unsigned* bkt;      // [PRUNE_NB, q] / null: GEMM_GROUPS epilogue prunes its gmax / hint stores (see above)
+    unsigned* thr;      // [q]
+    int kt;             // min(kg, nh)
 };
 
 constexpr int GEMM_GROUPS = 0;   // epilogue: group / half-tile maxima (top-k path)
@@ -365,6 +412,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
             }
         }
     } else {
+        // (pruned calls: the threshold this workgroup goes by, one relaxed device-scope load per query -- however stale,
+        // it is a lower bound of the kt-th largest half-tile key)
+        const bool prune = p.bkt != nullptr;
+        unsigned thr_seen[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int qidx = qblk * BNQ + wc * 64 + c * 16 + i;
+            thr_seen[c] = (prune && qidx < p.q) ? __hip_atomic_load(p.thr + qidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int qidx = qblk * BNQ + wc * 64 + c * 16 + i;
@@ -382,18 +438,31 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
                     }
                 hm[th] = fmaxf(m0, m1);
                 gm[th][0] = m0; gm[th][1] = m1;
-                const long long g = tile * (BM / GROUP) + wr * 16 + th * 8 + lg * 2;
-                if (qidx < p.q) {
-                    float* dst = p.gmax + (long long)qidx * p.ldg + g;
-                    if (g + 1 < p.ng) *(float2*)dst = make_float2(m0, m1);
-                    else if (g < p.ng) dst[0] = m0;
-                }
             }
             float h = fmaxf(hm[0], hm[1]);
             h = fmaxf(h, __shfl_xor(h, 16));
             h = fmaxf(h, __shfl_xor(h, 32));
             const long long ht = tile * 2 + wr;
-            if (lg == 0 && qidx < p.q && ht < p.nh) p.tmax[(long long)qidx * p.ldt + ht] = h;
+            const bool live = qidx < p.q && ht < p.nh;
+            const unsigned hk = half_key(h);
+            if (lg == 0 && live) {
+                p.tmax[(long long)qidx * p.ldt + ht] = h;
+                if (prune && hk > thr_seen[c])
+                    __hip_atomic_fetch_max(p.bkt + (long long)(ht % PRUNE_NB) * p.q + qidx, hk, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // the same for the four lg lanes of a query (h and thr_seen are): the shuffles below stay whole
+            const bool pass = !prune || hk >= thr_seen[c] || h != h;
+            if (pass && qidx < p.q) {
+#pragma unroll
+                for (int th = 0; th < 2; ++th) {
+                    const long long g = tile * (BM / GROUP) + wr * 16 + th * 8 + lg * 2;
+                    float* dst = p.gmax + (long long)qidx * p.ldg + g;
+                    if (g + 1 < p.ng) *(float2*)dst = make_float2(gm[th][0], gm[th][1]);
+                    else if (g < p.ng) dst[0] = gm[th][0];
+                }
+            }
+            if (__ballot(pass && live) == 0ull) continue;    // wave-uniform: no lane of this column has a hint to store
             // ---- the half tile's hint (HintEntry).  This lane's groups are G = th * 8 + lg * 2 + j of the half tile; the
             // lowest one attaining h, min-reduced over the four lg lanes of the query, is G*, and the lane that holds it
             // looks at its 8 scores: a* = the lowest row attaining h, r2 = the largest of the other seven (a running top-2:
@@ -427,11 +496,34 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
             for (int r = GROUP - 2; r >= 0; --r) astar = v[r] == h ? r : astar;
             const bool none = rank == 16;
             const bool owner = none ? lg == 0 : ((rank >> 1) & 3) == lg;
-            if (owner && qidx < p.q && ht < p.nh) {
+            if (owner && pass && live) {
                 HintEntry e;
                 e.r2 = none ? INFINITY : second;
                 e.id = none ? 0 : ((rank << 3) | astar);
                 p.hint[(long long)ht * p.q + qidx] = e;      // 16 lanes x 8 B in a row: whole 128-byte pieces
+            }
+        }
+        // ---- refresh: the workgroups of every PRUNE_REFRESH_TILES-th tile recompute the threshold of their query block's
+        // queries: a lane takes a query, its 64 classes in registers, and finds the kt-th largest bit by bit from the top
+        // (the largest T with at least kt classes >= T; 0 when fewer than kt are filled).  Published with an atomic max:
+        // thr only rises, and stays <= thr_final.
+        if (prune && tile % PRUNE_REFRESH_TILES == 0) {
+            const int qidx = qblk * BNQ + wid * 64 + lane;
+            if (wid < BNQ / 64 && qidx < p.q) {
+                unsigned v[PRUNE_NB];
+#pragma unroll
+                for (int cl = 0; cl < PRUNE_NB; ++cl)
+                    v[cl] = __hip_atomic_load(p.bkt + (long long)cl * p.q + qidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                unsigned t = 0u;
+#pragma unroll 1
+                for (int b = 31; b >= 32 - PRUNE_THR_BITS; --b) {
+                    const unsigned cand = t | (1u << b);
+                    int cnt = 0;
+#pragma unroll
+                    for (int cl = 0; cl < PRUNE_NB; ++cl) cnt += v[cl] >= cand ? 1 : 0;
+                    if (cnt >= p.kt) t = cand;
+                }
+                if (t != 0u) __hip_atomic_fetch_max(p.thr + qidx, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -546,13 +638,7 @@ __global__ __launch_bounds__(256) void score_gemv_kernel(GemmArgs p) {
 // the largest fp32 score any row outside the candidate set can have; otherwise the exhaustive pass re-scores
 // every group that could still hold a top-k row.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned f32_key(float x) {   // monotone: larger float -> larger key
-    unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(unsigned k) {   // inverse of f32_key
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+// (f32_key / key_f32, the ordering key of an fp32 score: in front of the score kernel, whose epilogue prunes by it)
 __device__ __forceinline__ unsigned long long pack_key(float score, unsigned id) {
     return ((unsigned long long)f32_key(score) << 32) | (unsigned long long)(~id);
 }
@@ -575,6 +661,7 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 }
 
 constexpr int FIN_THREADS = 512;            // merge / exhaustive workgroup; finish workgroup of the stand-alone variant
+constexpr size_t FIN_TV_LDS_MAX = 96 * 1024; // a query's half-tile maxima are staged in LDS up to this many bytes
 // finish kernel LDS carve (bytes) for kg selected groups:
 //   ckey u64 [kg*16] | ck64 i64 [kg*8] | cs64 f64 [kg*8] | crow i32 [kg*8] | sel i32 [kg+1] | sel2 i32 [kg+1] | misc 64 B
 __host__ __device__ inline size_t fin_lds_fixed(int kg) {
@@ -1234,6 +1321,10 @@ struct ExhaustiveArgs {
     double tau;
     const float* tau_scale;                                  // as in FinishArgs
     int limited; long long limit0;                           // as in FinishArgs
+    // a pruned score pass (dlc_cosine_topk): gmax holds the groups of the half tiles with key >= thr_final only
+    const float* tmax; long long ldt;                        // [q, ldt] half-tile maxima (always whole)
+    const unsigned* bkt; unsigned* thr; int kt; long long nq; // the prune state of the call ([64, nq], [nq]); bkt null = gmax is whole
+    int publish;                                             // keep mode: the kernel stores thr_final into thr[q]
 };
 constexpr int EXH_BATCH = 64;                               // groups per re-score batch
 constexpr int EXH_POOL = EXH_BATCH * GROUP + DLC_MAX_K;     // running top-k in front of the batch's rows
@@ -1254,11 +1345,30 @@ __device__ __forceinline__ void exhaustive_topk_body(const ExhaustiveArgs& a, do
     const long long ng_vis = a.limited ? (n_vis + GROUP - 1) / GROUP : a.ng;
     const double tau = scaled_tau(a.tau, a.tau_scale, qi);
     double theta = lower - tau;                                          // -inf - tau = -inf: everything qualifies
+    // Behind a pruned score pass a group qualifies by its HALF TILE first: below theta by tmax -> out (every group maximum
+    // of the half tile is <= tmax, so none of them qualified either); key(tmax) >= thr_final -> the score pass wrote its
+    // group maxima (thr_final, the kt-th largest of the final bkt entries, is >= every threshold the pass went by; the
+    // entries are maxima, so it does not depend on the order of the launch), qualify per group as ever; any other half
+    // tile -> all 16 groups.  Qualifying MORE groups changes nothing: the result is the k best of the rows looked at by
+    // (fp64 key descending, row index ascending), every row that belongs to it is in a group that qualified before, and
+    // the extra rows are real rows with their exact scores -- theta still only rises towards the true k-th score - tau.
+    const unsigned thr_final = a.bkt ? wave_kth_largest_u32(a.bkt[(long long)lane * a.nq + qi], a.kt) : 0u;
     int cnt = 0;                                                         // rows in the running top-k (pool[0 .. cnt))
     const char* qrow = a.Q + (long long)qi * a.ldq_b;
     for (long long c0 = 0; c0 < ng_vis; c0 += FIN_THREADS) {
         const long long g = c0 + tid;
-        const bool qual = g < ng_vis && (double)a.gmax[(long long)qi * a.ldg + g] >= theta;
+        bool qual = false;
+        if (g < ng_vis) {
+            if (a.bkt) {
+                const float tm = a.tmax[(long long)qi * a.ldt + g / GROUPS_PER_HALF];
+                if (!((double)tm < theta)) {
+                    const bool written = half_key(tm) >= thr_final || tm != tm;
+                    qual = !written || (double)a.gmax[(long long)qi * a.ldg + g] >= theta;
+                }
+            } else {
+                qual = (double)a.gmax[(long long)qi * a.ldg + g] >= theta;
+            }
+        }
         const unsigned long long bal = __ballot(qual);
         if (lane == 0) wcnt[w] = __popcll(bal);
         __syncthreads();
@@ -1320,6 +1430,10 @@ __device__ __forceinline__ void exhaustive_topk_body(const ExhaustiveArgs& a, do
 template <typename Tag>
 __global__ __launch_bounds__(FIN_THREADS) void exhaustive_topk_kernel(ExhaustiveArgs a) {
     const int qi = blockIdx.x;
+    if (a.publish && threadIdx.x < 64) {                     // (keep mode: the next call starts from this call's thr_final)
+        const unsigned t = wave_kth_largest_u32(a.bkt[(long long)threadIdx.x * a.nq + qi], a.kt);
+        if (threadIdx.x == 0) a.thr[qi] = t;
+    }
     if (a.status[qi] != 1) return;
     exhaustive_topk_body<Tag>(a, a.lower[(long long)qi * a.lower_stride]);
 }
@@ -1528,7 +1642,7 @@ __device__ __forceinline__ void small_topk_body(const SmallArgs& a) {
         return;
     }
     __syncthreads();                                           // the group maxima and the lists above are written; LDS is re-used
-    ExhaustiveArgs e;
+    ExhaustiveArgs e{};
     e.gmax = a.gmax; e.ldg = a.ldg; e.ng = ng_all;
     e.Q = a.Q; e.ldq_b = a.ldq_b; e.DB = a.DB; e.lddb_b = a.lddb_b;
     e.n = a.n; e.d = a.d; e.k = k; e.row_offset = a.row_offset;
@@ -1862,6 +1976,8 @@ SplitPlan split_plan(int64_t q, int64_t n, int64_t d) {
 
 struct WsLayout {
     size_t gmax, tmax, hint, part, status, s64, rs_ids, rs_max, rs_scores, rs_idx, rs_bound, total;
+    size_t prune, prune_total;   // the prune state (bkt [PRUNE_NB][q] then thr [q], one memset) BEHIND `total`: optional room
+    bool prunable;               // dlc_cosine_topk may prune the score pass's stores on this plan (set by ws_layout)
     long long ldg, ldt, ldp;
     int kg;
     SplitPlan sp;
@@ -1946,6 +2062,13 @@ WsLayout ws_layout(int64_t q, int64_t n, int64_t d, int k) {
         w.rs_bound = o; o += dlc::align_up((size_t)q * 4, 256);
     }
     w.total = o;
+    // The pruned score pass: where the hints are written (the one-pass MFMA plan), kg fits the classes, one workgroup per
+    // query re-scores (the spread re-score keeps the whole arrays), and the finish does not consume the tmax row in
+    // place (the exhaustive pass qualifies half tiles by it).
+    w.prunable = w.hints && w.kg <= PRUNE_NB && w.rparts <= 1 && (size_t)dlc::cdiv(n, (int64_t)HALF) * 4 <= FIN_TV_LDS_MAX;
+    w.prune = o;
+    if (w.prunable) o += dlc::align_up((size_t)q * (PRUNE_NB + 1) * 4, 256);
+    w.prune_total = o;
     return w;
 }
 
@@ -2068,11 +2191,18 @@ extern "C" size_t dlc_cosine_topk_workspace_bytes(int64_t q, int64_t n, int64_t 
     return ws_layout(q, n, d, k).total;
 }
 
+extern "C" size_t dlc_cosine_topk_prune_bytes(int64_t q, int64_t n, int64_t d, int k) {
+    if (q < 1 || n < 1 || d < BK || k < 1 || k > DLC_MAX_K) return 0;
+    const WsLayout w = ws_layout(q, n, d, k);
+    return w.prune_total - w.total;
+}
+
 namespace {
 
 struct MatchCall {
     GemmArgs a;
     WsLayout w;
+    bool publish_thr = false;    // a pruned call in keep mode: the exhaustive launch stores thr_final
 };
 
 int prepare_match(dlc_ctx* ctx, const char* what, int dtype, const void* Q, int64_t q, int64_t ldq, const void* DB,
@@ -2096,6 +2226,7 @@ int prepare_match(dlc_ctx* ctx, const char* what, int dtype, const void* Q, int6
     a.S = nullptr; a.lds = 0;
     a.nsplit = mc->w.sp.nsplit; a.kchunk = mc->w.sp.kchunk;
     a.P = (float*)(ws + mc->w.part); a.ldp = mc->w.ldp;
+    a.bkt = nullptr; a.thr = nullptr; a.kt = 0;               // only dlc_cosine_topk prunes (arm_prune)
     return DLC_OK;
 }
 
@@ -2128,7 +2259,7 @@ FinishArgs finish_args(const MatchCall& mc, int k, int64_t n, int64_t d, int64_t
 template <typename Tag, int THREADS, int RS_UNROLL, int MODE>
 int launch_finish(dlc_ctx* ctx, FinishArgs f, int64_t q, bool small_lds, hipStream_t st) {
     size_t dsm = fin_lds_fixed(f.kg);
-    f.tv_in_lds = MODE != FIN_RESCORE && !small_lds && (size_t)f.nh * 4 <= 96 * 1024;
+    f.tv_in_lds = MODE != FIN_RESCORE && !small_lds && (size_t)f.nh * 4 <= FIN_TV_LDS_MAX;
     if (f.tv_in_lds) dsm += (size_t)f.nh * 4;
     dsm = dlc::align_up(dsm, 16);
     void (*fk)(FinishArgs);
@@ -2154,8 +2285,13 @@ int run_select(dlc_ctx* ctx, int dtype, const FinishArgs& f, int64_t q, int flag
 
 // The exhaustive pass behind a certifying kernel: every workgroup whose query is certified leaves at once.
 int run_exhaustive(dlc_ctx* ctx, int dtype, const FinishArgs& f, int64_t q, const double* lower, int64_t lower_stride,
-                   float* out_s, double* out_s64, int64_t* out_i, int* status, hipStream_t st) {
+                   float* out_s, double* out_s64, int64_t* out_i, int* status, hipStream_t st,
+                   const MatchCall* pruned = nullptr) {
     ExhaustiveArgs e{};
+    if (pruned && pruned->a.bkt) {
+        e.tmax = f.tmax; e.ldt = f.ldt;
+        e.bkt = pruned->a.bkt; e.thr = pruned->a.thr; e.kt = pruned->a.kt; e.nq = pruned->a.q; e.publish = pruned->publish_thr ? 1 : 0;
+    }
     e.gmax = f.gmax; e.ldg = f.ldg; e.ng = f.ng;
     e.Q = f.Q; e.ldq_b = f.ldq_b; e.DB = f.DB; e.lddb_b = f.lddb_b;
     e.n = f.n; e.d = f.d; e.k = f.k; e.row_offset = f.row_offset;
@@ -2234,10 +2370,32 @@ int run_finish(dlc_ctx* ctx, int dtype, const MatchCall& mc, int k, int64_t n, i
         if (rc != DLC_OK) return rc;
     }
     if (direct) return DLC_OK;                                  // small_topk_kernel runs the exhaustive pass of its own queries
-    return run_exhaustive(ctx, dtype, f, q, s64 + (k - 1), k, out_scores, s64, out_idx, status, st);
+    return run_exhaustive(ctx, dtype, f, q, s64 + (k - 1), k, out_scores, s64, out_idx, status, st, &mc);
 }
 
 }  // namespace
+
+// dlc_cosine_topk on a prunable plan with the room behind the workspace: point the score pass at the prune state and
+// clear it on the stream.  Keep mode (tests) clears only the first call of a run of identical calls.
+int arm_prune(dlc_ctx* ctx, MatchCall& mc, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (ctx->prune_mode == DLC_PRUNE_OFF || !mc.w.prunable || workspace_bytes < mc.w.prune_total) return DLC_OK;
+    GemmArgs& a = mc.a;
+    a.bkt = (unsigned*)((char*)workspace + mc.w.prune);
+    a.thr = a.bkt + (size_t)a.q * PRUNE_NB;
+    a.kt = (int)std::min<long long>(mc.w.kg, a.nh);
+    bool clear = true;
+    if (ctx->prune_mode == DLC_PRUNE_KEEP) {
+        const void* id[3] = {workspace, a.Q, a.DB};
+        const long long shape[4] = {a.q, a.n, a.nk, mc.w.kg};
+        clear = !ctx->prune_kept || memcmp(id, ctx->prune_id, sizeof(id)) != 0 || memcmp(shape, ctx->prune_shape, sizeof(shape)) != 0;
+        memcpy(ctx->prune_id, id, sizeof(id));
+        memcpy(ctx->prune_shape, shape, sizeof(shape));
+        ctx->prune_kept = 1;
+        mc.publish_thr = true;
+    }
+    if (clear) DLC_HIP_CHECK(ctx, hipMemsetAsync(a.bkt, 0, (size_t)a.q * (PRUNE_NB + 1) * 4, st));
+    return DLC_OK;
+}
 
 extern "C" double dlc_cosine_score_error_bound(int64_t q, int64_t n, int64_t d, int k) {
     if (q < 1 || n < 1 || d < BK || k < 1 || k > DLC_MAX_K) return 0.0;
@@ -2256,6 +2414,8 @@ extern "C" int dlc_cosine_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     const bool direct = small_direct(mc, k);
+    rc = arm_prune(ctx, mc, workspace, workspace_bytes, (hipStream_t)stream);
+    if (rc != DLC_OK) return rc;
     rc = run_score(ctx, dtype, mc, (hipStream_t)stream, direct);
     if (rc != DLC_OK) return rc;
     return run_finish(ctx, dtype, mc, k, n, d, q, row_offset, out_scores, out_scores_f64, out_idx, out_status, workspace, 0,

@@ -29,6 +29,10 @@ struct dlc_ctx {
     int host_threads;                           // host copy threads of the staging (0 = min(16, hardware threads))
     unsigned long long* host_flag;              // 64 page-locked bytes: the one word dlc_sdav_similarity_matrix reads back
     hipEvent_t ev_flag;                         // ... and the event behind its copy
+    int prune_mode;                             // DLC_PRUNE_* (dlc_set_prune_mode): dlc_cosine_topk's pruned score pass
+    int prune_kept;                             // keep mode: the state below belongs to the last pruned call
+    const void* prune_id[3];                    // ... its workspace, queries and database
+    long long prune_shape[4];                   // ... and q, n, d / 64, kg
 };
 
 // ids of the kernels that need hipFuncAttributeMaxDynamicSharedMemorySize (bits of dlc_ctx::func_attr_set)

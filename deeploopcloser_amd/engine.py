@@ -1338,6 +1338,8 @@ class Engine:
         need = self.lib.dlc_cosine_topk_workspace_bytes(nq, n, d, k)
         if need == 0:
             raise ValueError("match_topk: k=%d outside 1..%d (or empty operand)" % (k, L.DLC_MAX_K))
+        if older_than is None:
+            need += self.lib.dlc_cosine_topk_prune_bytes(nq, n, d, k)      # room for the pruned score pass's state (dlc.h)
         ws = self.workspace("topk", need)
         if out is None:
             scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
@@ -1581,6 +1583,12 @@ class Engine:
     # ---- profiling hooks for bench.py ---------------------------------------------------
     def set_profiling(self, enabled):
         self._check(self.lib.dlc_set_profiling(self.ctx, 1 if enabled else 0))
+
+    def set_prune_mode(self, mode):
+        """dlc_set_prune_mode: "on" (default), "off" (match_topk's score pass writes every group maximum and hint) or
+        "keep" (tests: a repeated identical match_topk starts from its own final threshold; include/dlc.h)."""
+        self._check(self.lib.dlc_set_prune_mode(self.ctx, {"on": L.DLC_PRUNE_ON, "off": L.DLC_PRUNE_OFF,
+                                                           "keep": L.DLC_PRUNE_KEEP}[mode]))
 
     def profile_gemm_ms(self, capacity=256):
         """Durations (ms) of the last product-kernel launches (score GEMM, dense and Gram GEMMs;

@@ -902,6 +902,46 @@ int dlc_l2_normalize_rows(dlc_ctx* ctx, int src_dtype, const void* src, int64_t 
  */
 #define DLC_MAX_K 128
 size_t dlc_cosine_topk_workspace_bytes(int64_t q, int64_t n, int64_t d, int k);
+/*
+ * The pruned score pass (dlc_cosine_topk only).  The selection reads the group maxima and the half-tile hints (below)
+ * of the kt = min(kg, half tiles) half tiles of 128 rows with the largest maxima only, so on the one-pass MFMA plan the
+ * score pass of dlc_cosine_topk does not store the rest: per query it keeps a running lower bound of the kt-th largest
+ * half-tile maximum and writes a half tile's 16 group maxima and its hint only where the half tile's maximum reaches
+ * the bound.  The half-tile maxima themselves are always written.  The state -- per query 64 uint32 score keys
+ * bkt[64][q] (class major: the largest half-tile key seen in class `half tile % 64`, 0 = none) and one uint32 threshold thr[q] --
+ * sits BEHIND the workspace: dlc_cosine_topk_prune_bytes(q, n, d, k) is that room (0 where the plan does not prune), and
+ * a call prunes when its workspace holds dlc_cosine_topk_workspace_bytes + dlc_cosine_topk_prune_bytes bytes; with less
+ * it writes everything, as every other entry point does.  ABI: callers ask both functions, never compute the sizes;
+ * no array of the workspace moved.  The state is cleared on the stream before the score pass of every pruned call.
+ *   It prunes when   the plan writes the hints (one pass, not the <= 16384-row plan, more than 4 queries), kg = k + 4 <= 64,
+ *                    the re-score is not spread over several workgroups per query, and the shard has at most 24576 half
+ *                    tiles (3.1 M rows: beyond that the selection consumes the half-tile maxima in place).
+ *   Why it is safe   Every value bkt[b][q] ever holds is 0 or the key of a half tile of class b of this call, and classes
+ *                    are disjoint, so the kt-th largest of ANY snapshot of bkt[*][q] -- at any time, under any
+ *                    interleaving, with stale or lost updates -- is at most the call's true kt-th largest half-tile key.
+ *                    thr[q] only ever holds such a value rounded down to its top 20 bits (0 while fewer than kt classes are filled).  The selection
+ *                    takes half tiles at or above the true kt-th key only (ties by index), and such a half tile passes
+ *                    `key >= thr` whatever value of thr its workgroup saw: everything the selection reads was written.
+ *   The exhaustive   pass behind a pruned call computes thr_final, the kt-th largest of the final bkt[*][q] (a function of
+ *   pass             the half-tile maxima alone, >= every threshold the score pass went by), skips a half tile whose
+ *                    maximum is below its bound, goes by the group maxima where key(half-tile maximum) >= thr_final
+ *                    (they were written) and takes all 16 groups of any other half tile.  More groups, the same
+ *                    result: the exact top-k by (fp64 key descending, row ascending) over rows that include every row
+ *                    that can belong to it.
+ * Scores, rows and status are bit for bit those of the unpruned call.  dlc_set_prune_mode (one setting per context):
+ *   DLC_PRUNE_ON    the default.
+ *   DLC_PRUNE_OFF   dlc_cosine_topk writes everything, exactly as before the pruned pass existed.
+ *   DLC_PRUNE_KEEP  for tests: the state is cleared only on the first of a run of calls with the same workspace, Q, DB
+ *                   and shape, and every call leaves thr = thr_final behind.  A repeated call then starts from its own
+ *                   final threshold and writes exactly what pruning can never drop -- the extreme of the protocol,
+ *                   deterministic at any size.  The caller must not change the contents of Q or DB inside such a run.
+ *                   Setting any mode ends the run.
+ */
+#define DLC_PRUNE_ON 0
+#define DLC_PRUNE_OFF 1
+#define DLC_PRUNE_KEEP 2
+size_t dlc_cosine_topk_prune_bytes(int64_t q, int64_t n, int64_t d, int k);
+int dlc_set_prune_mode(dlc_ctx* ctx, int mode);
 int dlc_cosine_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t ldq,
                     const void* DB, int64_t n, int64_t lddb, int64_t d, int k, int64_t row_offset,
                     float* out_scores, double* out_scores_f64, int64_t* out_idx, int32_t* out_status,
