@@ -106,6 +106,12 @@ SIGNATURES = {
     "dlc_peak_topk_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_peak_topk_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _i64, _int, _i64, _int, _vp, _vp, _vp,
                                   _vp, _sz, _vp]),
+    "dlc_pr_cell_counts_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "dlc_pr_cell_counts": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _int, _vp, _vp,
+                                  _vp, _sz, _vp]),
+    "dlc_positive_rank_rows_workspace_bytes": (_sz, [_i64, _i64]),
+    "dlc_positive_rank_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _vp, _vp,
+                                      _vp, _sz, _vp]),
     "dlc_l2_normalize_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp]),
     "dlc_cosine_topk_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "dlc_cosine_topk": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

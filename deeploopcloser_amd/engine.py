@@ -1245,6 +1245,87 @@ class Engine:
             k, _ptr(o_s), _ptr(o_i), _ptr(poison), _ptr(ws), ws.numel(), self._stream()))
         return o_s, o_i
 
+    def _truth_mask(self, who, truth, rows, n):
+        """The checks of a truth mask [rows, >= n] (uint8 or bool on the device; non-zero = a true match) -> (truth, ld):
+        a row-strided view is taken as it is, anything else made contiguous."""
+        if not isinstance(truth, torch.Tensor) or truth.dim() != 2 or truth.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("%s: truth must be a 2-D uint8 or bool tensor" % who)
+        if truth.device != self.device:
+            raise ValueError("%s: truth must be on %s" % (who, self.device))
+        if truth.shape[0] != rows or truth.shape[1] < n:
+            raise ValueError("%s: truth [%d, %d] does not cover scores [%d, %d]" % (who, truth.shape[0], truth.shape[1], rows, n))
+        if truth.dtype == torch.bool:
+            truth = truth.view(torch.uint8)
+        if truth.stride(1) != 1 or (rows > 1 and truth.stride(0) < n):
+            truth = truth.contiguous()
+        return truth, truth.stride(0) if rows > 1 else max(n, truth.stride(0))
+
+    def sorted_thresholds(self, thresholds, is_int):
+        """The threshold table pr_cell_counts hands to the library, on the device: the numbers of `thresholds` (a sequence
+        or a tensor) ascending and distinct in the order of dlc.h -- -0.0 below +0.0, two thresholds -- as float64, or as
+        int64 for int64 rows (which take integers only).  A NaN, no threshold or more than 4096 distinct ones: ValueError."""
+        t = thresholds if isinstance(thresholds, torch.Tensor) else torch.as_tensor(np.asarray(thresholds))
+        if is_int and (t.is_floating_point() or t.dtype == torch.bool):
+            raise ValueError("pr_cell_counts: int64 rows take integer thresholds")
+        t = t.reshape(-1).to(device=self.device, dtype=torch.int64 if is_int else torch.float64)
+        if not is_int:
+            if bool(t.isnan().any()):
+                raise ValueError("pr_cell_counts: a threshold is NaN")
+            # the bits of a double as a signed integer, the magnitude of the negatives flipped: ordered as the numbers
+            # are, the two zeros apart; the flip is its own inverse
+            flip = lambda b: torch.where(b < 0, b ^ 0x7FFFFFFFFFFFFFFF, b)
+            t = flip(torch.unique(flip(t.view(torch.int64)))).view(torch.float64)
+        else:
+            t = torch.unique(t)
+        if not 1 <= t.numel() <= 4096:
+            raise ValueError("pr_cell_counts: %d distinct thresholds outside 1..4096" % t.numel())
+        return t.contiguous()
+
+    def pr_cell_counts(self, scores, truth, thresholds, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None):
+        """(pos [T + 1], neg [T + 1]) int64: the cell-level decisions behind a precision-recall curve, dlc_pr_cell_counts
+        (include/dlc.h).  Every cell row r of scores [rows, >= n] offers (its first clamp(limit0 + r * limit_step, 0, n),
+        limit0 None = n; never a NaN, nor `absent` in int64 rows) falls into the bin #{i : t_i <= x} (#{i : t_i < x} with
+        lower_is_better) of the thresholds and is counted there as a positive (truth [rows, >= n] non-zero) or a negative.
+        thresholds: any sequence or tensor of numbers; they are sorted and de-duplicated here (T = what is left, 1..4096),
+        a NaN is refused."""
+        scores, rows, n, ld = self._score_matrix("pr_cell_counts", scores, n, "count")
+        truth, ldt = self._truth_mask("pr_cell_counts", truth, rows, n)
+        is_int = scores.dtype == torch.int64
+        if absent is not None and not is_int:
+            raise ValueError("pr_cell_counts: absent is for int64 rows (a float row marks absence with NaN)")
+        t = self.sorted_thresholds(thresholds, is_int)
+        pos = torch.empty(t.numel() + 1, dtype=torch.int64, device=self.device)
+        neg = torch.empty(t.numel() + 1, dtype=torch.int64, device=self.device)
+        need = self.lib.dlc_pr_cell_counts_workspace_bytes(rows, n, t.numel())
+        if need == 0:
+            raise ValueError("pr_cell_counts: rows=%d, n=%d outside the supported sizes" % (rows, n))
+        ws = self.workspace("pr_cell_counts", need)
+        self._check(self.lib.dlc_pr_cell_counts(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(bool(lower_is_better)), int(absent is not None), 0 if absent is None else int(absent),
+            _ptr(truth), ldt, _ptr(t), t.numel(), _ptr(pos), _ptr(neg), _ptr(ws), ws.numel(), self._stream()))
+        return pos, neg
+
+    def positive_rank_rows(self, scores, truth, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None):
+        """(rank [rows], idx [rows], npos [rows]) int64: the retrieval protocol, dlc_positive_rank_rows (include/dlc.h).
+        Per row of scores [rows, >= n]: idx = the best offered cell that truth [rows, >= n] marks (ties -> the lower
+        column), rank = the number of offered cells that beat it (its slot in the row's top-k list), npos = the number of
+        offered marked cells; (-1, -1, 0) for a row without one.  Offered as in peak_topk_rows."""
+        scores, rows, n, ld = self._score_matrix("positive_rank_rows", scores, n, "rank")
+        truth, ldt = self._truth_mask("positive_rank_rows", truth, rows, n)
+        if absent is not None and scores.dtype != torch.int64:
+            raise ValueError("positive_rank_rows: absent is for int64 rows (a float row marks absence with NaN)")
+        rank, idx, npos = (torch.empty(rows, dtype=torch.int64, device=self.device) for _ in range(3))
+        need = self.lib.dlc_positive_rank_rows_workspace_bytes(rows, n)
+        if need == 0:
+            raise ValueError("positive_rank_rows: rows=%d, n=%d outside the supported sizes" % (rows, n))
+        ws = self.workspace("positive_rank_rows", need)
+        self._check(self.lib.dlc_positive_rank_rows(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
+            int(limit_step), int(bool(lower_is_better)), int(absent is not None), 0 if absent is None else int(absent),
+            _ptr(truth), ldt, _ptr(rank), _ptr(idx), _ptr(npos), _ptr(ws), ws.numel(), self._stream()))
+        return rank, idx, npos
+
     # ---- cosine + top-k -----------------------------------------------------------------
     @staticmethod
     def stored_width(d):

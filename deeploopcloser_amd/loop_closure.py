@@ -17,6 +17,11 @@ With --sequence L --chains every candidate line is followed by one line `chain<T
 the candidate was matched along, oldest frame first (the detectors' chains=True; dlc_sequence_chains /
 dlc_sequence_elastic_chains, include/dlc.h).
 
+With --positions FILE --radius R (one line of one or two integers per frame: where it was taken) the run is judged
+against ground truth: after the stream one line `pr<TAB>queries<TAB>..<TAB>loops<TAB>..<TAB>ap<TAB>..<TAB>recall_at_p1
+<TAB>..<TAB>best_f1<TAB>..<TAB>threshold<TAB>..` on stderr (evaluate.LoopClosureEvaluator over the best candidate of
+every frame), and with --pr-curve OUT.tsv the whole curve.  stdout is unchanged.
+
 Batching never changes a result: a batch of B frames is matched in one call against the longest
 prefix any of its frames may see, each frame keeping to the key-frames old enough for IT inside the
 selection (dlc_cosine_topk_older).  The same lists come from a match with k+B-1 candidates per frame
@@ -798,6 +803,15 @@ def main(argv=None):
                          "SDAV / CnnVtl on the fp16 matrix cores (--dtype is the cosine database's storage type)")
     ap.add_argument("--no-latency-mode", action="store_true",
                     help="keep the one-pass GEMMs (bit-identical to a large-batch encode) for small batches too")
+    ap.add_argument("--positions", default=None, metavar="FILE",
+                    help="ground truth: a text file with one line per frame, in the order of the sorted files, of one or two "
+                         "integers (a distance along the route or a frame index, or x and y); after the stream one line "
+                         "`pr` on stderr: average precision, recall at 100 %% precision and the best F1 of the best "
+                         "candidate per frame over every threshold (needs --radius)")
+    ap.add_argument("--radius", type=int, default=None, metavar="R",
+                    help="with --positions: a key-frame within R of a frame's position is the same place")
+    ap.add_argument("--pr-curve", default=None, metavar="OUT.tsv",
+                    help="with --positions: write the curve there -- threshold, tp, fp, precision, recall; strictest first")
     args = ap.parse_args(argv)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
@@ -847,7 +861,22 @@ def main(argv=None):
     if args.threshold is None:
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
+    if args.positions is None and (args.radius is not None or args.pr_curve is not None):
+        ap.error("--radius and --pr-curve need --positions")
+    if args.positions is not None and args.radius is None:
+        ap.error("--positions needs --radius")
+    if args.radius is not None and args.radius < 0:
+        ap.error("--radius must be >= 0")
+
     files = _frame_files(args.dataset_path, args.pattern)
+    if args.positions is not None:
+        from .evaluate import read_positions
+        try:
+            args.positions = read_positions(args.positions)
+        except (OSError, ValueError) as err:
+            ap.error("--positions: %s" % err)
+        if len(args.positions) != len(files):
+            ap.error("--positions: %d lines for %d frames" % (len(args.positions), len(files)))
     from .engine import default_engine
     eng = default_engine()
     latency = args.batch <= 16 and not args.no_latency_mode      # split-K encode GEMMs: ~8x lower latency per frame
@@ -876,6 +905,11 @@ def _stream(args, files):
         if args.weights:
             net.load_alexnet_npy(args.weights)
         describe = lambda fs: describe_cnn_vtl(fs, net, as_int8=args.metric == "distance")
+    judge = None
+    if args.positions is not None:
+        from .evaluate import LoopClosureEvaluator, pr_line
+        judge = LoopClosureEvaluator(args.positions, args.radius, args.exclusion,
+                                     lower_is_better=args.metric in ("distance", "sad"))
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
@@ -905,6 +939,8 @@ def _stream(args, files):
         s, i, *chain = det.query_and_insert(desc)
         found = det.loops(s, i, lo, *chain)                      # (the one host read of the step)
         lat.append(((time.perf_counter() - t0) * 1e3, len(chunk)))
+        if judge is not None:
+            judge.add(s, i, lo)                                  # (every candidate, whatever the reporting threshold)
         for frame, match, score, *pairs in found:
             print(("loop\t%d\t%s\t%d\t%s\t" + ("%d" if isinstance(score, int) else "%.4f"))
                   % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
@@ -917,6 +953,14 @@ def _stream(args, files):
     per_frame = float(ms.sum() / max(1, sum(c for _, c in steady)))
     print("latency\tbatch\t%d\tsteps\t%d\tfirst_step_ms\t%.2f\tms_per_step_median\t%.3f\tms_per_step_max\t%.3f\tms_per_frame\t%.3f"
           % (args.batch, len(lat), lat[0][0], float(np.median(ms)), float(ms.max()), per_frame), file=sys.stderr)
+    if judge is not None:
+        curve, _ = judge.result()
+        print(pr_line(judge.queries, curve), file=sys.stderr)
+        if args.pr_curve is not None:
+            with open(args.pr_curve, "w") as f:
+                f.write("threshold\ttp\tfp\tprecision\trecall\n")
+                for t, tp, fp, p, r in curve.rows():
+                    f.write(("%d" if isinstance(t, int) else "%.17g") % t + "\t%d\t%d\t%.6f\t%.6f\n" % (tp, fp, p, r))
     return 0
 
 

@@ -830,6 +830,72 @@ int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */
                        void* out_scores, int64_t* out_idx, const int64_t* poison,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Ground-truth evaluation of score rows: the last stage of the pipeline.  Given the rows a detector ranks by and a mask
+ * of the cells that are true matches, dlc_pr_cell_counts counts the decisions behind a precision-recall curve and
+ * dlc_positive_rank_rows the ranks behind recall@K.  Everything is integer counting: every result is exact and does not
+ * depend on the grid, the batching or the plan.
+ * INPUT (both calls).  M = scores [rows, ld], n <= ld columns in use, dtype DLC_F64, DLC_F32 or DLC_I64, exactly as
+ * dlc_peak_topk_rows takes them.  truth [rows, ld_truth] bytes, ld_truth >= n, any alignment: a non-zero byte marks the
+ * cell (r, j) as a true match, a POSITIVE; every other cell is a NEGATIVE.
+ * OFFERED CELLS.  Row r offers the cells j < lim(r) = clamp(limit0 + r * limit_step, 0, n) (any limit_step, negative
+ * included) that are present: for DLC_F64 / DLC_F32 a NaN is never offered (+inf and -inf are ordinary values); for
+ * DLC_I64 a cell equal to `absent` is not offered when has_absent != 0.  has_absent != 0 with a float dtype is
+ * DLC_ERR_BAD_ARG.
+ * ORDER.  The order of the numbers, -0.0 below +0.0: for the float dtypes the unsigned order of the ordered key of the
+ * fp64 value (an fp32 cell converts exactly), for DLC_I64 the order of the integers.  The ORDER OF MERIT is that order
+ * descending, or ascending with lower_is_better; ties -> the lower j.
+ * READS.  No cell at or past lim(r) and no column n .. ld-1 (n .. ld_truth-1), of the scores or of the truth, is read or
+ * has any influence.  Rows of scores need only their element's alignment (8 bytes, 4 for DLC_F32).  Any rows >= 1,
+ * 1 <= n < 2^31.  The outputs and the workspace must not overlap the inputs or each other.  Neither call synchronises.
+ *
+ * dlc_pr_cell_counts -- the cell-level protocol: every offered cell is a decision.
+ * thresholds: n_thresholds = T values t_0 .. t_{T-1} on the DEVICE, 1 <= T <= 4096, fp64 for the float dtypes and int64
+ * for DLC_I64, ASCENDING in the order of the numbers (for either sense of lower_is_better).  The BIN of an offered cell x is
+ *     b(x) = #{i : t_i <= x}           (with lower_is_better: b(x) = #{i : t_i < x}),
+ * comparisons in the order above, so that a detector run at threshold t_i reports exactly the cells
+ *     x >= t_i  <=>  b(x) > i          (with lower_is_better: x <= t_i  <=>  b(x) <= i).
+ * OUTPUT.  out_pos [T + 1], out_neg [T + 1] int64: the number of offered positive / negative cells in each bin.  Both are
+ * fully written (the caller need not clear them); when every lim(r) is 0 they are all zero and the call returns DLC_OK.
+ * The true positives at t_i are the sum of out_pos over the bins above i (with lower_is_better: up to i), the false
+ * positives the same sum of out_neg.  A bin index lies in 0 .. T whatever the table holds: one that is not ascending, or
+ * holds a NaN, gives unspecified counts (each offered cell still counted once) and no stray access.
+ * Workspace: dlc_pr_cell_counts_workspace_bytes(rows, n, T) bytes (0 = bad arguments): 16 (T + 1) bytes per workgroup of
+ * the count pass, at most 32 MiB.  Two launches on `stream`: the one pass over the matrix -- a workgroup keeps the
+ * threshold keys and a u32 histogram in LDS (8 T + 8 (T + 1) bytes) and moves it into its own u64 partials before any
+ * bin can reach 2^32 -- and the sum of the partials; no atomics on global memory, no memset.
+ *
+ * dlc_positive_rank_rows -- the retrieval protocol: where does a row's best true match stand in its ranking?  Per row:
+ *     out_idx[r]  = p, the best offered positive cell in the order of merit (ties -> the lower column),
+ *     out_rank[r] = the number of offered cells that BEAT p: better by merit, or equal and at a lower column,
+ *     out_npos[r] = the number of offered positive cells;
+ * a row without an offered positive gets (-1, -1, 0) (rank, idx, npos).  All three are int64 [rows].
+ * CONSEQUENCE.  out_rank[r] is the slot at which dlc_topk_rows_f64 and dlc_peak_topk_rows(suppress = 0) list column
+ * out_idx[r]: recall@K is the share of rows with 0 <= rank < K among those with npos > 0.
+ * Workspace: dlc_positive_rank_rows_workspace_bytes(rows, n) bytes (0 = bad arguments): 32 bytes per row and slab.  One
+ * launch when a workgroup takes a whole row (always from 2048 rows on: the second pass over the row comes out of the
+ * cache), else three (per slab the best positive, per slab the cells that beat the row's best, per row the sums); no
+ * atomics, no memset.
+ *
+ * Errors (both): DLC_ERR_BAD_ARG for a null pointer, an unknown dtype, rows < 1, n < 1, ld < n, ld_truth < n, has_absent
+ * with a float dtype, n_thresholds outside 1..4096 or a misaligned pointer; DLC_ERR_BAD_SHAPE for n >= 2^31;
+ * DLC_ERR_WORKSPACE for a workspace that is missing, too small or not 16-byte aligned.  Nothing is written then.
+ */
+size_t dlc_pr_cell_counts_workspace_bytes(int64_t rows, int64_t n, int n_thresholds);
+int dlc_pr_cell_counts(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */, const void* scores,
+                       int64_t rows, int64_t n, int64_t ld, int64_t limit0, int64_t limit_step,
+                       int lower_is_better, int has_absent, int64_t absent,
+                       const uint8_t* truth, int64_t ld_truth, const void* thresholds, int n_thresholds,
+                       int64_t* out_pos, int64_t* out_neg,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t dlc_positive_rank_rows_workspace_bytes(int64_t rows, int64_t n);
+int dlc_positive_rank_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */, const void* scores,
+                           int64_t rows, int64_t n, int64_t ld, int64_t limit0, int64_t limit_step,
+                           int lower_is_better, int has_absent, int64_t absent,
+                           const uint8_t* truth, int64_t ld_truth,
+                           int64_t* out_rank, int64_t* out_idx, int64_t* out_npos,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
  * Row L2-normalisation (optional mean-centring first) of src[n,d] (DLC_F32 or
