@@ -12,6 +12,7 @@ include/dlc.h, with the reference's Python call surface on top:
                                    + CnnVtlKeyframeDatabase: k nearest by that distance, or the distance rows themselves)
     SeqSlam, DifferenceCalculator, SadKeyframeDatabase   (SeqSLAM's own front-end: patch-normalised grey thumbnails compared
                                    by the sum of absolute differences -- no weights; new)
+        shift=S, width=w on them, on Engine.sad_rows and on SeqSlamLoopClosureDetector: the best of the lateral shifts -S .. S
     MathUtils                     (src/utils/MathUtils.py)
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)

@@ -17,7 +17,8 @@ DLC_ACT_NONE, DLC_ACT_SIGMOID, DLC_ACT_RELU = 0, 1, 2
 DLC_B_KN, DLC_B_NK = 0, 1
 DLC_MAX_K = 128
 DLC_MAX_STEP = 8             # the largest step of the elastic sequence search (d_max)
-DLC_ABI_VERSION = 20         # include/dlc.h; load() refuses a library built from another header
+DLC_MAX_SHIFT = 8            # the largest lateral shift of dlc_sad_u8_shift_rows (thumbnail columns)
+DLC_ABI_VERSION = 20        # include/dlc.h; load() refuses a library built from another header
 DLC_SELECT_COOP, DLC_SELECT_NO_HINTS = 1, 2
 DLC_PRUNE_ON, DLC_PRUNE_OFF, DLC_PRUNE_KEEP = 0, 1, 2     # dlc_set_prune_mode
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
@@ -91,6 +92,8 @@ SIGNATURES = {
                                         _vp]),
     "dlc_cnnvtl_distance_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dlc_sad_u8_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "dlc_sad_u8_shift_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _i64, _i64, _vp, _i64, _vp, _i64,
+                                     _vp]),
     "dlc_seqslam_describe_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp]),
     "dlc_sequence_topk_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "dlc_sequence_topk": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(C.c_int32), _int, _int,

@@ -87,10 +87,11 @@ def create_distance_matrix(dataset_path, out_png=None, network=None, pattern="*"
     return matrix
 
 
-def create_difference_matrix(dataset_path, out_png=None, network=None, pattern="*"):
+def create_difference_matrix(dataset_path, out_png=None, network=None, pattern="*", shift=None):
     """Frames -> SeqSLAM descriptors (seqslam.SeqSlam: patch-normalised grey thumbnails) -> int64 N x N matrix of their
     sums of absolute differences [-> PNG, drawn as the distance matrix is].  Device-resident (pipeline.py): uint8 frames
-    up, descriptors stay in HBM, the matrix comes down once.  No weights are needed."""
+    up, descriptors stay in HBM, the matrix comes down once.  No weights are needed.  shift = S: every cell the best of
+    the lateral shifts -S .. S of the thumbnail's columns (the width is network.size[1])."""
     from . import pipeline
     from .seqslam import SeqSlam
     files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
@@ -98,7 +99,7 @@ def create_difference_matrix(dataset_path, out_png=None, network=None, pattern="
         raise ValueError("Specified dataset is empty or could not find dataset")
     frames = np.stack([read_ppm(f) for f in files])                      # RGB
     network = network or SeqSlam()
-    matrix = pipeline.seqslam_difference_matrix_from_frames(frames, network)
+    matrix = pipeline.seqslam_difference_matrix_from_frames(frames, network, shift=shift)
     if out_png:
         _write_gray(out_png, distance_image(matrix))
     return matrix

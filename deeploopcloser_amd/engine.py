@@ -1005,13 +1005,51 @@ class Engine:
         """_rows16 for uint8 rows."""
         return self._rows16(x.view(torch.int8), d).view(torch.uint8)
 
-    def sad_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
+    def sad_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None, shift=None, width=None, shift_out=None):
         """int64 [Q, N]: the sum of absolute differences of every query row of q [Q, D] uint8 to the rows of db [N, D]
         uint8 (dlc_sad_u8_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r * limit_step,
         0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1, "not offered",
         when the engine allocates the result.  d: the descriptor length when the rows are padded (the bytes past d are
         ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows lie further apart than N (its
-        columns past N are left alone too)."""
+        columns past N are left alone too).
+        shift = S (1 .. min(DLC_MAX_SHIFT, width - 1); None or 0: the plain rows) with width = w, the thumbnail's columns
+        (d a multiple of it): the best of the lateral shifts -S .. S, rescaled to the plain SAD's scale
+        (dlc_sad_u8_shift_rows, include/dlc.h), exact.  shift_out: True, or a caller-kept int8 [Q, N] tensor or
+        row-strided view -- the call then returns (out, shift_out), the winning shift of every written cell (0 in the
+        cells that were not offered when it is allocated here)."""
+        if not shift:                                            # None or 0: today's path, call for call
+            if shift_out is not None and shift_out is not False:
+                raise ValueError("sad_rows: shift_out needs shift")
+            return self._sad_rows_plain(q, db, d, limit0, limit_step, out)
+        d = self._int8_pair("sad_rows", q, db, d, dtype=torch.uint8)
+        if width is None:
+            raise ValueError("sad_rows: shift needs width, the thumbnail's columns")
+        shift, width = int(shift), int(width)
+        if width < 1 or d < width or d % width != 0:
+            raise ValueError("sad_rows: d=%d is not a multiple of width=%d" % (d, width))
+        if not 0 <= shift <= min(L.DLC_MAX_SHIFT, width - 1):
+            raise ValueError("sad_rows: shift=%d outside 0..min(%d, width - 1 = %d)" % (shift, L.DLC_MAX_SHIFT, width - 1))
+        nq, n = q.shape[0], db.shape[0]
+        out = self._rows_out("sad_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
+        want_shift = shift_out is not None and shift_out is not False
+        sh = None
+        if want_shift:
+            sh = self._rows_out("sad_rows: shift_out", None if shift_out is True else shift_out, nq, n, torch.int8, "an int8",
+                                None if limit0 is None else 0)
+        if nq > 0 and n > 0 and d > 0:
+            q = self._rows16_u8(q, d)
+            db = self._rows16_u8(db, d)
+            self._check(self.lib.dlc_sad_u8_shift_rows(
+                self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d // width, width, shift,
+                n if limit0 is None else int(limit0), int(limit_step), _ptr(out), out.stride(0) if nq > 1 else n,
+                None if sh is None else _ptr(sh), 0 if sh is None else (sh.stride(0) if nq > 1 else n), self._stream()))
+            self._wrote(out)
+            if sh is not None:
+                self._wrote(sh)
+        return (out, sh) if want_shift else out
+
+    def _sad_rows_plain(self, q, db, d, limit0, limit_step, out):
+        """sad_rows without a shift: dlc_sad_u8_rows."""
         d = self._int8_pair("sad_rows", q, db, d, dtype=torch.uint8)
         nq, n = q.shape[0], db.shape[0]
         out = self._rows_out("sad_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)

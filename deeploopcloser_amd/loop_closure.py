@@ -639,10 +639,15 @@ class SeqSlamLoopClosureDetector:
     contrast = R, suppress = W, steps = (d_min, d_max) and chains = True mean what they mean there -- with contrast the
     sums are float64 and an empty slot is (+inf, -1).  max_difference is then compared with the sequence sum.
 
+    shift = S with width = w (the thumbnail's columns, dim a multiple of it; S in 0..min(DLC_MAX_SHIFT, w - 1)): every row
+    formed, in either form, is the shifted row (dlc_sad_u8_shift_rows: the best of the lateral shifts -S .. S, on the
+    plain SAD's scale), and everything behind the rows works on it unchanged.  The winning shifts are not returned here;
+    db.differences(..., return_shift=True) gives them.
+
     In both forms the lists do not depend on how the frames are batched."""
 
     def __init__(self, dim, k=5, max_difference=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None, steps=None, chains=False):
+                 contrast=None, suppress=None, steps=None, chains=False, shift=None, width=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -653,6 +658,17 @@ class SeqSlamLoopClosureDetector:
             raise ValueError("dim and capacity must be positive")
         if suppress is not None and not 0 <= suppress < 1 << 63:
             raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
+        if shift is not None and shift < 0:
+            raise ValueError("shift=%d must be >= 0" % shift)
+        if shift:                                            # (None or 0: the plain rows, as Engine.sad_rows takes them)
+            if width is None:
+                raise ValueError("shift needs width, the thumbnail's columns")
+            if width < 1 or dim % width != 0:
+                raise ValueError("dim=%d is not a multiple of width=%d" % (dim, width))
+            if not 0 <= shift <= min(L.DLC_MAX_SHIFT, width - 1):
+                raise ValueError("shift=%d outside 0..min(%d, width - 1 = %d)" % (shift, L.DLC_MAX_SHIFT, width - 1))
+        self.shift = None if shift is None else int(shift)
+        self.width = None if width is None else int(width)
         self.k, self.exclusion = int(k), int(exclusion)
         self.max_difference = max_difference if max_difference is None else (int if contrast is None else float)(max_difference)
         self.sequence = None if sequence is None else int(sequence)
@@ -695,11 +711,11 @@ class SeqSlamLoopClosureDetector:
                 self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
                                          dtype=torch.int64, device=db.engine.device)
             rows = self._rows[:b, :first + b]
-            db.differences(q, limit0=first - self.exclusion, limit_step=1, out=rows)
+            db.differences(q, limit0=first - self.exclusion, limit_step=1, out=rows, shift=self.shift, width=self.width)
             return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
                                             lower_is_better=True)
         # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
-        db.differences(q, limit0=first - self.exclusion, limit_step=1,
+        db.differences(q, limit0=first - self.exclusion, limit_step=1, shift=self.shift, width=self.width,
                        out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
         return self._seq.search(db.engine, b, first + b, first - self.exclusion)
 
@@ -795,6 +811,9 @@ def main(argv=None):
     ap.add_argument("--patch", type=int, default=8, help="--network seqslam: side of the normalisation tiles, 1..64")
     ap.add_argument("--strength", type=int, default=32,
                     help="--network seqslam: descriptor byte = 128 + strength * z-score, 1..127")
+    ap.add_argument("--shift", type=int, default=None, metavar="S",
+                    help="--network seqslam: compare over the lateral shifts -S .. S of the thumbnail's columns and keep the "
+                         "best (a place revisited a little to the side), 0 <= S <= %d and S < W of --size" % L.DLC_MAX_SHIFT)
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -819,6 +838,8 @@ def main(argv=None):
         ap.error("--metric similarity needs --network sdav")
     if (args.network == "seqslam") != (args.metric == "sad"):
         ap.error("--network seqslam and --metric sad need each other")
+    if args.shift is not None and args.network != "seqslam":
+        ap.error("--shift needs --network seqslam")
     if args.network == "seqslam":
         try:
             args.size = tuple(int(v) for v in args.size.lower().split("x"))
@@ -830,6 +851,8 @@ def main(argv=None):
             ap.error("--patch must be 1..64")
         if not 1 <= args.strength <= 127:
             ap.error("--strength must be 1..127")
+        if args.shift is not None and not 0 <= args.shift <= min(L.DLC_MAX_SHIFT, args.size[1] - 1):
+            ap.error("--shift must be 0..%d and below the W of --size" % L.DLC_MAX_SHIFT)
         if args.max_difference is not None and args.contrast is None:
             if args.max_difference < 0 or args.max_difference != int(args.max_difference):
                 ap.error("--max-difference must be a non-negative integer (any number with --contrast)")
@@ -932,7 +955,8 @@ def _stream(args, files):
             det = SeqSlamLoopClosureDetector(desc.shape[1], k=args.k, max_difference=args.max_difference,
                                              exclusion=args.exclusion, capacity=max(4096, len(files)), sequence=args.sequence,
                                              contrast=args.contrast, suppress=args.suppress, steps=args.steps,
-                                             chains=args.chains)
+                                             chains=args.chains, shift=args.shift,
+                                             width=None if args.shift is None else args.size[1])
         elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))

@@ -205,14 +205,15 @@ def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None,
     return out[:, :network.dim]
 
 
-def seqslam_difference_matrix_from_frames(frames, network, chunk_frames=256, device_result=False, timings=None):
+def seqslam_difference_matrix_from_frames(frames, network, chunk_frames=256, device_result=False, timings=None, shift=None):
     """Frames -> SeqSLAM descriptors -> the full N x N int64 matrix of their sums of absolute differences (the matrix
-    SeqSLAM's matcher starts from).  One upload, one download (device_result=True: none)."""
+    SeqSLAM's matcher starts from).  One upload, one download (device_result=True: none).  shift = S: the best of the
+    lateral shifts -S .. S of the thumbnail's columns instead (Engine.sad_rows with width = network.size[1])."""
     eng = network.engine
     cur = torch.cuda.current_stream(eng.device)
     d8 = seqslam_descriptors_from_frames(frames, network, chunk_frames, timings=timings)
     m = _mark(timings, "difference matrix", cur)
-    dm = eng.sad_rows(d8, d8)
+    dm = eng.sad_rows(d8, d8, shift=shift, width=None if shift is None else network.size[1])
     _done(timings, m, cur)
     if device_result:
         return dm

@@ -5,6 +5,9 @@ package was designed for, and its difference matrix.
     DifferenceCalculator    sum of absolute differences of descriptors: the full matrix, or a rectangular set of pairs
     SadKeyframeDatabase     the descriptors resident in HBM, a batch's difference rows against them (dlc_sad_u8_rows)
 
+shift = S with width = w on any of the three compares over the lateral shifts -S .. S of the thumbnail's columns and keeps
+the best, rescaled to the plain SAD's scale (dlc_sad_u8_shift_rows): a place revisited a little to the side still matches.
+
 The rows are int64 and lower is better, as the cnn_vtl distance rows are: sequence_topk / contrast_normalize /
 sequence_peaks / sequence_chains take them as they are, and SeqSlamLoopClosureDetector (loop_closure.py) is the streaming
 form.  Both definitions are exact and stated in include/dlc.h.
@@ -69,23 +72,31 @@ class DifferenceCalculator:
         return engine.to_device(x)
 
     @staticmethod
-    def difference_matrix(descriptors):
-        """Full N x N matrix incl. the diagonal (zeros), numpy int64: difference_rows(descriptors, descriptors).
-        descriptors: uint8 [N, D], NumPy or a tensor."""
-        e = default_engine()
-        d = DifferenceCalculator._rows(e, descriptors, "descriptors")
-        return e.sad_rows(d, d).cpu().numpy()
+    def _host(res):
+        """A sad_rows result, one tensor or (out, shift_out), as NumPy."""
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
 
     @staticmethod
-    def difference_rows(queries, descriptors):
+    def difference_matrix(descriptors, shift=None, width=None, return_shift=False):
+        """Full N x N matrix incl. the diagonal (zeros), numpy int64: difference_rows(descriptors, descriptors).
+        descriptors: uint8 [N, D], NumPy or a tensor.  shift, width, return_shift: as difference_rows takes them (the
+        shifted values are symmetric too -- shift s of (i, j) is shift -s of (j, i) -- the shifts are not)."""
+        e = default_engine()
+        d = DifferenceCalculator._rows(e, descriptors, "descriptors")
+        return DifferenceCalculator._host(e.sad_rows(d, d, shift=shift, width=width, shift_out=True if return_shift else None))
+
+    @staticmethod
+    def difference_rows(queries, descriptors, shift=None, width=None, return_shift=False):
         """numpy int64 [Q, N]: every query against every descriptor as one call (dlc_sad_u8_rows).  queries [Q, D] and
-        descriptors [N, D]: uint8, NumPy or tensors."""
+        descriptors [N, D]: uint8, NumPy or tensors.  shift = S with width = w (the thumbnail's columns): the best of the
+        lateral shifts -S .. S instead (dlc_sad_u8_shift_rows); return_shift: (rows, numpy int8 [Q, N] of the winning
+        shifts)."""
         e = default_engine()
         q = DifferenceCalculator._rows(e, queries, "queries")
         x = DifferenceCalculator._rows(e, descriptors, "descriptors")
         if q.shape[1] != x.shape[1]:
             raise ValueError("difference_rows: queries [Q, D] and descriptors [N, D] with one D")
-        return e.sad_rows(q, x).cpu().numpy()
+        return DifferenceCalculator._host(e.sad_rows(q, x, shift=shift, width=width, shift_out=True if return_shift else None))
 
 
 class SadKeyframeDatabase(_ByteRowStore):
@@ -97,11 +108,14 @@ class SadKeyframeDatabase(_ByteRowStore):
 
     DTYPE, KIND = torch.uint8, "SeqSLAM"
 
-    def differences(self, queries, limit0=None, limit_step=0, out=None):
+    def differences(self, queries, limit0=None, limit_step=0, out=None, shift=None, width=None, return_shift=False):
         """int64 [Q, len(self)] on the device: the SAD of each query row to every stored key-frame.  queries: [Q, dim]
         uint8, or stored rows [Q, stored_width(dim)] such as a slice of `rows` (the padding is ignored).  limit0 /
         limit_step: query r is written in its first limit0 + r * limit_step cells only (default: all); the others keep
         what `out` held (a caller-kept int64 [Q, len(self)] tensor or row-strided view), or hold -1 when the result is
-        allocated here."""
+        allocated here.  shift = S with width = w (the thumbnail's columns, dim a multiple of it): the best of the lateral
+        shifts -S .. S (dlc_sad_u8_shift_rows); return_shift: (rows, int8 [Q, len(self)] of the winning shifts, 0 where a
+        cell was not offered) -- the lateral offset of the revisit in thumbnail columns."""
         q = self._queries("differences", queries)
-        return self.engine.sad_rows(q, self.rows, d=self.dim, limit0=limit0, limit_step=limit_step, out=out)
+        return self.engine.sad_rows(q, self.rows, d=self.dim, limit0=limit0, limit_step=limit_step, out=out, shift=shift,
+                                    width=width, shift_out=True if return_shift else None)

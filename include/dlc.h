@@ -617,6 +617,43 @@ int dlc_sad_u8_rows(dlc_ctx* ctx, const uint8_t* queries, int64_t Q, int64_t ldq
                     int64_t limit0, int64_t limit_step,
                     int64_t* out, int64_t ld_out, void* stream);
 
+/*
+ * The same difference with tolerance to a lateral shift of the revisit: the best of the +-S thumbnail columns (the
+ * remedy of the SeqSLAM family -- Milford's low-resolution work; SMART, Pepperell, Corke & Milford 2014 -- for a place
+ * revisited half a lane to the side, which displaces the thumbnail by a few columns and spoils the cell-by-cell SAD).
+ * DEFINITION.  A descriptor is a thumbnail of h rows and w columns, uint8, row-major, D = h * w.  For -S <= s <= S
+ * (S = max_shift):
+ *     sad_s(q, d) = sum over y < h, over x with 0 <= x < w and 0 <= x + s < w, of |q[y][x] - d[y][x + s]|
+ *     v_s         = floor(sad_s * w / (w - |s|))          (int64; the overlap is w - |s| columns in every row)
+ *     out         = min over s of v_s
+ *     shift       = the s of the minimum; ties go to the first in the order 0, -1, +1, -2, +2, ..., -S, +S
+ * A query column is compared with the key-frame column s to its right: when the query's content is the key-frame's
+ * moved 8 columns to the left, shift = +8.  The rescaling by w / (w - |s|) keeps every shift on the scale of the plain
+ * SAD, so thresholds keep their meaning.  S = 0 is dlc_sad_u8_rows bit for bit, with shift = 0 everywhere.  Only
+ * horizontal whole-column shifts.
+ * CONTRACT.  dlc_sad_u8_rows' word for word, with D = h * w: out[r * ld_out + j] is written for 0 <= j < lim(r) =
+ * clamp(limit0 + r * limit_step, 0, N), any limit_step; EVERY OTHER WORD OF out KEEPS ITS VALUE; when every lim(r) is 0
+ * nothing is launched and the call returns DLC_OK.  Both bases 16-byte aligned, ldq and ldd multiples of 16 bytes
+ * (>= h * w); bytes h * w .. ld-1 of a row may hold anything and change nothing; queries may be rows of db; the outputs
+ * must not overlap the operands or each other.  shift_out may be null; when given it is int8 [Q, ld_shift],
+ * ld_shift >= N, written in exactly the cells in which out is written, and EVERY OTHER BYTE OF IT KEEPS ITS VALUE.
+ * Ranges: 0 <= S <= DLC_MAX_SHIFT, S < w, w <= 65536, h * w <= 2^24 (so sad_s * w < 2^48), N < 2^32, Q <= 2^20.
+ * No workspace; one launch on `stream` (the tiles of dlc_sad_u8_rows with fewer db rows per thread, all 2 S + 1 sums
+ * of a pair accumulated in one pass over the staged bytes, plain stores: no memset, no atomics); never synchronises.
+ * Every w >= 1 is served; w a multiple of 16 takes the fast path (16-byte loads, compile-time edge masks).  Integers
+ * throughout, the rescaling an exact 64-bit division: the result is exact and does not depend on the plan, nor on how
+ * the queries are batched.
+ * Errors: DLC_ERR_BAD_ARG for what dlc_sad_u8_rows refuses (a null pointer, Q or N < 1, ldq or ldd < h * w, ld_out < N,
+ * a misaligned base or pitch), h < 1, w < 1, max_shift < 0, or ld_shift < N with a non-null shift_out;
+ * DLC_ERR_BAD_SHAPE for max_shift > DLC_MAX_SHIFT, max_shift >= w, w > 65536, h * w > 2^24, N >= 2^32 or Q > 2^20.
+ * Nothing is written then.
+ */
+#define DLC_MAX_SHIFT 8
+int dlc_sad_u8_shift_rows(dlc_ctx* ctx, const uint8_t* queries, int64_t Q, int64_t ldq,
+                          const uint8_t* db, int64_t N, int64_t ldd, int h, int w, int max_shift,
+                          int64_t limit0, int64_t limit_step,
+                          int64_t* out, int64_t ld_out, int8_t* shift_out, int64_t ld_shift, void* stream);
+
 /* ---- match: sequence-consistent search over a score matrix (not in the reference) ----------- */
 /*
  * The trajectory search of SeqSLAM (Milford & Wyeth, ICRA 2012) over a dense score matrix -- rows of
