@@ -391,6 +391,9 @@ int dlc_quant_gather_i8(dlc_ctx* ctx, const double* const* segs, const int64_t* 
  *                              Workspace: dlc_cnnvtl_encode_split_workspace_bytes(n, h / s2d, w / s2d, s2d * s2d * c, ...);
  *   dlc_cnnvtl_layers_split    debug / test entry: layers layer_a .. layer_b on x = layer_a's fp32 input (the [h, w, c] given
  *                              are LAYER 0's input, the workspace is the encode call's); feats[l - layer_a] receives layer l.
+ *                              Its *status reports layer INPUTS only (bit 0): the output flag (bit 1) rides on the per-frame
+ *                              min / max fold, which only dlc_cnnvtl_encode_split runs -- a caller of this entry that needs
+ *                              to know looks at the returned outputs.
  * All are stream-ordered.
  */
 size_t dlc_cnnvtl_split_panels_bytes(int n_layers, const int32_t* geom);
