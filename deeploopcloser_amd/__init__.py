@@ -21,6 +21,7 @@ include/dlc.h, with the reference's Python call surface on top:
     sequence_chains (and chains=True on sequence_topk / sequence_peaks / the detectors): the L matched key-frames behind a candidate; new
     peak_topk / sequence_peaks / uniqueness_ratio   (distinct-place candidates: picks more than `suppress` columns apart; new)
     LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector   (streaming; all take sequence=L, suppress=W)
+    fuse_scores, FusedLoopClosureDetector   (multi-descriptor fusion: score rows normalised per row, weighted and summed; new)
     ground_truth / pr_curve_cells / recall_at / pr_curve_queries / PRCurve / LoopClosureEvaluator   (ground-truth evaluation: PR curves, average precision, recall@K; new)
 
 Importing the package is cheap and works without a GPU; constructing any of
@@ -42,10 +43,13 @@ from . import tensor_wrapper
 from . import sequence
 from .sequence import slope_offsets, sequence_topk, sequence_scores, sequence_chains, contrast_normalize, peak_topk, sequence_peaks, uniqueness_ratio
 from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector
+from .loop_closure import FusedLoopClosureDetector
+from . import fusion
+from .fusion import fuse_scores
 from . import evaluate
 from .evaluate import ground_truth, pr_curve_cells, recall_at, pr_curve_queries, PRCurve, LoopClosureEvaluator
 
-__all__ = ["ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

@@ -22,6 +22,9 @@ DLC_ABI_VERSION = 20        # include/dlc.h; load() refuses a library built from
 DLC_SELECT_COOP, DLC_SELECT_NO_HINTS = 1, 2
 DLC_PRUNE_ON, DLC_PRUNE_OFF, DLC_PRUNE_KEEP = 0, 1, 2     # dlc_set_prune_mode
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
+DLC_MAX_FUSE = 8             # the most score sources dlc_fuse_rows takes
+DLC_FUSE_NONE, DLC_FUSE_ZSCORE, DLC_FUSE_MINMAX = 0, 1, 2
+DLC_FUSE_PLAN_AUTO, DLC_FUSE_PLAN_ROW, DLC_FUSE_PLAN_SLAB = 0, 1, 2
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -106,6 +109,9 @@ SIGNATURES = {
     "dlc_sequence_chains": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(C.c_int32), _int, _int,
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "dlc_contrast_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
+    "dlc_fuse_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "dlc_fuse_rows": (_int, [_vp, _int, C.POINTER(_int), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_dbl), C.POINTER(_int),
+                             _i64, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp, _sz, _vp]),
     "dlc_peak_topk_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_peak_topk_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _i64, _int, _i64, _int, _vp, _vp, _vp,
                                   _vp, _sz, _vp]),

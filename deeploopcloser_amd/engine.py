@@ -1249,6 +1249,63 @@ class Engine:
         self._wrote(out)
         return out[:, :n]
 
+    _FUSE_NORMS = {"none": L.DLC_FUSE_NONE, "zscore": L.DLC_FUSE_ZSCORE, "minmax": L.DLC_FUSE_MINMAX}
+    _FUSE_PLANS = {None: L.DLC_FUSE_PLAN_AUTO, "auto": L.DLC_FUSE_PLAN_AUTO, "row": L.DLC_FUSE_PLAN_ROW,
+                   "slab": L.DLC_FUSE_PLAN_SLAB}
+
+    def fuse_rows(self, sources, weights=None, lower_is_better=False, norm="zscore", n=None, limit0=None, limit_step=0,
+                  out=None, plan=None):
+        """Several score rows of the same frames against the same key-frames fused into one (dlc_fuse_rows,
+        include/dlc.h): fp64 [rows, n], higher is better, cell (r, j) = the sum over the sources, in their order, of
+        weights[i] * the source's cell normalised within ITS row's first clamp(limit0 + r * limit_step, 0, n) cells
+        (limit0 None = n) -- norm "zscore": (x - mean) / sample std, "minmax": (x - min) / (max - min), "none": x -- with
+        the sign turned for a source that is lower_is_better (a bool, or one per source).  Every row sum is the TREE of
+        dlc.h, so a row does not depend on its batch or on the plan.  sources: 1..8 matrices [rows, >= n], each fp64, fp32
+        or int64 on the device (a row-strided view is taken as it is); weights: None (all 1) or one finite number per
+        source.  Cells that are not offered keep what `out` held, and hold NaN when the engine allocates the result.
+        out: as contrast_rows takes it.  plan: None / "auto", "row" or "slab" (dlc.h)."""
+        sources = list(sources)
+        if not 1 <= len(sources) <= L.DLC_MAX_FUSE:
+            raise ValueError("fuse_rows: %d sources outside 1..%d" % (len(sources), L.DLC_MAX_FUSE))
+        m = len(sources)
+        if norm not in self._FUSE_NORMS:
+            raise ValueError("fuse_rows: norm=%r is none of %s" % (norm, sorted(self._FUSE_NORMS)))
+        if plan not in self._FUSE_PLANS:
+            raise ValueError("fuse_rows: plan=%r is none of auto, row, slab" % (plan,))
+        w = np.ones(m, dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != m or not np.isfinite(w).all():
+            raise ValueError("fuse_rows: weights must be %d finite numbers" % m)
+        lib = np.asarray(lower_is_better, dtype=bool).reshape(-1)
+        if lib.shape[0] == 1:
+            lib = np.repeat(lib, m)
+        if lib.shape[0] != m:
+            raise ValueError("fuse_rows: lower_is_better must be a bool or one per source (%d)" % m)
+        mats, lds = [], []
+        for i, s in enumerate(sources):
+            s, rows_i, n_i, ld = self._score_matrix("fuse_rows: source %d" % i, s, n, "fuse")
+            if i and (rows_i, n_i) != (rows, n):
+                raise ValueError("fuse_rows: source %d is [%d, %d], source 0 [%d, %d]" % (i, rows_i, n_i, rows, n))
+            rows, n = rows_i, n_i
+            mats.append(s)
+            lds.append(ld)
+        out = self._rows_out("fuse_rows: out", out, rows, n, torch.float64, "a float64",
+                             float("nan") if limit0 is not None or limit_step != 0 else None, wider=True)
+        ld_out = out.stride(0) if rows > 1 else n
+        ws, need = None, 0
+        if self._FUSE_PLANS[plan] != L.DLC_FUSE_PLAN_ROW:
+            need = self.lib.dlc_fuse_rows_workspace_bytes(rows, n, m)
+            if need == 0:
+                raise ValueError("fuse_rows: rows=%d, n=%d outside the supported sizes" % (rows, n))
+            ws = self.workspace("fuse_rows", need)
+        self._check(self.lib.dlc_fuse_rows(
+            self.ctx, m, (C.c_int * m)(*[self._SEQ_DTYPES[s.dtype] for s in mats]),
+            (C.c_void_p * m)(*[s.data_ptr() for s in mats]), (C.c_int64 * m)(*lds), (C.c_double * m)(*w.tolist()),
+            (C.c_int * m)(*[int(v) for v in lib]), rows, n, n if limit0 is None else int(limit0), int(limit_step),
+            self._FUSE_NORMS[norm], self._FUSE_PLANS[plan], _ptr(out), ld_out, _ptr(ws), ws.numel() if ws is not None else 0,
+            self._stream()))
+        self._wrote(out)
+        return out[:, :n]
+
     def peak_topk_rows(self, scores, k, suppress, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None,
                        poison=None):
         """(scores [rows, k], idx [rows, k] int64): distinct-place candidates, the windowed peak top-k of

@@ -13,6 +13,13 @@ top-k path and reports the candidates whose cosine score reaches `threshold`.
 --network seqslam --metric sad is SeqSLAM itself, front to back and without weights: patch-normalised grey thumbnails
 (--size, --patch, --strength), their sums of absolute differences, then the sequence search (SeqSlamLoopClosureDetector).
 
+    python -m deeploopcloser_amd.loop_closure DATASET_DIR --fuse sad,distance --sequence 10
+
+--fuse MEMBER,MEMBER[,...] (sad, distance, cosine) runs several descriptors side by side and ranks by ONE fused score:
+each member's rows normalised (--fuse-norm zscore | minmax | none), weighted (--fuse-weights) and summed, higher is better
+(FusedLoopClosureDetector; dlc_fuse_rows, include/dlc.h).  sad is SeqSLAM's thumbnails (--size, --patch, --strength,
+--shift); distance and cosine share one CnnVtl forward per batch (--weights).
+
 With --sequence L --chains every candidate line is followed by one line `chain<TAB>frame:key-frame<TAB>...`: the L pairs
 the candidate was matched along, oldest frame first (the detectors' chains=True; dlc_sequence_chains /
 dlc_sequence_elastic_chains, include/dlc.h).
@@ -726,6 +733,146 @@ class SeqSlamLoopClosureDetector:
         return _loops(diff, ids, first_id, self.max_difference, lower_is_better=True, chains=chains)
 
 
+FUSE_MEMBERS = ("cosine", "distance", "sad")
+FUSE_NORMS = ("zscore", "minmax", "none")
+
+
+class FusedLoopClosureDetector:
+    """The streaming question asked with SEVERAL descriptors at once: every member keeps its own key-frame store and
+    forms its own raw rows per batch -- each new frame against the key-frames more than `exclusion` frames older -- and
+    ONE dlc_fuse_rows (include/dlc.h) turns them into one row: each member's row normalised within itself (`norm`:
+    "zscore", "minmax" or "none"), the sign of the distances turned, weighted (`weights`: None = all 1, or one finite
+    number per member) and summed.  The fused row is float64 and higher is better; the k best cells are the candidates.
+    A hand-crafted descriptor and a deep one fail in different places; what both agree on stands out of the sum.
+
+    members: a list of specs, all on one engine --
+        ("cosine", dim, {"dtype": "bf16", "center": False})   KeyframeDatabase, its fp64 cosine scores (scores_f64)
+        ("distance", dim)                                     CnnVtlKeyframeDatabase, the cnn_vtl distance (distances)
+        ("sad", dim, {"shift": S, "width": w})                SadKeyframeDatabase, SeqSLAM's SAD (differences)
+    (the dict is optional).  query_and_insert takes one [B, dim_i] tensor per member, all with the same B.
+
+    The fused rows go where the sequence search keeps its rows (_SequenceRows: float64, L = 1 when sequence is None, so
+    suppress = W works without sequence, as in the SeqSLAM detector) and sequence = L, slopes, contrast = R,
+    suppress = W, steps = (d_min, d_max) and chains = True mean what they mean in the other detectors.  A fused row
+    depends on its frame's raw rows alone (the row sums of dlc_fuse_rows do not depend on the batch), so the lists do not
+    depend on how the frames are batched.  Results are (scores float64 [B, k], ids int64 [B, k][, chain]), (-inf, -1)
+    in empty slots; `threshold` (None: all k) is compared with the fused score -- with sequence=L the sum of L of them."""
+
+    def __init__(self, members, weights=None, norm="zscore", k=5, threshold=None, exclusion=30, capacity=4096, device=None,
+                 sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False):
+        from .distance import CnnVtlKeyframeDatabase
+        from .seqslam import SadKeyframeDatabase
+        members = [tuple(m) if isinstance(m, (tuple, list)) else (m,) for m in members]
+        if not 1 <= len(members) <= L.DLC_MAX_FUSE:
+            raise ValueError("%d members outside 1..%d" % (len(members), L.DLC_MAX_FUSE))
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if exclusion < 0:
+            raise ValueError("exclusion must be >= 0")
+        if capacity < 1:
+            raise ValueError("capacity must be positive")
+        if norm not in FUSE_NORMS:
+            raise ValueError("norm=%r is none of %s" % (norm, ", ".join(FUSE_NORMS)))
+        w = np.ones(len(members)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != len(members) or not np.isfinite(w).all():
+            raise ValueError("weights must be %d finite numbers" % len(members))
+        if sequence is None:
+            for name, value in (("chains", chains or None), ("slopes", slopes), ("steps", steps), ("contrast", contrast)):
+                if value is not None:
+                    raise ValueError("%s needs sequence=L" % name)
+        self.weights, self.norm = [float(v) for v in w], norm
+        self.k, self.exclusion = int(k), int(exclusion)
+        self.threshold = None if threshold is None else float(threshold)
+        self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
+        self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
+        self._seq = _SequenceRows(1 if self.sequence is None else self.sequence, slopes, self.k, torch.float64, self.contrast,
+                                  False, self.suppress, steps, self.chains)
+        self.slopes, self.steps = self._seq.slopes, self._seq.steps
+        self.kinds, self.dbs, self._options = [], [], []
+        for spec in members:
+            if not 2 <= len(spec) <= 3 or spec[0] not in FUSE_MEMBERS:
+                raise ValueError("a member is (kind, dim[, options]) with kind one of %s" % ", ".join(FUSE_MEMBERS))
+            kind, dim, opt = spec[0], int(spec[1]), dict(spec[2]) if len(spec) == 3 and spec[2] else {}
+            allowed = {"cosine": ("dtype", "center"), "distance": (), "sad": ("shift", "width")}[kind]
+            if set(opt) - set(allowed):
+                raise ValueError("member %s takes the options %s" % (kind, ", ".join(allowed) or "(none)"))
+            if kind == "cosine":
+                db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=opt.get("dtype", "bf16"),
+                                            center=opt.get("center", False), device=device)
+            elif kind == "distance":
+                db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+            else:
+                shift, width = opt.get("shift"), opt.get("width")
+                if shift:
+                    if width is None or width < 1 or dim % width != 0:
+                        raise ValueError("sad: shift needs width, the thumbnail's columns, with dim a multiple of it")
+                    if not 0 <= shift <= min(L.DLC_MAX_SHIFT, width - 1):
+                        raise ValueError("sad: shift=%d outside 0..min(%d, width - 1 = %d)" % (shift, L.DLC_MAX_SHIFT, width - 1))
+                db = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+            self.kinds.append(kind)
+            self.dbs.append(db)
+            self._options.append(opt)
+        self.engine = self.dbs[0].engine
+        self.lower_is_better = [kind != "cosine" for kind in self.kinds]
+
+    def __len__(self):
+        return len(self.dbs[0])
+
+    def _member_rows(self, i, first, b, out):
+        """Member i's raw rows of frames first .. first + b - 1 against the key-frames, each frame the ones old enough."""
+        db, kind, lim = self.dbs[i], self.kinds[i], first - self.exclusion
+        q = db.rows[first:first + b]
+        if kind == "cosine":
+            db.scores_f64(q, limit0=lim, limit_step=1, out=out)
+        elif kind == "distance":
+            db.distances(q, limit0=lim, limit_step=1, out=out)
+        else:
+            db.differences(q, limit0=lim, limit_step=1, out=out, shift=self._options[i].get("shift"),
+                           width=self._options[i].get("width"))
+
+    def query_and_insert(self, descriptors):
+        """The next B frames, one descriptor tensor [B, dim_i] per member in the members' order (floats for cosine, int8
+        for distance, uint8 for sad; ids len(self) .. len(self)+B-1) -> (scores [B, k] float64, ids [B, k] int64) on the
+        device, best first, (-inf, -1) where fewer than k key-frames are old enough; the frames are key-frames
+        afterwards.  With chains=True a third tensor, chain [B, k, L] int32."""
+        descriptors = list(descriptors)
+        if len(descriptors) != len(self.dbs):
+            raise ValueError("query_and_insert: %d descriptor tensors for %d members" % (len(descriptors), len(self.dbs)))
+        eng = self.engine
+        xs = []
+        for db, kind, x in zip(self.dbs, self.kinds, descriptors):
+            x = db._as_float(x) if kind == "cosine" else eng.to_device(x)
+            xs.append(x.unsqueeze(0) if x.dim() == 1 else x)
+        b = int(xs[0].shape[0])
+        if any(x.dim() != 2 or x.shape[0] != b for x in xs):
+            raise ValueError("query_and_insert: every member's descriptors must be [B, dim] with one B")
+        if b == 0:
+            out = _nothing_older(0, self.k, float("-inf"), torch.float64, eng.device)
+            return out + (_no_chains(0, self.k, self.sequence, eng.device),) if self.chains else out
+        first = len(self)
+        for db, x in zip(self.dbs, xs):
+            if db.append(x)[0] != first:
+                raise RuntimeError("FusedLoopClosureDetector: the members' stores are out of step")
+        capacity, n = max(db.capacity for db in self.dbs), first + b
+        raws = []
+        for i, kind in enumerate(self.kinds):
+            dtype = torch.float64 if kind == "cosine" else torch.int64
+            ws = eng.workspace("fuse_member_%d" % i, b * capacity * 8)[:b * capacity * 8]
+            raws.append(ws.view(dtype).view(b, capacity)[:, :n])
+            self._member_rows(i, first, b, raws[-1])
+        eng.fuse_rows(raws, weights=self.weights, lower_is_better=self.lower_is_better, norm=self.norm,
+                      limit0=first - self.exclusion, limit_step=1, out=self._seq.raw_rows(b, capacity, eng)[:, :n])
+        return self._seq.search(eng, b, n, first - self.exclusion)
+
+    def loops(self, scores, ids, first_id, chains=None):
+        """[(frame id, matched key-frame id, fused score)] of the candidates at or above the threshold (None: all of
+        them; with sequence=L the score is the sum along the candidate's line).  chains: the third result of
+        query_and_insert with chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs."""
+        return _loops(scores, ids, first_id, self.threshold, chains=chains)
+
+
 def _frame_files(dataset_path, pattern):
     files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
     if not files:
@@ -814,6 +961,16 @@ def main(argv=None):
     ap.add_argument("--shift", type=int, default=None, metavar="S",
                     help="--network seqslam: compare over the lateral shifts -S .. S of the thumbnail's columns and keep the "
                          "best (a place revisited a little to the side), 0 <= S <= %d and S < W of --size" % L.DLC_MAX_SHIFT)
+    ap.add_argument("--fuse", default=None, metavar="MEMBER,MEMBER[,...]",
+                    help="multi-descriptor fusion: two or three of sad (SeqSLAM's thumbnails: --size, --patch, --strength, "
+                         "--shift), distance and cosine (both from one CnnVtl forward per batch), each member's rows "
+                         "normalised, weighted and summed into one score, higher is better (FusedLoopClosureDetector); "
+                         "goes with --sequence, --contrast, --suppress, --steps, --chains and --positions, not with "
+                         "--network / --metric")
+    ap.add_argument("--fuse-weights", default=None, metavar="W,W[,...]",
+                    help="with --fuse: one finite weight per member (default: all 1)")
+    ap.add_argument("--fuse-norm", choices=list(FUSE_NORMS), default=None,
+                    help="with --fuse: how each member's row is normalised before the sum (default: zscore)")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -832,15 +989,37 @@ def main(argv=None):
     ap.add_argument("--pr-curve", default=None, metavar="OUT.tsv",
                     help="with --positions: write the curve there -- threshold, tp, fp, precision, recall; strictest first")
     args = ap.parse_args(argv)
+    if args.fuse is None and (args.fuse_weights is not None or args.fuse_norm is not None):
+        ap.error("--fuse-weights and --fuse-norm need --fuse")
+    if args.fuse is not None:
+        args.fuse = [v.strip() for v in args.fuse.split(",")]
+        if not 2 <= len(args.fuse) <= len(FUSE_MEMBERS) or any(v not in FUSE_MEMBERS for v in args.fuse) or \
+                len(set(args.fuse)) != len(args.fuse):
+            ap.error("--fuse takes two or three different members of %s, comma-separated" % ", ".join(FUSE_MEMBERS))
+        if args.network != "cnn_vtl" or args.metric != "cosine":
+            ap.error("--fuse chooses the descriptors and the measures itself: it excludes --network and --metric")
+        if args.fuse_weights is None:
+            args.fuse_weights = [1.0] * len(args.fuse)
+        else:
+            try:
+                args.fuse_weights = [float(v) for v in args.fuse_weights.split(",")]
+            except ValueError:
+                ap.error("--fuse-weights must be numbers, comma-separated")
+            if len(args.fuse_weights) != len(args.fuse):
+                ap.error("--fuse-weights: %d weights for %d members" % (len(args.fuse_weights), len(args.fuse)))
+            if not all(np.isfinite(v) for v in args.fuse_weights):
+                ap.error("--fuse-weights must be finite")
+        args.fuse_norm = args.fuse_norm or "zscore"
+    thumbnails = args.network == "seqslam" or (args.fuse is not None and "sad" in args.fuse)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
     if args.metric == "similarity" and args.network != "sdav":
         ap.error("--metric similarity needs --network sdav")
     if (args.network == "seqslam") != (args.metric == "sad"):
         ap.error("--network seqslam and --metric sad need each other")
-    if args.shift is not None and args.network != "seqslam":
-        ap.error("--shift needs --network seqslam")
-    if args.network == "seqslam":
+    if args.shift is not None and not thumbnails:
+        ap.error("--shift needs --network seqslam (or --fuse with sad)")
+    if thumbnails:
         try:
             args.size = tuple(int(v) for v in args.size.lower().split("x"))
         except ValueError:
@@ -857,16 +1036,16 @@ def main(argv=None):
             if args.max_difference < 0 or args.max_difference != int(args.max_difference):
                 ap.error("--max-difference must be a non-negative integer (any number with --contrast)")
             args.max_difference = int(args.max_difference)
-    if args.sequence is not None and args.metric not in ("similarity", "sad"):
-        ap.error("--sequence needs --metric similarity or sad")
+    if args.sequence is not None and args.metric not in ("similarity", "sad") and args.fuse is None:
+        ap.error("--sequence needs --metric similarity or sad (or --fuse)")
     if args.sequence is not None and not 1 <= args.sequence <= 64:
         ap.error("--sequence must be 1..64")
     if args.contrast is not None and args.sequence is None:
         ap.error("--contrast needs --sequence")
     if args.contrast is not None and not 1 <= args.contrast <= 32:
         ap.error("--contrast must be 1..32")
-    if args.suppress is not None and args.sequence is None:
-        ap.error("--suppress needs --sequence")
+    if args.suppress is not None and args.sequence is None and args.fuse is None:
+        ap.error("--suppress needs --sequence (or --fuse)")
     if args.suppress is not None and args.suppress < 0:
         ap.error("--suppress must be >= 0")
     if args.steps is not None:
@@ -881,7 +1060,7 @@ def main(argv=None):
         args.steps = (d_min, d_max)
     if args.chains and args.sequence is None:
         ap.error("--chains needs --sequence")
-    if args.threshold is None:
+    if args.threshold is None and args.fuse is None:             # (--fuse: every candidate, as the fused scale is the norm's)
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
     if args.positions is None and (args.radius is not None or args.pr_curve is not None):
@@ -907,8 +1086,47 @@ def main(argv=None):
         return _stream(args, files)
 
 
+def _fused_stream(args, files):
+    """--fuse: (describe, make detector): one descriptor tensor per member and batch -- the thumbnails for sad, ONE CnnVtl
+    forward for distance and cosine -- and the FusedLoopClosureDetector over the first batch's widths."""
+    from .input import read_ppm
+    thumbs = cnn = None
+    if "sad" in args.fuse:
+        from . import pipeline
+        from .seqslam import SeqSlam
+        thumbs = SeqSlam(size=args.size, patch=args.patch, strength=args.strength)
+    if "distance" in args.fuse or "cosine" in args.fuse:
+        from .cnn_vtl import CnnVtl
+        cnn = CnnVtl(input_shape=[args.batch] + list(read_ppm(files[0]).shape), dtype=args.encoder_dtype)
+        if args.weights:
+            cnn.load_alexnet_npy(args.weights)
+
+    def describe(fs):
+        deep = describe_cnn_vtl(fs, cnn, as_int8=True) if cnn is not None else None
+        sad = pipeline.seqslam_descriptors_from_frames(np.stack([read_ppm(f) for f in fs]), thumbs) if thumbs is not None else None
+        return [sad if m == "sad" else (deep if m == "distance" else deep.to(torch.float32)) for m in args.fuse]
+
+    def detector(desc):
+        members = []
+        for m, d in zip(args.fuse, desc):
+            if m == "sad":
+                members.append((m, d.shape[1], {} if args.shift is None else {"shift": args.shift, "width": args.size[1]}))
+            elif m == "cosine":
+                members.append((m, d.shape[1], {"dtype": args.dtype, "center": True}))
+            else:
+                members.append((m, d.shape[1]))
+        return FusedLoopClosureDetector(members, weights=args.fuse_weights, norm=args.fuse_norm, k=args.k,
+                                        threshold=args.threshold, exclusion=args.exclusion, capacity=max(4096, len(files)),
+                                        sequence=args.sequence, contrast=args.contrast, suppress=args.suppress,
+                                        steps=args.steps, chains=args.chains)
+    return describe, detector
+
+
 def _stream(args, files):
-    if args.network == "sdav":
+    fused = None
+    if args.fuse is not None:
+        describe, fused = _fused_stream(args, files)
+    elif args.network == "sdav":
         from .sdav import SDAV
         net = SDAV(dtype=args.encoder_dtype)
         if args.weights:
@@ -932,16 +1150,18 @@ def _stream(args, files):
     if args.positions is not None:
         from .evaluate import LoopClosureEvaluator, pr_line
         judge = LoopClosureEvaluator(args.positions, args.radius, args.exclusion,
-                                     lower_is_better=args.metric in ("distance", "sad"))
+                                     lower_is_better=fused is None and args.metric in ("distance", "sad"))
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
         chunk = files[lo:lo + args.batch]
         t0 = time.perf_counter()
         desc = describe(chunk)
-        if args.metric == "similarity":
+        if fused is None and args.metric == "similarity":
             desc = desc.view(len(chunk), net.input_shape[0], -1)         # [B, P, H]: the frames' patch descriptors
-        if det is None and args.metric == "similarity":
+        if det is None and fused is not None:
+            det = fused(desc)
+        elif det is None and args.metric == "similarity":
             # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,

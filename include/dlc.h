@@ -828,6 +828,67 @@ int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, int64_t rows,
                       double* out, int64_t ld_out, void* stream);
 
 /*
+ * Multi-descriptor fusion of score rows: m row sets that compare the same frames with the same key-frames -- cosine scores
+ * (dlc_cosine_score_rows), cnn_vtl distances (dlc_cnnvtl_distance_rows), SADs (dlc_sad_u8_rows), SDAV similarities --
+ * each normalised within its own row, weighted and summed into ONE fp64, higher-is-better row that everything behind
+ * the rows takes (dlc_contrast_rows, dlc_sequence_topk, dlc_peak_topk_rows, dlc_pr_cell_counts).  The sum of per-query
+ * standardised similarities of several descriptors (Schubert et al.; Hausler et al., Multi-Process Fusion): a
+ * hand-crafted descriptor and a deep one fail in different places.
+ * INPUT.  m sources S_0 .. S_{m-1}, 1 <= m <= DLC_MAX_FUSE, described by five HOST arrays of length m: S_i = scores[i] is
+ * a device matrix [rows, lds[i]] of dtype dtypes[i] (DLC_F64, DLC_F32 or DLC_I64), all sources using their first n
+ * columns; weights[i] is any finite double; lower_is_better[i] != 0 says that S_i is a distance.  Row r offers its first
+ * lim(r) = clamp(limit0 + r * limit_step, 0, n) cells (the convention of dlc_contrast_rows; any limit_step, negative
+ * included).  x_j = (double) S_i[r][j] (exact from fp32; from int64 rounded to nearest even, exact below 2^53).
+ * ARITHMETIC.  All of it is fp64, every operation rounded on its own (no fma contraction), division and sqrt the IEEE
+ * correctly rounded ones.
+ * THE SUM OF A ROW, TREE(v_0 .. v_{c-1}).  P is the smallest power of two >= c and v_j = -0.0 for c <= j < P;
+ *     T(lo, 1) = v_lo;   T(lo, len) = T(lo, len / 2) + T(lo + len / 2, len / 2);   TREE = T(0, P).
+ * x + (-0.0) = x for every x, so padding to any larger power of two gives the same bits, and every aligned power-of-two
+ * block of columns is a node of the tree whatever n, the tiling or the plan: the sum is parallel, and a row's result
+ * depends on that row and its limit alone.  (A left-to-right sum gives other bits.)
+ * PER SOURCE i AND ROW r with c = lim(r) >= 1, u:
+ *   DLC_FUSE_NONE:    u_j = x_j, or -x_j if lower_is_better[i].
+ *   DLC_FUSE_ZSCORE:  mean = TREE(x) / (double)c;  d_j = x_j - mean;  sd = sqrt(TREE(d_j * d_j) / (double)(c - 1)) (the
+ *                     sample standard deviation, as dlc_contrast_rows uses);  u_j = 0.0 if c < 2 or sd == 0.0, else
+ *                     d_j / sd, or (mean - x_j) / sd if lower_is_better[i].  A NaN or an infinity among the offered
+ *                     cells gives what IEEE arithmetic gives: a NaN row, which no search offers.
+ *   DLC_FUSE_MINMAX:  lo, hi = the least and the greatest offered cell in the order of the numbers, -0.0 below +0.0;
+ *                     if any offered cell is NaN every u_j is NaN;  range = hi - lo;  u_j = 0.0 if range == 0.0, else
+ *                     (x_j - lo) / range, or (hi - x_j) / range if lower_is_better[i].
+ * OUTPUT.  t_i = weights[i] * u_j and out[r][j] = ((t_0 + t_1) + ...) + t_{m-1}, starting FROM t_0, not from 0.  The
+ * fused row is always higher-is-better.  out is fp64 [rows, ld_out], ld_out >= n.  Only offered cells are written:
+ * EVERY OTHER WORD OF out KEEPS ITS VALUE, the cells at or past lim(r) and the columns n .. ld_out-1.  No source cell at
+ * or past its row's limit, and no column n .. ld-1, is read.  When every lim(r) is 0 nothing is launched and the call
+ * returns DLC_OK.  out must not overlap a source; sources may alias each other.
+ * CONSEQUENCES.  m = 1, DLC_FUSE_NONE, weight 1.0 is an exact conversion copy.  The result does not depend on the plan,
+ * the batching of rows or any ld (NaN payloads aside).  With DLC_FUSE_ZSCORE, a source swapped for its negation together
+ * with its lower_is_better flag leaves the bits unchanged.
+ * PLANS.  DLC_FUSE_PLAN_ROW: one workgroup per row, one launch, no workspace (it is ignored): the row is swept for its
+ * statistic(s) and once more to write, the re-reads served by L2.  DLC_FUSE_PLAN_SLAB, for few long rows (a streaming
+ * batch against >= 10^5 key-frames): workgroups cover (row, slab of 4096 columns); at most three launches -- the slabs'
+ * sums or min / max, the slabs' squared deviations, the write -- with the slab partials in the workspace, folded by
+ * every workgroup of the next launch with the same tree; no atomics, no memset.  It needs
+ * dlc_fuse_rows_workspace_bytes(rows, n, m) bytes, 16-byte aligned.  DLC_FUSE_PLAN_AUTO picks SLAB when the workspace
+ * suffices, some row offers >= 8192 columns and rows < 2 x the device's compute units (docs/LAB.md 25: the measurement
+ * behind the rule), else ROW.  A forced plan works at every shape.  Loads and stores are 16 bytes per lane where the
+ * addresses allow; sources need only their element's alignment (8 bytes, 4 for DLC_F32), out 8 bytes.  Every launch is on
+ * `stream`; the call never synchronises.  Any rows >= 1, 1 <= n < 2^31.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, m outside 1..DLC_MAX_FUSE, an unknown dtype, norm or plan, a non-finite
+ * weight, rows < 1, n < 1, lds[i] < n, ld_out < n or a pointer not aligned to its element; DLC_ERR_BAD_SHAPE for
+ * n >= 2^31; DLC_ERR_WORKSPACE for DLC_FUSE_PLAN_SLAB with a workspace that is missing, too small or not 16-byte
+ * aligned.  Nothing is written then.  dlc_fuse_rows_workspace_bytes returns 0 for rows < 1, n < 1, n >= 2^31 or m
+ * outside 1..DLC_MAX_FUSE.
+ */
+#define DLC_MAX_FUSE 8
+enum { DLC_FUSE_NONE = 0, DLC_FUSE_ZSCORE = 1, DLC_FUSE_MINMAX = 2 };
+enum { DLC_FUSE_PLAN_AUTO = 0, DLC_FUSE_PLAN_ROW = 1, DLC_FUSE_PLAN_SLAB = 2 };
+size_t dlc_fuse_rows_workspace_bytes(int64_t rows, int64_t n, int m);
+int dlc_fuse_rows(dlc_ctx* ctx, int m, const int* dtypes, const void* const* scores, const int64_t* lds,
+                  const double* weights, const int* lower_is_better,
+                  int64_t rows, int64_t n, int64_t limit0, int64_t limit_step, int norm, int plan,
+                  double* out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Distinct-place candidates: the windowed peak top-k of score rows -- the last step of SeqSLAM's matcher (Milford &
  * Wyeth, ICRA 2012, III-D: the best trajectory, then the best one outside a window of key-frames around it).  A revisit
  * of key-frame j scores almost as well against j - 1, j + 1, ...: a plain top-k fills up with the neighbours of one peak.
