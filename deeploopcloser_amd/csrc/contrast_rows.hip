@@ -12,7 +12,7 @@
 //   other wave (a row's ends, a radius between two RBs) selects the identity (-0.0 / +0.0) for what is not in the window.
 //   The four results of a lane go back through LDS so that the wave's stores are coalesced: 16 bytes per lane from the
 //   first 16-byte aligned cell on, 8 bytes for the cell before it and at the row's limit.  Only offered cells are written.
-#include "dlc_internal.h"
+#include "score_rows.h"
 
 // every product and every sum rounded on its own (hipcc contracts a * b + c into an fma otherwise), as NumPy's are
 #pragma clang fp contract(off)
@@ -32,13 +32,6 @@ struct CrArgs {
     long long n;
     int radius;
 };
-
-template <int DT>
-__device__ __forceinline__ double cr_load(const void* M, long long at) {
-    if (DT == DLC_F64) return ((const double*)M)[at];
-    if (DT == DLC_F32) return (double)((const float*)M)[at];
-    return (double)((const long long*)M)[at];                     // round to nearest even; exact below 2^53
-}
 
 // The four cells of a lane from their 4 + 2 RB window elements x (x[c + t]: cell c's element t, its own at t = RB).
 // tlo[c] .. thi[c]: the elements of cell c's window, looked at only when !WHOLE.
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(64 * CR_WAVES) void contrast_rows_kernel(const CrAr
             for (int cc = lane; cc < SEGW; cc += 64) {
                 const long long col = slab0 - RB + cc;
                 double v = -0.0;
-                if (col >= 0 && col < lim) v = cr_load<DT>(a.M, row + col);
+                if (col >= 0 && col < lim) v = rows_f64<DT>(a.M, row + col);
                 seg[w][cc] = v;
             }
         }
@@ -151,30 +144,26 @@ extern "C" int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, in
                                  int64_t limit0, int64_t limit_step, int radius,
                                  double* out, int64_t ld_out, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: dtype must be DLC_F64, DLC_F32 or DLC_I64");
-    if (!scores || !out || rows < 1 || n < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: bad argument");
+    if (!out || (((uintptr_t)out) & 7)) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: out must be set and aligned to 8 bytes");
     if (radius < 1 || radius > CR_MAX_RADIUS)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: radius=%d outside 1..%d", radius, CR_MAX_RADIUS);
-    if (ld < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: ld=%lld < n=%lld", (long long)ld, (long long)n);
     if (ld_out < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: ld_out=%lld < n=%lld", (long long)ld_out, (long long)n);
-    if ((((uintptr_t)scores) & (dtype == DLC_F32 ? 3 : 7)) || (((uintptr_t)out) & 7))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "contrast_rows: scores and out must be aligned to their element");
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "contrast_rows: n must be below 2^31");
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, 0, 0, 0};
+    const int rc = rows_check(ctx, "contrast_rows", s, nullptr, DLC_ERR_BAD_SHAPE);
+    if (rc != DLC_OK) return rc;
     // columns any row offers (limits are linear in the row, so the largest sits at an end)
     const int64_t cols = dlc::max_row_limit(0, rows - 1, n, limit0, limit_step);
     if (cols == 0) return DLC_OK;
     CrArgs a;
-    a.M = scores; a.out = out; a.ld = ld; a.ld_out = ld_out; a.limit0 = limit0; a.limit_step = limit_step;
+    rows_fill(a, s);
+    a.out = out; a.ld_out = ld_out;
     a.slabs = dlc::cdiv(cols, CR_SLAB);
     if (rows > 0x7fffffffffffffffll / a.slabs) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "contrast_rows: rows * n too large");
-    a.items = rows * a.slabs; a.n = n; a.radius = radius;
+    a.items = rows * a.slabs; a.radius = radius;
     const int64_t want = dlc::cdiv(a.items, CR_WAVES);
     const unsigned blocks = (unsigned)(want < CR_MAX_BLOCKS ? want : CR_MAX_BLOCKS);
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLC_F64) return cr_launch<DLC_F64>(ctx, a, blocks, st);
-    if (dtype == DLC_F32) return cr_launch<DLC_F32>(ctx, a, blocks, st);
-    return cr_launch<DLC_I64>(ctx, a, blocks, st);
+    return rows_dispatch(dtype, [&](auto dt) { return cr_launch<dt.value>(ctx, a, blocks, st); });
 }

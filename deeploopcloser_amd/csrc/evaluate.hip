@@ -19,6 +19,7 @@
 // A cell is topk_list.h's TlPair, as in peak_rows.hip: a KEY whose unsigned order is the order of merit (the ordered key
 // of the fp64 value, or the biased int64, complemented when lower is better) and a TAG (~column << 32: larger = lower
 // column).  a.before(b) is "a beats b".
+#include "score_rows.h"
 #include "topk_list.h"
 
 namespace {
@@ -33,7 +34,6 @@ constexpr long long EV_FLUSH_ITEMS = (1ll << 31) / EV_CHUNK;       // items betw
 constexpr int RK_TILE = 1024;                     // columns a slab of the rank pass is a multiple of
 constexpr int RK_MAX_WG = 2048;                   // workgroups the slab passes aim at (rows x slabs)
 constexpr int RK_MAX_BLOCKS = 1 << 20;            // more items than this: a workgroup takes several, one after the other
-constexpr unsigned long long EV_SIGN = 0x8000000000000000ull;
 
 struct EvMatrix {
     const void* M;
@@ -41,19 +41,6 @@ struct EvMatrix {
     long long rows, n, ld, ldt, limit0, limit_step, absent;
     int lower, has_absent;
 };
-
-// The key of the cell at `at` in the order of the numbers; false: the cell is not offered (a NaN, the absent value).
-template <int DT>
-__device__ __forceinline__ bool ev_key(const EvMatrix& a, long long at, unsigned long long& key) {
-    if (DT == DLC_I64) {
-        const long long v = ((const long long*)a.M)[at];
-        key = (unsigned long long)v ^ EV_SIGN;
-        return !(a.has_absent && v == a.absent);
-    }
-    const double v = DT == DLC_F64 ? ((const double*)a.M)[at] : (double)((const float*)a.M)[at];
-    key = dlc_f64_key(v);
-    return v == v;
-}
 
 // ---- counts ---------------------------------------------------------------------------------------------------------------
 struct PrArgs {
@@ -88,7 +75,7 @@ __global__ __launch_bounds__(256) void pr_count_kernel(const PrArgs a) {
     unsigned long long* keys = ev_lds;                                // [T]
     unsigned* hist = (unsigned*)(ev_lds + T);                         // [2][T + 1]: negatives, then positives
     for (int i = tid; i < T; i += 256)
-        keys[i] = DT == DLC_I64 ? (unsigned long long)((const long long*)a.thresholds)[i] ^ EV_SIGN
+        keys[i] = DT == DLC_I64 ? (unsigned long long)((const long long*)a.thresholds)[i] ^ ROWS_SIGN
                                 : dlc_f64_key(((const double*)a.thresholds)[i]);
     for (int i = tid; i < nb; i += 256) hist[i] = 0u;
     __syncthreads();
@@ -120,7 +107,7 @@ __global__ __launch_bounds__(256) void pr_count_kernel(const PrArgs a) {
                 x[u] = 0ull;
                 cls[u] = -1;
                 if (j < lim) {
-                    const bool ok = ev_key<DT>(a.m, r * a.m.ld + j, x[u]);
+                    const bool ok = rows_key<DT>(a.m.M, r * a.m.ld + j, a.m.has_absent, a.m.absent, x[u]);
                     const int pos = a.m.truth[r * a.m.ldt + j] != 0;
                     cls[u] = ok ? pos : -1;
                 }
@@ -213,7 +200,7 @@ __device__ __forceinline__ void rk_scan_best(const EvMatrix& m, long long r, lon
         for (int u = 0; u < 4; ++u) {
             const long long j = j0 + u * 256;
             unsigned long long key = 0ull;
-            const bool pos = j < c1 && ev_key<DT>(m, r * m.ld + j, key) && m.truth[r * m.ldt + j] != 0;
+            const bool pos = j < c1 && rows_key<DT>(m.M, r * m.ld + j, m.has_absent, m.absent, key) && m.truth[r * m.ldt + j] != 0;
             const TlPair e = rk_entry(m, key, j);
             best = TlPair::pick(pos && e.before(best), e, best);
             npos += pos ? 1ull : 0ull;
@@ -230,7 +217,7 @@ __device__ __forceinline__ unsigned long long rk_scan_beat(const EvMatrix& m, lo
         for (int u = 0; u < 4; ++u) {
             const long long j = j0 + u * 256;
             unsigned long long key = 0ull;
-            const bool ok = j < c1 && ev_key<DT>(m, r * m.ld + j, key);
+            const bool ok = j < c1 && rows_key<DT>(m.M, r * m.ld + j, m.has_absent, m.absent, key);
             cnt += ok && rk_entry(m, key, j).before(p) ? 1ull : 0ull;
         }
     }
@@ -349,29 +336,13 @@ int rk_launch(dlc_ctx* ctx, const RkArgs& a, hipStream_t st) {
 }
 
 // The checks the two entry points share; DLC_OK: m is filled in.
-int ev_matrix(dlc_ctx* ctx, const char* who, int dtype, const void* scores, int64_t rows, int64_t n, int64_t ld, int64_t limit0,
-              int64_t limit_step, int lower_is_better, int has_absent, int64_t absent, const uint8_t* truth, int64_t ld_truth,
-              EvMatrix& m) {
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: dtype must be DLC_F64, DLC_F32 or DLC_I64", who);
-    if (!scores || !truth || rows < 1 || n < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: bad argument", who);
-    if (ld < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
-    if (ld_truth < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: ld_truth=%lld < n=%lld", who, (long long)ld_truth, (long long)n);
-    if (has_absent && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: an absent value is for DLC_I64; a float row marks absence with NaN", who);
-    if (((uintptr_t)scores) & (dtype == DLC_F32 ? 3 : 7))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: scores must be aligned to their element", who);
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: n must be below 2^31", who);
-    m.M = scores; m.truth = truth; m.rows = rows; m.n = n; m.ld = ld; m.ldt = ld_truth; m.limit0 = limit0;
-    m.limit_step = limit_step; m.absent = absent; m.lower = lower_is_better ? 1 : 0; m.has_absent = has_absent ? 1 : 0;
-    return DLC_OK;
-}
-
-int ev_workspace(dlc_ctx* ctx, const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
-    if (need == 0) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: rows * n too large", who);
-    if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (or not 16-byte aligned)", who,
-                         workspace ? workspace_bytes : (size_t)0, need);
+int ev_matrix(dlc_ctx* ctx, const char* who, const ScoreRows& s, const uint8_t* truth, int64_t ld_truth, EvMatrix& m) {
+    if (!truth) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: bad argument", who);
+    if (ld_truth < s.n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: ld_truth=%lld < n=%lld", who, (long long)ld_truth, (long long)s.n);
+    const int rc = rows_check(ctx, who, s, nullptr, DLC_ERR_BAD_SHAPE);
+    if (rc != DLC_OK) return rc;
+    rows_fill(m, s);
+    m.truth = truth; m.rows = s.rows; m.ldt = ld_truth; m.absent = s.absent; m.lower = s.lower; m.has_absent = s.has_absent;
     return DLC_OK;
 }
 
@@ -390,15 +361,15 @@ extern "C" int dlc_pr_cell_counts(dlc_ctx* ctx, int dtype, const void* scores, i
                                   int64_t* out_pos, int64_t* out_neg, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     PrArgs a;
-    const int rc = ev_matrix(ctx, "pr_cell_counts", dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better, has_absent,
-                             absent, truth, ld_truth, a.m);
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, has_absent != 0, absent};
+    const int rc = ev_matrix(ctx, "pr_cell_counts", s, truth, ld_truth, a.m);
     if (rc != DLC_OK) return rc;
     if (!thresholds || !out_pos || !out_neg) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "pr_cell_counts: bad argument");
     if (n_thresholds < 1 || n_thresholds > EV_MAX_T)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "pr_cell_counts: n_thresholds=%d outside 1..%d", n_thresholds, EV_MAX_T);
     if ((((uintptr_t)thresholds) & 7) || (((uintptr_t)out_pos) & 7) || (((uintptr_t)out_neg) & 7))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "pr_cell_counts: thresholds and the outputs must be aligned to their element");
-    const int wrc = ev_workspace(ctx, "pr_cell_counts", workspace, workspace_bytes,
+    const int wrc = rows_check_workspace(ctx, "pr_cell_counts", workspace, workspace_bytes,
                                  dlc_pr_cell_counts_workspace_bytes(rows, n, n_thresholds));
     if (wrc != DLC_OK) return wrc;
     const int T = n_thresholds;
@@ -420,8 +391,7 @@ extern "C" int dlc_pr_cell_counts(dlc_ctx* ctx, int dtype, const void* scores, i
             DLC_LAUNCH_CHECK(ctx, "pr_count_kernel");
             return DLC_OK;
         };
-        const int lrc = dtype == DLC_F64 ? launch(pr_count_kernel<DLC_F64>)
-                      : dtype == DLC_F32 ? launch(pr_count_kernel<DLC_F32>) : launch(pr_count_kernel<DLC_I64>);
+        const int lrc = rows_dispatch(dtype, [&](auto dt) { return launch(pr_count_kernel<dt.value>); });
         if (lrc != DLC_OK) return lrc;
     }
     hipLaunchKernelGGL(pr_reduce_kernel, dim3((unsigned)dlc::cdiv(2 * (T + 1), 256)), dim3(256), 0, st,
@@ -443,13 +413,13 @@ extern "C" int dlc_positive_rank_rows(dlc_ctx* ctx, int dtype, const void* score
                                       int64_t* out_npos, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     RkArgs a;
-    const int rc = ev_matrix(ctx, "positive_rank_rows", dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better,
-                             has_absent, absent, truth, ld_truth, a.m);
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, has_absent != 0, absent};
+    const int rc = ev_matrix(ctx, "positive_rank_rows", s, truth, ld_truth, a.m);
     if (rc != DLC_OK) return rc;
     if (!out_rank || !out_idx || !out_npos) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "positive_rank_rows: bad argument");
     if ((((uintptr_t)out_rank) & 7) || (((uintptr_t)out_idx) & 7) || (((uintptr_t)out_npos) & 7))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "positive_rank_rows: the outputs must be aligned to their element");
-    const int wrc = ev_workspace(ctx, "positive_rank_rows", workspace, workspace_bytes,
+    const int wrc = rows_check_workspace(ctx, "positive_rank_rows", workspace, workspace_bytes,
                                  dlc_positive_rank_rows_workspace_bytes(rows, n));
     if (wrc != DLC_OK) return wrc;
     a.ws = (unsigned long long*)workspace; a.out_rank = (long long*)out_rank; a.out_idx = (long long*)out_idx;
@@ -461,7 +431,5 @@ extern "C" int dlc_positive_rank_rows(dlc_ctx* ctx, int dtype, const void* score
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLC_F64) return rk_launch<DLC_F64>(ctx, a, st);
-    if (dtype == DLC_F32) return rk_launch<DLC_F32>(ctx, a, st);
-    return rk_launch<DLC_I64>(ctx, a, st);
+    return rows_dispatch(dtype, [&](auto dt) { return rk_launch<dt.value>(ctx, a, st); });
 }

@@ -15,7 +15,7 @@
 //         workgroup of the next launch folds its row's partials by the same tree.  No atomics, no memset.
 //   Loads and stores are 16 bytes per lane where the cell's address allows it (an 8-byte element whose group starts in
 //   the upper half of its 16 bytes goes as 8 + 16 + 8), element by element at a row's limit.
-#include "dlc_internal.h"
+#include "score_rows.h"
 
 // every product and every sum rounded on its own (hipcc contracts a * b + c into an fma otherwise), as NumPy's are
 #pragma clang fp contract(off)
@@ -197,7 +197,7 @@ struct FrRange {
 // the threads' ranges folded over the workgroup -> (lo, hi) in every thread.  mm: 3 * FR_WAVES words.
 __device__ __forceinline__ void fr_range_fold(FrRange g, double* mm, double& lo, double& hi) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const double qnan = __longlong_as_double(ROWS_NAN_BITS);
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const double ol = __shfl_xor(g.l, off), oh = __shfl_xor(g.h, off);
@@ -410,7 +410,7 @@ extern "C" int dlc_fuse_rows(dlc_ctx* ctx, int m, const int* dtypes, const void*
                              double* out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (m < 1 || m > DLC_MAX_FUSE) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: m=%d outside 1..%d", m, DLC_MAX_FUSE);
-    if (!dtypes || !scores || !lds || !weights || !lower_is_better || !out || rows < 1 || n < 1)
+    if (!dtypes || !scores || !lds || !weights || !lower_is_better || !out)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: bad argument");
     if (norm != DLC_FUSE_NONE && norm != DLC_FUSE_ZSCORE && norm != DLC_FUSE_MINMAX)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: unknown norm %d", norm);
@@ -421,16 +421,15 @@ extern "C" int dlc_fuse_rows(dlc_ctx* ctx, int m, const int* dtypes, const void*
     FrArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < m; ++i) {
-        if (dtypes[i] != DLC_F64 && dtypes[i] != DLC_F32 && dtypes[i] != DLC_I64)
-            return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: source %d: dtype must be DLC_F64, DLC_F32 or DLC_I64", i);
-        if (!scores[i]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: source %d is null", i);
-        if (((uintptr_t)scores[i]) & (dtypes[i] == DLC_F32 ? 3 : 7))
-            return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: source %d must be aligned to its element", i);
-        if (lds[i] < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: lds[%d]=%lld < n=%lld", i, (long long)lds[i], (long long)n);
+        const int rc = rows_check_matrix(ctx, "fuse_rows", dtypes[i], scores[i], lds[i], n);
+        if (rc != DLC_OK) return rc;
         if (!(weights[i] - weights[i] == 0.0)) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "fuse_rows: weights[%d] is not finite", i);
         a.src[i] = scores[i]; a.ld[i] = lds[i]; a.w[i] = weights[i]; a.dt[i] = dtypes[i]; a.lib[i] = lower_is_better[i] != 0;
     }
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "fuse_rows: n must be below 2^31");
+    // the operand's shape, which the sources share, once: on the first of them
+    const ScoreRows s0 = {dtypes[0], scores[0], rows, n, lds[0], limit0, limit_step, 0, 0, 0};
+    const int rc = rows_check(ctx, "fuse_rows", s0, nullptr, DLC_ERR_BAD_SHAPE);
+    if (rc != DLC_OK) return rc;
     const size_t need = fr_workspace(rows, n, m);
     const bool ws_ok = need != 0 && workspace && workspace_bytes >= need && !(((uintptr_t)workspace) & 15);
     if (plan == DLC_FUSE_PLAN_SLAB && !ws_ok)

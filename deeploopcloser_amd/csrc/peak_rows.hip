@@ -17,6 +17,7 @@
 // or the biased int64, complemented when lower is better) and a TAG (~column << 32: larger = lower column).  (0, 0) is
 // the empty slot: below every entry, since a column < 2^31 leaves the tag's top bit set.  Entries of a row are distinct,
 // so the result does not depend on the plan.
+#include "score_rows.h"
 #include "topk_list.h"
 
 namespace {
@@ -25,8 +26,6 @@ constexpr int PK_CHUNK = 256;              // columns of a chunk
 constexpr int PK_CELLS = PK_CHUNK / 64;    // cells of a lane
 constexpr int PK_MAX_WG = 2048;            // workgroups the chunk pass aims at (rows x slabs)
 constexpr int PK_MAX_BLOCKS = 1 << 20;     // more items than this: a workgroup takes several, one after the other
-constexpr unsigned long long PK_SIGN = 0x8000000000000000ull;
-constexpr long long PK_NAN_BITS = 0x7ff8000000000000ll;
 
 struct PkArgs {
     const void* M;
@@ -37,19 +36,6 @@ struct PkArgs {
     long long* out_idx;
     int lower, has_absent, k;
 };
-
-// The key of the cell at `at`; false: the cell is not offered (a NaN, the absent value).
-template <int DT>
-__device__ __forceinline__ bool pk_key(const PkArgs& a, long long at, unsigned long long& key) {
-    if (DT == DLC_I64) {
-        const long long v = ((const long long*)a.M)[at];
-        key = (unsigned long long)v ^ PK_SIGN;
-        return !(a.has_absent && v == a.absent);
-    }
-    const double v = DT == DLC_F64 ? ((const double*)a.M)[at] : (double)((const float*)a.M)[at];
-    key = dlc_f64_key(v);
-    return v == v;
-}
 
 __device__ __forceinline__ TlPair pk_wave_best(TlPair m) {
 #pragma unroll
@@ -73,7 +59,7 @@ __device__ __forceinline__ TlPair pk_chunk_best(const PkArgs& a, long long row, 
     for (int t = 0; t < PK_CELLS; ++t) {                          // (the four loads are in flight together)
         const long long j = j0 + t * 64 + lane;
         key[t] = 0ull;
-        ok[t] = j < lim && pk_key<DT>(a, row + j, key[t]);
+        ok[t] = j < lim && rows_key<DT>(a.M, row + j, a.has_absent, a.absent, key[t]);
     }
     if (SUPP) {
         // lane i holds picks i and 64 + i; near0 / near1: those whose window reaches [j0, j0 + 255]
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(256) void peak_picks_kernel(const PkArgs a) {
     auto emit = [&](long long slot, TlPair m) {
         const bool none = m.is_empty();
         const unsigned long long k2 = a.lower ? ~m.key : m.key;
-        if (IS_INT) ((long long*)a.out_scores)[slot] = none ? -1ll : (long long)(k2 ^ PK_SIGN);
+        if (IS_INT) ((long long*)a.out_scores)[slot] = none ? -1ll : (long long)(k2 ^ ROWS_SIGN);
         else ((double*)a.out_scores)[slot] = none ? (a.lower ? INFINITY : -INFINITY) : dlc_f64_unkey(k2);
         a.out_idx[slot] = none ? -1ll : (long long)(~(unsigned)(m.tag >> 32));
     };
@@ -137,7 +123,7 @@ __global__ __launch_bounds__(256) void peak_picks_kernel(const PkArgs a) {
     for (long long r = blockIdx.x; r < a.rows; r += gridDim.x) {
         if (poisoned) {
             for (int t = tid; t < k; t += 256) {
-                ((double*)a.out_scores)[r * k + t] = __longlong_as_double(PK_NAN_BITS);
+                ((double*)a.out_scores)[r * k + t] = __longlong_as_double(ROWS_NAN_BITS);
                 a.out_idx[r * k + t] = -1;
             }
             continue;
@@ -210,30 +196,20 @@ extern "C" int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype, const void* scores, i
                                   int has_absent, int64_t absent, int k, void* out_scores, int64_t* out_idx,
                                   const int64_t* poison, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: dtype must be DLC_F64, DLC_F32 or DLC_I64");
-    if (!scores || !out_scores || !out_idx || rows < 1 || n < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: bad argument");
-    if (ld < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: ld=%lld < n=%lld", (long long)ld, (long long)n);
+    if (!out_scores || !out_idx || (((uintptr_t)out_scores) & 7) || (((uintptr_t)out_idx) & 7))
+        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: the outputs must be set and aligned to their element");
     if (suppress < 0) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: suppress=%lld is negative", (long long)suppress);
     if (k < 1 || k > DLC_MAX_K) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: k=%d outside 1..%d", k, DLC_MAX_K);
-    if (has_absent && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: an absent value is for DLC_I64; a float row marks absence with NaN");
-    if (poison && dtype == DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: the poison word marks fp64 outputs; DLC_I64 has none");
-    if ((((uintptr_t)scores) & (dtype == DLC_F32 ? 3 : 7)) || (((uintptr_t)out_scores) & 7) || (((uintptr_t)out_idx) & 7) ||
-        (((uintptr_t)poison) & 7))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "peak_topk_rows: scores, the outputs and poison must be aligned to their element");
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "peak_topk_rows: n must be below 2^31");
-    const size_t need = dlc_peak_topk_rows_workspace_bytes(rows, n, k);
-    if (need == 0) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "peak_topk_rows: rows * n too large");
-    if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "peak_topk_rows: workspace %zu < %zu bytes (or not 16-byte aligned)",
-                         workspace ? workspace_bytes : (size_t)0, need);
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, has_absent != 0, absent};
+    int rc = rows_check(ctx, "peak_topk_rows", s, poison, DLC_ERR_BAD_SHAPE);
+    if (rc == DLC_OK)
+        rc = rows_check_workspace(ctx, "peak_topk_rows", workspace, workspace_bytes, dlc_peak_topk_rows_workspace_bytes(rows, n, k));
+    if (rc != DLC_OK) return rc;
     PkArgs a;
-    a.M = scores; a.table = (unsigned long long*)workspace; a.rows = rows; a.n = n; a.ld = ld; a.limit0 = limit0;
-    a.limit_step = limit_step; a.nch = dlc::cdiv(n, PK_CHUNK); a.suppress = suppress; a.absent = absent;
-    a.poison = (const long long*)poison; a.out_scores = out_scores; a.out_idx = (long long*)out_idx;
-    a.lower = lower_is_better ? 1 : 0; a.has_absent = has_absent ? 1 : 0; a.k = k;
+    rows_fill(a, s);
+    a.table = (unsigned long long*)workspace; a.rows = rows; a.nch = dlc::cdiv(n, PK_CHUNK); a.suppress = suppress;
+    a.absent = absent; a.poison = (const long long*)poison; a.out_scores = out_scores; a.out_idx = (long long*)out_idx;
+    a.lower = s.lower; a.has_absent = s.has_absent; a.k = k;
     // columns any row offers (limits are linear in the row, so the largest sits at an end); none: the pick pass alone
     // writes the empty lists
     const int64_t cols = dlc::max_row_limit(0, rows - 1, n, limit0, limit_step);
@@ -246,7 +222,5 @@ extern "C" int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype, const void* scores, i
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLC_F64) return pk_launch<DLC_F64>(ctx, a, chunk_blocks, pick_blocks, st);
-    if (dtype == DLC_F32) return pk_launch<DLC_F32>(ctx, a, chunk_blocks, pick_blocks, st);
-    return pk_launch<DLC_I64>(ctx, a, chunk_blocks, pick_blocks, st);
+    return rows_dispatch(dtype, [&](auto dt) { return pk_launch<dt.value>(ctx, a, chunk_blocks, pick_blocks, st); });
 }

@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
                 const long long base = (rbase - (L - 1) + wrow) * a.ld;
                 for (int cc = lane; cc < wc; cc += 64) {
                     const long long c = j0 - maxoff + cc;
-                    unsigned long long bits = IS_INT ? 0ull : (unsigned long long)SQ_NAN_BITS;
-                    if (c >= 0 && c < lim) bits = sq_load_bits<DT>(a.M, base + c);
+                    unsigned long long bits = IS_INT ? 0ull : (unsigned long long)ROWS_NAN_BITS;
+                    if (c >= 0 && c < lim) bits = rows_bits<DT>(a.M, base + c);
                     win[(size_t)wrow * wc + cc] = bits;
                 }
             }
@@ -131,33 +131,33 @@ __global__ __launch_bounds__(256) void sequence_scan_kernel(const SqArgs a, cons
                         int s = 0;
                         for (; s + 4 <= L; s += 4) acc += (el(s) + el(s + 1)) + (el(s + 2) + el(s + 3));
                         for (; s < L; ++s) acc += el(s);
-                        key = acc ^ SQ_SIGN;
+                        key = acc ^ ROWS_SIGN;
                     } else {
-                        double facc = 0.0;
+                        double facc = 0.0;                        // (sequence_chains_kernel sums the same way)
                         unsigned long long iacc = 0ull;
                         for (int s = 0; s < L; ++s) {
                             const long long jj = j - o[s];
                             const bool in = active && jj >= 0 && jj < lims[lr + L - 1 - s];
                             ok &= in;
-                            const unsigned long long bits = in ? sq_load_bits<DT>(a.M, (r - s) * a.ld + jj)
-                                                               : (IS_INT ? 0ull : (unsigned long long)SQ_NAN_BITS);
+                            const unsigned long long bits = in ? rows_bits<DT>(a.M, (r - s) * a.ld + jj)
+                                                               : (IS_INT ? 0ull : (unsigned long long)ROWS_NAN_BITS);
                             if (IS_INT) iacc += bits;
                             else facc = s == 0 ? __longlong_as_double((long long)bits) : facc + __longlong_as_double((long long)bits);
                         }
                         if (!IS_INT) ok = facc == facc;
-                        key = IS_INT ? (iacc ^ SQ_SIGN) : dlc_f64_key(facc);
+                        key = IS_INT ? (iacc ^ ROWS_SIGN) : dlc_f64_key(facc);
                     }
                     if (a.lower) key = ~key;
                     if (ok && (!have || key > bk)) { have = true; bk = key; bv = v; }
                 }
                 have = have && active;
-                if (a.seq_out && j < slab1) {
+                if (a.seq_out && j < slab1) {                      // (sq_store_dense, spelled out: docs/LAB.md 26)
                     const unsigned long long k2 = a.lower ? ~bk : bk;
                     const long long at = (r - a.row0) * a.ld_out + j;
-                    if (IS_INT) ((long long*)a.seq_out)[at] = have ? (long long)(k2 ^ SQ_SIGN) : -1ll;
-                    else ((double*)a.seq_out)[at] = have ? dlc_f64_unkey(k2) : __longlong_as_double(SQ_NAN_BITS);
+                    if (IS_INT) ((long long*)a.seq_out)[at] = have ? (long long)(k2 ^ ROWS_SIGN) : -1ll;
+                    else ((double*)a.seq_out)[at] = have ? dlc_f64_unkey(k2) : __longlong_as_double(ROWS_NAN_BITS);
                 }
-                if (a.part) {
+                if (a.part) {                                     // (the elastic scan offers the same way: docs/LAB.md 26)
                     const TlPair cand = {bk, ((unsigned long long)(~(unsigned)j) << 32) | (unsigned)bv};
                     for (unsigned long long todo = __ballot(have && cand.before(wl.kth)); todo; todo &= todo - 1) {
                         const TlPair x = cand.shfl(__ffsll((long long)todo) - 1);
@@ -216,35 +216,20 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
                                  void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace, size_t workspace_bytes,
                                  void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: dtype must be DLC_F64, DLC_F32 or DLC_I64");
-    if (!scores || !offsets || rows < 1 || row0 < 0 || row0 >= rows || n < 1 || ld < n)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: bad argument");
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: n must be below 2^31");
+    if (!offsets) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: bad argument");
     if (L < 1 || L > SQ_MAX_L) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: L=%d outside 1..%d", L, SQ_MAX_L);
     if (n_slopes < 1 || n_slopes > SQ_MAX_SLOPES)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: n_slopes=%d outside 1..%d", n_slopes, SQ_MAX_SLOPES);
-    const bool lists = out_scores != nullptr || out_idx != nullptr || out_slope != nullptr;
-    if (lists && (!out_scores || !out_idx))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: out_scores and out_idx come together");
-    if (!lists && !seq_out) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: no output given");
-    if (seq_out && ld_out < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: ld_out < n");
-    if (lists && (k < 1 || k > DLC_MAX_K))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: k=%d outside 1..%d", k, DLC_MAX_K);
-    if (poison && dtype == DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_topk: the poison word marks fp64 outputs; DLC_I64 has none");
     SqOffsets offs;
     int maxoff = 0;
-    const int bad = sq_pack_offsets(ctx, "sequence_topk", offsets, n_slopes, L, &offs, &maxoff);
-    if (bad != DLC_OK) return bad;
+    int rc = sq_pack_offsets(ctx, "sequence_topk", offsets, n_slopes, L, &offs, &maxoff);
+    if (rc != DLC_OK) return rc;
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, 0, 0};
+    SqArgs a;
+    rc = sq_front(ctx, "sequence_topk", s, row0, L, k, out_scores, out_idx, out_slope, seq_out, ld_out, poison, workspace,
+                  workspace_bytes, dlc_sequence_topk_workspace_bytes(rows, n, L, n_slopes, k), a);
+    if (rc != DLC_OK) return rc;
     const int64_t rows_out = rows - row0;
-    size_t need = 0;
-    if (lists) {
-        need = dlc_sequence_topk_workspace_bytes(rows, n, L, n_slopes, k);
-        if (!workspace || workspace_bytes < need)
-            return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sequence_topk: workspace %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0,
-                             need);
-    }
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
     hipStream_t st = (hipStream_t)stream;
@@ -253,46 +238,22 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
     const int64_t cols = seq_out ? n : dlc::max_row_limit(row0, rows - 1, n, limit0, limit_step);
     dlc::SlabSplit slabs = {1, 1};
     if (cols > 0) slabs = dlc::split_slabs(dlc::cdiv(rows, SQ_MAX_RB), dlc::cdiv(cols, SQ_SLAB_UNIT), TL_MAX_SLABS);
-    const int64_t G = slabs.G;
     // a few rows (a streamed batch): smaller row blocks, down to a row per wave, until the chip has a workgroup per CU --
     // the window's extra rows then come from L2, and a wave's serial chain of additions is what the call takes
     int rb_cap = SQ_MAX_RB;
-    while (rb_cap > 4 && dlc::cdiv(rows_out, rb_cap) * G < 256) rb_cap /= 2;
-    const SqPlan p = sq_plan(rows_out, L, n_slopes, maxoff, lists ? k : 1, lists, rb_cap);
-    SqArgs a;
-    a.M = scores; a.rows = rows; a.row0 = row0; a.n = n; a.ld = ld; a.limit0 = limit0; a.limit_step = limit_step;
-    a.tiles_per_slab = slabs.tiles_per_slab; a.ld_out = ld_out; a.part = lists ? (unsigned long long*)workspace : nullptr; a.seq_out = seq_out;
-    a.poison = (const long long*)poison; a.L = L; a.V = n_slopes; a.maxoff = maxoff; a.lower = lower_is_better ? 1 : 0; a.k = lists ? k : 1;
-    a.rb = p.rb; a.ct = p.ct; a.wc = p.ct + maxoff;
+    while (rb_cap > 4 && dlc::cdiv(rows_out, rb_cap) * slabs.G < 256) rb_cap /= 2;
+    const SqPlan p = sq_plan(rows_out, L, n_slopes, maxoff, a.k, a.part != nullptr, rb_cap);
+    a.tiles_per_slab = slabs.tiles_per_slab; a.V = n_slopes; a.maxoff = maxoff; a.rb = p.rb; a.ct = p.ct; a.wc = p.ct + maxoff;
     const int64_t blocks = dlc::cdiv(rows_out, p.rb);
     if (blocks > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sequence_topk: too many rows for one launch");
     auto launch = [&](auto kern) -> int {
         DLC_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)G), dim3(256), p.lds, st, a, offs);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)slabs.G), dim3(256), p.lds, st, a, offs);
         DLC_LAUNCH_CHECK(ctx, "sequence_scan_kernel");
         return DLC_OK;
     };
-    int rc;
-    if (p.staged) {
-        if (dtype == DLC_F64) rc = launch(sequence_scan_kernel<DLC_F64, true>);
-        else if (dtype == DLC_F32) rc = launch(sequence_scan_kernel<DLC_F32, true>);
-        else rc = launch(sequence_scan_kernel<DLC_I64, true>);
-    } else {
-        if (dtype == DLC_F64) rc = launch(sequence_scan_kernel<DLC_F64, false>);
-        else if (dtype == DLC_F32) rc = launch(sequence_scan_kernel<DLC_F32, false>);
-        else rc = launch(sequence_scan_kernel<DLC_I64, false>);
-    }
+    if (p.staged) rc = rows_dispatch(dtype, [&](auto dt) { return launch(sequence_scan_kernel<dt.value, true>); });
+    else rc = rows_dispatch(dtype, [&](auto dt) { return launch(sequence_scan_kernel<dt.value, false>); });
     if (rc != DLC_OK) return rc;
-    if (lists) {
-        if (dtype == DLC_I64)
-            hipLaunchKernelGGL(sequence_merge_kernel<true>, dim3((unsigned)rows_out), dim3(256), 0, st,
-                               (const unsigned long long*)workspace, (int)G, k, a.lower, out_scores, (long long*)out_idx,
-                               (int*)out_slope, (const long long*)poison);
-        else
-            hipLaunchKernelGGL(sequence_merge_kernel<false>, dim3((unsigned)rows_out), dim3(256), 0, st,
-                               (const unsigned long long*)workspace, (int)G, k, a.lower, out_scores, (long long*)out_idx,
-                               (int*)out_slope, (const long long*)poison);
-        DLC_LAUNCH_CHECK(ctx, "sequence_merge_kernel");
-    }
-    return DLC_OK;
+    return sq_launch_merge(ctx, dtype, a, slabs.G, out_scores, out_idx, out_slope, st);
 }

@@ -53,8 +53,8 @@ __device__ __forceinline__ void ch_write(const ChArgs& a, long long slot, long l
     a.chain[slot * a.L + t] = col;
     if (!a.cells) return;
     const long long rho = r - (a.L - 1) + t;                      // fp64 goes out by its bits: the conversion from fp32 is exact
-    ((long long*)a.cells)[slot * a.L + t] = col >= 0 ? (long long)sq_load_bits<DT>(a.M, rho * a.ld + col)
-                                                      : (DT == DLC_I64 ? -1ll : SQ_NAN_BITS);
+    ((long long*)a.cells)[slot * a.L + t] = col >= 0 ? (long long)rows_bits<DT>(a.M, rho * a.ld + col)
+                                                      : (DT == DLC_I64 ? -1ll : ROWS_NAN_BITS);
 }
 
 template <int DT>
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(64) void sequence_elastic_chains_kernel(const ChArg
             for (int q = 0; q < CH_MAX_Q; ++q) {
                 const int b = q * 64 + lane;
                 const long long c = (long long)lo + b;
-                x[q] = (q * 64 < wt && b < wt && c >= 0 && c < lim) ? sq_load_bits<DT>(a.M, rho * a.ld + c) : 0ull;
+                x[q] = (q * 64 < wt && b < wt && c >= 0 && c < lim) ? rows_bits<DT>(a.M, rho * a.ld + c) : 0ull;
             }
         };
         unsigned long long cur[CH_MAX_Q], nxt[CH_MAX_Q];
@@ -145,19 +145,19 @@ __global__ __launch_bounds__(256) void sequence_chains_kernel(const ChArgs a, co
     unsigned long long key = 0ull;
     if (ok) {                                                     // lane v: Z_v, newest row first
         const short* o = offs.o + lane * L;
-        double facc = 0.0;
+        double facc = 0.0;                                        // (sequence_scan_kernel<DT, false> sums the same way)
         unsigned long long iacc = 0ull;
         for (int s = 0; s < L; ++s) {
             const long long jj = j - o[s];
             const bool in = jj >= 0 && jj < dlc::row_limit(r - s, a.n, a.limit0, a.limit_step);
             ok &= in;
-            const unsigned long long bits = in ? sq_load_bits<DT>(a.M, (r - s) * a.ld + jj)
-                                               : (IS_INT ? 0ull : (unsigned long long)SQ_NAN_BITS);
+            const unsigned long long bits = in ? rows_bits<DT>(a.M, (r - s) * a.ld + jj)
+                                               : (IS_INT ? 0ull : (unsigned long long)ROWS_NAN_BITS);
             if (IS_INT) iacc += bits;
             else facc = s == 0 ? __longlong_as_double((long long)bits) : facc + __longlong_as_double((long long)bits);
         }
         if (!IS_INT) ok = facc == facc;
-        key = IS_INT ? (iacc ^ SQ_SIGN) : dlc_f64_key(facc);
+        key = IS_INT ? (iacc ^ ROWS_SIGN) : dlc_f64_key(facc);
         if (a.lower) key = ~key;
     }
     bool have = false;
@@ -172,32 +172,21 @@ __global__ __launch_bounds__(256) void sequence_chains_kernel(const ChArgs a, co
     if (lane == 0 && a.slope) a.slope[slot] = bv;
 }
 
-// What the two entry points check alike; `who` names the caller in the message.
-int ch_check(dlc_ctx* ctx, const char* who, int dtype, const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld,
-             int L, int k, const int64_t* idx, const int32_t* out_chain, const int64_t* poison) {
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: dtype must be DLC_F64, DLC_F32 or DLC_I64", who);
-    if (!scores || !idx || !out_chain || rows < 1 || row0 < 0 || row0 >= rows || n < 1 || ld < n)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: bad argument", who);
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: n must be below 2^31", who);
+// What the two entry points check alike (`who` names the caller in the message); DLC_OK: a holds what they fill alike.
+int ch_front(dlc_ctx* ctx, const char* who, const ScoreRows& s, int64_t row0, int L, int k, const int64_t* idx, int32_t* out_chain,
+             void* out_cells, int32_t* out_slope, const int64_t* poison, ChArgs& a) {
+    const int rc = rows_check(ctx, who, s, poison, DLC_ERR_BAD_ARG);
+    if (rc != DLC_OK) return rc;
+    if (!idx || !out_chain || row0 < 0 || row0 >= s.rows) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: bad argument", who);
     if (L < 1 || L > SQ_MAX_L) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: L=%d outside 1..%d", who, L, SQ_MAX_L);
     if (k < 1 || k > DLC_MAX_K) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: k=%d outside 1..%d", who, k, DLC_MAX_K);
-    if (poison && dtype == DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: the poison word marks fp64 outputs; DLC_I64 has none", who);
-    if ((rows - row0) * (int64_t)k > 0x7fffffffll)
+    if ((s.rows - row0) * (int64_t)k > 0x7fffffffll)
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: too many candidates for one launch", who);
+    rows_fill(a, s);
+    a.rows = s.rows; a.row0 = row0; a.slots = (s.rows - row0) * k; a.idx = (const long long*)idx; a.chain = out_chain;
+    a.cells = out_cells; a.slope = out_slope; a.poison = (const long long*)poison; a.L = L; a.d_min = 0; a.d_max = 0; a.V = 0;
+    a.lower = s.lower; a.k = k; a.W = 0;
     return DLC_OK;
-}
-
-ChArgs ch_args(const void* scores, int64_t rows, int64_t row0, int64_t n, int64_t ld, int64_t limit0, int64_t limit_step, int L,
-               int lower_is_better, int k, const int64_t* idx, int32_t* out_chain, void* out_cells, int32_t* out_slope,
-               const int64_t* poison) {
-    ChArgs a;
-    a.M = scores; a.rows = rows; a.row0 = row0; a.n = n; a.ld = ld; a.limit0 = limit0; a.limit_step = limit_step;
-    a.slots = (rows - row0) * k; a.idx = (const long long*)idx; a.chain = out_chain; a.cells = out_cells; a.slope = out_slope;
-    a.poison = (const long long*)poison; a.L = L; a.d_min = 0; a.d_max = 0; a.V = 0; a.lower = lower_is_better ? 1 : 0; a.k = k;
-    a.W = 0;
-    return a;
 }
 
 }  // namespace
@@ -207,23 +196,24 @@ extern "C" int dlc_sequence_elastic_chains(dlc_ctx* ctx, int dtype, const void* 
                                            int lower_is_better, int k, const int64_t* idx, int32_t* out_chain, void* out_cells,
                                            const int64_t* poison, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    const int bad = ch_check(ctx, "sequence_elastic_chains", dtype, scores, rows, row0, n, ld, L, k, idx, out_chain, poison);
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, 0, 0};
+    ChArgs a;
+    const int bad = ch_front(ctx, "sequence_elastic_chains", s, row0, L, k, idx, out_chain, out_cells, nullptr, poison, a);
     if (bad != DLC_OK) return bad;
     if (d_min < 0 || d_min > d_max || d_max > DLC_MAX_STEP)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_chains: steps %d..%d: need 0 <= d_min <= d_max <= %d", d_min,
                          d_max, DLC_MAX_STEP);
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    ChArgs a = ch_args(scores, rows, row0, n, ld, limit0, limit_step, L, lower_is_better, k, idx, out_chain, out_cells, nullptr,
-                       poison);
     a.d_min = d_min; a.d_max = d_max;
     a.W = ((L - 1) * (d_max - d_min) + 1 + 63) / 64 * 64;         // <= 64 * CH_MAX_Q
     const size_t lds = dlc::align_up((size_t)a.W * 8 + (size_t)L * a.W, 16);   // <= 36 KB
     const dim3 grid((unsigned)a.slots);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLC_F64) hipLaunchKernelGGL(sequence_elastic_chains_kernel<DLC_F64>, grid, dim3(64), lds, st, a);
-    else if (dtype == DLC_F32) hipLaunchKernelGGL(sequence_elastic_chains_kernel<DLC_F32>, grid, dim3(64), lds, st, a);
-    else hipLaunchKernelGGL(sequence_elastic_chains_kernel<DLC_I64>, grid, dim3(64), lds, st, a);
+    rows_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(sequence_elastic_chains_kernel<dt.value>, grid, dim3(64), lds, st, a);
+        return 0;
+    });
     DLC_LAUNCH_CHECK(ctx, "sequence_elastic_chains_kernel");
     return DLC_OK;
 }
@@ -233,7 +223,9 @@ extern "C" int dlc_sequence_chains(dlc_ctx* ctx, int dtype, const void* scores, 
                                    int lower_is_better, int k, const int64_t* idx, int32_t* out_chain, void* out_cells,
                                    int32_t* out_slope, const int64_t* poison, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    const int bad = ch_check(ctx, "sequence_chains", dtype, scores, rows, row0, n, ld, L, k, idx, out_chain, poison);
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, 0, 0};
+    ChArgs a;
+    const int bad = ch_front(ctx, "sequence_chains", s, row0, L, k, idx, out_chain, out_cells, out_slope, poison, a);
     if (bad != DLC_OK) return bad;
     if (!offsets) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_chains: bad argument");
     if (n_slopes < 1 || n_slopes > SQ_MAX_SLOPES)
@@ -244,14 +236,13 @@ extern "C" int dlc_sequence_chains(dlc_ctx* ctx, int dtype, const void* scores, 
     if (bad_table != DLC_OK) return bad_table;
     dlc::DeviceGuard guard(ctx->device);
     if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    ChArgs a = ch_args(scores, rows, row0, n, ld, limit0, limit_step, L, lower_is_better, k, idx, out_chain, out_cells, out_slope,
-                       poison);
     a.V = n_slopes;
     const dim3 grid((unsigned)dlc::cdiv(a.slots, 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLC_F64) hipLaunchKernelGGL(sequence_chains_kernel<DLC_F64>, grid, dim3(256), 0, st, a, offs);
-    else if (dtype == DLC_F32) hipLaunchKernelGGL(sequence_chains_kernel<DLC_F32>, grid, dim3(256), 0, st, a, offs);
-    else hipLaunchKernelGGL(sequence_chains_kernel<DLC_I64>, grid, dim3(256), 0, st, a, offs);
+    rows_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(sequence_chains_kernel<dt.value>, grid, dim3(256), 0, st, a, offs);
+        return 0;
+    });
     DLC_LAUNCH_CHECK(ctx, "sequence_chains_kernel");
     return DLC_OK;
 }

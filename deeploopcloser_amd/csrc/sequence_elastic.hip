@@ -66,11 +66,8 @@ __global__ __launch_bounds__(256) void sequence_elastic_scan_kernel(const ElArgs
     for (long long j0 = slab0; j0 < slab1; j0 += ct) {
         const int top = slab1 - j0 < ct ? (int)(slab1 - j0) : ct;   // the tile's columns in use
         if (!search) {
-            for (int jl = lane; jl < top; jl += 64) {
-                const long long at = (r - a.row0) * a.ld_out + j0 + jl;
-                if (IS_INT) ((long long*)a.seq_out)[at] = -1ll;
-                else ((double*)a.seq_out)[at] = __longlong_as_double(SQ_NAN_BITS);
-            }
+            for (int jl = lane; jl < top; jl += 64)
+                sq_store_dense<IS_INT>(a.seq_out, (r - a.row0) * a.ld_out + j0 + jl, false, 0ull);
             continue;
         }
         const int qtop = (lead + top - 1) >> 6;
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(256) void sequence_elastic_scan_kernel(const ElArgs
                 const int b = q * 64 + lane;
                 const long long c = j0 - lead + b;
                 const bool in = c >= 0 && c < lim;
-                const unsigned long long bits = in ? sq_load_bits<DT>(a.M, base + c) : 0ull;
+                const unsigned long long bits = in ? rows_bits<DT>(a.M, base + c) : 0ull;
                 bool ok = in;
                 unsigned long long key = 0ull;                    // (the best predecessor's, then the cell's own)
                 int span = 0;
@@ -100,8 +97,8 @@ __global__ __launch_bounds__(256) void sequence_elastic_scan_kernel(const ElArgs
                 // (el_level_key of sequence_merge.h, spelled out: through the function the same arithmetic is scheduled
                 // differently and this kernel measured 8-17 % slower, docs/LAB.md 19)
                 if (IS_INT) {
-                    const unsigned long long sum = t > 0 ? ((key ^ flip) ^ SQ_SIGN) + bits : bits;
-                    key = (sum ^ SQ_SIGN) ^ flip;
+                    const unsigned long long sum = t > 0 ? ((key ^ flip) ^ ROWS_SIGN) + bits : bits;
+                    key = (sum ^ ROWS_SIGN) ^ flip;
                 } else {
                     const double x = __longlong_as_double((long long)bits);
                     const double sum = t > 0 ? dlc_f64_unkey(key ^ flip) + x : x;
@@ -118,13 +115,8 @@ __global__ __launch_bounds__(256) void sequence_elastic_scan_kernel(const ElArgs
                     continue;
                 }
                 const bool have = ok && c < slab1;                // (b >= lead here: c >= j0)
-                if (a.seq_out && c < slab1) {
-                    const unsigned long long k2 = key ^ flip;
-                    const long long at = (r - a.row0) * a.ld_out + c;
-                    if (IS_INT) ((long long*)a.seq_out)[at] = have ? (long long)(k2 ^ SQ_SIGN) : -1ll;
-                    else ((double*)a.seq_out)[at] = have ? dlc_f64_unkey(k2) : __longlong_as_double(SQ_NAN_BITS);
-                }
-                if (a.part) {
+                if (a.seq_out && c < slab1) sq_store_dense<IS_INT>(a.seq_out, (r - a.row0) * a.ld_out + c, have, key ^ flip);
+                if (a.part) {                                     // (the line scan offers the same way: docs/LAB.md 26)
                     const TlPair cand = {key, ((unsigned long long)(~(unsigned)c) << 32) | (unsigned)span};
                     for (unsigned long long todo = __ballot(have && cand.before(wl.kth)); todo; todo &= todo - 1) {
                         const TlPair x = cand.shfl(__ffsll((long long)todo) - 1);
@@ -173,31 +165,16 @@ extern "C" int dlc_sequence_elastic_topk(dlc_ctx* ctx, int dtype, const void* sc
                                          void* seq_out, int64_t ld_out, const int64_t* poison, void* workspace,
                                          size_t workspace_bytes, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (dtype != DLC_F64 && dtype != DLC_F32 && dtype != DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: dtype must be DLC_F64, DLC_F32 or DLC_I64");
-    if (!scores || rows < 1 || row0 < 0 || row0 >= rows || n < 1 || ld < n)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: bad argument");
-    if (n > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: n must be below 2^31");
     if (L < 1 || L > EL_MAX_L) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: L=%d outside 1..%d", L, EL_MAX_L);
     if (d_min < 0 || d_min > d_max || d_max > DLC_MAX_STEP)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: steps %d..%d: need 0 <= d_min <= d_max <= %d", d_min, d_max,
                          DLC_MAX_STEP);
-    const bool lists = out_scores != nullptr || out_idx != nullptr || out_span != nullptr;
-    if (lists && (!out_scores || !out_idx))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: out_scores and out_idx come together");
-    if (!lists && !seq_out) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: no output given");
-    if (seq_out && ld_out < n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: ld_out < n");
-    if (lists && (k < 1 || k > DLC_MAX_K))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: k=%d outside 1..%d", k, DLC_MAX_K);
-    if (poison && dtype == DLC_I64)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_topk: the poison word marks fp64 outputs; DLC_I64 has none");
+    const ScoreRows s = {dtype, scores, rows, n, ld, limit0, limit_step, lower_is_better != 0, 0, 0};
+    ElArgs a;
+    const int rc = sq_front(ctx, "sequence_elastic_topk", s, row0, L, k, out_scores, out_idx, out_span, seq_out, ld_out, poison,
+                            workspace, workspace_bytes, dlc_sequence_elastic_topk_workspace_bytes(rows, n, L, d_min, d_max, k), a);
+    if (rc != DLC_OK) return rc;
     const int64_t rows_out = rows - row0;
-    if (lists) {
-        const size_t need = dlc_sequence_elastic_topk_workspace_bytes(rows, n, L, d_min, d_max, k);
-        if (!workspace || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < need)
-            return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sequence_elastic_topk: workspace %zu < %zu bytes, or not 16-byte aligned",
-                             workspace ? workspace_bytes : (size_t)0, need);
-    }
     const int64_t blocks = dlc::cdiv(rows_out, EL_ROWS);
     if (rows_out > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sequence_elastic_topk: too many rows for one launch");
     dlc::DeviceGuard guard(ctx->device);
@@ -209,26 +186,12 @@ extern "C" int dlc_sequence_elastic_topk(dlc_ctx* ctx, int dtype, const void* sc
     const ElPlan p = el_plan(L, d_max, blocks, cols);
     dlc::SlabSplit slabs = {1, 1};
     if (cols > 0) slabs = dlc::split_slabs(dlc::cdiv(rows, EL_ROWS), dlc::cdiv(cols, p.ct), TL_MAX_SLABS);
-    ElArgs a;
-    a.M = scores; a.rows = rows; a.row0 = row0; a.n = n; a.ld = ld; a.limit0 = limit0; a.limit_step = limit_step;
-    a.tiles_per_slab = slabs.tiles_per_slab; a.ld_out = ld_out; a.part = lists ? (unsigned long long*)workspace : nullptr;
-    a.seq_out = seq_out; a.poison = (const long long*)poison; a.L = L; a.d_min = d_min; a.d_max = d_max;
-    a.lower = lower_is_better ? 1 : 0; a.k = lists ? k : 1; a.ct = p.ct; a.lead = p.lead;
+    a.tiles_per_slab = slabs.tiles_per_slab; a.d_min = d_min; a.d_max = d_max; a.ct = p.ct; a.lead = p.lead;
     const dim3 grid((unsigned)blocks, (unsigned)slabs.G);
-    if (dtype == DLC_F64) hipLaunchKernelGGL(sequence_elastic_scan_kernel<DLC_F64>, grid, dim3(256), p.lds, st, a);
-    else if (dtype == DLC_F32) hipLaunchKernelGGL(sequence_elastic_scan_kernel<DLC_F32>, grid, dim3(256), p.lds, st, a);
-    else hipLaunchKernelGGL(sequence_elastic_scan_kernel<DLC_I64>, grid, dim3(256), p.lds, st, a);
+    rows_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(sequence_elastic_scan_kernel<dt.value>, grid, dim3(256), p.lds, st, a);
+        return 0;
+    });
     DLC_LAUNCH_CHECK(ctx, "sequence_elastic_scan_kernel");
-    if (lists) {
-        if (dtype == DLC_I64)
-            hipLaunchKernelGGL(sequence_merge_kernel<true>, dim3((unsigned)rows_out), dim3(256), 0, st,
-                               (const unsigned long long*)workspace, (int)slabs.G, k, a.lower, out_scores, (long long*)out_idx,
-                               (int*)out_span, (const long long*)poison);
-        else
-            hipLaunchKernelGGL(sequence_merge_kernel<false>, dim3((unsigned)rows_out), dim3(256), 0, st,
-                               (const unsigned long long*)workspace, (int)slabs.G, k, a.lower, out_scores, (long long*)out_idx,
-                               (int*)out_span, (const long long*)poison);
-        DLC_LAUNCH_CHECK(ctx, "sequence_merge_kernel");
-    }
-    return DLC_OK;
+    return sq_launch_merge(ctx, dtype, a, slabs.G, out_scores, out_idx, out_span, st);
 }

@@ -42,6 +42,17 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _limits(n, limit0, limit_step):
+    """(limit0, limit_step) as the library takes them: row r offers its first clamp(limit0 + r * limit_step, 0, n) cells,
+    limit0 None = n."""
+    return n if limit0 is None else int(limit0), int(limit_step)
+
+
+def _absent(absent):
+    """(has_absent, absent) as the library takes them; None: no value marks a cell as absent."""
+    return int(absent is not None), 0 if absent is None else int(absent)
+
+
 def check_steps(steps):
     """(d_min, d_max) of an elastic sequence search's steps, checked: two integers, 0 <= d_min <= d_max <= 8."""
     try:
@@ -949,7 +960,7 @@ class Engine:
         need = self.lib.dlc_cnnvtl_distance_topk_workspace_bytes(nq, n, d, k)
         ws = self.workspace("distance_topk", need)
         self._check(self.lib.dlc_cnnvtl_distance_topk(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                                       n if limit0 is None else int(limit0), int(limit_step), int(k),
+                                                       *_limits(n, limit0, limit_step), int(k),
                                                        _ptr(dist), _ptr(idx), _ptr(ws), ws.numel(), self._stream()))
         return dist, idx
 
@@ -967,14 +978,15 @@ class Engine:
         if nq == 0 or n == 0:
             return out
         if d == 0:                                               # empty descriptors: every distance is 0
-            lim = (n if limit0 is None else int(limit0)) + int(limit_step) * torch.arange(nq, device=self.device)
+            lim0, step = _limits(n, limit0, limit_step)
+            lim = lim0 + step * torch.arange(nq, device=self.device)
             out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
             return out
         q = self._rows16(q, d)
         db = self._rows16(db, d)
         ld_out = out.stride(0) if nq > 1 else n
         self._check(self.lib.dlc_cnnvtl_distance_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                                       n if limit0 is None else int(limit0), int(limit_step), _ptr(out),
+                                                       *_limits(n, limit0, limit_step), _ptr(out),
                                                        ld_out, self._stream()))
         self._wrote(out)
         return out
@@ -1041,7 +1053,7 @@ class Engine:
             db = self._rows16_u8(db, d)
             self._check(self.lib.dlc_sad_u8_shift_rows(
                 self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d // width, width, shift,
-                n if limit0 is None else int(limit0), int(limit_step), _ptr(out), out.stride(0) if nq > 1 else n,
+                *_limits(n, limit0, limit_step), _ptr(out), out.stride(0) if nq > 1 else n,
                 None if sh is None else _ptr(sh), 0 if sh is None else (sh.stride(0) if nq > 1 else n), self._stream()))
             self._wrote(out)
             if sh is not None:
@@ -1056,19 +1068,28 @@ class Engine:
         if nq == 0 or n == 0:
             return out
         if d == 0:                                               # empty descriptors: every difference is 0
-            lim = (n if limit0 is None else int(limit0)) + int(limit_step) * torch.arange(nq, device=self.device)
+            lim0, step = _limits(n, limit0, limit_step)
+            lim = lim0 + step * torch.arange(nq, device=self.device)
             out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
             return out
         q = self._rows16_u8(q, d)
         db = self._rows16_u8(db, d)
         ld_out = out.stride(0) if nq > 1 else n
         self._check(self.lib.dlc_sad_u8_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                              n if limit0 is None else int(limit0), int(limit_step), _ptr(out), ld_out,
+                                              *_limits(n, limit0, limit_step), _ptr(out), ld_out,
                                               self._stream()))
         self._wrote(out)
         return out
 
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
+    # the dtype of what a score-row call derives from its rows: int64 from int64 rows, else float64
+    _OUT_DTYPES = {torch.float64: torch.float64, torch.float32: torch.float64, torch.int64: torch.int64}
+
+    def _check_poison(self, who, poison, is_int):
+        """A poison word that is given: a device int64 [1] -- which marks fp64 outputs, so int64 rows take none."""
+        if is_int:
+            raise ValueError("%s: the poison word marks fp64 outputs; int64 rows have none" % who)
+        self._check_out("poison", poison, (1,), torch.int64)
 
     def _score_matrix(self, who, scores, n, nothing):
         """The checks of a score-matrix operand [rows, >= n] (fp64, fp32 or int64 on the device) -> (scores, rows, n, ld):
@@ -1085,6 +1106,13 @@ class Engine:
             scores = scores.contiguous()
         return scores, rows, n, scores.stride(0) if rows > 1 else max(n, scores.stride(0))
 
+    def _offset_table(self, who, offsets, length):
+        """The HOST table offsets [V, L] of a line search as the library takes it: (V, the int32 table's pointer)."""
+        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
+        if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
+            raise ValueError("%s: offsets must be an integer table [n_slopes, L=%d]" % (who, int(length)))
+        return off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32))      # (the pointer keeps the array alive)
+
     def sequence_topk(self, scores, length, offsets, k=None, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,
                       dense=False, poison=None):
         """The sequence search of dlc_sequence_topk (include/dlc.h) over scores [rows, >= n] (fp64, fp32 or int64 on the
@@ -1094,37 +1122,10 @@ class Engine:
         idx int64, slope int32, dense): fp64 scores (int64 for int64 input); k None -> no lists (None three times);
         dense: the [rows - row0, n] cell scores as well (NaN / -1 where a cell is not offered), else None.
         poison: a device int64 [1] read by the kernels; non-zero -> every fp64 slot NaN, idx and slope -1."""
-        scores, rows, n, ld = self._score_matrix("sequence_topk", scores, n, "search")
-        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
-        if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
-            raise ValueError("sequence_topk: offsets must be an integer table [n_slopes, L=%d]" % int(length))
-        if not 0 <= int(row0) < rows:
-            raise ValueError("sequence_topk: row0=%d outside 0..%d" % (row0, rows - 1))
-        if k is None and not dense:
-            raise ValueError("sequence_topk: neither lists (k) nor the dense scores were asked for")
-        if k is not None and not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("sequence_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if poison is not None:
-            self._check_out("poison", poison, (1,), torch.int64)
-        out_dtype = torch.int64 if scores.dtype == torch.int64 else torch.float64
-        ro = rows - int(row0)
-        o_s = o_i = o_v = seq = ws = None
-        if k is not None:
-            o_s = torch.empty((ro, k), dtype=out_dtype, device=self.device)
-            o_i = torch.empty((ro, k), dtype=torch.int64, device=self.device)
-            o_v = torch.empty((ro, k), dtype=torch.int32, device=self.device)
-            need = self.lib.dlc_sequence_topk_workspace_bytes(rows, n, int(length), off.shape[0], int(k))
-            if need == 0:
-                raise ValueError("sequence_topk: L=%d, %d slopes, k=%d, n=%d outside the supported sizes" % (length, off.shape[0], k, n))
-            ws = self.workspace("sequence_topk", need)
-        if dense:
-            seq = torch.empty((ro, n), dtype=out_dtype, device=self.device)
-        self._check(self.lib.dlc_sequence_topk(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(length), off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(lower_is_better)),
-            1 if k is None else int(k), _ptr(o_s), _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws),
-            ws.numel() if ws is not None else 0, self._stream()))
-        return o_s, o_i, o_v, seq
+        mat = self._score_matrix("sequence_topk", scores, n, "search")
+        table = self._offset_table("sequence_topk", offsets, length)
+        return self._sequence_search("sequence_topk", self.lib.dlc_sequence_topk, self.lib.dlc_sequence_topk_workspace_bytes, mat,
+                                     length, table[:1], table, k, row0, limit0, limit_step, lower_is_better, dense, poison)
 
     def sequence_elastic_topk(self, scores, length, steps, k=None, row0=0, n=None, limit0=None, limit_step=0,
                               lower_is_better=False, dense=False, poison=None):
@@ -1134,35 +1135,45 @@ class Engine:
         the k best cells among its first clamp(limit0 + r * limit_step, 0, n) (limit0 None = n).  Returns (scores
         [rows - row0, k], idx int64, span int32, dense) as sequence_topk does, the span -- the key-frames the chosen chain
         covers -- in the slope's place.  poison: as in sequence_topk."""
-        scores, rows, n, ld = self._score_matrix("sequence_elastic_topk", scores, n, "search")
-        d_min, d_max = check_steps(steps)
+        mat = self._score_matrix("sequence_elastic_topk", scores, n, "search")
+        steps = check_steps(steps)
         if not 1 <= int(length) <= 64:
             raise ValueError("sequence_elastic_topk: L=%d outside 1..64" % int(length))
+        return self._sequence_search("sequence_elastic_topk", self.lib.dlc_sequence_elastic_topk,
+                                     self.lib.dlc_sequence_elastic_topk_workspace_bytes, mat, length, steps, steps, k, row0,
+                                     limit0, limit_step, lower_is_better, dense, poison)
+
+    def _sequence_search(self, who, call, size, mat, length, size_args, call_args, k, row0, limit0, limit_step, lower_is_better,
+                         dense, poison):
+        """What the two searches do alike once each has checked its table or steps: the other checks, the three lists,
+        the workspace, the dense buffer and the call.  call, size: dlc_<who> and dlc_<who>_workspace_bytes; size_args:
+        what `size` takes between L and k; call_args: what `call` takes between L and lower_is_better."""
+        scores, rows, n, ld = mat
         if not 0 <= int(row0) < rows:
-            raise ValueError("sequence_elastic_topk: row0=%d outside 0..%d" % (row0, rows - 1))
+            raise ValueError("%s: row0=%d outside 0..%d" % (who, row0, rows - 1))
         if k is None and not dense:
-            raise ValueError("sequence_elastic_topk: neither lists (k) nor the dense scores were asked for")
+            raise ValueError("%s: neither lists (k) nor the dense scores were asked for" % who)
         if k is not None and not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("sequence_elastic_topk: k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+            raise ValueError("%s: k=%d outside 1..%d" % (who, k, L.DLC_MAX_K))
         if poison is not None:
-            self._check_out("poison", poison, (1,), torch.int64)
-        out_dtype = torch.int64 if scores.dtype == torch.int64 else torch.float64
+            self._check_poison(who, poison, scores.dtype == torch.int64)
+        out_dtype = self._OUT_DTYPES[scores.dtype]
         ro = rows - int(row0)
         o_s = o_i = o_v = seq = ws = None
         if k is not None:
             o_s = torch.empty((ro, k), dtype=out_dtype, device=self.device)
             o_i = torch.empty((ro, k), dtype=torch.int64, device=self.device)
             o_v = torch.empty((ro, k), dtype=torch.int32, device=self.device)
-            need = self.lib.dlc_sequence_elastic_topk_workspace_bytes(rows, n, int(length), d_min, d_max, int(k))
+            need = size(rows, n, int(length), *size_args, int(k))
             if need == 0:
-                raise ValueError("sequence_elastic_topk: L=%d, k=%d, n=%d outside the supported sizes" % (length, k, n))
-            ws = self.workspace("sequence_elastic_topk", need)
+                raise ValueError("%s: L=%d, k=%d, n=%d outside the supported sizes" % (who, length, k, n))
+            ws = self.workspace(who, need)
         if dense:
             seq = torch.empty((ro, n), dtype=out_dtype, device=self.device)
-        self._check(self.lib.dlc_sequence_elastic_topk(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(length), d_min, d_max, int(bool(lower_is_better)), 1 if k is None else int(k), _ptr(o_s),
-            _ptr(o_i), _ptr(o_v), _ptr(seq), n, _ptr(poison), _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
+        self._check(call(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, *_limits(n, limit0, limit_step),
+            int(length), *call_args, int(bool(lower_is_better)), 1 if k is None else int(k), _ptr(o_s), _ptr(o_i), _ptr(o_v),
+            _ptr(seq), n, _ptr(poison), _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
         return o_s, o_i, o_v, seq
 
     def _chain_args(self, who, scores, length, idx, row0, n, poison):
@@ -1177,10 +1188,24 @@ class Engine:
         if idx.shape[0] != rows - int(row0) or not 1 <= idx.shape[1] <= L.DLC_MAX_K:
             raise ValueError("%s: idx [%d, %d]: need [%d, 1..%d]" % (who, idx.shape[0], idx.shape[1], rows - int(row0), L.DLC_MAX_K))
         if poison is not None:
-            if scores.dtype == torch.int64:
-                raise ValueError("%s: the poison word marks fp64 outputs; int64 rows have none" % who)
-            self._check_out("poison", poison, (1,), torch.int64)
+            self._check_poison(who, poison, scores.dtype == torch.int64)
         return scores, rows, n, ld, idx.contiguous(), idx.shape[1]
+
+    def _sequence_chains(self, who, call, scores, length, call_args, idx, row0, n, limit0, limit_step, lower_is_better, cells, poison,
+                         with_slope):
+        """What the two chain calls do alike on top of _chain_args: the outputs and the call -> (chain, cells, slope).
+        call: dlc_<who>; call_args: what it takes between L and lower_is_better; with_slope: it writes the winning slope
+        as well."""
+        scores, rows, n, ld, idx, k = self._chain_args(who, scores, length, idx, row0, n, poison)
+        shape = (rows - int(row0), k, int(length))
+        chain = torch.empty(shape, dtype=torch.int32, device=self.device)
+        o_c = torch.empty(shape, dtype=self._OUT_DTYPES[scores.dtype], device=self.device) if cells else None
+        slope = torch.empty(shape[:2], dtype=torch.int32, device=self.device) if with_slope else None
+        self._check(call(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, *_limits(n, limit0, limit_step),
+            int(length), *call_args, int(bool(lower_is_better)), k, _ptr(idx), _ptr(chain), _ptr(o_c),
+            *((_ptr(slope),) if with_slope else ()), _ptr(poison), self._stream()))
+        return chain, o_c, slope
 
     def sequence_elastic_chains(self, scores, length, steps, idx, row0=0, n=None, limit0=None, limit_step=0,
                                 lower_is_better=False, cells=False, poison=None):
@@ -1190,19 +1215,9 @@ class Engine:
         first.  Returns (chain int32 [rows - row0, k, L], cells or None): cells=True adds the matrix cells along the chain
         (fp64, int64 for int64 scores), which summed oldest first give the candidate's score bit for bit.  A slot that
         is no chain (empty, past the row's limit, no valid chain, poisoned) holds -1 and NaN / -1."""
-        scores, rows, n, ld, idx, k = self._chain_args("sequence_elastic_chains", scores, length, idx, row0, n, poison)
-        d_min, d_max = check_steps(steps)
-        ro = rows - int(row0)
-        chain = torch.empty((ro, k, int(length)), dtype=torch.int32, device=self.device)
-        o_c = None
-        if cells:
-            o_c = torch.empty((ro, k, int(length)), dtype=torch.int64 if scores.dtype == torch.int64 else torch.float64,
-                              device=self.device)
-        self._check(self.lib.dlc_sequence_elastic_chains(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(length), d_min, d_max, int(bool(lower_is_better)), k, _ptr(idx), _ptr(chain), _ptr(o_c),
-            _ptr(poison), self._stream()))
-        return chain, o_c
+        return self._sequence_chains("sequence_elastic_chains", self.lib.dlc_sequence_elastic_chains, scores, length,
+                                     check_steps(steps), idx, row0, n, limit0, limit_step, lower_is_better, cells, poison,
+                                     False)[:2]
 
     def sequence_chains(self, scores, length, offsets, idx, row0=0, n=None, limit0=None, limit_step=0, lower_is_better=False,
                         cells=False, poison=None):
@@ -1211,22 +1226,9 @@ class Engine:
         its winning line, oldest frame first.  Returns (chain int32 [rows - row0, k, L], cells or None, slope int32
         [rows - row0, k]): the cells summed NEWEST first give the candidate's score bit for bit; slope is the row of the
         table that won.  A slot that is no chain holds -1 (cells NaN / -1, slope -1)."""
-        scores, rows, n, ld, idx, k = self._chain_args("sequence_chains", scores, length, idx, row0, n, poison)
-        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32)
-        if off.ndim != 2 or off.shape[1] != int(length) or not np.array_equal(off, np.asarray(offsets)):
-            raise ValueError("sequence_chains: offsets must be an integer table [n_slopes, L=%d]" % int(length))
-        ro = rows - int(row0)
-        chain = torch.empty((ro, k, int(length)), dtype=torch.int32, device=self.device)
-        slope = torch.empty((ro, k), dtype=torch.int32, device=self.device)
-        o_c = None
-        if cells:
-            o_c = torch.empty((ro, k, int(length)), dtype=torch.int64 if scores.dtype == torch.int64 else torch.float64,
-                              device=self.device)
-        self._check(self.lib.dlc_sequence_chains(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, int(row0), n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(length), off.shape[0], off.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(lower_is_better)), k,
-            _ptr(idx), _ptr(chain), _ptr(o_c), _ptr(slope), _ptr(poison), self._stream()))
-        return chain, o_c, slope
+        table = self._offset_table("sequence_chains", offsets, length)
+        return self._sequence_chains("sequence_chains", self.lib.dlc_sequence_chains, scores, length, table, idx, row0, n, limit0,
+                                     limit_step, lower_is_better, cells, poison, True)
 
     def contrast_rows(self, scores, radius, n=None, limit0=None, limit_step=0, out=None):
         """SeqSLAM's local contrast normalisation of score rows (dlc_contrast_rows, include/dlc.h): fp64 [rows, n], cell
@@ -1244,7 +1246,7 @@ class Engine:
                              float("nan") if limit0 is not None or limit_step != 0 else None, wider=True)
         ld_out = out.stride(0) if rows > 1 else n
         self._check(self.lib.dlc_contrast_rows(self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld,
-                                                n if limit0 is None else int(limit0), int(limit_step), int(radius), _ptr(out),
+                                                *_limits(n, limit0, limit_step), int(radius), _ptr(out),
                                                 ld_out, self._stream()))
         self._wrote(out)
         return out[:, :n]
@@ -1300,7 +1302,7 @@ class Engine:
         self._check(self.lib.dlc_fuse_rows(
             self.ctx, m, (C.c_int * m)(*[self._SEQ_DTYPES[s.dtype] for s in mats]),
             (C.c_void_p * m)(*[s.data_ptr() for s in mats]), (C.c_int64 * m)(*lds), (C.c_double * m)(*w.tolist()),
-            (C.c_int * m)(*[int(v) for v in lib]), rows, n, n if limit0 is None else int(limit0), int(limit_step),
+            (C.c_int * m)(*[int(v) for v in lib]), rows, n, *_limits(n, limit0, limit_step),
             self._FUSE_NORMS[norm], self._FUSE_PLANS[plan], _ptr(out), ld_out, _ptr(ws), ws.numel() if ws is not None else 0,
             self._stream()))
         self._wrote(out)
@@ -1325,19 +1327,17 @@ class Engine:
         if absent is not None and not is_int:
             raise ValueError("peak_topk_rows: absent is for int64 rows (a float row marks absence with NaN)")
         if poison is not None:
-            if is_int:
-                raise ValueError("peak_topk_rows: the poison word marks fp64 outputs; int64 rows have none")
-            self._check_out("poison", poison, (1,), torch.int64)
-        o_s = torch.empty((rows, k), dtype=torch.int64 if is_int else torch.float64, device=self.device)
+            self._check_poison("peak_topk_rows", poison, is_int)
+        o_s = torch.empty((rows, k), dtype=self._OUT_DTYPES[scores.dtype], device=self.device)
         o_i = torch.empty((rows, k), dtype=torch.int64, device=self.device)
         need = self.lib.dlc_peak_topk_rows_workspace_bytes(rows, n, k)
         if need == 0:
             raise ValueError("peak_topk_rows: rows=%d, n=%d outside the supported sizes" % (rows, n))
         ws = self.workspace("peak_topk_rows", need)
         self._check(self.lib.dlc_peak_topk_rows(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(bool(lower_is_better)), suppress, int(absent is not None), 0 if absent is None else int(absent),
-            k, _ptr(o_s), _ptr(o_i), _ptr(poison), _ptr(ws), ws.numel(), self._stream()))
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, *_limits(n, limit0, limit_step),
+            int(bool(lower_is_better)), suppress, *_absent(absent), k, _ptr(o_s), _ptr(o_i), _ptr(poison), _ptr(ws), ws.numel(),
+            self._stream()))
         return o_s, o_i
 
     def _truth_mask(self, who, truth, rows, n):
@@ -1396,8 +1396,8 @@ class Engine:
             raise ValueError("pr_cell_counts: rows=%d, n=%d outside the supported sizes" % (rows, n))
         ws = self.workspace("pr_cell_counts", need)
         self._check(self.lib.dlc_pr_cell_counts(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(bool(lower_is_better)), int(absent is not None), 0 if absent is None else int(absent),
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, *_limits(n, limit0, limit_step),
+            int(bool(lower_is_better)), *_absent(absent),
             _ptr(truth), ldt, _ptr(t), t.numel(), _ptr(pos), _ptr(neg), _ptr(ws), ws.numel(), self._stream()))
         return pos, neg
 
@@ -1416,8 +1416,8 @@ class Engine:
             raise ValueError("positive_rank_rows: rows=%d, n=%d outside the supported sizes" % (rows, n))
         ws = self.workspace("positive_rank_rows", need)
         self._check(self.lib.dlc_positive_rank_rows(
-            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, n if limit0 is None else int(limit0),
-            int(limit_step), int(bool(lower_is_better)), int(absent is not None), 0 if absent is None else int(absent),
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, *_limits(n, limit0, limit_step),
+            int(bool(lower_is_better)), *_absent(absent),
             _ptr(truth), ldt, _ptr(rank), _ptr(idx), _ptr(npos), _ptr(ws), ws.numel(), self._stream()))
         return rank, idx, npos
 
@@ -1749,7 +1749,7 @@ class Engine:
         if both and nq > 1 and o_k.stride(0) != ld_out:
             raise ValueError("cosine_score_rows: out and out_keys must have one row stride (%d, %d)" % (ld_out, o_k.stride(0)))
         self._check(self.lib.dlc_cosine_score_rows(self.ctx, _TORCH_TO_DLC[q.dtype], _ptr(q), nq, q.stride(0), _ptr(db), n,
-                                                    db.stride(0), d, n if limit0 is None else int(limit0), int(limit_step),
+                                                    db.stride(0), d, *_limits(n, limit0, limit_step),
                                                     _ptr(o_s), _ptr(o_k), ld_out, self._stream()))
         for t in (o_s, o_k):
             if t is not None:

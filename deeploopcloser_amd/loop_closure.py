@@ -70,6 +70,13 @@ def _nothing_older(b, k, fill, dtype, device):
             torch.full((b, k), -1, dtype=torch.int64, device=device))
 
 
+def _empty_result(b, k, fill, dtype, device, chains, length):
+    """A detector's result for b frames none of which has a candidate: _nothing_older's (scores, ids), and with chains
+    the chain [b, k, L] too, -1 everywhere."""
+    out = _nothing_older(b, k, fill, dtype, device)
+    return out + (torch.full((b, k, length), -1, dtype=torch.int32, device=device),) if chains else out
+
+
 def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None, chains=False):
     """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
     if sequence is not None:
@@ -103,11 +110,6 @@ def _loops(values, ids, first_id, limit, lower_is_better=False, chains=None):
     length = ch.shape[2]
     return [f + ([(f[0] - (length - 1) + t, int(ch[r, c, t])) for t in range(length)],)
             for f, (r, c) in zip(found, zip(*np.nonzero(ok)))]
-
-
-def _no_chains(b, k, length, device):
-    """chain [b, k, L] of b frames none of which has a candidate: -1 everywhere."""
-    return torch.full((b, k, length), -1, dtype=torch.int32, device=device)
 
 
 class LoopClosureDetector:
@@ -180,9 +182,8 @@ class LoopClosureDetector:
             raise ValueError("descriptors must be [B, dim]")
         outs = [self._step(x[lo:lo + self.max_batch]) for lo in range(0, x.shape[0], self.max_batch)]
         if not outs:
-            out = _nothing_older(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
-                                 self.db.engine.device)
-            return out + (_no_chains(0, self.k, self.sequence, self.db.engine.device),) if self.chains else out
+            return _empty_result(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
+                                 self.db.engine.device, self.chains, self.sequence)
         if len(outs) == 1:                                   # (torch.cat of one tensor is a copy: two launches per batch)
             return outs[0]
         return tuple(torch.cat(t) for t in zip(*outs))
@@ -435,9 +436,8 @@ class SdavLoopClosureDetector:
 
     def _nothing_older(self, b):
         """(-inf, -1) in every slot of b frames' lists; (NaN, -1) once the stream is poisoned."""
-        s, i = _nothing_older(b, self.k, float("-inf"), torch.float64, self.stream.engine.device)
-        out = (torch.where(self.poisoned != 0, float("nan"), s), i)
-        return out + (_no_chains(b, self.k, self.sequence, i.device),) if self.chains else out
+        s, *rest = _empty_result(b, self.k, float("-inf"), torch.float64, self.stream.engine.device, self.chains, self.sequence)
+        return (torch.where(self.poisoned != 0, float("nan"), s), *rest)
 
     # ---- two batches in flight ------------------------------------------------------------------------------------------
     # query_and_insert runs a batch's six launches one behind the other: copy, quantisation, the strip's product kernel (200
@@ -613,11 +613,8 @@ class CnnVtlLoopClosureDetector:
             return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
                                                   limit0=first - self.exclusion, limit_step=1)
         if b == 0:
-            if self.contrast is not None:
-                out = _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
-            else:
-                out = _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
-            return out + (_no_chains(0, self.k, self.sequence, db.engine.device),) if self.chains else out
+            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
+            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
         # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
         db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
                      out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
@@ -707,11 +704,8 @@ class SeqSlamLoopClosureDetector:
         first, _ = db.append(x)
         b = x.shape[0]
         if b == 0:
-            if self.contrast is not None:
-                out = _nothing_older(0, self.k, float("inf"), torch.float64, db.engine.device)
-            else:
-                out = _nothing_older(0, self.k, -1, torch.int64, db.engine.device)
-            return out + (_no_chains(0, self.k, self.sequence, db.engine.device),) if self.chains else out
+            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
+            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
         q = db.rows[first:first + b]
         if self._seq is None:
             if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
@@ -849,8 +843,7 @@ class FusedLoopClosureDetector:
         if any(x.dim() != 2 or x.shape[0] != b for x in xs):
             raise ValueError("query_and_insert: every member's descriptors must be [B, dim] with one B")
         if b == 0:
-            out = _nothing_older(0, self.k, float("-inf"), torch.float64, eng.device)
-            return out + (_no_chains(0, self.k, self.sequence, eng.device),) if self.chains else out
+            return _empty_result(0, self.k, float("-inf"), torch.float64, eng.device, self.chains, self.sequence)
         first = len(self)
         for db, x in zip(self.dbs, xs):
             if db.append(x)[0] != first:

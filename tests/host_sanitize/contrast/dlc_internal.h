@@ -13,6 +13,7 @@
 #define DLC_ERR_BAD_ARG -1
 #define DLC_ERR_BAD_SHAPE -2
 #define DLC_ERR_HIP -4
+#define DLC_ERR_WORKSPACE -5
 enum { DLC_F32 = 2, DLC_F64 = 3, DLC_I64 = 6 };
 struct dlc_ctx { int device; };
 typedef void* hipStream_t;
@@ -26,6 +27,12 @@ inline dim3 threadIdx, blockIdx, gridDim;
 #define __launch_bounds__(x)
 inline void __syncthreads() {}
 inline int __builtin_amdgcn_readfirstlane(int v) { return v; }
+// what csrc/score_rows.h names beside the loader the kernel uses
+inline long long __double_as_longlong(double v) { long long d; memcpy(&d, &v, 8); return d; }
+inline unsigned long long dlc_f64_key(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
 template <typename K, typename A> void emu_launch(K kern, dim3 grid, dim3 block, const A& a) {
     gridDim = grid;
     for (unsigned b = 0; b < grid.x; ++b)

@@ -11,6 +11,7 @@ from conftest import ROOT
 def test_kernel_text_on_the_host_under_sanitizers(tmp_path):
     here = os.path.join(ROOT, "tests", "host_sanitize", "contrast")
     shutil.copy(os.path.join(ROOT, "deeploopcloser_amd", "csrc", "contrast_rows.hip"), str(tmp_path / "contrast_rows.cpp"))
+    shutil.copy(os.path.join(ROOT, "deeploopcloser_amd", "csrc", "score_rows.h"), str(tmp_path / "score_rows.h"))
     for name in ("dlc_internal.h", "driver.cpp"):
         shutil.copy(os.path.join(here, name), str(tmp_path / name))
     exe = str(tmp_path / "contrast_host")

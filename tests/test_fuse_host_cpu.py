@@ -14,6 +14,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"          # the vector types of the kern
 def test_kernel_text_on_the_host_under_sanitizers(tmp_path):
     here = os.path.join(ROOT, "tests", "host_sanitize", "fuse")
     shutil.copy(os.path.join(ROOT, "deeploopcloser_amd", "csrc", "fuse_rows.hip"), str(tmp_path / "fuse_rows.cpp"))
+    shutil.copy(os.path.join(ROOT, "deeploopcloser_amd", "csrc", "score_rows.h"), str(tmp_path / "score_rows.h"))
     for name in ("dlc_internal.h", "driver.cpp"):
         shutil.copy(os.path.join(here, name), str(tmp_path / name))
     exe = str(tmp_path / "fuse_host")

@@ -295,6 +295,11 @@ def test_bad_arguments(dlc):
               "null out_chain": dict(chain=None), "rows 0": dict(rows=0), "row0 = rows": dict(row0=8), "row0 < 0": dict(row0=-1),
               "n 0": dict(n=0), "ld < n": dict(ld=49), "n 2^31": dict(n=1 << 31, ld=1 << 31), "L 0": dict(L=0), "L 65": dict(L=65),
               "k 0": dict(k=0), "k 129": dict(k=129), "poison with int64": dict(dtype=_lib.DLC_I64, poison=pw)}
+    # a scores pointer off its element's alignment, inside a buffer a row larger than the call describes
+    big = torch.zeros(9 * 50, dtype=torch.float64, device=e.device)
+    assert big.data_ptr() % 8 == 0
+    for name, dt, shift in (("f64", _lib.DLC_F64, 4), ("f32", _lib.DLC_F32, 2), ("i64", _lib.DLC_I64, 4)):
+        common["misaligned scores " + name] = dict(dtype=dt, scores=C.c_void_p(big.data_ptr() + shift))
     # elastic
     names = ["ctx", "dtype", "scores", "rows", "row0", "n", "ld", "limit0", "step", "L", "d_min", "d_max", "lower", "k", "idx",
              "chain", "cells", "poison", "stream"]

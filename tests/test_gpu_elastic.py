@@ -377,6 +377,11 @@ def test_bad_arguments(dlc):
            "ld_out < n": but(ld_out=49), "n 2^31": but(n=1 << 31, ld=1 << 31), "L 0": but(L=0), "L 65": but(L=65),
            "d_min > d_max": but(d_min=3), "d_min < 0": but(d_min=-1), "d_max 9": but(d_max=9), "k 0": but(k=0),
            "k 129": but(k=129), "poison with int64": but(dtype=_lib.DLC_I64, poison=pw)}
+    # a scores pointer off its element's alignment, inside a buffer a row larger than the call describes
+    big = torch.zeros(9 * 50, dtype=torch.float64, device=e.device)
+    assert big.data_ptr() % 8 == 0
+    for name, dt, shift in (("f64", _lib.DLC_F64, 4), ("f32", _lib.DLC_F32, 2), ("i64", _lib.DLC_I64, 4)):
+        bad["misaligned scores " + name] = but(dtype=dt, scores=C.c_void_p(big.data_ptr() + shift))
     for what, args in bad.items():
         assert f(*args) == _lib.DLC_ERR_BAD_ARG, what
         assert b"sequence_elastic_topk" in e.lib.dlc_last_error(e.ctx), what

@@ -1,6 +1,7 @@
 """GPU sequence search (dlc_sequence_topk, Engine.sequence_topk, deeploopcloser_amd.sequence, SdavLoopClosureDetector with
 sequence=L, the CLI) against the NumPy restatement of the definition (tests/sequence_oracle.py).  Every comparison is
 exact: integers by value, fp64 by bit pattern, NaN slots by position."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -15,6 +16,7 @@ import sequence_oracle as so
 pytestmark = pytest.mark.gpu
 
 MAX_K = 128
+SENTINEL = 0x5A5A5A5A5A5A5A5A
 
 
 @pytest.fixture(scope="module")
@@ -221,6 +223,40 @@ def test_bad_arguments(dlc):
     for args in ((0, 50, 3, 1, 3), (8, 0, 3, 1, 3), (8, 1 << 31, 3, 1, 3), (8, 50, 0, 1, 3), (8, 50, 65, 1, 3), (8, 50, 3, 0, 3),
                  (8, 50, 3, 17, 3), (8, 50, 3, 1, 0), (8, 50, 3, 1, MAX_K + 1)):
         assert e.lib.dlc_sequence_topk_workspace_bytes(*args) == 0
+    # the library's own checks of the pointers the engine never gets wrong; no call here reaches a launch
+    from deeploopcloser_amd import _lib
+    need = e.lib.dlc_sequence_topk_workspace_bytes(8, 50, 3, 1, 4)
+    o_s = torch.full((8, 4), SENTINEL, dtype=torch.int64, device=e.device)
+    o_i = torch.full((8, 4), SENTINEL, dtype=torch.int64, device=e.device)
+    o_v = torch.full((8, 4), 0x5A5A5A5A, dtype=torch.int32, device=e.device)
+    ws = torch.empty(need + 16, dtype=torch.uint8, device=e.device)
+    assert ws.data_ptr() % 16 == 0
+    off = (C.c_int32 * 3)(0, 1, 2)
+    names = ["ctx", "dtype", "scores", "rows", "row0", "n", "ld", "limit0", "step", "L", "n_slopes", "offsets", "lower", "k",
+             "out_s", "out_i", "out_v", "seq", "ld_out", "poison", "ws", "bytes", "stream"]
+    good = (e.ctx, _lib.DLC_F64, C.c_void_p(m.data_ptr()), 8, 0, 50, 50, 50, 0, 3, 1, off, 0, 4, C.c_void_p(o_s.data_ptr()),
+            C.c_void_p(o_i.data_ptr()), C.c_void_p(o_v.data_ptr()), None, 50, None, C.c_void_p(ws.data_ptr()), need, None)
+    assert len(good) == len(names)
+
+    def but(**change):
+        return tuple(change.get(name, v) for name, v in zip(names, good))
+
+    f = e.lib.dlc_sequence_topk
+    assert f(*good) == _lib.DLC_OK
+    torch.cuda.synchronize()
+    assert o_i[2:, 0].tolist() == [2] * 6 and o_i[:2, 0].tolist() == [-1] * 2      # (column 2 is the first with a whole line)
+    o_s.fill_(SENTINEL), o_i.fill_(SENTINEL), o_v.fill_(0x5A5A5A5A)
+    # a scores pointer off its element's alignment, inside a buffer a row larger than the call describes
+    big = torch.zeros(9 * 50, dtype=torch.float64, device=e.device)
+    assert big.data_ptr() % 8 == 0
+    for name, dt, shift in (("f64", _lib.DLC_F64, 4), ("f32", _lib.DLC_F32, 2), ("i64", _lib.DLC_I64, 4)):
+        assert f(*but(dtype=dt, scores=C.c_void_p(big.data_ptr() + shift))) == _lib.DLC_ERR_BAD_ARG, name
+        assert b"sequence_topk" in e.lib.dlc_last_error(e.ctx), name
+    assert f(*but(n=1 << 31, ld=1 << 31)) == _lib.DLC_ERR_BAD_ARG
+    assert f(*but(ws=C.c_void_p(ws.data_ptr() + 8))) == _lib.DLC_ERR_WORKSPACE
+    assert b"sequence_topk" in e.lib.dlc_last_error(e.ctx)
+    torch.cuda.synchronize()
+    assert all(bool((t == SENTINEL).all()) for t in (o_s, o_i)) and bool((o_v == 0x5A5A5A5A).all()), "an error wrote"
 
 
 def test_module_functions_numpy_and_tensors(dlc):
