@@ -25,6 +25,10 @@ DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 DLC_MAX_FUSE = 8             # the most score sources dlc_fuse_rows takes
 DLC_FUSE_NONE, DLC_FUSE_ZSCORE, DLC_FUSE_MINMAX = 0, 1, 2
 DLC_FUSE_PLAN_AUTO, DLC_FUSE_PLAN_ROW, DLC_FUSE_PLAN_SLAB = 0, 1, 2
+DLC_TRACK_AUTO, DLC_TRACK_RESIDENT, DLC_TRACK_ROWS = 0, 1, 2
+DLC_TRACK_RESIDENT_MAX = 8192   # the most columns the RESIDENT plan of dlc_track_rows keeps in LDS
+DLC_TRACK_JUMP, DLC_TRACK_FROM_NULL, DLC_TRACK_ORIGIN, DLC_TRACK_ABSENT = -1, -2, -3, -128     # back-pointer codes
+DLC_TRACK_END_FILTERED, DLC_TRACK_NO_PATH = -2, -2
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -115,6 +119,10 @@ SIGNATURES = {
     "dlc_peak_topk_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_peak_topk_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _i64, _int, _i64, _int, _vp, _vp, _vp,
                                   _vp, _sz, _vp]),
+    "dlc_track_rows_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "dlc_track_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _dbl, _dbl, _dbl, _int, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "dlc_track_backtrace": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "dlc_pr_cell_counts_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_pr_cell_counts": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _int, _vp, _vp,
                                   _vp, _sz, _vp]),

@@ -47,6 +47,7 @@ enum {
     DLC_ATTR_SPLIT_F16 = 51,     // gemm_split_f16_kernel
     DLC_ATTR_DS_DMA = 52,        // distinctive_score_dma_kernel
     DLC_ATTR_CONV_SPLIT_F16 = 53,    // gemm_split_f16_kernel<SP_CONV>
+    DLC_ATTR_TRACK_BASE = 54,    // track_resident_kernel: + {fp64, fp32, int64 -> 0, 1, 2} * 2 + (8 columns per thread ? 1 : 0)  -> bits 54..59
 };
 
 namespace dlc {

@@ -1340,6 +1340,89 @@ class Engine:
             self._stream()))
         return o_s, o_i
 
+    _TRACK_PLANS = {None: L.DLC_TRACK_AUTO, "auto": L.DLC_TRACK_AUTO, "resident": L.DLC_TRACK_RESIDENT, "rows": L.DLC_TRACK_ROWS}
+
+    def track_state(self, n, dtype):
+        """A fresh state of track_rows for rows of `dtype`: (V [n], head [4]) -- V float64 (int64 for int64 rows) holding
+        the absent mark, NaN / INT64_MIN, and an all-zero head."""
+        out = self._OUT_DTYPES[dtype]
+        mark = float("nan") if out == torch.float64 else -(1 << 63)
+        return (torch.full((int(n),), mark, dtype=out, device=self.device), torch.zeros(4, dtype=torch.int64, device=self.device))
+
+    def track_rows(self, scores, V, head, steps=(0, 2), jump=0.0, gate=0.0, null_score=float("nan"), n=None, limit0=None,
+                   limit_step=0, lower_is_better=False, plan=None, back=False, dense=False):
+        """Place tracking, the max-plus filter of dlc_track_rows (include/dlc.h), over the next rows of a traversal:
+        scores [rows, >= n] (fp64, fp32 or int64 on the device; a row-strided view is taken as it is), row r offering its
+        first clamp(limit0 + r * limit_step, 0, n) cells (limit0 None = n).  V [>= n] and head [4] are the state
+        (track_state), updated in place.  steps = (d_min, d_max): the key-frames a place may advance per frame at no
+        cost; jump: the cost of any other place; gate: the cost of entering or leaving "no loop"; null_score: what a
+        frame that closes no loop scores, NaN = there is no such state.  Returns (place, g, G, U, backU, back, dense):
+        per row the filtered place (int64, -1 = no loop), the best column g, its value G and the no-loop value U (fp64,
+        int64 for int64 rows; absent = NaN / INT64_MIN), the no-loop state's back-pointer (int8); back: the cells'
+        back-pointers int8 [rows, n] (back=True, or an int8 tensor [rows, >= n] to write them into), else None; dense:
+        V of every row [rows, n], else None.  plan: None / "auto", "resident" (n <= 8192) or "rows"."""
+        who = "track_rows"
+        scores, rows, n, ld = self._score_matrix(who, scores, n, "track")
+        d_min, d_max = check_steps(steps)
+        if plan not in self._TRACK_PLANS:
+            raise ValueError("%s: plan=%r is none of auto, resident, rows" % (who, plan))
+        out_dtype = self._OUT_DTYPES[scores.dtype]
+        if not isinstance(V, torch.Tensor) or V.dim() != 1 or V.dtype != out_dtype or V.device != self.device or V.shape[0] < n \
+                or not V.is_contiguous():
+            raise ValueError("%s: V must be a contiguous %s tensor [>= %d] on %s" % (who, out_dtype, n, self.device))
+        self._check_out("head", head, (4,), torch.int64)
+        o_back = None
+        if isinstance(back, torch.Tensor):
+            if back.dim() != 2 or back.dtype != torch.int8 or back.device != self.device or back.shape[0] != rows \
+                    or back.shape[1] < n or back.stride(1) != 1 or (rows > 1 and back.stride(0) < n):
+                raise ValueError("%s: back must be an int8 tensor [%d, >= %d] on %s with unit column stride" % (who, rows, n, self.device))
+            o_back = back
+        elif back:
+            o_back = torch.empty((rows, n), dtype=torch.int8, device=self.device)
+        ld_back = 0 if o_back is None else (o_back.stride(0) if rows > 1 else max(n, o_back.stride(0)))
+        o_dense = torch.empty((rows, n), dtype=out_dtype, device=self.device) if dense else None
+        place, g = (torch.empty(rows, dtype=torch.int64, device=self.device) for _ in range(2))
+        o_G, o_U = (torch.empty(rows, dtype=out_dtype, device=self.device) for _ in range(2))
+        o_bu = torch.empty(rows, dtype=torch.int8, device=self.device)
+        need = self.lib.dlc_track_rows_workspace_bytes(rows, n, self._TRACK_PLANS[plan])
+        if need == 0:
+            raise ValueError("%s: rows=%d, n=%d outside what plan %r takes" % (who, rows, n, plan))
+        ws = self.workspace(who, need)
+        self._check(self.lib.dlc_track_rows(
+            self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld, *_limits(n, limit0, limit_step), d_min, d_max,
+            int(bool(lower_is_better)), float(jump), float(gate), float(null_score), self._TRACK_PLANS[plan], _ptr(V), _ptr(head),
+            _ptr(place), _ptr(g), _ptr(o_G), _ptr(o_U), _ptr(o_bu), _ptr(o_back), ld_back, _ptr(o_dense), n, _ptr(ws), ws.numel(),
+            self._stream()))
+        for t in (V, head) + ((back,) if isinstance(back, torch.Tensor) else ()):
+            self._wrote(t)
+        return place, g, o_G, o_U, o_bu, o_back, o_dense
+
+    def track_backtrace(self, back, backU, g, end=L.DLC_TRACK_END_FILTERED, place_last=None, n=None):
+        """The labelling behind a state (dlc_track_backtrace, include/dlc.h): back int8 [rows, >= n], backU int8 [rows] and
+        g int64 [rows] are track_rows' outputs for every row of a traversal so far; end: the last row's state to start
+        from -- a column, -1 for no loop, or DLC_TRACK_END_FILTERED (the default): place_last, a device int64 [1], the last
+        row's filtered place.  Returns path int64 [rows]: every row's key-frame, -1 = no loop, -2 where no path exists."""
+        who = "track_backtrace"
+        if not isinstance(back, torch.Tensor) or back.dim() != 2 or back.dtype != torch.int8 or back.device != self.device \
+                or back.shape[0] < 1 or back.stride(1) != 1:
+            raise ValueError("%s: back must be an int8 tensor [rows, >= n] on %s" % (who, self.device))
+        rows = back.shape[0]
+        n = back.shape[1] if n is None else int(n)
+        if not 1 <= n <= back.shape[1]:
+            raise ValueError("%s: n=%d outside 1..%d" % (who, n, back.shape[1]))
+        self._check_out("backU", backU, (rows,), torch.int8)
+        self._check_out("g", g, (rows,), torch.int64)
+        end = int(end)
+        if end == L.DLC_TRACK_END_FILTERED:
+            self._check_out("place_last", place_last, (1,), torch.int64)
+        elif not -1 <= end < n:
+            raise ValueError("%s: end=%d is no column of %d, -1 or DLC_TRACK_END_FILTERED" % (who, end, n))
+        path = torch.empty(rows, dtype=torch.int64, device=self.device)
+        self._check(self.lib.dlc_track_backtrace(
+            self.ctx, rows, n, _ptr(back), back.stride(0) if rows > 1 else max(n, back.stride(0)), _ptr(backU), _ptr(g),
+            _ptr(place_last if end == L.DLC_TRACK_END_FILTERED else None), end, _ptr(path), self._stream()))
+        return path
+
     def _truth_mask(self, who, truth, rows, n):
         """The checks of a truth mask [rows, >= n] (uint8 or bool on the device; non-zero = a true match) -> (truth, ld):
         a row-strided view is taken as it is, anything else made contiguous."""

@@ -77,10 +77,13 @@ def _empty_result(b, k, fill, dtype, device, chains, length):
     return out + (torch.full((b, k, length), -1, dtype=torch.int32, device=device),) if chains else out
 
 
-def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None, chains=False):
+def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None, chains=False,
+                     track=None):
     """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
     if sequence is not None:
-        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps, chains)
+        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps, chains, track)
+    if track is not None:
+        raise ValueError("track needs sequence=L (L = 1 searches the frame scores themselves)")
     if chains:
         raise ValueError("chains needs sequence=L")
     if slopes is not None:
@@ -143,10 +146,15 @@ class LoopClosureDetector:
 
     chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert returns a third
     tensor, chain int32 [B, k, L] -- for every candidate the key-frame id each of the last L frames was matched to, oldest
-    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs."""
+    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs.
+
+    track = {steps, jump, gate, null_score, history} (needs sequence=L, L = 1 allowed; on every detector that searches
+    through _SequenceRows): a tracking.PlaceTracker runs over the same rows, after `contrast` and with the same limits --
+    here the int64 key rows, so jump, gate and null_score are integers in units of 2^-40.  It is `detector.tracker`:
+    tracker.path() is the smoothed labelling of every frame so far.  query_and_insert returns what it returns without."""
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, track=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -158,9 +166,10 @@ class LoopClosureDetector:
         self.suppress = None if suppress is None else int(suppress)
         self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress,
-                                     steps=steps, chains=self.chains)
+                                     steps=steps, chains=self.chains, track=track)
+        self.tracker = None
         if self._seq is not None:
-            self.slopes, self.steps = self._seq.slopes, self._seq.steps
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
         self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     def __len__(self):
@@ -246,9 +255,16 @@ class _SequenceRows:
     chains = True adds the candidates' chains: after the picks, over the same window, limits and order, the column each
     of the L frames of a candidate was matched to, oldest frame first (dlc_sequence_chains, with steps
     dlc_sequence_elastic_chains, include/dlc.h: one more launch, formed again for the k cells of every row alone, so the
-    picks of `suppress` are served too).  A chain depends on the L rows behind its cell alone."""
+    picks of `suppress` are served too).  A chain depends on the L rows behind its cell alone.
 
-    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None, steps=None, chains=False):
+    track = a dict of tracking.PlaceTracker's options (steps, jump, gate, null_score, history) runs a place tracker
+    beside the search: every batch's rows go through PlaceTracker.update exactly as the search reads them -- behind the
+    contrast front, the same columns and limits, the detector's order of merit -- before the search itself.  `tracker` is
+    that PlaceTracker (None without track=): tracker.path() is the smoothed labelling of every frame so far, last_place
+    the filtered places of the last batch.  The search's lists are what they are without it."""
+
+    def __init__(self, length, slopes, k, dtype, contrast=None, lower_is_better=False, suppress=None, steps=None, chains=False,
+                 track=None):
         from .engine import check_steps
         from .sequence import slope_offsets
         if not 1 <= length <= 64:
@@ -271,6 +287,19 @@ class _SequenceRows:
         self.contrast, self.raw_dtype, self._raw = contrast, dtype, None
         self._raw_item = torch.empty((), dtype=dtype).element_size()
         self.context, self.dtype, self.buf = length - 1, dtype if contrast is None else torch.float64, None
+        self.tracker = self.last_place = None
+        if track is not None:
+            self.set_track(track)
+
+    def set_track(self, track):
+        """track=: the place tracker of these rows, before the first of them."""
+        from .tracking import PlaceTracker
+        if not isinstance(track, dict) or not set(track) <= {"steps", "jump", "gate", "null_score", "history"}:
+            raise ValueError("track must be a dict of steps, jump, gate, null_score, history")
+        if self.buf is not None:
+            raise ValueError("track: the stream has begun")
+        self.tracker = PlaceTracker(lower_is_better=self.lower_is_better, **track)
+        return self.tracker
 
     def batch_rows(self, b, capacity, device):
         """Where the next batch's b score rows go: rows L - 1 .. L - 2 + b (the buffer is re-laid, the context kept, when
@@ -312,6 +341,12 @@ class _SequenceRows:
             keep = buf[b:b + ctx]
             buf[:ctx] = keep.clone() if b < ctx else keep             # (source and destination overlap for short batches)
 
+    def track(self, engine, b, n, limit0):
+        """track=: the batch's b rows, as the search is about to read them, through the place tracker."""
+        if self.tracker is not None:
+            self.tracker.engine = engine
+            self.last_place = self.tracker.update(self.buf[self.context:self.context + b], n=n, limit0=limit0, limit_step=1)[0]
+
     def search(self, engine, b, n, limit0, poison=None):
         """(values [b, k], ids [b, k]) of the batch's b frames, whose raw rows are written: over the first n columns, the
         batch's row r offering limit0 + r of them and every context row one fewer than the row behind it (matrix row m
@@ -319,6 +354,7 @@ class _SequenceRows:
         read).  With chains a third tensor, chain [b, k, L] int32.  Then the last L - 1 rows become the next batch's
         context."""
         self.normalise(engine, n, limit0)
+        self.track(engine, b, n, limit0)
         search = engine.sequence_topk if self.steps is None else engine.sequence_elastic_topk
         s, i, _, dense = search(self.window(b), self.length, self.slopes if self.steps is None else self.steps,
                                 k=self.k if self.suppress is None else None, row0=self.context, n=n,
@@ -373,7 +409,8 @@ class SdavLoopClosureDetector:
     lists them as pairs."""
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
-                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, **stream_args):
+                 device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, track=None,
+                 **stream_args):
         from .similarity import SimilarityStream
         if k < 1:
             raise ValueError("k must be >= 1")
@@ -386,9 +423,10 @@ class SdavLoopClosureDetector:
         self.suppress = None if suppress is None else int(suppress)
         self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress,
-                                     steps=steps, chains=self.chains)
+                                     steps=steps, chains=self.chains, track=track)
+        self.tracker = None
         if self._seq is not None:
-            self.slopes, self.steps = self._seq.slopes, self._seq.steps
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
         self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
                                        **stream_args)
@@ -414,6 +452,7 @@ class SdavLoopClosureDetector:
         if first + b - 1 == 0:                                        # the very first frame alone: nothing older
             if self._seq is not None:                                 # (its row offers nothing, and is context all the same)
                 self._seq.batch_rows(b, st.capacity, eng.device)
+                self._seq.track(eng, b, 1, 0)                         # (the tracker counts every frame)
                 self._seq.advance(b)
             return self._nothing_older(b)
         # frame first + r against every older frame, all B of them in one pair of launches (dlc_sdav_stream_query_batch):
@@ -572,7 +611,7 @@ class CnnVtlLoopClosureDetector:
     frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs."""
 
     def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None, steps=None, chains=False):
+                 contrast=None, suppress=None, steps=None, chains=False, track=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -589,9 +628,10 @@ class CnnVtlLoopClosureDetector:
         self.suppress = None if suppress is None else int(suppress)
         self.chains = bool(chains)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=self.suppress, steps=steps, chains=self.chains)
+                                     suppress=self.suppress, steps=steps, chains=self.chains, track=track)
+        self.tracker = None
         if self._seq is not None:
-            self.slopes, self.steps = self._seq.slopes, self._seq.steps
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
         from .distance import CnnVtlKeyframeDatabase
         self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
@@ -651,7 +691,7 @@ class SeqSlamLoopClosureDetector:
     In both forms the lists do not depend on how the frames are batched."""
 
     def __init__(self, dim, k=5, max_difference=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None, steps=None, chains=False, shift=None, width=None):
+                 contrast=None, suppress=None, steps=None, chains=False, shift=None, width=None, track=None):
         if not 1 <= k <= L.DLC_MAX_K:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         if exclusion < 0:
@@ -682,9 +722,10 @@ class SeqSlamLoopClosureDetector:
         # (without sequence=L `suppress` is served here, by the peak selection over the frame rows themselves)
         self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
                                      suppress=None if self.sequence is None else self.suppress, steps=steps,
-                                     chains=self.chains)
+                                     chains=self.chains, track=track)
+        self.tracker = None
         if self._seq is not None:
-            self.slopes, self.steps = self._seq.slopes, self._seq.steps
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
         self._rows = None                                    # without sequence: the batch's difference rows [b, capacity]
         from .seqslam import SadKeyframeDatabase
         self.db = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
@@ -783,7 +824,7 @@ class FusedLoopClosureDetector:
         self.chains = bool(chains)
         self._seq = _SequenceRows(1 if self.sequence is None else self.sequence, slopes, self.k, torch.float64, self.contrast,
                                   False, self.suppress, steps, self.chains)
-        self.slopes, self.steps = self._seq.slopes, self._seq.steps
+        self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, None
         self.kinds, self.dbs, self._options = [], [], []
         for spec in members:
             if not 2 <= len(spec) <= 3 or spec[0] not in FUSE_MEMBERS:
@@ -813,6 +854,13 @@ class FusedLoopClosureDetector:
 
     def __len__(self):
         return len(self.dbs[0])
+
+    def start_tracking(self, track):
+        """What track= is on the other detectors (LoopClosureDetector), asked for before the first frame: a
+        tracking.PlaceTracker over the fused rows, behind `contrast`, with the search's limits.  Returns it; it is
+        `detector.tracker` from then on."""
+        self.tracker = self._seq.set_track(track)
+        return self.tracker
 
     def _member_rows(self, i, first, b, out):
         """Member i's raw rows of frames first .. first + b - 1 against the key-frames, each frame the ones old enough."""
@@ -939,6 +987,13 @@ def main(argv=None):
     ap.add_argument("--steps", default=None, metavar="DMIN:DMAX",
                     help="with --sequence: the elastic search -- from frame to frame the matched key-frame steps back "
                          "DMIN..DMAX key-frames (0 <= DMIN <= DMAX <= 8) instead of following a straight line")
+    ap.add_argument("--track", default=None, metavar="JUMP:GATE:NULL",
+                    help="with --sequence: a place tracker over the same score rows (a Viterbi filter with a no-loop state): "
+                         "JUMP the cost of changing place, GATE of entering or leaving `no loop`, NULL the score of a frame "
+                         "that closes no loop; after the stream one line `track FRAME KEYFRAME` for every frame the "
+                         "smoothed path places")
+    ap.add_argument("--track-steps", default=None, metavar="DMIN:DMAX",
+                    help="with --track: the key-frames a place advances per frame at no cost (default 0:2)")
     ap.add_argument("--chains", action="store_true",
                     help="with --sequence: under every candidate a line `chain` with the L frame:key-frame pairs it was "
                          "matched along, oldest frame first")
@@ -1053,6 +1108,21 @@ def main(argv=None):
         args.steps = (d_min, d_max)
     if args.chains and args.sequence is None:
         ap.error("--chains needs --sequence")
+    if args.track_steps is not None and args.track is None:
+        ap.error("--track-steps needs --track")
+    if args.track is not None:
+        if args.sequence is None:
+            ap.error("--track needs --sequence")
+        try:
+            jump, gate, null = (float(x) for x in args.track.split(":"))
+            d_min, d_max = (0, 2) if args.track_steps is None else (int(x) for x in args.track_steps.split(":"))
+        except ValueError:
+            ap.error("--track must be JUMP:GATE:NULL (numbers) and --track-steps DMIN:DMAX")
+        if not (np.isfinite(jump) and np.isfinite(gate) and jump >= 0 and gate >= 0) or np.isnan(null):
+            ap.error("--track: JUMP and GATE must be finite and not negative, NULL a number")
+        if not 0 <= d_min <= d_max <= L.DLC_MAX_STEP:
+            ap.error("--track-steps must be DMIN:DMAX with 0 <= DMIN <= DMAX <= %d" % L.DLC_MAX_STEP)
+        args.track = dict(steps=(d_min, d_max), jump=jump, gate=gate, null_score=null)
     if args.threshold is None and args.fuse is None:             # (--fuse: every candidate, as the fused scale is the norm's)
         args.threshold = float("-inf") if args.metric == "similarity" else 0.9
 
@@ -1154,13 +1224,15 @@ def _stream(args, files):
             desc = desc.view(len(chunk), net.input_shape[0], -1)         # [B, P, H]: the frames' patch descriptors
         if det is None and fused is not None:
             det = fused(desc)
+            if args.track is not None:
+                det.start_tracking(args.track)
         elif det is None and args.metric == "similarity":
             # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
             # has only seen its first batch when it must fix it
             det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
                                           exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
                                           contrast=args.contrast, suppress=args.suppress, steps=args.steps,
-                                          chains=args.chains)
+                                          chains=args.chains, track=args.track)
         elif det is None and args.metric == "distance":
             det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
                                             exclusion=args.exclusion, capacity=max(4096, len(files)))
@@ -1169,7 +1241,7 @@ def _stream(args, files):
                                              exclusion=args.exclusion, capacity=max(4096, len(files)), sequence=args.sequence,
                                              contrast=args.contrast, suppress=args.suppress, steps=args.steps,
                                              chains=args.chains, shift=args.shift,
-                                             width=None if args.shift is None else args.size[1])
+                                             width=None if args.shift is None else args.size[1], track=args.track)
         elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))
@@ -1183,6 +1255,10 @@ def _stream(args, files):
                   % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
             if pairs:
                 print(chain_line(pairs[0]))
+    if args.track is not None:                                   # the smoothed labelling of the whole stream
+        for frame, place in enumerate(det.tracker.path().cpu().tolist()):
+            if place >= 0:
+                print("track\t%d\t%d" % (frame, place))
     print("frames\t%d\tkey-frames\t%d" % (len(files), len(det)), file=sys.stderr)
     # the first step pays one-time costs (the library's first launches, workspaces, the database's reservation): reported apart
     steady = lat[1:] if len(lat) > 1 else lat

@@ -6,8 +6,8 @@
  *
  * Builds a small key-frame database on the device (float rows -> L2-normalised bf16 with
  * dlc_l2_normalize_rows), asks for the top-3 matches of two of its own rows and checks that
- * each row finds itself first with score ~1.  Device memory comes from the HIP runtime; the
- * library itself never allocates.
+ * each row finds itself first with score ~1; then runs the place tracker over three small score rows.
+ * Device memory comes from the HIP runtime; the library itself never allocates.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -55,6 +55,22 @@ int main(void) {
         printf("\n");
         ok = ok && hi[q * K] == 500 + q && hs[q * K] > 0.99f && hs[q * K] < 1.01f && hs[q * K + 1] < 0.5f;
     }
+    /* Place tracking (dlc_track_rows) over three frames' score rows against four key-frames: nothing, then key-frame 1,
+       then key-frame 2.  steps 0..2, jump 4, gate 4, a frame without a loop scores 2.  The state is V [4] and four words
+       of head; an all-zero head starts a traversal.  One buffer: rows, V, G, U, then head, place and the int8 pointers. */
+    const double frames[12] = {0, 0, 0, 0,   0, 5, 0, 0,   0, 0, 5, 0};
+    double* t; int64_t place[3];
+    CHECK_HIP(hipMalloc((void**)&t, 8 * (12 + 4 + 3 + 3 + 4 + 3 + 1)));
+    CHECK_HIP(hipMemcpy(t, frames, sizeof(frames), hipMemcpyHostToDevice));
+    int64_t* head = (int64_t*)(t + 22);
+    CHECK_HIP(hipMemset(head, 0, 4 * 8));
+    CHECK_DLC(dlc_track_rows(ctx, DLC_F64, t, 3, 4, 4, 4, 0, 0, 2, 0, 4.0, 4.0, 2.0, DLC_TRACK_AUTO, t + 12, head, head + 4, NULL,
+                             t + 16, t + 19, (int8_t*)(head + 7), NULL, 0, NULL, 0, NULL, 0, NULL));
+    CHECK_HIP(hipMemcpy(place, head + 4, sizeof(place), hipMemcpyDeviceToHost));   /* (a blocking copy: the stream is done) */
+    printf("filtered places: %lld %lld %lld\n", (long long)place[0], (long long)place[1], (long long)place[2]);
+    ok = ok && place[0] == -1 && place[1] == 1 && place[2] == 2;
+    hipFree(t);
+
     hipFree(ws); hipFree(idx); hipFree(scores); hipFree(rows); hipFree(rows_f32); free(host);
     dlc_destroy(ctx);
     printf(ok ? "c_abi_demo ok\n" : "c_abi_demo FAILED\n");

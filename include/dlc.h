@@ -932,6 +932,87 @@ int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * PLACE TRACKING: a belief carried from frame to frame, with a state for "this frame closes no loop" -- the max-plus
+ * (Viterbi) form of a filter over places.  The searches above ask whether a match holds over the last L frames; this
+ * recursion runs over the whole traversal, gives an estimate per frame as the frames arrive and, by its back-pointers,
+ * the best labelling of every frame so far: a key-frame or "nowhere".
+ * Operand as the other score-row entry points take it: M = scores [rows, ld], n columns in use, DLC_F64, DLC_F32 or
+ * DLC_I64, lim(r) = clamp(limit0 + r * limit_step, 0, n) for the call's row r.  Arithmetic is fp64 for float rows (the
+ * conversion is exact) and wrapping int64 for DLC_I64.  "Best" is the order of merit of the searches: the order of the
+ * numbers, -0.0 below +0.0, the minimum instead of the maximum with lower_is_better.  A penalty p WORSENS a value v:
+ * v - p, or v + p with lower_is_better -- one operation, done once per row.
+ * Parameters: 0 <= d_min <= d_max <= DLC_MAX_STEP; jump >= 0, gate >= 0, finite; null_score, NaN = there is no no-loop
+ * state.  For DLC_I64 all three are integers of magnitude <= 2^53 and are used as int64.
+ * STATE after row r: V_r(c) for 0 <= c < n, each absent or a number; U_r, the no-loop state, absent or a number; G_r, the
+ * best present V_r(c), and g_r, the lowest c attaining it (-1 if none).  Before the first row ever seen everything is
+ * absent, and an ORIGIN O = 0 is available to that first row only.
+ * DEFINITION.  CELL RULE: for c < lim(r) with x = M[r][c] not NaN the predecessor P is the best present candidate of
+ *     1. move, d = d_min .. d_max, lowest d first:  V_{r-1}(c - d)
+ *     2. jump:                                      G_{r-1} worsened by jump
+ *     3. from no-loop:                              U_{r-1} worsened by gate
+ *     4. origin, first row only:                    0
+ * the EARLIER in this list among equals.  V_r(c) = P + x, present iff P exists and the sum is not NaN; every other cell of
+ * the row is absent.  back_r(c) records the choice: d for a move, DLC_TRACK_JUMP (the predecessor is column g_{r-1}),
+ * DLC_TRACK_FROM_NULL, DLC_TRACK_ORIGIN; DLC_TRACK_ABSENT for an absent cell.
+ * NO-LOOP STATE, when there is one: U_r = Q + null_score, Q the best present candidate of
+ *     1. stay:    U_{r-1}                           (code 0)
+ *     2. leave:   G_{r-1} worsened by gate          (DLC_TRACK_JUMP)
+ *     3. origin, first row only: 0                  (DLC_TRACK_ORIGIN)
+ * the earlier among equals; present iff Q exists and the sum is not NaN, else absent with the code DLC_TRACK_ABSENT.
+ * The FILTERED PLACE of row r is g_r if G_r is present and strictly better than U_r, or if U_r is absent; otherwise -1.
+ * CONSEQUENCE.  While nothing is NaN and nothing wraps, V_r(c) and U_r are the best sums over ALL labellings of rows
+ * 0 .. r (a column below its row's limit, or nowhere, per row) that end in that state, of the cells of the places and
+ * null_score per nowhere, worsened per transition by 0 for a step within [d_min, d_max], by jump to any other place
+ * and by gate between a place and nowhere (IEEE addition is monotone; verified by enumeration of every labelling,
+ * tests/test_track_cpu.py).  Each cell is one maximum over exact values and one addition in a fixed place, so the result
+ * is exact on integer rows, reproducible on fp64 rows, and does not depend on how the rows are batched or on the plan.
+ * STATE IN MEMORY, owned by the caller and transparent: V [n], fp64 (int64 for DLC_I64), absent = NaN (INT64_MIN: an int64
+ * sum that wraps to exactly INT64_MIN reads as absent); head, four 8-byte device words: the rows seen, U, G, g.  head with
+ * rows seen = 0 (an all-zero head) is the fresh state, and V is not read then.  V holds V of the row before the call's
+ * first on entry and of its last row on return.  n may grow between calls: the new entries of V hold the absent mark.
+ * OUTPUT per row of the call: out_place int64; out_g int64 (may be NULL: g_r, what dlc_track_backtrace follows through a
+ * jump); out_G, out_U (typed and marked as V); out_backU int8.  Optional: out_back int8 [rows, ld_back] (ld_back >= n),
+ * back_r(c) in its first n columns -- cells not offered or absent hold DLC_TRACK_ABSENT -- columns n .. keep their bits;
+ * dense [rows, ld_dense] (typed as V, ld_dense >= n) receives V_r, absent cells the mark, columns n .. keep their bits.
+ * Nothing at or past a row's limit, and no column n .. ld - 1, is read.  Never synchronises.
+ * PLANS, identical bits: DLC_TRACK_RESIDENT -- ONE launch, one workgroup of up to 1024 threads that keeps V_{r-1} and V_r
+ * in LDS and runs every row of the call, for n <= DLC_TRACK_RESIDENT_MAX (DLC_ERR_UNSUPPORTED above it); DLC_TRACK_ROWS --
+ * one launch per row over column tiles and one more at the end, any n, V alternating in the workspace, no atomics;
+ * DLC_TRACK_AUTO -- RESIDENT for n <= 3072, where it is the faster, ROWS above (docs/LAB.md 27).
+ * Workspace: dlc_track_rows_workspace_bytes(rows, n, plan) bytes (0 = bad arguments), 16-byte aligned; the RESIDENT
+ * plan reads none of it (workspace may be NULL then).
+ * Errors: DLC_ERR_BAD_ARG (a parameter outside the ranges above, a missing or misaligned pointer, ld < n, ld_back < n,
+ * ld_dense < n), DLC_ERR_BAD_SHAPE (n >= 2^31), DLC_ERR_UNSUPPORTED, DLC_ERR_WORKSPACE; nothing is written then.
+ *
+ * dlc_track_backtrace: the labelling behind a state.  out_back [rows, ld_back], out_backU [rows] and g [rows] are
+ * dlc_track_rows' outputs for rows 0 .. rows - 1 of a traversal (several calls' outputs one after the other).  end: the
+ * state of the last row to start from -- a column, -1 for nowhere, or DLC_TRACK_END_FILTERED: the device word
+ * *place_last, the last row's out_place (place_last may be NULL otherwise).  out_path [rows] int64 receives every row's
+ * state on the way back to row 0, a column or -1; from a row whose state is absent on, DLC_TRACK_NO_PATH.  Started from
+ * the better of G and U of the last row, the path is a best labelling of the whole traversal.  ONE launch of one wave;
+ * never synchronises.
+ */
+#define DLC_TRACK_AUTO 0
+#define DLC_TRACK_RESIDENT 1
+#define DLC_TRACK_ROWS 2
+#define DLC_TRACK_RESIDENT_MAX 8192       /* two LDS buffers of n 8-byte words: 128 KiB of the 160 KiB a workgroup may declare */
+#define DLC_TRACK_JUMP (-1)
+#define DLC_TRACK_FROM_NULL (-2)
+#define DLC_TRACK_ORIGIN (-3)
+#define DLC_TRACK_ABSENT (-128)
+#define DLC_TRACK_END_FILTERED (-2)
+#define DLC_TRACK_NO_PATH (-2)
+size_t dlc_track_rows_workspace_bytes(int64_t rows, int64_t n, int plan);
+int dlc_track_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I64 */, const void* scores, int64_t rows, int64_t n,
+                   int64_t ld, int64_t limit0, int64_t limit_step, int d_min, int d_max, int lower_is_better, double jump,
+                   double gate, double null_score, int plan, void* V, int64_t* head, int64_t* out_place, int64_t* out_g,
+                   void* out_G, void* out_U, int8_t* out_backU, int8_t* out_back, int64_t ld_back, void* dense,
+                   int64_t ld_dense, void* workspace, size_t workspace_bytes, void* stream);
+int dlc_track_backtrace(dlc_ctx* ctx, int64_t rows, int64_t n, const int8_t* out_back, int64_t ld_back,
+                        const int8_t* out_backU, const int64_t* g, const int64_t* place_last, int64_t end,
+                        int64_t* out_path, void* stream);
+
+/*
  * Ground-truth evaluation of score rows: the last stage of the pipeline.  Given the rows a detector ranks by and a mask
  * of the cells that are true matches, dlc_pr_cell_counts counts the decisions behind a precision-recall curve and
  * dlc_positive_rank_rows the ranks behind recall@K.  Everything is integer counting: every result is exact and does not
