@@ -19,7 +19,7 @@ DLC_MAX_K = 128
 DLC_MAX_STEP = 8             # the largest step of the elastic sequence search (d_max)
 DLC_MAX_SHIFT = 8            # the largest lateral shift of dlc_sad_u8_shift_rows (thumbnail columns)
 DLC_ABI_VERSION = 20        # include/dlc.h; load() refuses a library built from another header
-DLC_SELECT_COOP, DLC_SELECT_NO_HINTS = 1, 2
+DLC_SELECT_COOP, DLC_SELECT_NO_HINTS, DLC_SELECT_SERIAL = 1, 2, 4
 DLC_PRUNE_ON, DLC_PRUNE_OFF, DLC_PRUNE_KEEP = 0, 1, 2     # dlc_set_prune_mode
 DLC_SIM_FORCE_F64, DLC_SIM_NO_HOST_SYNC = 1, 2
 DLC_MAX_FUSE = 8             # the most score sources dlc_fuse_rows takes

@@ -662,6 +662,12 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 
 constexpr int FIN_THREADS = 512;            // merge / exhaustive workgroup; finish workgroup of the stand-alone variant
 constexpr size_t FIN_TV_LDS_MAX = 96 * 1024; // a query's half-tile maxima are staged in LDS up to this many bytes
+constexpr int FIN_LV = 16;                  // half-tile maxima a lane of the 512-thread finish keeps in registers
+// The 512-thread finish (and the 256-thread group selection) reads up to 8 waves x 64 lanes x FIN_LV = 8192 half-tile
+// maxima of a query straight into registers: no LDS copy, and the workspace row is not written.
+inline bool fin_register_path(int threads, bool groups_mode, int64_t nh) {
+    return (threads == 512 || groups_mode) && dlc::cdiv(nh, (int64_t)(threads / 64)) <= 64 * FIN_LV;
+}
 // finish kernel LDS carve (bytes) for kg selected groups:
 //   ckey u64 [kg*16] | ck64 i64 [kg*8] | cs64 f64 [kg*8] | crow i32 [kg*8] | sel i32 [kg+1] | sel2 i32 [kg+1] | misc 64 B
 __host__ __device__ inline size_t fin_lds_fixed(int kg) {
@@ -851,6 +857,9 @@ struct FinishArgs {
     const float* dense_S;         // small-database plan: the fp32 score matrix [q, ld_s] is in the workspace, so the
     long long ld_s;               // candidates are ROWS: the k + rslack best fp32 scores of the selected groups
     int rslack;
+    const unsigned* bkt;          // [PRUNE_NB, nq] or null: the pruned score pass's class maxima of THIS launch (dlc_cosine_topk,
+                                  // whole database, kg <= PRUNE_NB): their kt-th largest is a second lower bound for level 1
+    int serial;                   // DLC_SELECT_SERIAL: the general extraction / full rankings instead of the filtered ones (tests)
     int limited;                  // 1: query qi may only see rows < limit0 + qi (the streaming detector's batches); the group and
     long long limit0;             // half-tile maxima of the score pass stay upper bounds of what it may see
 };
@@ -900,38 +909,93 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // [nh] half-tile maxima of this query: staged in LDS, or consumed in place in the workspace
     // row (which the next GEMM rewrites anyway) when LDS is to be kept small or the shard is huge
+    constexpr int LV = FIN_LV;                 // a lane's level-1 values live in registers when its slice has <= LV of them
+    // (not in the small-footprint fused form, which has to stay under ~110 VGPRs to sit beside a GEMM workgroup)
+    const int nh1 = MODE == FIN_RESCORE ? 0 : (a.limited ? (int)((n + HALF - 1) / HALF) : a.nh);
+    const bool regs1 = (THREADS == 512 || MODE == FIN_GROUPS) && (nh1 + FIN_WAVES - 1) / FIN_WAVES <= 64 * LV;
     float* tv = a.tv_in_lds ? (float*)(dsm + fin_lds_fixed(kg)) : a.tmax + (long long)qi * a.ldt;
-    if (a.tv_in_lds)
+    // (the register path reads its values straight from the workspace row and never writes them: no staging -- launch_finish
+    // asks for none where it can tell; a limit can still shrink a staged shard into the register path)
+    if (a.tv_in_lds && !regs1)
         for (int e = tid; e < a.nh; e += FIN_THREADS) tv[e] = a.tmax[(long long)qi * a.ldt + e];
     for (int e = tid; e <= kg; e += FIN_THREADS) { sel[e] = -1; sel2[e] = -1; }
-    if (tid < 16) misc[tid] = 0u;
+    if (tid < 16) misc[tid] = tid == 14 ? 0xffffffffu : 0u;
     __syncthreads();
     int kg2;
     unsigned bkey = 0u;      // fp32 key of the largest group maximum left behind by the selection; 0 = nothing left behind
     const bool use_hint = MODE == FIN_FUSED && THREADS == 512 && a.hint != nullptr && !a.dense_S && !a.limited;
     if constexpr (MODE != FIN_RESCORE) {
     // ---- level 1: the kt half tiles with the largest maximum (ties -> lower tile).
-    // Each wave extracts the kt best of its slice by repeated wave arg-max (DPP, no barrier);
-    // the FIN_WAVES * kt survivors are ranked together.  What a wave has left after its kt extractions
-    // (misc[w]) and the survivor of rank kt bound every half tile that is not selected.
-    const int nh = a.limited ? (int)((n + HALF - 1) / HALF) : a.nh;
+    // General path: each wave extracts the kt best of its slice by repeated wave arg-max (DPP, no barrier); the
+    // FIN_WAVES * kt survivors are ranked together.  What a wave has left after its kt extractions (misc[w]) and the
+    // survivor of rank kt bound every half tile that is not selected.
+    // Register path: FILTER, THEN RANK (include/dlc.h, "the filtered selection").  T = the largest, over the waves, of the
+    // kt-th largest lane maximum of a wave: kt lanes of one wave hold kt distinct half tiles with a key >= T (T = 0: no wave
+    // has kt non-empty lanes) -- and, behind the pruned score pass, of the kt-th largest class maximum.  Every key
+    // >= max(T, 1) is posted to ckey and the posted keys are ranked; a key that is not posted is < T <= the kt-th largest key, so it is neither selected nor tied with a selected one, and the (kt+1)-th
+    // largest key overall -- the bound of what is left behind -- is the larger of the (kt+1)-th posted key and the best
+    // key not posted.  Keys are unique (the half-tile index is part of them), so the posted order does not matter.  More
+    // posted keys than ckey holds (a database of identical rows): the general extraction runs on the registers instead.
+    const int nh = nh1;
     const int kt = min(kg, nh);
+    int m1 = FIN_WAVES * kt;                   // keys in ckey for the level-1 ranking
     {
         const int chunk = (nh + FIN_WAVES - 1) / FIN_WAVES;
         const int lo_e = w * chunk, hi_e = min(nh, lo_e + chunk);
         unsigned bh = 0, bl = 0;               // this lane's best key (hi, lo); 0,0 = none
-        constexpr int LV = 16;                 // a lane's values live in registers when its slice has <= LV of them
-        // (not in the small-footprint fused form, which has to stay under ~110 VGPRs to sit beside a GEMM workgroup)
-        if ((THREADS == 512 || MODE == FIN_GROUPS) && chunk <= 64 * LV) {
-            // (up to 8 waves x 1024 half tiles = 1 M rows per shard: the benchmark; an owner's rescan is then
-            // 16 register compares instead of 16 dependent LDS reads, 24 times per wave)
+        unsigned rest;                         // the best half tile this wave did not hand in
+        if (regs1) {
+            // (up to 8 waves x 1024 half tiles = 1 M rows per shard: the benchmark)
             unsigned vk[LV];                   // score keys; 0 = none / retired
+            const float* tg = a.tmax + (long long)qi * a.ldt;
+            // (pruned calls: wave 0 also takes the query's 64 class maxima -- the SAFETY comment at PRUNE_NB: the kt-th
+            // largest of them is a lower bound of the kt-th largest half-tile key, and far closer to it than a wave's own)
+            const bool classes = !a.serial && a.bkt != nullptr && w == 0;
+            const unsigned cv = classes ? a.bkt[(long long)lane * a.nq + qi] : 0u;
 #pragma unroll
             for (int j = 0; j < LV; ++j) {
                 const int e = lo_e + lane + 64 * j;
-                const float v = e < hi_e ? tv[e] : -INFINITY;
+                const float v = e < hi_e ? tg[e] : -INFINITY;
                 vk[j] = v == -INFINITY ? 0u : f32_key(v);
             }
+            bool filtered = false;
+            if (!a.serial) {
+                unsigned lmax = 0u;
+#pragma unroll
+                for (int j = 0; j < LV; ++j) lmax = max(lmax, vk[j]);
+                // (any of the bounds will do: wave 0 hands in the classes' instead of its own, not both -- one chain per wave)
+                const unsigned tw = wave_kth_largest_u32(classes ? cv : lmax, kt);
+                if (lane == 0) misc[w] = tw;
+                __syncthreads();
+                unsigned T = 1u;
+#pragma unroll
+                for (int ww = 0; ww < FIN_WAVES; ++ww) T = max(T, misc[ww]);
+                int cnt = 0;
+#pragma unroll
+                for (int j = 0; j < LV; ++j) cnt += __popcll(__ballot(vk[j] >= T));
+                int base = 0;
+                if (lane == 0 && cnt) base = (int)atomicAdd(&misc[12], (unsigned)cnt);
+                base = __builtin_amdgcn_readfirstlane(base);
+                const int cap = kg * GPH;
+                unsigned um = 0u;
+#pragma unroll
+                for (int j = 0; j < LV; ++j) {
+                    const bool p = vk[j] >= T;
+                    const unsigned long long b = __ballot(p);
+                    const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+                    if (p) {
+                        if (slot < cap) ckey[slot] = ((unsigned long long)vk[j] << 32) | ~(unsigned)(lo_e + lane + 64 * j);
+                    } else um = max(um, vk[j]);
+                    base += __popcll(b);
+                }
+                rest = wave_max_u32(um);
+                __syncthreads();               // every T is read, every key is posted
+                const int posted = (int)misc[12];
+                filtered = posted <= cap;
+                if (filtered) m1 = posted;
+            }
+            if (!filtered) {
+            // (an owner's rescan is 16 register compares, 24 times per wave)
             auto rescan_regs = [&]() {
                 bh = 0; bl = 0;
 #pragma unroll
@@ -953,6 +1017,8 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
                     rescan_regs();
                 }
             }
+            rest = wave_max_u32(bh);
+            }
         } else {
         auto rescan = [&]() {
             bh = 0; bl = 0;
@@ -973,12 +1039,12 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
                 rescan();
             }
         }
+        rest = wave_max_u32(bh);
         }
-        const unsigned rest = wave_max_u32(bh);          // the best half tile this wave did not hand in
         if (lane == 0) misc[w] = rest;
     }
     __syncthreads();
-    rank_select(ckey, FIN_WAVES * kt, kt, sel, true);    // sel[rank] = slot in ckey
+    rank_select(ckey, m1, kt, sel, true);                // sel[rank] = slot in ckey
     __syncthreads();
 #pragma unroll
     for (int ww = 0; ww < FIN_WAVES; ++ww) bkey = max(bkey, misc[ww]);
@@ -988,7 +1054,9 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
 
     // ---- level 2: among their groups, the kg2 groups with the largest maximum (+ the best one left behind)
     const int m2 = kt * GPH;
-    for (int e = tid; e < m2; e += FIN_THREADS) {
+    kg2 = min(kg, m2);
+    int c2 = m2;                                         // keys in ckey for the level-2 ranking
+    auto group_key = [&](int e) -> unsigned long long {
         const int ht = sel[e / GPH];
         const long long g = (long long)ht * GPH + (e % GPH);
         float gm = (ht >= 0 && g < ng) ? a.gmax[(long long)qi * a.ldg + g] : 0.0f;
@@ -1000,11 +1068,39 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
             gm = -INFINITY;
             for (long long row = g * GROUP; row < n; ++row) gm = fmaxf(gm, a.dense_S[(long long)qi * a.ld_s + row]);
         }
-        ckey[e] = (ht >= 0 && g < ng) ? pack_key(gm, (unsigned)g) : 0ull;
+        return (ht >= 0 && g < ng) ? pack_key(gm, (unsigned)g) : 0ull;
+    };
+    if (THREADS == 512 && !a.serial && m2 <= FIN_THREADS) {
+        // Filter, then rank, as level 1: a thread per group key, a selected half tile's 16 keys in 16 consecutive lanes.
+        // T2 = the smallest, over the kt selected half tiles, of the largest score key (the key's high word) among a half
+        // tile's groups: kt distinct groups have a score key >= T2.  Where kt >= kg2 a key below T2 is neither among the
+        // kg2 best nor tied with one of them (the ranking compares the high word first), so only the keys >= T2 are
+        // ranked, and the best key that is not joins what is left behind.  kt < kg2 (fewer half tiles than groups to keep),
+        // or a selected half tile without a key: T2 = 0, every key is ranked.
+        const unsigned long long ke = tid < m2 ? group_key(tid) : 0ull;
+        const unsigned hi = (unsigned)(ke >> 32);
+        unsigned rm = hi;
+#pragma unroll
+        for (int o = 1; o < GPH; o <<= 1) rm = max(rm, (unsigned)__shfl_xor((int)rm, o));
+        if (tid < m2 && (tid & (GPH - 1)) == 0) atomicMin(&misc[14], rm);
+        __syncthreads();
+        const unsigned T2 = kt >= kg2 ? misc[14] : 0u;
+        const bool p = ke != 0ull && hi >= T2;
+        const unsigned long long b = __ballot(p);
+        int base = 0;
+        if (lane == 0 && b) base = (int)atomicAdd(&misc[13], (unsigned)__popcll(b));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (p) ckey[base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u))] = ke;
+        const unsigned um = wave_max_u32(p ? 0u : hi);
+        if (lane == 0 && um) atomicMax(&misc[15], um);
+        __syncthreads();
+        c2 = (int)misc[13];
+        bkey = max(bkey, misc[15]);
+    } else {
+        for (int e = tid; e < m2; e += FIN_THREADS) ckey[e] = group_key(e);
+        __syncthreads();
     }
-    __syncthreads();
-    kg2 = min(kg, m2);
-    rank_select(ckey, m2, kg2, sel2, true);
+    rank_select(ckey, c2, kg2, sel2, true);
     __syncthreads();
     if (sel2[kg2] >= 0) bkey = max(bkey, (unsigned)(ckey[sel2[kg2]] >> 32));
     if constexpr (MODE == FIN_GROUPS) {
@@ -1167,7 +1263,9 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     // waves instead, one row at a time (wave w: candidates w, w + FIN_WAVES, ...) -- nine rows of 8 KB were one wave's
     // 8 rows and a second wave's one.  Same value either way (rescore1_f64).
     const char* qrow = a.Q + (long long)qi * a.ldq_b;
-    if (MODE == FIN_FUSED && a.dense_S != nullptr) {                   // (only the fused form runs the small-database plan)
+    const int* frow = crow;                               // the rows behind ck64 / cs64, and how many slots they have
+    int mf = m3;
+    if (MODE == FIN_FUSED && a.dense_S != nullptr) {                // (only the fused form runs the small-database plan)
         for (int ci = w; ci < m3; ci += FIN_WAVES) {
             const int id = __builtin_amdgcn_readfirstlane(crow[ci]);
             const double sc = id < 0 ? 0.0 : rescore1_f64<Tag>(qrow, a.DB + (long long)id * a.lddb_b, a.d, lane);
@@ -1183,7 +1281,17 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
         const int n1 = __builtin_amdgcn_readfirstlane((int)misc[10]), n8 = __builtin_amdgcn_readfirstlane((int)misc[11]);
         const int* wl1 = (const int*)ckey;
         const int* wl8 = wl1 + kg;
-        for (int e = tid; e < m3; e += FIN_THREADS) { cs64[e] = -INFINITY; ck64[e] = KEY64_EMPTY; }
+        // The scores land in a COMPACT list -- single row s at s, row r of whole group s8 at n1 + 8 s8 + r, their rows in
+        // crow2 (behind the work lists) -- so that the final ranking walks the n1 + 8 n8 slots that were scored instead of
+        // all m3 (most of them empty behind a champion row).  The ranking is by (key, row) over the same scored rows.
+        // (DLC_SELECT_SERIAL keeps every score in its candidate's slot)
+        const bool compact = !a.serial;
+        int* crow2 = (int*)ckey + 2 * kg;
+        if (compact) { mf = n1 + GROUP * n8; frow = crow2; }
+        for (int e = tid; e < mf; e += FIN_THREADS) {
+            cs64[e] = -INFINITY; ck64[e] = KEY64_EMPTY;
+            if (compact) crow2[e] = -1;
+        }
         // (each slot has one writer after this: the barrier orders the defaults before the scores)
         __syncthreads();
         const int per = (n1 + FIN_WAVES - 1) / FIN_WAVES;
@@ -1215,8 +1323,10 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
                 if (lane == r && r < cnt && ids3[r] >= 0) {
-                    cs64[slot[r]] = sc[r];
-                    ck64[slot[r]] = f64_key(sc[r]);
+                    const int at = compact ? s + r : slot[r];
+                    cs64[at] = sc[r];
+                    ck64[at] = f64_key(sc[r]);
+                    if (compact) crow2[at] = ids3[r];
                 }
             s += cnt;
         }
@@ -1234,8 +1344,10 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
 #pragma unroll
             for (int r = 0; r < GROUP; ++r)
                 if (lane == r && ids[r] >= 0) {
-                    cs64[e0 + r] = acc[r];
-                    ck64[e0 + r] = f64_key(acc[r]);
+                    const int at = compact ? n1 + s8 * GROUP + r : e0 + r;
+                    cs64[at] = acc[r];
+                    ck64[at] = f64_key(acc[r]);
+                    if (compact) crow2[at] = ids[r];
                 }
         }
     } else
@@ -1271,14 +1383,14 @@ __device__ __forceinline__ void finish_topk_body(const FinishArgs& a) {
     __syncthreads();
 
     // ---- final top-k of the re-scored rows: fp64 key descending, ties -> lower row
-    rank_select64(ck64, crow, m3, k, sel);
+    rank_select64(ck64, frow, mf, k, sel);
     __syncthreads();
     for (int e = tid; e < k; e += FIN_THREADS) {
         const int c = sel[e];
         if (c >= 0) {
             if (a.out_s) a.out_s[oq * k + e] = (float)cs64[c];
             a.out_s64[oq * k + e] = cs64[c];
-            a.out_i[oq * k + e] = (long long)crow[c] + a.row_offset;
+            a.out_i[oq * k + e] = (long long)frow[c] + a.row_offset;
         }
     }
     if constexpr (MODE == FIN_FUSED) {
@@ -2063,9 +2175,11 @@ WsLayout ws_layout(int64_t q, int64_t n, int64_t d, int k) {
     }
     w.total = o;
     // The pruned score pass: where the hints are written (the one-pass MFMA plan), kg fits the classes, one workgroup per
-    // query re-scores (the spread re-score keeps the whole arrays), and the finish does not consume the tmax row in
-    // place (the exhaustive pass qualifies half tiles by it).
-    w.prunable = w.hints && w.kg <= PRUNE_NB && w.rparts <= 1 && (size_t)dlc::cdiv(n, (int64_t)HALF) * 4 <= FIN_TV_LDS_MAX;
+    // query re-scores (the spread re-score keeps the whole arrays), and the finish does not write the tmax row (the
+    // exhaustive pass qualifies half tiles by it): the 512-thread form takes the maxima into registers, or stages them in LDS.
+    const int64_t nh = dlc::cdiv(n, (int64_t)HALF);
+    const bool finish_keeps_tmax = fin_register_path(512, false, nh) || (size_t)nh * 4 <= FIN_TV_LDS_MAX;
+    w.prunable = w.hints && w.kg <= PRUNE_NB && w.rparts <= 1 && finish_keeps_tmax;
     w.prune = o;
     if (w.prunable) o += dlc::align_up((size_t)q * (PRUNE_NB + 1) * 4, 256);
     w.prune_total = o;
@@ -2259,7 +2373,8 @@ FinishArgs finish_args(const MatchCall& mc, int k, int64_t n, int64_t d, int64_t
 template <typename Tag, int THREADS, int RS_UNROLL, int MODE>
 int launch_finish(dlc_ctx* ctx, FinishArgs f, int64_t q, bool small_lds, hipStream_t st) {
     size_t dsm = fin_lds_fixed(f.kg);
-    f.tv_in_lds = MODE != FIN_RESCORE && !small_lds && (size_t)f.nh * 4 <= FIN_TV_LDS_MAX;
+    f.tv_in_lds = MODE != FIN_RESCORE && !small_lds && !fin_register_path(THREADS, MODE == FIN_GROUPS, f.nh) &&
+                  (size_t)f.nh * 4 <= FIN_TV_LDS_MAX;
     if (f.tv_in_lds) dsm += (size_t)f.nh * 4;
     dsm = dlc::align_up(dsm, 16);
     void (*fk)(FinishArgs);
@@ -2274,8 +2389,10 @@ int launch_finish(dlc_ctx* ctx, FinishArgs f, int64_t q, bool small_lds, hipStre
 }
 
 template <int MODE>
-int run_select(dlc_ctx* ctx, int dtype, const FinishArgs& f, int64_t q, int flags, hipStream_t st) {
+int run_select(dlc_ctx* ctx, int dtype, const FinishArgs& f_in, int64_t q, int flags, hipStream_t st) {
     const bool coop = (flags & DLC_SELECT_COOP) != 0;
+    FinishArgs f = f_in;
+    f.serial = (flags & DLC_SELECT_SERIAL) ? 1 : 0;
     if (dtype == DLC_BF16)
         return coop ? launch_finish<dlc_bf16_tag, 256, 1, MODE>(ctx, f, q, true, st)
                     : launch_finish<dlc_bf16_tag, 512, 4, MODE>(ctx, f, q, false, st);
@@ -2353,6 +2470,7 @@ int run_finish(dlc_ctx* ctx, int dtype, const MatchCall& mc, int k, int64_t n, i
         // half-tile hints: where the plan's score pass wrote them, for the stand-alone form looking at the whole database
         if (mc.w.hints && !limited && !(flags & (DLC_SELECT_COOP | DLC_SELECT_NO_HINTS)))
             f.hint = (const HintEntry*)(ws + mc.w.hint);
+        if (mc.a.bkt && !limited && mc.w.kg <= PRUNE_NB) f.bkt = mc.a.bkt;      // (armed by dlc_cosine_topk only)
         rc = run_select<FIN_FUSED>(ctx, dtype, f, q, flags, st);
         if (rc != DLC_OK) return rc;
     } else {

@@ -1644,9 +1644,10 @@ class Engine:
                                                       ws.numel(), st))
 
     def select_topk(self, q, db, k, ws, scores, idx, row_offset=0, coop=False, stream=None, scores_f64=None, status=None,
-                    tau_scale=None, hints=True):
+                    tau_scale=None, hints=True, serial=False):
         """Stage 2 of match_topk (selection, fp64 re-score, final top-k, certificate, exhaustive pass) from the workspace.
-        hints=False re-scores every selected group whole (DLC_SELECT_NO_HINTS): the same results, more rows gathered."""
+        hints=False re-scores every selected group whole (DLC_SELECT_NO_HINTS): the same results, more rows gathered.
+        serial=True selects without the threshold filter (DLC_SELECT_SERIAL): the same results, for tests."""
         self._check_stored(q, db)
         self._check_ws(ws)
         self._check_out("scores", scores, (q.shape[0], k), torch.float32)
@@ -1661,7 +1662,8 @@ class Engine:
                                                      _ptr(scores), _ptr(scores_f64), _ptr(idx), _ptr(status),
                                                      _ptr(tau_scale), _ptr(ws), ws.numel(),
                                                      (L.DLC_SELECT_COOP if coop else 0) |
-                                                     (0 if hints else L.DLC_SELECT_NO_HINTS), st))
+                                                     (0 if hints else L.DLC_SELECT_NO_HINTS) |
+                                                     (L.DLC_SELECT_SERIAL if serial else 0), st))
 
     def _check_ws(self, ws):
         if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != self.device:
@@ -1673,9 +1675,9 @@ class Engine:
             raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
         return kg
 
-    def select_groups(self, q, db, k, ws, grp_ids, grp_max, coop=False, stream=None):
+    def select_groups(self, q, db, k, ws, grp_ids, grp_max, coop=False, stream=None, serial=False):
         """Stage 2a: the kg best groups of every query: shard-local ids [Q,kg] and grp_max [Q,kg+1] = their maxima +
-        (last column) the best maximum among the groups that are not listed."""
+        (last column) the best maximum among the groups that are not listed.  serial=True: DLC_SELECT_SERIAL."""
         self._check_stored(q, db)
         self._check_ws(ws)
         kg = self.groups_per_query(k)
@@ -1685,7 +1687,8 @@ class Engine:
         self._check(self.lib.dlc_cosine_select_groups(self.ctx, _TORCH_TO_DLC[q.dtype], _ptr(q), q.shape[0], q.stride(0),
                                                        _ptr(db), db.shape[0], db.stride(0), q.shape[1], k, _ptr(ws),
                                                        ws.numel(), _ptr(grp_ids), _ptr(grp_max),
-                                                       L.DLC_SELECT_COOP if coop else 0, st))
+                                                       (L.DLC_SELECT_COOP if coop else 0) |
+                                                       (L.DLC_SELECT_SERIAL if serial else 0), st))
 
     def rescore_topk(self, q, db, k, grp_ids, grp_max, scores_f64, idx, bound=None, all_max=None, row_offset=0, coop=False,
                      stream=None, tau_scale=None):

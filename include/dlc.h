@@ -37,7 +37,7 @@ extern "C" {
 
 /* Raised when a prototype, a struct or the meaning of an existing argument value changes.  A new bit in a `flags`
  * argument (zero keeps the old behaviour) and a larger *_workspace_bytes() answer (callers ask, never compute) change
- * neither: DLC_SELECT_NO_HINTS and the hint array of dlc_cosine_topk_workspace_bytes came in at 20. */
+ * neither: DLC_SELECT_NO_HINTS, DLC_SELECT_SERIAL and the hint array of dlc_cosine_topk_workspace_bytes came in at 20. */
 #define DLC_ABI_VERSION 20
 
 typedef struct dlc_ctx dlc_ctx;
@@ -1249,9 +1249,13 @@ double dlc_cosine_score_error_bound_any_plan(int64_t d);
  * of LDS) whose workgroups can share a CU with a running score GEMM.  DLC_SELECT_NO_HINTS makes the
  * selection ignore the score pass's half-tile hints (below) and re-score every selected group whole: the
  * same results bit for bit, more rows gathered -- it is there so that tests can hold the two against each other.
+ * DLC_SELECT_SERIAL (dlc_cosine_select_topk and dlc_cosine_select_groups) does the same for the filtered selection
+ * (below): the 512-thread kernels extract the best half tiles one at a time and rank every key, as the general path
+ * does -- the same results bit for bit, group_max's bound column included.
  */
 #define DLC_SELECT_COOP 1
 #define DLC_SELECT_NO_HINTS 2
+#define DLC_SELECT_SERIAL 4
 int dlc_cosine_score_groups(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, int64_t ldq,
                             const void* DB, int64_t n, int64_t lddb, int64_t d, int k,
                             void* workspace, size_t workspace_bytes, void* stream);
@@ -1327,6 +1331,23 @@ int dlc_cosine_select_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q, in
  *                          hence an fp64 score < u_k - tau <= s_k -- it is never in the top-k, never ties with its k-th
  *                          score, cannot fail the certificate (s_k > r2 + tau) and does not move the `lower` the
  *                          exhaustive round starts from.  Scores, rows and status are those of DLC_SELECT_NO_HINTS.
+ *   the filtered selection (the 512-thread kernels, up to 8192 half tiles per shard; integer keys only: the ordering key of
+ *                          an fp32 maximum, then the lower index.)  The kt = min(kg, half tiles) best half tiles: every lane
+ *                          holds up to 16 keys, T = the largest over the 8 waves of the kt-th largest LANE MAXIMUM of a wave
+ *                          (0 where a wave has fewer than kt lanes with a key).  kt lanes hold kt distinct half tiles, so at
+ *                          least kt keys are >= T, i.e. T <= the kt-th largest key.  Behind the pruned score pass T is also
+ *                          raised to the kt-th largest of the query's 64 class maxima, a lower bound of the kt-th largest key
+ *                          by the pruned pass's own argument (distinct classes hold distinct half tiles).  Only the keys >= max(T, 1) are ranked.
+ *                          A key that is not ranked is < T <= the kt-th largest: it is neither selected nor tied with a
+ *                          selected key.  The (kt+1)-th largest key overall -- what column kg and the certificate bound the
+ *                          rest by -- is the larger of the (kt+1)-th ranked key and the best key not ranked.  More ranked
+ *                          keys than the kernel has room for (16 kg; a database of identical rows): the general one-by-one
+ *                          extraction runs instead.  The kg groups inside them, the same way: T2 = the smallest, over
+ *                          the kt selected half tiles, of the largest group key of a half tile; kt distinct groups have
+ *                          a key >= T2, so where kt >= the number of groups to keep only the keys >= T2 are ranked and the
+ *                          best other key joins the rest (T2 = 0, every key ranked, otherwise).  The final top-k ranks the
+ *                          rows that were re-scored, without the empty slots of the rows that were not.  Lists, order,
+ *                          status and bounds are those of DLC_SELECT_SERIAL.
  *   the exhaustive round   Touches the queries with status 1 only: their lists are replaced and their status becomes
  *                          2; every other query's status, scores and rows are left as they are.  lower_stride = 0
  *                          reads one number for every query.  tau must be >= 0 (NaN is refused), lower_stride >= 0.
