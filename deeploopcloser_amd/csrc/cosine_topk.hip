@@ -194,6 +194,18 @@ constexpr int HALF_BYTES = 128 * 128;
 // the database operand's form: streamed once, so its cache policy is a separate knob
 DLC_DMA_S_FORM(dma_s_stream, DLC_A_CACHE_POLICY)
 
+// Pieces a wave may leave in flight at the wait of a K iteration with `left` iterations behind it (the kernel's "wait
+// rule" has the derivation): what it has issued for K tiles above the next one, 8 pieces a tile, none past the last tile.
+constexpr int tail_vmcnt_a(int left) {       // whole tiles t+2 .. t+A_STAGES-1, and A1 of tile t+A_STAGES
+    const int whole = (left < A_STAGES - 1 ? left : A_STAGES - 1) - 1;
+    return 8 * (whole > 0 ? whole : 0) + (left >= A_STAGES ? 4 : 0);
+}
+constexpr int tail_vmcnt_b(int left) { return left >= 2 ? 8 : 0; }      // tile t+2 whole
+static_assert(A_STAGES == 2 || A_STAGES == 3, "the database ring is 2 or 3 K tiles deep");
+static_assert(A_STAGES != 2 || (tail_vmcnt_a(2) == 4 && tail_vmcnt_a(1) == 0 && tail_vmcnt_a(0) == 0), "2-deep A ring");
+static_assert(A_STAGES != 3 || (tail_vmcnt_a(3) == 12 && tail_vmcnt_a(2) == 8 && tail_vmcnt_a(1) == 0 && tail_vmcnt_a(0) == 0),
+              "3-deep A ring");
+
 // MASKQ: instantiation for a last query block with fewer than 193 queries -- waves whose 64-query
 // column block lies entirely past q skip their fragment reads and MFMAs (they still stage and
 // synchronise), so 5..192 queries do not pay, at the power cap, for 256 queries' matrix work.
@@ -291,23 +303,34 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
 #define DLC_RELEASE()    \
     DLC_WAIT_LGKM0();    \
     wg_barrier()
-    // DMA of half H of K tile t2 into ring position POS (K offset clamped past the end: the
-    // redundant DMA lands in a dead half and keeps the vmcnt bookkeeping uniform)
+    // DMA of half H of K tile t2 into ring position POS.  THE K TAIL: no DMA is issued for a K tile >= nk, so the callers
+    // below name only tiles that exist (the prologue asks nk, the peeled last iterations know their distance from the
+    // end at compile time) and the steady loop carries no clamp.
+    // THE WAIT RULE: at the wait behind m6 of iteration t (and at the prologue's wait, t = -1) a wave may leave in flight
+    // exactly the pieces it has issued for K tiles above t + 1.  vmcnt counts a wave's own pieces in issue order, 8 per K
+    // tile (2 halves x 4), and by that wait the wave has issued, of the tiles below nk,
+    //   an A wave: tiles <= t + A_STAGES - 1 whole, and A1 (4 pieces) of tile t + A_STAGES (its A0 follows the wait);
+    //   a B wave:  tiles <= t + 2 whole.
+    // With L = nk - 1 - t iterations left behind the current one that is tail_vmcnt_a(L) / tail_vmcnt_b(L) below:
+    //   A, 2-deep ring: 4 while L >= 2, then 0;   A, 3-deep: 12 while L >= 3, 8 at L = 2, then 0;   B: 8 while L >= 2, then 0.
+    // An immediate larger than what is in flight would fall through with half of tile t + 1 still on its way.
 #define DLC_ISSUE_A(POS, H, t2)                                                                      \
     do {                                                                                             \
-        if (is_a) {                                                                                  \
-            int kk_ = (t2) < nk ? (t2) : nk - 1;                                                     \
-            dma_s_stream(voff[H], a_base + (long long)kk_ * 128, lds_stage + (POS) + (H) * HALF_BYTES); \
-        }                                                                                            \
+        if (is_a)                                                                                    \
+            dma_s_stream(voff[H], a_base + (long long)(t2) * 128, lds_stage + (POS) + (H) * HALF_BYTES); \
     } while (0)
     // wave 4 + j stages exactly the queries of column block j: nobody reads them when that block is idle
     const bool b_on = !MASKQ || (qblk * BNQ + ridx * 64 < p.q);
 #define DLC_ISSUE_B(POS, H, t2)                                                                      \
     do {                                                                                             \
-        if (!is_a && b_on) {                                                                         \
-            int kk_ = (t2) < nk ? (t2) : nk - 1;                                                     \
-            dma_s(voff[H], b_base + (long long)kk_ * 128, lds_stage + B_RING + (POS) + (H) * HALF_BYTES); \
-        }                                                                                            \
+        if (!is_a && b_on)                                                                           \
+            dma_s(voff[H], b_base + (long long)(t2) * 128, lds_stage + B_RING + (POS) + (H) * HALF_BYTES); \
+    } while (0)
+#define DLC_WAIT_TILE(L)                                                                             \
+    do {                                                                                             \
+        if constexpr (tail_vmcnt_a(L) == tail_vmcnt_b(L)) DLC_WAIT_VMCNT(tail_vmcnt_a(L));           \
+        else if (is_a) DLC_WAIT_VMCNT(tail_vmcnt_a(L));                                              \
+        else DLC_WAIT_VMCNT(tail_vmcnt_b(L));                                                        \
     } while (0)
 
     // Workgroups of one round would otherwise walk K in lockstep, all CUs touching the same
@@ -317,18 +340,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
         const int steps = (int)((tile >> 3) % p.stagger_phases) * p.stagger_mult;
         for (int s_ = 0; s_ < steps; ++s_) __builtin_amdgcn_s_sleep(DLC_STAGGER_SLEEP);
     }
-    // ---- prologue: A tiles 0..A_STAGES-1 and B tiles 0,1 issued (per-tile order A1,A0 / B0,B1, as the
-    // steady state issues them); then wait for tile 0.
+    // ---- prologue: A tiles 0..A_STAGES-1 and B tiles 0,1 issued, those below nk (nk is 1 or 2 for a 64-d or 128-d
+    // database and for a short last split-K chunk; per-tile order A1,A0 / B0,B1, as the steady state issues them); then
+    // wait for tile 0 -- the wait rule at t = -1: the tiles above 0 that were issued stay in flight.
 #pragma unroll
     for (int s_ = 0; s_ < A_STAGES; ++s_) {
-        DLC_ISSUE_A(s_ * A_TILE, 1, s_);
-        DLC_ISSUE_A(s_ * A_TILE, 0, s_);
+        if (s_ < nk) {
+            DLC_ISSUE_A(s_ * A_TILE, 1, s_);
+            DLC_ISSUE_A(s_ * A_TILE, 0, s_);
+        }
     }
     DLC_ISSUE_B(0 * B_TILE, 0, 0);
     DLC_ISSUE_B(0 * B_TILE, 1, 0);
-    DLC_ISSUE_B(1 * B_TILE, 0, 1);
-    DLC_ISSUE_B(1 * B_TILE, 1, 1);
-    if (is_a) { if constexpr (A_STAGES == 3) DLC_WAIT_VMCNT(16); else DLC_WAIT_VMCNT(8); }
+    if (nk > 1) {
+        DLC_ISSUE_B(1 * B_TILE, 0, 1);
+        DLC_ISSUE_B(1 * B_TILE, 1, 1);
+    }
+    if (nk == 1) DLC_WAIT_VMCNT(0);
+    else if (A_STAGES == 3 && is_a && nk > 2) DLC_WAIT_VMCNT(16);
     else DLC_WAIT_VMCNT(8);                                 // K tile 0 landed (this wave's share)
     wg_barrier();
     DLC_READ_A(faX, rdA0, 0);
@@ -341,42 +370,62 @@ __global__ __launch_bounds__(NTHREADS, 2) void score_gemm_kernel(GemmArgs p) {
     // Mini-phase m issues the reads of m+1 first, then its own MFMAs.  A half of the current
     // tile is dead once its k1 slice has been read (A1 after m3, B0 after m4, B1 after m5, A0
     // after m6): a barrier there, then the DMA that refills it -- A halves with K tile t+A_STAGES, B
-    // halves with t+2.  At the end of m6 each wave waits for its own stream: an A wave leaves
-    // A1(t+2) in flight (vmcnt 4; three halves / vmcnt 12 with a 3-deep ring), a B wave B0(t+2), B1(t+2) (vmcnt 8); K
-    // tile t+1, whose first slices are read in m7 / m8, has then landed.
-    for (int t = 0; t < nk; ++t) {
-        DLC_READ_B(fbY, rdB0, HALF_BYTES);
-        DLC_MFMA(faX, fbX, 0, 0);                                  // m1
-        DLC_READ_A(faY, rdA0, HALF_BYTES);
-        DLC_MFMA(faX, fbY, 0, 1);                                  // m2
-        DLC_READ_A(faX, rdA1, HALF_BYTES);
-        DLC_MFMA(faY, fbY, 1, 1);                                  // m3
-        DLC_RELEASE();                                             // A1 read by everyone
-        DLC_READ_B(fbY, rdB1, 0);
-        DLC_ISSUE_A(aoff, 1, t + A_STAGES);
-        DLC_MFMA(faY, fbX, 1, 0);                                  // m4
-        DLC_RELEASE();                                             // B0
-        DLC_READ_B(fbX, rdB1, HALF_BYTES);
-        DLC_ISSUE_B(boff, 0, t + 2);
-        DLC_MFMA(faX, fbY, 1, 0);                                  // m5
-        DLC_RELEASE();                                             // B1
-        DLC_READ_A(faY, rdA1, 0);
-        DLC_ISSUE_B(boff, 1, t + 2);
-        DLC_MFMA(faX, fbX, 1, 1);                                  // m6
-        if (is_a) { if constexpr (A_STAGES == 3) DLC_WAIT_VMCNT(12); else DLC_WAIT_VMCNT(4); }
-        else DLC_WAIT_VMCNT(8);                                    // K tile t+1 landed (this wave's share)
-        DLC_RELEASE();                                             // A0; and t+1 visible to all
-        DLC_ISSUE_A(aoff, 0, t + A_STAGES);
-        aoff = aoff == (A_STAGES - 1) * A_TILE ? 0u : aoff + A_TILE;   // ring positions of K tile t+1
-        boff ^= B_TILE;
-        rdA0 = rdA0_l + aoff; rdA1 = rdA1_l + aoff; rdB0 = rdB0_l + boff; rdB1 = rdB1_l + boff;
-        DLC_READ_A(faX, rdA0, 0);
-        DLC_MFMA(faY, fbX, 0, 1);                                  // m7
-        DLC_READ_B(fbX, rdB0, 0);
-        DLC_MFMA(faY, fbY, 0, 0);                                  // m8
+    // halves with t+2, each only where that tile exists.  At the end of m6 each wave waits for its own stream by the
+    // wait rule above: in the steady state an A wave leaves A1(t+2) in flight (vmcnt 4; three halves / vmcnt 12 with a
+    // 3-deep ring), a B wave B0(t+2), B1(t+2) (vmcnt 8); K tile t+1, whose first slices are read in m7 / m8, has then
+    // landed.  (The last tile has no successor: its m7 / m8 read a ring position that nothing refilled, into fragment
+    // registers that nobody uses.)
+    // DLC_K_TILE(L): iteration t with L = nk - 1 - t iterations left behind it, L a compile-time constant.  Every L >=
+    // A_STAGES is the steady state, and L = 1 and L = 0 are one and the same code: nothing to issue, nothing left in flight.
+#define DLC_K_TILE(L)                                                                                \
+    do {                                                                                             \
+        DLC_READ_B(fbY, rdB0, HALF_BYTES);                                                           \
+        DLC_MFMA(faX, fbX, 0, 0);                                  /* m1 */                          \
+        DLC_READ_A(faY, rdA0, HALF_BYTES);                                                           \
+        DLC_MFMA(faX, fbY, 0, 1);                                  /* m2 */                          \
+        DLC_READ_A(faX, rdA1, HALF_BYTES);                                                           \
+        DLC_MFMA(faY, fbY, 1, 1);                                  /* m3 */                          \
+        DLC_RELEASE();                                             /* A1 read by everyone */         \
+        DLC_READ_B(fbY, rdB1, 0);                                                                    \
+        if constexpr ((L) >= A_STAGES) DLC_ISSUE_A(aoff, 1, t + A_STAGES);                           \
+        DLC_MFMA(faY, fbX, 1, 0);                                  /* m4 */                          \
+        DLC_RELEASE();                                             /* B0 */                          \
+        DLC_READ_B(fbX, rdB1, HALF_BYTES);                                                           \
+        if constexpr ((L) >= 2) DLC_ISSUE_B(boff, 0, t + 2);                                         \
+        DLC_MFMA(faX, fbY, 1, 0);                                  /* m5 */                          \
+        DLC_RELEASE();                                             /* B1 */                          \
+        DLC_READ_A(faY, rdA1, 0);                                                                    \
+        if constexpr ((L) >= 2) DLC_ISSUE_B(boff, 1, t + 2);                                         \
+        DLC_MFMA(faX, fbX, 1, 1);                                  /* m6 */                          \
+        DLC_WAIT_TILE(L);                                          /* K tile t+1 landed (this wave's share) */ \
+        DLC_RELEASE();                                             /* A0; and t+1 visible to all */  \
+        if constexpr ((L) >= A_STAGES) DLC_ISSUE_A(aoff, 0, t + A_STAGES);                           \
+        aoff = aoff == (A_STAGES - 1) * A_TILE ? 0u : aoff + A_TILE;   /* ring positions of K tile t+1 */ \
+        boff ^= B_TILE;                                                                              \
+        rdA0 = rdA0_l + aoff; rdA1 = rdA1_l + aoff; rdB0 = rdB0_l + boff; rdB1 = rdB1_l + boff;      \
+        DLC_READ_A(faX, rdA0, 0);                                                                    \
+        DLC_MFMA(faY, fbX, 0, 1);                                  /* m7 */                          \
+        DLC_READ_B(fbX, rdB0, 0);                                                                    \
+        DLC_MFMA(faY, fbY, 0, 0);                                  /* m8 */                          \
+        ++t;                                                                                         \
+    } while (0)
+    // The steady loop, then the last A_STAGES iterations (fewer where nk is smaller) peeled off it: vmcnt takes an
+    // immediate, so the tail's shorter waits and missing issues are code of their own and the loop pays nothing for them,
+    // not even the clamp.  The last two iterations are a loop of their own and not two copies: straight-line copies cost
+    // 30-40 VGPRs (the accumulators were renamed from copy to copy), the loop costs 1-4.
+    static_assert(tail_vmcnt_a(1) == 0 && tail_vmcnt_b(1) == 0 && tail_vmcnt_a(0) == 0 && tail_vmcnt_b(0) == 0 && A_STAGES >= 2,
+                  "DLC_K_TILE(1) serves L = 0 too");
+    int t = 0;
+    while (t < nk - A_STAGES) DLC_K_TILE(A_STAGES);
+    if constexpr (A_STAGES == 3) {
+        if (nk > 2) DLC_K_TILE(2);
     }
-    DLC_WAIT_VMCNT(0);   // the clamped tail DMAs must not outlive the workgroup's LDS
+#pragma unroll 1
+    while (t < nk) DLC_K_TILE(1);
+    DLC_WAIT_VMCNT(0);   // rule 6 of lds_dma.h; it guards the protocol, not a tail DMA: nothing is in flight behind the last wait
     DLC_WAIT_LGKM0();
+#undef DLC_K_TILE
+#undef DLC_WAIT_TILE
 #undef DLC_ISSUE_A
 #undef DLC_ISSUE_B
 #undef DLC_READ_A
