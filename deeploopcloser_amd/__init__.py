@@ -23,6 +23,7 @@ include/dlc.h, with the reference's Python call surface on top:
     LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector   (streaming; all take sequence=L, suppress=W)
     fuse_scores, FusedLoopClosureDetector   (multi-descriptor fusion: score rows normalised per row, weighted and summed; new)
     PlaceTracker, track_places (and track= on the detectors): a Viterbi filter over score rows with a "no loop" state -- the place per frame and the smoothed labelling of the traversal; new
+    Vlad, vlad_frame_descriptors (and pool= on describe_sdav, loop_closure --pool vlad; python -m deeploopcloser_amd.train_vlad): a k-means codebook of patch descriptors and VLAD pooling -- one orderless row per frame in front of KeyframeDatabase; new
     ground_truth / pr_curve_cells / recall_at / pr_curve_queries / PRCurve / LoopClosureEvaluator   (ground-truth evaluation: PR curves, average precision, recall@K; new)
 
 Importing the package is cheap and works without a GPU; constructing any of
@@ -37,7 +38,7 @@ from .cnn_vtl import CnnVtl
 from .similarity import SimilarityCalculator, SimilarityStream
 from .distance import DistanceCalculator, CnnVtlKeyframeDatabase
 from .seqslam import SeqSlam, DifferenceCalculator, SadKeyframeDatabase
-from .matching import encode, match, match_topk, KeyframeDatabase, MatchPipeline, flatten_frame_descriptors
+from .matching import encode, match, match_topk, KeyframeDatabase, MatchPipeline, flatten_frame_descriptors, vlad_frame_descriptors
 from .dist import ShardedKeyframeDatabase, shard_bounds, merge_topk_torch
 from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, read_ppm
 from . import tensor_wrapper
@@ -49,10 +50,12 @@ from . import fusion
 from .fusion import fuse_scores
 from . import tracking
 from .tracking import PlaceTracker, track_places
+from . import vlad
+from .vlad import Vlad
 from . import evaluate
 from .evaluate import ground_truth, pr_curve_cells, recall_at, pr_curve_queries, PRCurve, LoopClosureEvaluator
 
-__all__ = ["PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

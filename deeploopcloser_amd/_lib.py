@@ -29,6 +29,9 @@ DLC_TRACK_AUTO, DLC_TRACK_RESIDENT, DLC_TRACK_ROWS = 0, 1, 2
 DLC_TRACK_RESIDENT_MAX = 8192   # the most columns the RESIDENT plan of dlc_track_rows keeps in LDS
 DLC_TRACK_JUMP, DLC_TRACK_FROM_NULL, DLC_TRACK_ORIGIN, DLC_TRACK_ABSENT = -1, -2, -3, -128     # back-pointer codes
 DLC_TRACK_END_FILTERED, DLC_TRACK_NO_PATH = -2, -2
+DLC_VLAD_MAX_WORDS, DLC_VLAD_MAX_PATCHES = 256, 1024   # the most words of a codebook and patches of a frame (dlc_vlad_encode)
+DLC_KMEANS_BLOCK = 1024      # rows of a block of dlc_kmeans_step's member sums (the leaves of its TREE)
+DLC_VLAD_NORM_NONE, DLC_VLAD_NORM_INTRA = 0, 1
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -123,6 +126,11 @@ SIGNATURES = {
     "dlc_track_rows": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _dbl, _dbl, _dbl, _int, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
     "dlc_track_backtrace": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dlc_vlad_assign": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _i64, _vp, _vp, _vp]),
+    "dlc_vlad_encode_workspace_bytes": (_sz, [_i64, _int, _i64, _int]),
+    "dlc_vlad_encode": (_int, [_vp, _vp, _i64, _int, _i64, _i64, _vp, _int, _i64, _int, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dlc_kmeans_step_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "dlc_kmeans_step": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dlc_pr_cell_counts_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_pr_cell_counts": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _int, _vp, _vp,
                                   _vp, _sz, _vp]),

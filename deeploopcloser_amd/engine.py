@@ -1308,6 +1308,98 @@ class Engine:
         self._wrote(out)
         return out[:, :n]
 
+    _VLAD_NORMS = {"none": L.DLC_VLAD_NORM_NONE, "intra": L.DLC_VLAD_NORM_INTRA}
+
+    def _f64_rows(self, who, what, t, width=None):
+        """The checks of an fp64 operand [rows, H] on the device -> (t, rows, H, ld): a row-strided view is taken as it
+        is (its padding columns are never read), anything else made contiguous."""
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float64 or t.device != self.device:
+            raise ValueError("%s: %s must be a 2-D float64 tensor on %s" % (who, what, self.device))
+        rows, h = t.shape
+        if rows < 1 or h < 1:
+            raise ValueError("%s: %s is [%d, %d]: nothing to do" % (who, what, rows, h))
+        if width is not None and h != width:
+            raise ValueError("%s: %s is %d wide, the rows are %d" % (who, what, h, width))
+        if t.stride(1) != 1 or (rows > 1 and t.stride(0) < h):
+            t = t.contiguous()
+        return t, rows, h, t.stride(0) if rows > 1 else max(h, t.stride(0))
+
+    def _codebook(self, who, centroids, width):
+        c, k, _, ldc = self._f64_rows(who, "the codebook", centroids, width)
+        if k > L.DLC_VLAD_MAX_WORDS or k * width >= 1 << 31:
+            raise ValueError("%s: a codebook of %d words x %d outside 1..%d words, K * H < 2^31" % (who, k, width,
+                                                                                                  L.DLC_VLAD_MAX_WORDS))
+        return c, k, ldc
+
+    def vlad_assign(self, x, centroids, with_dist=False):
+        """a int32 [rows]: the nearest word of every row of x [rows, H] (fp64 on the device) in the codebook [K, H] by the
+        squared distance DIST of include/dlc.h (dlc_vlad_assign) -- the lowest index among equals, -1 for a row whose
+        distances are all NaN.  with_dist: (a, the distances fp64 [rows])."""
+        x, rows, h, ldx = self._f64_rows("vlad_assign", "x", x)
+        c, k, ldc = self._codebook("vlad_assign", centroids, h)
+        a = torch.empty(rows, dtype=torch.int32, device=self.device)
+        d = torch.empty(rows, dtype=torch.float64, device=self.device) if with_dist else None
+        self._check(self.lib.dlc_vlad_assign(self.ctx, _ptr(x), rows, h, ldx, _ptr(c), k, ldc, _ptr(a), _ptr(d), self._stream()))
+        return (a, d) if with_dist else a
+
+    def vlad_encode(self, x, centroids, patches=30, norm="intra", out=None, with_assign=False):
+        """VLAD descriptors fp64 [frames, K * H] of x [frames * patches, H] (fp64 on the device; frame f owns rows
+        f * patches ..) against the codebook [K, H] (dlc_vlad_encode, include/dlc.h): per word the sum of the residuals
+        x - c_k of the frame's patches assigned to it, in patch order; norm "intra": every word's block divided by its
+        L2 norm, "none": as summed.  The global L2 normalisation is the database's (KeyframeDatabase / normalize).  A
+        frame's row does not depend on its batch.  out: a float64 tensor [frames, >= K * H] with unit column stride to
+        write into (columns past K * H keep their bits).  with_assign: (out, the assignments int32 [frames * patches])."""
+        if norm not in self._VLAD_NORMS:
+            raise ValueError("vlad_encode: norm=%r is none of %s" % (norm, sorted(self._VLAD_NORMS)))
+        patches = int(patches)
+        if not 1 <= patches <= L.DLC_VLAD_MAX_PATCHES:
+            raise ValueError("vlad_encode: patches=%d outside 1..%d" % (patches, L.DLC_VLAD_MAX_PATCHES))
+        x, rows, h, ldx = self._f64_rows("vlad_encode", "x", x)
+        if rows % patches:
+            raise ValueError("vlad_encode: %d rows are no whole number of frames of %d patches" % (rows, patches))
+        frames = rows // patches
+        c, k, ldc = self._codebook("vlad_encode", centroids, h)
+        if out is None:
+            out = torch.empty((frames, k * h), dtype=torch.float64, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float64 or out.device != self.device or \
+                out.shape[0] != frames or out.shape[1] < k * h or out.stride(1) != 1 or (frames > 1 and out.stride(0) < k * h):
+            raise ValueError("vlad_encode: out must be a float64 tensor [%d, >= %d] on %s with unit column stride"
+                             % (frames, k * h, self.device))
+        ld_out = out.stride(0) if frames > 1 else max(k * h, out.stride(0))
+        a = torch.empty(rows, dtype=torch.int32, device=self.device) if with_assign else None
+        need = self.lib.dlc_vlad_encode_workspace_bytes(frames, patches, h, k)
+        if need == 0:
+            raise ValueError("vlad_encode: frames=%d, H=%d, K=%d outside the supported sizes" % (frames, h, k))
+        ws = self.workspace("vlad_encode", need)
+        self._check(self.lib.dlc_vlad_encode(self.ctx, _ptr(x), frames, patches, h, ldx, _ptr(c), k, ldc, self._VLAD_NORMS[norm],
+                                             _ptr(out), ld_out, _ptr(a), _ptr(ws), ws.numel(), self._stream()))
+        self._wrote(out)
+        return (out[:, :k * h], a) if with_assign else out[:, :k * h]
+
+    def kmeans_step(self, x, centroids, prev_assign=None):
+        """One Lloyd step of dlc_kmeans_step (include/dlc.h) over x [rows, H] (fp64 on the device) from the codebook
+        [K, H]: (new codebook fp64 [K, H], assignments int32 [rows], counts int64 [K], inertia fp64 [1], changed int64
+        [1]) -- all device tensors, nothing is read back.  Member sums run in row order within blocks of 1024 rows and by
+        a fixed tree over the blocks, so the step is a function of its operands' bits; an empty word keeps its centre.
+        changed counts the rows whose assignment differs from prev_assign (int32 [rows]; None: every row)."""
+        x, rows, h, ldx = self._f64_rows("kmeans_step", "x", x)
+        c, k, ldc = self._codebook("kmeans_step", centroids, h)
+        if prev_assign is not None:
+            self._check_out("kmeans_step: prev_assign", prev_assign, (rows,), torch.int32)
+        c_out = torch.empty((k, h), dtype=torch.float64, device=self.device)
+        a = torch.empty(rows, dtype=torch.int32, device=self.device)
+        counts = torch.empty(k, dtype=torch.int64, device=self.device)
+        inertia = torch.empty(1, dtype=torch.float64, device=self.device)
+        changed = torch.empty(1, dtype=torch.int64, device=self.device)
+        need = self.lib.dlc_kmeans_step_workspace_bytes(rows, h, k)
+        if need == 0:
+            raise ValueError("kmeans_step: rows=%d, H=%d, K=%d outside the supported sizes" % (rows, h, k))
+        ws = self.workspace("kmeans_step", need)
+        self._check(self.lib.dlc_kmeans_step(self.ctx, _ptr(x), rows, h, ldx, _ptr(c), k, ldc, _ptr(c_out), h, _ptr(prev_assign),
+                                             _ptr(a), _ptr(counts), _ptr(inertia), _ptr(changed), _ptr(ws), ws.numel(),
+                                             self._stream()))
+        return c_out, a, counts, inertia, changed
+
     def peak_topk_rows(self, scores, k, suppress, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None,
                        poison=None):
         """(scores [rows, k], idx [rows, k] int64): distinct-place candidates, the windowed peak top-k of

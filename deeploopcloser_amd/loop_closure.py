@@ -914,6 +914,9 @@ class FusedLoopClosureDetector:
         return _loops(scores, ids, first_id, self.threshold, chains=chains)
 
 
+SDAV_CLI_WIDTH = 2500       # columns of a patch descriptor of the CLI's SDAV: the reference's network (SDAV.py:31-32), --weights or not
+
+
 def _frame_files(dataset_path, pattern):
     files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
     if not files:
@@ -921,9 +924,19 @@ def _frame_files(dataset_path, pattern):
     return files
 
 
-def describe_sdav(files, network=None, key_points_fn=None):
+def describe_sdav(files, network=None, key_points_fn=None, pool=None):
     """Frames -> one [30*2500] place descriptor per frame (patches -> SDAV.transform, flattened), a DEVICE tensor: the
-    uint8 frames go up once, grey / key-points / patches / encoder run back to back in HBM (pipeline.py)."""
+    uint8 frames go up once, grey / key-points / patches / encoder run back to back in HBM (pipeline.py).
+    pool: a fitted vlad.Vlad -- the frame's patch descriptors are pooled into one orderless VLAD row [K * H] instead of
+    being concatenated; None: the concatenation, as ever."""
+    desc = _describe_sdav_flat(files, network, key_points_fn)
+    if pool is None:
+        return desc
+    p = (network.input_shape[0] if network is not None else 30)
+    return pool.transform_tensor(desc.view(len(files) * p, -1), patches=p)
+
+
+def _describe_sdav_flat(files, network=None, key_points_fn=None):
     from . import pipeline
     from .input import read_ppm
     from .sdav import SDAV
@@ -1019,6 +1032,11 @@ def main(argv=None):
                     help="with --fuse: one finite weight per member (default: all 1)")
     ap.add_argument("--fuse-norm", choices=list(FUSE_NORMS), default=None,
                     help="with --fuse: how each member's row is normalised before the sum (default: zscore)")
+    ap.add_argument("--pool", choices=["flatten", "vlad"], default=None,
+                    help="--network sdav --metric cosine: the frame descriptor -- flatten, the concatenation of the patch "
+                         "descriptors (the default), or vlad, their orderless VLAD pooling over the codebook of --codebook")
+    ap.add_argument("--codebook", default=None, metavar="FILE",
+                    help="with --pool vlad: the .npz written by python -m deeploopcloser_amd.train_vlad")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -1058,6 +1076,21 @@ def main(argv=None):
             if not all(np.isfinite(v) for v in args.fuse_weights):
                 ap.error("--fuse-weights must be finite")
         args.fuse_norm = args.fuse_norm or "zscore"
+    if args.pool == "vlad":
+        if args.fuse is not None or args.network != "sdav" or args.metric != "cosine":
+            ap.error("--pool vlad needs --network sdav --metric cosine")
+        if args.codebook is None:
+            ap.error("--pool vlad needs --codebook")
+    elif args.codebook is not None:
+        ap.error("--codebook needs --pool vlad")
+    if args.codebook is not None:
+        try:
+            with np.load(args.codebook, allow_pickle=False) as z:
+                args.codebook_width = int(z["centroids"].shape[1])
+        except (OSError, ValueError, KeyError, IndexError) as err:
+            ap.error("--codebook: %s" % err)
+        if args.codebook_width != SDAV_CLI_WIDTH:
+            ap.error("--codebook: its words are %d wide, the encoder's descriptors %d" % (args.codebook_width, SDAV_CLI_WIDTH))
     thumbnails = args.network == "seqslam" or (args.fuse is not None and "sad" in args.fuse)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
@@ -1194,7 +1227,11 @@ def _stream(args, files):
         net = SDAV(dtype=args.encoder_dtype)
         if args.weights:
             net.load_weights(args.weights)
-        describe = lambda fs: describe_sdav(fs, net)
+        pool = None
+        if args.pool == "vlad":
+            from .vlad import Vlad
+            pool = Vlad.load(args.codebook)
+        describe = (lambda fs: describe_sdav(fs, net)) if pool is None else (lambda fs: describe_sdav(fs, net, pool=pool))
     elif args.network == "seqslam":
         from . import pipeline
         from .input import read_ppm

@@ -24,6 +24,12 @@ def flatten_frame_descriptors(h, patches=30):
     return h.reshape(h.shape[0] // patches, patches * h.shape[1])
 
 
+def vlad_frame_descriptors(h, vlad, patches=30):
+    """The orderless counterpart of flatten_frame_descriptors: one VLAD row [K * H] per frame from the flat [B*30, H]
+    patch descriptors and a fitted vlad.Vlad -- fp64 on the device, ready for KeyframeDatabase (which L2-normalises)."""
+    return vlad.transform_tensor(h, patches)
+
+
 class KeyframeDatabase:
     """A shard of stored (L2-normalised bf16 / fp16) key-frame descriptors resident in HBM.
 

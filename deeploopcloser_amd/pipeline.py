@@ -109,6 +109,21 @@ def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, 
     return desc
 
 
+def sdav_place_descriptors_from_frames(frames, network, vlad, parser=None, key_points=None, chunk_frames=256, timings=None):
+    """frames -> patches -> SDAV descriptors -> one VLAD row per frame, fp64 [N, K * H] ON THE DEVICE: the orderless place
+    descriptor (vlad.Vlad, fitted) in front of KeyframeDatabase.  Everything in front of the pooling is
+    sdav_descriptors_from_frames'; a frame's row depends on that frame and the codebook alone."""
+    eng = network.engine
+    cur = torch.cuda.current_stream(eng.device)
+    desc = sdav_descriptors_from_frames(frames, network, parser, key_points, chunk_frames, timings)
+    if desc.shape[0] == 0:
+        return torch.empty((0, vlad.dim), dtype=torch.float64, device=eng.device)
+    m = _mark(timings, "VLAD pooling", cur)
+    out = vlad.transform_tensor(desc)
+    _done(timings, m, cur)
+    return out
+
+
 def sdav_similarity_matrix_from_frames(frames, network, parser=None, key_points=None, chunk_frames=256, mu=0.5, sigma=0.2,
                                        a=10, b=-10, as_int64=True, device_result=False, timings=None):
     """create_similarity_matrix.py:23-38 end to end: frames -> patches -> SDAV descriptors -> the all-vs-all similarity matrix

@@ -1078,6 +1078,65 @@ int dlc_positive_rank_rows(dlc_ctx* ctx, int dtype /* DLC_F64 | DLC_F32 | DLC_I6
                            int64_t* out_rank, int64_t* out_idx, int64_t* out_npos,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Orderless place descriptors: a k-means codebook of patch descriptors and VLAD pooling (Jegou et al., CVPR 2010; the
+ * pooling of NetVLAD).  A frame's P patch descriptors come in key-point response order, which a viewpoint change
+ * permutes; their concatenation then compares unrelated patches.  VLAD describes the frame by the per-word sums of
+ * residuals x - c_k instead: a fixed-length row [K * H] that does not depend on the order of the patches and goes into
+ * dlc_l2_normalize_rows and the cosine top-k as it is.
+ * INPUT.  x is fp64 [rows, ldx] and the codebook fp64 [K, ldc], both using their first H columns; no other column of
+ * either is ever read.  1 <= K <= DLC_VLAD_MAX_WORDS, 1 <= H, K * H < 2^31, 1 <= P <= DLC_VLAD_MAX_PATCHES, 1 <= rows,
+ * frames < 2^31, ld >= H, ld_out >= K * H.
+ * ARITHMETIC.  All of it is fp64, every operation rounded on its own (no fma contraction), division and sqrt the IEEE
+ * correctly rounded ones.  TREE is the parallel sum defined at dlc_fuse_rows (pad with -0.0 to a power of two, add
+ * halves recursively).
+ * DIST(x, c):  d = +0.0;  for h = 0 .. H-1 ascending:  t = x_h - c_h;  q = t * t;  d = d + q.  One serial chain in h: any
+ * tiling of (row, word) pairs gives the same bits, and the sum is never split along H or formed from a Gram product.
+ * ASSIGNMENT.  a(x) = the lowest k whose DIST(x, c_k) is not NaN and is <= every other non-NaN distance (+inf can win);
+ * -1 if every distance is NaN.  A copy of a centroid at a higher index is never taken.  dlc_vlad_assign writes
+ * out_assign[n] = a(x_n) and, if out_dist is given, out_dist[n] = DIST(x_n, c_a(n)) (a quiet NaN for a(n) = -1).
+ * VLAD of frame f (rows f * P .. f * P + P - 1).  R_k[h] = the sum of x_ph - c_kh over the patches p with a(p) = k, in
+ * ascending p, starting FROM the first member's term, not from 0; +0.0 for a word without a member; patches with
+ * a = -1 belong to no word.  DLC_VLAD_NORM_NONE: out[f][k * H + h] = R_k[h].  DLC_VLAD_NORM_INTRA: n_k =
+ * sqrt(TREE_h(R_k[h] * R_k[h])); the word's H outputs are +0.0 if n_k == 0.0, else R_k[h] / n_k (NaN and inf give what
+ * IEEE gives).  The global L2 normalisation is dlc_l2_normalize_rows' when the row is stored.  Only out[f][0 .. K*H-1]
+ * is written; columns K * H .. ld_out-1 keep their bits.  A frame's row depends on its P rows and the codebook alone:
+ * not on the batch, ldx, ldc or ld_out.  out_assign (optional) receives a() of all frames * P rows.  out must not overlap
+ * x or the codebook.  dlc_vlad_encode always needs dlc_vlad_encode_workspace_bytes(frames, P, H, K) bytes.
+ * ONE LLOYD STEP (dlc_kmeans_step) over rows x[0 .. rows-1] with codebook c_in.  a(n) as above, written to out_assign.
+ * Rows are cut into blocks of DLC_KMEANS_BLOCK consecutive rows.  S_{b,k}[h] = the sum of x_nh over the members of k in
+ * block b in ascending n, starting from the first member's value; -0.0 for a block without a member of k.
+ * S_k[h] = TREE_b(S_{b,k}[h]).  out_counts[k] = the number of members.  c_out_k[h] = S_k[h] / (double)count_k if
+ * count_k > 0, else c_in_k[h]: an empty word keeps its centre.  *out_inertia = TREE over the blocks of the block's sum
+ * s = +0.0; s = s + DIST(x_n, c_in_a(n)) over its rows with a(n) >= 0 in ascending n.  *out_changed = the number of rows
+ * with a(n) != prev_assign[n]; rows if prev_assign is NULL.  The step is a function of the rows in their order and of
+ * c_in: no plan, no grid, no atomics.  c_out must not overlap c_in, out_assign must not overlap prev_assign.
+ * LAUNCHES.  All on `stream`, none synchronises; memory and workspaces (16-byte aligned) are the caller's.  assign: 1;
+ * encode: assign, residual sums, (INTRA) the norm; k-means step: assign, block sums, block statistics, finish.
+ * Errors: DLC_ERR_BAD_ARG for a null or misaligned pointer, rows / frames / H / K / P < 1, ld < H, ld_out < K * H, an
+ * unknown norm or an overlap named above; DLC_ERR_BAD_SHAPE for K > DLC_VLAD_MAX_WORDS, P > DLC_VLAD_MAX_PATCHES,
+ * K * H >= 2^31, rows or frames >= 2^31; DLC_ERR_WORKSPACE for a workspace that is missing, too small or not 16-byte
+ * aligned.  Nothing is written then.  The *_workspace_bytes functions return 0 for refused shapes.
+ */
+#define DLC_VLAD_MAX_WORDS 256
+#define DLC_VLAD_MAX_PATCHES 1024
+#define DLC_KMEANS_BLOCK 1024
+enum { DLC_VLAD_NORM_NONE = 0, DLC_VLAD_NORM_INTRA = 1 };
+int dlc_vlad_assign(dlc_ctx* ctx, const double* x, int64_t rows, int64_t H, int64_t ldx,
+                    const double* centroids, int K, int64_t ldc,
+                    int32_t* out_assign, double* out_dist /* may be NULL */, void* stream);
+size_t dlc_vlad_encode_workspace_bytes(int64_t frames, int P, int64_t H, int K);
+int dlc_vlad_encode(dlc_ctx* ctx, const double* x, int64_t frames, int P, int64_t H, int64_t ldx,
+                    const double* centroids, int K, int64_t ldc, int norm,
+                    double* out, int64_t ld_out, int32_t* out_assign /* [frames * P], may be NULL */,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t dlc_kmeans_step_workspace_bytes(int64_t rows, int64_t H, int K);
+int dlc_kmeans_step(dlc_ctx* ctx, const double* x, int64_t rows, int64_t H, int64_t ldx,
+                    const double* c_in, int K, int64_t ldc, double* c_out, int64_t ldc_out,
+                    const int32_t* prev_assign /* may be NULL */, int32_t* out_assign,
+                    int64_t* out_counts /* [K] */, double* out_inertia /* device, 1 */,
+                    int64_t* out_changed /* device, 1 */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
  * Row L2-normalisation (optional mean-centring first) of src[n,d] (DLC_F32 or
