@@ -32,6 +32,9 @@ DLC_TRACK_END_FILTERED, DLC_TRACK_NO_PATH = -2, -2
 DLC_VLAD_MAX_WORDS, DLC_VLAD_MAX_PATCHES = 256, 1024   # the most words of a codebook and patches of a frame (dlc_vlad_encode)
 DLC_KMEANS_BLOCK = 1024      # rows of a block of dlc_kmeans_step's member sums (the leaves of its TREE)
 DLC_VLAD_NORM_NONE, DLC_VLAD_NORM_INTRA = 0, 1
+DLC_PCA_CHUNK = 1024         # columns of x of one serial chain of dlc_pca_project; the chunks' sums are added in order
+DLC_PCA_MAX_COMPONENTS, DLC_PCA_SPLIT_MAX_ROWS = 8192, 64
+DLC_PCA_PLAN_AUTO, DLC_PCA_PLAN_ONE_PASS, DLC_PCA_PLAN_SPLIT = 0, 1, 2
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -131,6 +134,8 @@ SIGNATURES = {
     "dlc_vlad_encode": (_int, [_vp, _vp, _i64, _int, _i64, _i64, _vp, _int, _i64, _int, _vp, _i64, _vp, _vp, _sz, _vp]),
     "dlc_kmeans_step_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_kmeans_step": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dlc_pca_project_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "dlc_pca_project": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _i64, _vp, _vp, _i64, _int, _vp, _sz, _vp]),
     "dlc_pr_cell_counts_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_pr_cell_counts": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _int, _vp, _vp,
                                   _vp, _sz, _vp]),

@@ -1400,6 +1400,53 @@ class Engine:
                                              self._stream()))
         return c_out, a, counts, inertia, changed
 
+    _PCA_PLANS = {"auto": L.DLC_PCA_PLAN_AUTO, "one_pass": L.DLC_PCA_PLAN_ONE_PASS, "split": L.DLC_PCA_PLAN_SPLIT}
+
+    def pca_project(self, x, basis, mean=None, scale=None, out=None, plan="auto"):
+        """((x - mean) . basis) * scale, fp64 [rows, M], of x [rows, D] (fp64 on the device) against the basis [D, M]
+        (fp64 or fp32, component c in column c), mean fp64 [D] and scale fp64 [M] (either None: left out) --
+        dlc_pca_project, include/dlc.h: serial chains over chunks of 1024 columns of x, the chunks added in order, so a
+        row's bits depend on the row and the model alone, not on its batch or the plan.  plan "one_pass": a workgroup
+        walks all of D; "split" (<= 64 rows): the chunks are spread over the chip; "auto" chooses.  out: a float64
+        tensor [rows, >= M] with unit column stride to write into (columns past M keep their bits)."""
+        if plan not in self._PCA_PLANS:
+            raise ValueError("pca_project: plan=%r is none of %s" % (plan, sorted(self._PCA_PLANS)))
+        x, rows, d, ldx = self._f64_rows("pca_project", "x", x)
+        if not isinstance(basis, torch.Tensor) or basis.dim() != 2 or basis.dtype not in (torch.float64, torch.float32) or \
+                basis.device != self.device or basis.shape[0] != d or basis.shape[1] < 1:
+            raise ValueError("pca_project: the basis must be a float64 or float32 tensor [%d, M] on %s" % (d, self.device))
+        m = basis.shape[1]
+        if m > L.DLC_PCA_MAX_COMPONENTS:
+            raise ValueError("pca_project: %d components outside 1..%d" % (m, L.DLC_PCA_MAX_COMPONENTS))
+        if basis.stride(1) != 1 or (d > 1 and basis.stride(0) < m):
+            basis = basis.contiguous()
+        ldb = basis.stride(0) if d > 1 else max(m, basis.stride(0))
+        for what, v, n in (("mean", mean, d), ("scale", scale, m)):
+            if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.device != self.device or
+                                  tuple(v.shape) != (n,)):
+                raise ValueError("pca_project: %s must be a float64 tensor [%d] on %s" % (what, n, self.device))
+        mean = mean.contiguous() if mean is not None else None
+        scale = scale.contiguous() if scale is not None else None
+        if out is None:
+            out = torch.empty((rows, m), dtype=torch.float64, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float64 or out.device != self.device or \
+                out.shape[0] != rows or out.shape[1] < m or out.stride(1) != 1 or (rows > 1 and out.stride(0) < m):
+            raise ValueError("pca_project: out must be a float64 tensor [%d, >= %d] on %s with unit column stride"
+                             % (rows, m, self.device))
+        ld_out = out.stride(0) if rows > 1 else max(m, out.stride(0))
+        code = self._PCA_PLANS[plan]
+        if code == L.DLC_PCA_PLAN_SPLIT and rows > L.DLC_PCA_SPLIT_MAX_ROWS:
+            raise ValueError("pca_project: plan 'split' takes at most %d rows, not %d" % (L.DLC_PCA_SPLIT_MAX_ROWS, rows))
+        if rows >= 1 << 31 or d >= 1 << 31:
+            raise ValueError("pca_project: rows=%d, D=%d outside the supported sizes" % (rows, d))
+        need = self.lib.dlc_pca_project_workspace_bytes(rows, d, m, code)
+        ws = self.workspace("pca_project", need) if need else None
+        self._check(self.lib.dlc_pca_project(
+            self.ctx, _ptr(x), rows, d, ldx, _ptr(mean), L.DLC_F64 if basis.dtype == torch.float64 else L.DLC_F32, _ptr(basis), m,
+            ldb, _ptr(scale), _ptr(out), ld_out, code, _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
+        self._wrote(out)
+        return out[:, :m]
+
     def peak_topk_rows(self, scores, k, suppress, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None,
                        poison=None):
         """(scores [rows, k], idx [rows, k] int64): distinct-place candidates, the windowed peak top-k of

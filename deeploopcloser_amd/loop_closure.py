@@ -914,6 +914,7 @@ class FusedLoopClosureDetector:
         return _loops(scores, ids, first_id, self.threshold, chains=chains)
 
 
+SDAV_CLI_PATCHES = 30       # patches of a frame of the CLI's SDAV: the concatenation is 30 * 2500 wide
 SDAV_CLI_WIDTH = 2500       # columns of a patch descriptor of the CLI's SDAV: the reference's network (SDAV.py:31-32), --weights or not
 
 
@@ -934,6 +935,13 @@ def describe_sdav(files, network=None, key_points_fn=None, pool=None):
         return desc
     p = (network.input_shape[0] if network is not None else 30)
     return pool.transform_tensor(desc.view(len(files) * p, -1), patches=p)
+
+
+def describe_sdav_compact(files, network=None, key_points_fn=None, pool=None, pca=None):
+    """describe_sdav, then the rows projected by a fitted pca.Pca of their width (75 000 for the concatenation, K * 2500
+    behind a pool) to [frames, M]: the compact descriptor KeyframeDatabase stores.  pca None: describe_sdav's rows."""
+    desc = describe_sdav(files, network, key_points_fn, pool)
+    return desc if pca is None else pca.transform_tensor(desc)
 
 
 def _describe_sdav_flat(files, network=None, key_points_fn=None):
@@ -1037,6 +1045,9 @@ def main(argv=None):
                          "descriptors (the default), or vlad, their orderless VLAD pooling over the codebook of --codebook")
     ap.add_argument("--codebook", default=None, metavar="FILE",
                     help="with --pool vlad: the .npz written by python -m deeploopcloser_amd.train_vlad")
+    ap.add_argument("--pca", default=None, metavar="FILE",
+                    help="--network sdav --metric cosine: project the frame descriptor (of either --pool) with the .npz "
+                         "written by python -m deeploopcloser_amd.train_pca before it is stored and matched")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -1091,6 +1102,20 @@ def main(argv=None):
             ap.error("--codebook: %s" % err)
         if args.codebook_width != SDAV_CLI_WIDTH:
             ap.error("--codebook: its words are %d wide, the encoder's descriptors %d" % (args.codebook_width, SDAV_CLI_WIDTH))
+    if args.pca is not None:
+        if args.fuse is not None or args.network != "sdav" or args.metric != "cosine":
+            ap.error("--pca needs --network sdav --metric cosine")
+        try:
+            with np.load(args.pca, allow_pickle=False) as z:
+                pca_width = int(z["basis"].shape[0])
+            want = SDAV_CLI_PATCHES * SDAV_CLI_WIDTH
+            if args.pool == "vlad":
+                with np.load(args.codebook, allow_pickle=False) as z:
+                    want = int(z["centroids"].shape[0]) * SDAV_CLI_WIDTH
+        except (OSError, ValueError, KeyError, IndexError) as err:
+            ap.error("--pca: %s" % err)
+        if pca_width != want:
+            ap.error("--pca: its rows are %d wide, the frame descriptor %d" % (pca_width, want))
     thumbnails = args.network == "seqslam" or (args.fuse is not None and "sad" in args.fuse)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
@@ -1232,6 +1257,10 @@ def _stream(args, files):
             from .vlad import Vlad
             pool = Vlad.load(args.codebook)
         describe = (lambda fs: describe_sdav(fs, net)) if pool is None else (lambda fs: describe_sdav(fs, net, pool=pool))
+        if getattr(args, "pca", None) is not None:         # (callers that build the namespace themselves may not know --pca)
+            from .pca import Pca
+            compact = Pca.load(args.pca)
+            describe = lambda fs: describe_sdav_compact(fs, net, pool=pool, pca=compact)
     elif args.network == "seqslam":
         from . import pipeline
         from .input import read_ppm

@@ -109,18 +109,24 @@ def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, 
     return desc
 
 
-def sdav_place_descriptors_from_frames(frames, network, vlad, parser=None, key_points=None, chunk_frames=256, timings=None):
+def sdav_place_descriptors_from_frames(frames, network, vlad, parser=None, key_points=None, chunk_frames=256, timings=None,
+                                       pca=None):
     """frames -> patches -> SDAV descriptors -> one VLAD row per frame, fp64 [N, K * H] ON THE DEVICE: the orderless place
     descriptor (vlad.Vlad, fitted) in front of KeyframeDatabase.  Everything in front of the pooling is
-    sdav_descriptors_from_frames'; a frame's row depends on that frame and the codebook alone."""
+    sdav_descriptors_from_frames'; a frame's row depends on that frame and the codebook alone.
+    pca: a fitted pca.Pca of the VLAD row's width -- the rows are projected (and whitened) to [N, M]; None: as pooled."""
     eng = network.engine
     cur = torch.cuda.current_stream(eng.device)
     desc = sdav_descriptors_from_frames(frames, network, parser, key_points, chunk_frames, timings)
     if desc.shape[0] == 0:
-        return torch.empty((0, vlad.dim), dtype=torch.float64, device=eng.device)
+        return torch.empty((0, vlad.dim if pca is None else pca.dim), dtype=torch.float64, device=eng.device)
     m = _mark(timings, "VLAD pooling", cur)
     out = vlad.transform_tensor(desc)
     _done(timings, m, cur)
+    if pca is not None:
+        m = _mark(timings, "PCA projection", cur)
+        out = pca.transform_tensor(out)
+        _done(timings, m, cur)
     return out
 
 

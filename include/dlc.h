@@ -1137,6 +1137,50 @@ int dlc_kmeans_step(dlc_ctx* ctx, const double* x, int64_t rows, int64_t H, int6
                     int64_t* out_counts /* [K] */, double* out_inertia /* device, 1 */,
                     int64_t* out_changed /* device, 1 */, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Compact place descriptors: the PCA projection (and whitening) of a pooled row -- out = ((x - mean) . basis) * scale
+ * (Jegou & Chum, ECCV 2012).  A VLAD row of the reference's SDAV is 40 000 wide and the concatenation 75 000; the
+ * projection takes either to the <= 4096 columns the cosine top-k stores.  The sum order is STATED, and chosen so that
+ * it can be cut along D: a frame projected alone while streaming has the bits it had in the batch that built the
+ * database.
+ * INPUT.  x is fp64 [rows, ldx] using its first D columns; mean fp64 [D] or NULL; basis [D, ldb] in DLC_F64 or DLC_F32,
+ * component c in column c, using its first M columns; scale fp64 [M] or NULL.  No column of x past D and no column of
+ * basis past M is ever read.  1 <= rows, D < 2^31, 1 <= M <= DLC_PCA_MAX_COMPONENTS, ldx >= D, ldb >= M, ld_out >= M.
+ * ARITHMETIC.  All of it is fp64, every operation rounded on its own (no fma contraction).  For row r and component c:
+ * b_d = (double)basis[d][c] (exact for fp32);  t_d = x[r][d] - mean[d], or x[r][d] when mean is NULL.  Chunk j covers
+ * d = DLC_PCA_CHUNK * j .. min(D, DLC_PCA_CHUNK * (j + 1)) - 1.  Within a chunk  s_j = +0.0;  for d ascending:
+ * q = t_d * b_d;  s_j = s_j + q.  Then  y = s_0;  for j = 1, 2, .. ascending:  y = y + s_j.  out[r][c] = y * scale[c],
+ * or y when scale is NULL.  NaN and inf give what IEEE gives.  Only out[r][0 .. M-1] is written; columns M .. ld_out-1
+ * keep their bits.  A row's bits depend on that row, mean, basis and scale alone: not on rows, the pitches, the plan or
+ * the workspace.  out must not overlap x, mean, basis or scale.
+ * PLANS.  DLC_PCA_PLAN_ONE_PASS: a workgroup owns a (row tile, column tile), walks every chunk itself and keeps s and
+ * y per output; no workspace.  DLC_PCA_PLAN_SPLIT (rows <= DLC_PCA_SPLIT_MAX_ROWS): a workgroup takes one chunk of a
+ * tile and stores every s_j to the workspace [rows][chunks][M]; a finish kernel forms y in chunk order and applies
+ * scale -- a frame's gigabyte of basis is streamed by the whole chip.  DLC_PCA_PLAN_AUTO: SPLIT if rows <=
+ * DLC_PCA_SPLIT_MAX_ROWS, D > DLC_PCA_CHUNK and ONE_PASS would launch fewer than 256 workgroups (ceil(rows / RT) *
+ * ceil(M / CW) with RT = 2 for rows <= 2, else 8, and CW = 512 for rows > 2 and M > 256, else 256); otherwise ONE_PASS.  No atomics;
+ * t_d is formed once per (row, d); the basis is read along c.
+ * LAUNCHES.  All on `stream`, none synchronises; memory and the workspace (16-byte aligned) are the caller's.
+ * ONE_PASS: 1; SPLIT: partial sums, finish.  dlc_pca_project_workspace_bytes(rows, D, M, plan) is host arithmetic: the
+ * bytes the plan (AUTO: the plan it chooses) needs -- 0 under ONE_PASS, at least rows * chunks * M * 8 under SPLIT --
+ * and 0 for refused shapes.
+ * Errors: DLC_ERR_BAD_ARG for a null (x, basis, out) or misaligned pointer, rows / D / M < 1, ldx < D, ldb < M,
+ * ld_out < M, an unknown dtype or plan, or out overlapping an input; DLC_ERR_BAD_SHAPE for M > DLC_PCA_MAX_COMPONENTS,
+ * rows or D >= 2^31, or SPLIT with more than DLC_PCA_SPLIT_MAX_ROWS rows; DLC_ERR_WORKSPACE for a workspace (SPLIT)
+ * that is missing, too small or not 16-byte aligned.  Nothing is written then.
+ * The training mean needs no entry point of its own: dlc_kmeans_step with K = 1 is a defined column mean.
+ */
+#define DLC_PCA_CHUNK 1024
+#define DLC_PCA_MAX_COMPONENTS 8192
+#define DLC_PCA_SPLIT_MAX_ROWS 64
+enum { DLC_PCA_PLAN_AUTO = 0, DLC_PCA_PLAN_ONE_PASS = 1, DLC_PCA_PLAN_SPLIT = 2 };
+size_t dlc_pca_project_workspace_bytes(int64_t rows, int64_t D, int M, int plan);
+int dlc_pca_project(dlc_ctx* ctx, const double* x, int64_t rows, int64_t D, int64_t ldx,
+                    const double* mean /* [D], may be NULL */,
+                    int basis_dtype /* DLC_F64 | DLC_F32 */, const void* basis /* [D, ldb], component c in column c */,
+                    int M, int64_t ldb, const double* scale /* [M], may be NULL */,
+                    double* out, int64_t ld_out, int plan, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
  * Row L2-normalisation (optional mean-centring first) of src[n,d] (DLC_F32 or
