@@ -35,6 +35,8 @@ struct dlc_ctx {
     long long prune_shape[4];                   // ... and q, n, d / 64, kg
 };
 
+#include "dlc_hd.h"                             // dlc::fail, the size and row-limit helpers, dlc_f64_key: HIP-free, shared with the host tests
+
 // ids of the kernels that need hipFuncAttributeMaxDynamicSharedMemorySize (bits of dlc_ctx::func_attr_set)
 enum {
     DLC_ATTR_GEMM_BASE = 0,      // + tag (0 bf16, 1 f16) * 8 + mode (0..3) * 2 + maskq   -> bits 0..15
@@ -53,16 +55,6 @@ enum {
 namespace dlc {
 
 void staging_free(dlc_host_staging* s);
-
-inline int fail(dlc_ctx* ctx, int status, const char* fmt, ...) {
-    if (ctx) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(ctx->err, sizeof(ctx->err), fmt, ap);
-        va_end(ap);
-    }
-    return status;
-}
 
 #define DLC_HIP_CHECK(ctx, expr)                                                              \
     do {                                                                                      \
@@ -92,32 +84,6 @@ inline int profiled(dlc_ctx* ctx, hipStream_t st, F&& launch) {
     DLC_HIP_CHECK(ctx, hipEventRecord(ctx->ev_stop[slot], st));
     ctx->prof_calls++;
     return DLC_OK;
-}
-
-__host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-__host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// Columns row r of a selection may see, of n: linear in the row, so over a range of rows the largest sits at one end.
-__host__ __device__ __forceinline__ int64_t row_limit(int64_t r, int64_t n, int64_t limit0, int64_t limit_step) {
-    const int64_t l = limit0 + r * limit_step;
-    return l < 0 ? 0 : (l > n ? n : l);
-}
-// The largest row_limit of rows r_first .. r_last: at one end of the range (host entry points size their launches by it).
-inline int64_t max_row_limit(int64_t r_first, int64_t r_last, int64_t n, int64_t limit0, int64_t limit_step) {
-    const int64_t la = row_limit(r_first, n, limit0, limit_step), lb = row_limit(r_last, n, limit0, limit_step);
-    return la > lb ? la : lb;
-}
-
-// A scan's column tiles shared out among G slabs so that row_tiles x G comes to about max_wg workgroups.  max_slabs
-// bounds G for every smaller col_tiles too (the split's own G is not monotonic in col_tiles): it sizes the workspace.
-struct SlabSplit { int64_t G, tiles_per_slab; };
-inline int64_t max_slabs(int64_t row_tiles, int64_t col_tiles, int64_t max_wg) {
-    const int64_t cap = cdiv(max_wg, row_tiles);
-    return col_tiles < cap ? col_tiles : cap;
-}
-inline SlabSplit split_slabs(int64_t row_tiles, int64_t col_tiles, int64_t max_wg) {
-    const int64_t tps = cdiv(col_tiles, max_slabs(row_tiles, col_tiles, max_wg));
-    return {cdiv(col_tiles, tps), tps};
 }
 
 // RAII-free device guard: the C ABI is re-entrant per context and each context
@@ -161,16 +127,4 @@ __device__ __forceinline__ long long f64_key(double s) {
     if (!(x > -4.0e18)) return KEY64_EMPTY + 1;           // -inf, NaN, absurdly negative: last
     if (x > 4.0e18) return 0x7fffffffffffffffll;
     return __double2ll_rn(x);                             // round half to even, as np.round
-}
-
-// Order-preserving 64-bit key of a double (atomicMin / atomicMax on unsigned long long): per-frame minima / maxima of
-// the CnnVtl descriptor are folded this way by several kernels (cnnvtl.hip, the convolution epilogue of gemm_dma_f64.hip).
-// keys[2 f] = key of the minimum of frame f (initially ~0), keys[2 f + 1] = key of its maximum (initially 0).
-__device__ __forceinline__ unsigned long long dlc_f64_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dlc_f64_unkey(unsigned long long k) {
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
 }

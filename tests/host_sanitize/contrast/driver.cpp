@@ -1,9 +1,11 @@
 // contrast_rows.hip on the host: the kernel's own text (copied beside this file as contrast_rows.cpp, with the stand-in
-// dlc_internal.h of this directory in front of it) run thread by thread against the definition of include/dlc.h written as
-// plain loops per cell, under AddressSanitizer + UBSan: every load, every store and every LDS index of the kernel is a
-// checked access to a host array of exactly the caller's size.  tests/test_contrast_host_cpu.py builds and runs it.
+// ../dlc_internal.h in front of it) run with one host thread per GPU thread, its barriers real ones, against the
+// definition of include/dlc.h written as plain loops per cell, under AddressSanitizer + UBSan: every load, every store and
+// every LDS index of the kernel is a checked access to a host array of exactly the caller's size.
+// tests/test_contrast_host_cpu.py builds and runs it.
 #include "contrast_rows.cpp"
 #include <vector>
+#include <algorithm>
 #include <random>
 #pragma clang fp contract(off)
 static double ref_cell(const std::vector<double>& x, long long j, long long lim, int R) {
@@ -35,7 +37,7 @@ template <typename T> static long long run(int dt, long long rows, long long n, 
     if (rc != 0) { printf("rc %d\n", rc); return 1; }
     long long bad = 0;
     for (long long r = 0; r < rows; ++r) {
-        long long lim = dlc::row_limit(r, n, limit0, step);
+        long long lim = std::clamp(limit0 + r * step, 0ll, n);          // include/dlc.h's words, not the library's dlc::row_limit
         std::vector<double> x(n);
         for (long long c = 0; c < n; ++c) x[c] = (double)m[1 + r * ld + c];
         for (long long j = 0; j < ldo; ++j) {

@@ -4,6 +4,7 @@
 // against a sentinel.  Built with -fsanitize=address,undefined (tests/test_fuse_host_cpu.py).
 #include "dlc_internal.h"
 #include "fuse_rows.cpp"
+#include <algorithm>
 #include <random>
 static double tree(const std::vector<double>& v, size_t lo, size_t len) {
     if (len == 1) return lo < v.size() ? v[lo] : -0.0;
@@ -30,7 +31,7 @@ int main() {
         const long long limit0 = n - 2, step = 1, ldo = n + 1;
         std::vector<double> ref(rows * ldo, -7.0);
         for (long long r = 0; r < rows; ++r) {
-            long long c = dlc::row_limit(r, n, limit0, step);
+            long long c = std::clamp(limit0 + r * step, 0ll, n);        // include/dlc.h's words, not the library's dlc::row_limit
             if (!c) continue;
             for (int i = 0; i < m; ++i) {
                 std::vector<double> x(c);

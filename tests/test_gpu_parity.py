@@ -1137,7 +1137,7 @@ def _low_contrast(shape, g, device, spread=1e-3):
 
 
 def _unkey(k):
-    """dlc_f64_key inverted (csrc/dlc_internal.h): ordered 64-bit keys -> doubles."""
+    """dlc_f64_key inverted (csrc/dlc_hd.h): ordered 64-bit keys -> doubles."""
     k = k.astype(np.uint64)
     top = (k >> np.uint64(63)).astype(bool)
     u = np.where(top, k & np.uint64(0x7fffffffffffffff), ~k)
