@@ -25,6 +25,7 @@ include/dlc.h, with the reference's Python call surface on top:
     PlaceTracker, track_places (and track= on the detectors): a Viterbi filter over score rows with a "no loop" state -- the place per frame and the smoothed labelling of the traversal; new
     Vlad, vlad_frame_descriptors (and pool= on describe_sdav, loop_closure --pool vlad; python -m deeploopcloser_amd.train_vlad): a k-means codebook of patch descriptors and VLAD pooling -- one orderless row per frame in front of KeyframeDatabase; new
     Pca (and loop_closure.describe_sdav_compact(pool=, pca=), pca= on sdav_place_descriptors_from_frames, loop_closure --pca; python -m deeploopcloser_amd.train_pca): PCA and whitening of a pooled row down to the <= 4096 columns the cosine top-k stores, by a projection whose sum order is stated -- the same bits alone or in a batch; new
+    GeometricVerifier, verify_candidates (and Engine.verify_pairs, loop_closure --verify): geometric verification of loop candidates -- the frames' patches matched, every two-match similarity of the matched key-points tried in integer arithmetic, the agreeing matches counted: exact, a function of the pair alone; new
     ground_truth / pr_curve_cells / recall_at / pr_curve_queries / PRCurve / LoopClosureEvaluator   (ground-truth evaluation: PR curves, average precision, recall@K; new)
 
 Importing the package is cheap and works without a GPU; constructing any of
@@ -55,10 +56,12 @@ from . import vlad
 from .vlad import Vlad
 from . import pca
 from .pca import Pca
+from . import verification
+from .verification import GeometricVerifier, verify_candidates
 from . import evaluate
 from .evaluate import ground_truth, pr_curve_cells, recall_at, pr_curve_queries, PRCurve, LoopClosureEvaluator
 
-__all__ = ["Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["GeometricVerifier", "verify_candidates", "Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

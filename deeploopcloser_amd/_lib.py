@@ -35,6 +35,8 @@ DLC_VLAD_NORM_NONE, DLC_VLAD_NORM_INTRA = 0, 1
 DLC_PCA_CHUNK = 1024         # columns of x of one serial chain of dlc_pca_project; the chunks' sums are added in order
 DLC_PCA_MAX_COMPONENTS, DLC_PCA_SPLIT_MAX_ROWS = 8192, 64
 DLC_PCA_PLAN_AUTO, DLC_PCA_PLAN_ONE_PASS, DLC_PCA_PLAN_SPLIT = 0, 1, 2
+DLC_VERIFY_MAX_PATCHES = 64  # the most patches of a frame dlc_verify_pairs matches (one bit of its inlier mask each)
+DLC_VERIFY_SIMILARITY, DLC_VERIFY_TRANSLATION = 0, 1
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -136,6 +138,9 @@ SIGNATURES = {
     "dlc_kmeans_step": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dlc_pca_project_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "dlc_pca_project": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _i64, _vp, _vp, _i64, _int, _vp, _sz, _vp]),
+    "dlc_verify_pairs_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "dlc_verify_pairs": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _i64, _vp, _i64, _int, _int, _int, _int, _int,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dlc_pr_cell_counts_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "dlc_pr_cell_counts": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _i64, _vp, _int, _vp, _vp,
                                   _vp, _sz, _vp]),

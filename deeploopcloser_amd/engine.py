@@ -1447,6 +1447,81 @@ class Engine:
         self._wrote(out)
         return out[:, :m]
 
+    _VERIFY_MODELS = {"similarity": L.DLC_VERIFY_SIMILARITY, "translation": L.DLC_VERIFY_TRANSLATION}
+
+    def _patch_store(self, who, what, desc, pts):
+        """The checks of a frame store -> (desc, pts, frames, P, H, ld): descriptors fp64 [frames, P, H] or
+        [frames * P, H] on the device (a row-strided 2-D view is taken as it is) and points int32 [frames, P, 2]."""
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or pts.shape[2] != 2 or pts.dtype != torch.int32 or \
+                pts.device != self.device or pts.shape[0] < 1 or pts.shape[1] < 1:
+            raise ValueError("%s: %s points must be an int32 tensor [frames, P, 2] on %s" % (who, what, self.device))
+        frames, p = pts.shape[0], pts.shape[1]
+        if isinstance(desc, torch.Tensor) and desc.dim() == 3:
+            if desc.shape[0] != frames or desc.shape[1] != p:
+                raise ValueError("%s: %s descriptors %s do not go with points %s" % (who, what, tuple(desc.shape), tuple(pts.shape)))
+            desc = desc.contiguous().view(frames * p, desc.shape[2])
+        desc, rows, h, ld = self._f64_rows(who, "%s descriptors" % what, desc)
+        if rows != frames * p:
+            raise ValueError("%s: %d %s descriptor rows are not %d frames of %d patches" % (who, rows, what, frames, p))
+        return desc, pts.contiguous(), frames, p, h, ld
+
+    def verify_pairs(self, q_desc, q_pts, db_desc, db_pts, cand, model="similarity", tol=3, max_scale=2.0, mutual=True,
+                     with_mask=False, with_match=False):
+        """Geometric verification of loop candidates (dlc_verify_pairs, include/dlc.h): for every pair (query frame r,
+        key-frame cand[r, s]) the patches are matched by DIST (nearest neighbour, mutual: cross-checked), a 2-D
+        `model` ("similarity": rotation + uniform scale + translation from two matches; "translation": from one) is
+        fitted to the matched key-points by trying EVERY hypothesis in integer arithmetic, and the matches within `tol`
+        pixels of the best one are counted.  Exact and a function of the pair alone.
+
+        q_desc fp64 [Q, P, H] (or [Q * P, H]) with q_pts int32 [Q, P, 2]; db_desc / db_pts the same for N key-frames;
+        cand int64 [Q, k] (ids outside 0..N-1 give 0 inliers).  max_scale: the similarity's scale must lie within
+        [1 / s, s], 1 <= s <= 16, taken as round(16 s) / 16; None: no bound.  Points are (x, y) with 0 <= x, y <= 8191;
+        any other point is absent, (-1, -1) being what the Harris pass writes past a frame's point count.
+        -> (inliers int32 [Q, k], n_matches int32 [Q, k]) on the device; with_mask: + hyp int32 [Q, k, 2] and mask int64
+        [Q, k] (bit p: match p is an inlier; the uint64 word of the C ABI); with_match: + match int32 [Q, k, P]."""
+        who = "verify_pairs"
+        if model not in self._VERIFY_MODELS:
+            raise ValueError("%s: model=%r is none of %s" % (who, model, sorted(self._VERIFY_MODELS)))
+        if int(tol) != tol or not 0 <= tol <= 255:
+            raise ValueError("%s: tol=%r outside 0..255" % (who, tol))
+        s16 = 0
+        if max_scale is not None:
+            s16 = int(round(16 * float(max_scale)))
+            if not 16 <= s16 <= 256:
+                raise ValueError("%s: max_scale=%r outside 1..16" % (who, max_scale))
+        qd, qp, q, p, h, ldq = self._patch_store(who, "query", q_desc, q_pts)
+        dd, dp, n, p2, h2, ldd = self._patch_store(who, "key-frame", db_desc, db_pts)
+        if p != p2 or h != h2:
+            raise ValueError("%s: queries of %d patches x %d against key-frames of %d x %d" % (who, p, h, p2, h2))
+        if p > L.DLC_VERIFY_MAX_PATCHES:
+            raise ValueError("%s: %d patches outside 1..%d" % (who, p, L.DLC_VERIFY_MAX_PATCHES))
+        if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int64 or cand.device != self.device or \
+                cand.shape[0] != q or not 1 <= cand.shape[1] <= L.DLC_MAX_K:
+            raise ValueError("%s: cand must be an int64 tensor [%d, 1..%d] on %s" % (who, q, L.DLC_MAX_K, self.device))
+        k = cand.shape[1]
+        if cand.stride(1) != 1 or (q > 1 and cand.stride(0) < k):
+            cand = cand.contiguous()
+        ld_cand = cand.stride(0) if q > 1 else max(k, cand.stride(0))
+        need = self.lib.dlc_verify_pairs_workspace_bytes(q, k, p)
+        if need == 0:
+            raise ValueError("%s: Q=%d, k=%d, P=%d outside the supported sizes" % (who, q, k, p))
+        ws = self.workspace("verify_pairs", need)
+        inliers = torch.empty((q, k), dtype=torch.int32, device=self.device)
+        matches = torch.empty((q, k), dtype=torch.int32, device=self.device)
+        hyp = torch.empty((q, k, 2), dtype=torch.int32, device=self.device) if with_mask else None
+        mask = torch.empty((q, k), dtype=torch.int64, device=self.device) if with_mask else None
+        match = torch.empty((q, k, p), dtype=torch.int32, device=self.device) if with_match else None
+        self._check(self.lib.dlc_verify_pairs(
+            self.ctx, _ptr(qd), ldq, _ptr(qp), q, _ptr(dd), ldd, _ptr(dp), n, p, h, _ptr(cand), ld_cand, k,
+            self._VERIFY_MODELS[model], int(tol), s16, int(bool(mutual)), _ptr(inliers), _ptr(matches), _ptr(hyp), _ptr(mask),
+            _ptr(match), None, _ptr(ws), ws.numel(), self._stream()))
+        out = (inliers, matches)
+        if with_mask:
+            out += (hyp, mask)
+        if with_match:
+            out += (match,)
+        return out
+
     def peak_topk_rows(self, scores, k, suppress, n=None, limit0=None, limit_step=0, lower_is_better=False, absent=None,
                        poison=None):
         """(scores [rows, k], idx [rows, k] int64): distinct-place candidates, the windowed peak top-k of

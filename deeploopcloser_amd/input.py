@@ -90,10 +90,12 @@ class CvInputParser:
         self.engine = default_engine(device)
         self._grid = {}
 
-    def parse_batch(self, frames):
+    def parse_batch(self, frames, return_key_points=False):
         """frames uint8 [F,H,W,3] RGB or [F,H,W] grey -> [F, n_patches, patch_size^2] float64 on the GPU:
         grey conversion, Harris key-points, patch gather, nothing through the host.  A frame with
-        fewer than n_patches corners is topped up with grid points (the network needs the shape)."""
+        fewer than n_patches corners is topped up with grid points (the network needs the shape).
+        return_key_points: (patches, the int32 [F, n_patches, 2] points the patches were cut at) -- what
+        verification.GeometricVerifier takes beside the patches' descriptors."""
         e = self.engine
         fr = e.to_device(frames)
         gray = e.rgb_to_gray(fr.to(torch.uint8)) if fr.dim() == 4 else fr.to(torch.uint8)
@@ -104,7 +106,8 @@ class CvInputParser:
         if shape not in self._grid:                        # resident top-up points per frame size
             self._grid[shape] = torch.from_numpy(_centres(grid_key_points(shape, self.n_patches), self.n_patches)).to(e.device)
         pts = torch.where(pts < 0, self._grid[shape].unsqueeze(0).expand_as(pts), pts)
-        return e.extract_patches(gray, pts, self.patch_size)
+        patches = e.extract_patches(gray, pts, self.patch_size)
+        return (patches, pts) if return_key_points else patches
 
     def parse_tensor(self, image, key_points=None):
         e = self.engine

@@ -944,7 +944,9 @@ def describe_sdav_compact(files, network=None, key_points_fn=None, pool=None, pc
     return desc if pca is None else pca.transform_tensor(desc)
 
 
-def _describe_sdav_flat(files, network=None, key_points_fn=None):
+def _describe_sdav_flat(files, network=None, key_points_fn=None, return_key_points=False):
+    """return_key_points: (the rows, the int32 [frames, P, 2] device tensor of the points the patches were cut at) -- frames
+    of one size only."""
     from . import pipeline
     from .input import read_ppm
     from .sdav import SDAV
@@ -952,6 +954,8 @@ def _describe_sdav_flat(files, network=None, key_points_fn=None):
     p = network.input_shape[0]
     frames = [read_ppm(f) for f in files]
     if any(fr.shape != frames[0].shape for fr in frames):
+        if return_key_points:
+            raise ValueError("key-points are returned for frames of one size only")
         # a chunk of frames of several sizes (the reference parses them one by one, CvInputParser.py:30-33): each frame's
         # patches are gathered on the device on its own, as drivers.create_similarity_matrix does
         from .input import CvInputParser
@@ -961,6 +965,9 @@ def _describe_sdav_flat(files, network=None, key_points_fn=None):
     kp = None
     if key_points_fn:
         kp = pipeline.key_point_array([key_points_fn(fr.shape[:2]) for fr in frames], p, network.engine)
+    if return_key_points:
+        desc, pts = pipeline.sdav_descriptors_from_frames(np.stack(frames), network, key_points=kp, return_key_points=True)
+        return desc.view(len(files), -1), pts
     desc = pipeline.sdav_descriptors_from_frames(np.stack(frames), network, key_points=kp)
     return desc.view(len(files), -1)
 
@@ -1065,7 +1072,33 @@ def main(argv=None):
                     help="with --positions: a key-frame within R of a frame's position is the same place")
     ap.add_argument("--pr-curve", default=None, metavar="OUT.tsv",
                     help="with --positions: write the curve there -- threshold, tp, fp, precision, recall; strictest first")
+    ap.add_argument("--verify", type=int, default=None, metavar="MIN_INLIERS",
+                    help="--network sdav: geometric verification of every candidate (verification.GeometricVerifier) -- the "
+                         "frames' patches are matched, a 2-D transform is fitted to the matched key-points and a candidate "
+                         "with fewer than MIN_INLIERS agreeing matches is not reported; every `loop` line is followed by "
+                         "one line `verify<TAB>inliers<TAB>matches`")
+    ap.add_argument("--verify-tol", type=int, default=None, metavar="T", help="with --verify: the inlier tolerance in pixels, 0..255 (3)")
+    ap.add_argument("--verify-model", choices=["similarity", "translation"], default=None,
+                    help="with --verify: rotation + scale + translation from two matches (default), or translation from one")
+    ap.add_argument("--verify-max-scale", type=float, default=None, metavar="S",
+                    help="with --verify: the similarity's scale stays within [1 / S, S], 1..16 (2)")
     args = ap.parse_args(argv)
+    if args.verify is None and (args.verify_tol is not None or args.verify_model is not None or args.verify_max_scale is not None):
+        ap.error("--verify-tol, --verify-model and --verify-max-scale need --verify")
+    if args.verify is not None:
+        if args.fuse is not None or args.network != "sdav":
+            ap.error("--verify needs --network sdav (the patch descriptors and key-points are the SDAV front-end's)")
+        if args.verify < 0:
+            ap.error("--verify must be >= 0")
+        if args.chains:
+            ap.error("--verify excludes --chains")
+        args.verify_tol = 3 if args.verify_tol is None else args.verify_tol
+        if not 0 <= args.verify_tol <= 255:
+            ap.error("--verify-tol must be 0..255")
+        args.verify_model = args.verify_model or "similarity"
+        args.verify_max_scale = 2.0 if args.verify_max_scale is None else args.verify_max_scale
+        if not 1.0 <= args.verify_max_scale <= 16.0:
+            ap.error("--verify-max-scale must be 1..16")
     if args.fuse is None and (args.fuse_weights is not None or args.fuse_norm is not None):
         ap.error("--fuse-weights and --fuse-norm need --fuse")
     if args.fuse is not None:
@@ -1244,7 +1277,8 @@ def _fused_stream(args, files):
 
 
 def _stream(args, files):
-    fused = None
+    fused = verifier = None
+    local = []                                                   # --verify: the batch's (patch descriptors, key-points)
     if args.fuse is not None:
         describe, fused = _fused_stream(args, files)
     elif args.network == "sdav":
@@ -1252,7 +1286,7 @@ def _stream(args, files):
         net = SDAV(dtype=args.encoder_dtype)
         if args.weights:
             net.load_weights(args.weights)
-        pool = None
+        pool = compact = None
         if args.pool == "vlad":
             from .vlad import Vlad
             pool = Vlad.load(args.codebook)
@@ -1261,6 +1295,20 @@ def _stream(args, files):
             from .pca import Pca
             compact = Pca.load(args.pca)
             describe = lambda fs: describe_sdav_compact(fs, net, pool=pool, pca=compact)
+        if getattr(args, "verify", None) is not None:
+            from .verification import GeometricVerifier, keep_accepted
+            patches = net.input_shape[0]
+            verifier = GeometricVerifier(patches=patches, width=net.hidden_units[-1], capacity=max(1024, len(files)),
+                                         min_inliers=args.verify, model=args.verify_model, tol=args.verify_tol,
+                                         max_scale=args.verify_max_scale)
+
+            def describe(fs):
+                # the frames' patch descriptors and key-points stay behind for the verifier; the place rows are formed
+                # from the same descriptors as without --verify
+                flat, pts = _describe_sdav_flat(fs, net, return_key_points=True)
+                local[:] = [flat.view(len(fs), patches, -1), pts]
+                rows = flat if pool is None else pool.transform_tensor(flat.view(len(fs) * patches, -1), patches=patches)
+                return rows if compact is None else compact.transform_tensor(rows)
     elif args.network == "seqslam":
         from . import pipeline
         from .input import read_ppm
@@ -1312,6 +1360,14 @@ def _stream(args, files):
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))
         s, i, *chain = det.query_and_insert(desc)
+        verdict = None
+        if verifier is not None:
+            # the batch's frames become resident, then every candidate is verified: rejected slots leave the lists
+            verifier.append(*local)
+            inl, nm = verifier.verify(lo, i)
+            s, i, inl, nm = keep_accepted(inl >= verifier.min_inliers, s, i, float("-inf"), inl, nm)
+            ids, inl, nm = i.cpu().numpy(), inl.cpu().numpy(), nm.cpu().numpy()
+            verdict = {(lo + r, int(ids[r, c])): (int(inl[r, c]), int(nm[r, c])) for r, c in zip(*np.nonzero(ids >= 0))}
         found = det.loops(s, i, lo, *chain)                      # (the one host read of the step)
         lat.append(((time.perf_counter() - t0) * 1e3, len(chunk)))
         if judge is not None:
@@ -1321,6 +1377,8 @@ def _stream(args, files):
                   % (frame, os.path.basename(files[frame]), match, os.path.basename(files[match]), score))
             if pairs:
                 print(chain_line(pairs[0]))
+            if verdict is not None:
+                print("verify\t%d\t%d" % verdict[(frame, match)])
     if args.track is not None:                                   # the smoothed labelling of the whole stream
         for frame, place in enumerate(det.tracker.path().cpu().tolist()):
             if place >= 0:

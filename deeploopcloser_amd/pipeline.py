@@ -45,12 +45,19 @@ def stage_ms(timings):
     return out
 
 
-def _patches(parser, dev_frames, key_points, lo, hi):
-    """uint8 frames of one chunk on the device -> [B, P, patch^2] fp64 (grey, key-points, gather: CvInputParser.py:19-49)."""
+def _patches(parser, dev_frames, key_points, lo, hi, points_out=None):
+    """uint8 frames of one chunk on the device -> [B, P, patch^2] fp64 (grey, key-points, gather: CvInputParser.py:19-49).
+    points_out: an int32 [N, P, 2] tensor whose rows lo .. hi - 1 receive the points the patches were cut at."""
     if key_points is None:
-        return parser.parse_batch(dev_frames)
+        if points_out is None:
+            return parser.parse_batch(dev_frames)
+        x, pts = parser.parse_batch(dev_frames, return_key_points=True)
+        points_out[lo:hi] = pts
+        return x
     e = parser.engine
     gray = e.rgb_to_gray(dev_frames) if dev_frames.dim() == 4 else dev_frames
+    if points_out is not None:
+        points_out[lo:hi] = key_points[lo:hi]
     return e.extract_patches(gray, key_points[lo:hi], parser.patch_size)
 
 
@@ -67,22 +74,26 @@ def key_point_array(key_points_per_frame, n_patches, engine):
     return torch.from_numpy(np.stack(rows)).to(engine.device)
 
 
-def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, chunk_frames=256, timings=None):
+def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, chunk_frames=256, timings=None,
+                                 return_key_points=False):
     """frames: uint8 [N, H, W, 3] RGB (or [N, H, W] grey), a host ndarray or a device tensor -> the frames' SDAV descriptors
     [N, P, H_last] fp64 ON THE DEVICE (CvInputParser.parse + SDAV.transform of create_similarity_matrix.py:23-27, batched).
     key_points: None (the build's Harris detector) or an int32 device tensor [N, P, 2] (key_point_array).
     A host array is uploaded in chunks of `chunk_frames` frames whose transfer overlaps the previous chunk's kernels; the
-    encoder is batch-invariant, so chunking changes no bit."""
+    encoder is batch-invariant, so chunking changes no bit.
+    return_key_points: (descriptors, the int32 [N, P, 2] device tensor of the points the patches were cut at) -- the
+    Harris pass's, topped up as CvInputParser.parse_batch does, or the caller's own."""
     eng = network.engine
     parser = parser or CvInputParser(network.input_shape[0], int(round(np.sqrt(network.input_shape[1]))), device=eng.device)
     p, hw = network.input_shape[0], network.hidden_units[-1]
     n = int(frames.shape[0])
     desc = torch.empty((n, p, hw), dtype=torch.float64, device=eng.device)
+    points = torch.empty((n, p, 2), dtype=torch.int32, device=eng.device) if return_key_points else None
     cur = torch.cuda.current_stream(eng.device)
 
     def consume(dev, lo, hi):
         m = _mark(timings, "front-end (grey, key-points, patches)", cur)
-        x = _patches(parser, dev, key_points, lo, hi)
+        x = _patches(parser, dev, key_points, lo, hi, points)
         _done(timings, m, cur)
         m = _mark(timings, "SDAV.transform", cur)
         if network.dtype == torch.float64:                      # straight into its place (behind the call the copy was 638 MB
@@ -92,7 +103,7 @@ def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, 
         _done(timings, m, cur)
 
     if n == 0:
-        return desc
+        return (desc, points) if return_key_points else desc
     if isinstance(frames, torch.Tensor):
         dev = frames.to(eng.device)
         if dev.dtype != torch.uint8:
@@ -106,7 +117,7 @@ def sdav_descriptors_from_frames(frames, network, parser=None, key_points=None, 
             a = a.astype(np.uint8)
         n_chunks = max(1, -(-n // max(1, int(chunk_frames))))
         eng.for_each_chunk(a, -(-n // n_chunks), consume, first=FIRST_CHUNK_FRAMES)
-    return desc
+    return (desc, points) if return_key_points else desc
 
 
 def sdav_place_descriptors_from_frames(frames, network, vlad, parser=None, key_points=None, chunk_frames=256, timings=None,

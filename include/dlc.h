@@ -1181,6 +1181,67 @@ int dlc_pca_project(dlc_ctx* ctx, const double* x, int64_t rows, int64_t D, int6
                     int M, int64_t ldb, const double* scale /* [M], may be NULL */,
                     double* out, int64_t ld_out, int plan, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Geometric verification of loop candidates over patch key-points: the last stage of a loop closer.  Every detector
+ * above reports a candidate on appearance alone; two frames that look alike but are different places (perceptual
+ * aliasing) pass all of them.  This stage matches the P patches of the query frame to those of the candidate, fits a
+ * 2-D transform to the matched key-points and counts the matches that agree with it.  The matching uses DIST of
+ * dlc_vlad_assign; the geometry is an EXHAUSTIVE search in integer arithmetic -- no random sampling, no floating
+ * point -- so the result is a function of the inputs alone, whatever the launch plan or the batching.
+ * A PAIR is (query frame r, candidate key-frame c = cand[r * ld_cand + s]), 0 <= r < Q, 0 <= s < k.  INPUT.  The P patch
+ * descriptors of each frame, fp64, H columns: frame f's patch p is row f * P + p of its matrix (q_desc [Q * P, ldq],
+ * db_desc [N * P, ldd]; no column past H is ever read); the P key-points of each frame, int32 (x, y) (q_pts [Q, P, 2],
+ * db_pts [N, P, 2]).  1 <= P <= DLC_VERIFY_MAX_PATCHES, 1 <= H, 1 <= k <= DLC_MAX_K, 1 <= Q <= 2^31 / DLC_MAX_K,
+ * 1 <= N < 2^31, ld >= H, ld_cand >= k.
+ * POINT VALIDITY.  A point is PRESENT iff 0 <= x <= 8191 and 0 <= y <= 8191 (every intermediate below stays under
+ * 2^57).  (-1, -1), what dlc_harris_keypoints_u8 writes past a frame's point count, is absent.
+ * PATCH MATCHING.  D[p][j] = DIST(q_p, d_j) exactly as defined at dlc_vlad_assign: d = +0.0; for h ascending:
+ * t = x_h - c_h; q = t * t; d = d + q -- no fma, never split along H, never formed from a Gram product.  DIST is
+ * symmetric bit for bit, so one P x P table serves both directions.  m(p) = the lowest j whose D[p][j] is not NaN and is
+ * <= every other non-NaN entry of row p (+inf can win); -1 if the whole row is NaN.  r(j) = the same rule down column
+ * j, taking the lowest p.  mutual = 1: match p is kept iff m(p) >= 0 and r(m(p)) == p (the cross-check); mutual = 0:
+ * iff m(p) >= 0.  A kept match is dropped if either of its two points is absent.  The surviving set is M; a_p is the
+ * query's point p and b_p the candidate's point m(p).  The arg-mins never depend on the points.
+ * DLC_VERIFY_SIMILARITY: rotation + uniform scale + translation, orientation-preserving, fixed by two matches.  The
+ * hypotheses are the pairs (s, t), s < t, both in M, in ascending lexicographic order.  u = a_t - a_s, v = b_t - b_s.
+ * The hypothesis is VALID iff |u|^2 > 0 and |v|^2 > 0 and, when max_scale_x16 = S > 0 (16 <= S <= 256),
+ * 256 |v|^2 <= S^2 |u|^2 and 256 |u|^2 <= S^2 |v|^2: the scale lies within [16 / S, S / 16].  For i in M, da = a_i - a_s,
+ * db = b_i - b_s, all int64:
+ *     re = (db.x * u.x - db.y * u.y) - (v.x * da.x - v.y * da.y)
+ *     im = (db.x * u.y + db.y * u.x) - (v.x * da.y + v.y * da.x)
+ *     inlier(i)  <=>  re * re + im * im <= tol * tol * (u.x * u.x + u.y * u.y)
+ * which is |b_i - (b_s + (v / u)(a_i - a_s))| <= tol in complex numbers, multiplied through by |u|.  The count of a
+ * hypothesis is its number of inliers (s and t always count).  The result is the valid hypothesis with the largest
+ * count, the first in order among equals; with no valid hypothesis: inliers 0, hypothesis (-1, -1), mask 0.
+ * DLC_VERIFY_TRANSLATION: one-match hypotheses s in M, ascending.  e = (b_i - a_i) - (b_s - a_s); inlier(i) iff
+ * e.x^2 + e.y^2 <= tol^2.  The same selection; the hypothesis is (s, -1).  0 <= tol <= 255.
+ * OUTPUTS per pair, [Q, k]-shaped with row pitch k (pair r * k + s): out_inliers int32; out_matches int32 = |M|;
+ * out_hyp int32 x 2 (optional); out_mask uint64 (optional): bit p is set iff match p is an inlier of the winning
+ * hypothesis; out_match int32 [P] (optional): m(p) for p in M, else -1; out_dist fp64 [P, P] (optional): the table D.
+ * A pair whose candidate id is < 0 or >= N writes inliers 0, matches 0, hyp (-1, -1), mask 0 and match -1 and leaves
+ * its out_dist slot untouched.  A pair's result depends on that pair's 2 P descriptors and 2 P points alone: not on Q,
+ * k, the pitches or which other pairs are in the call.
+ * LAUNCHES.  Two on `stream` (the tables; the resolution), none synchronises; memory and the workspace (16-byte
+ * aligned) are the caller's.  The call always needs dlc_verify_pairs_workspace_bytes(Q, k, P) bytes: the tables live
+ * there unless out_dist is given.  Nothing but the stated outputs and the workspace is written.
+ * Errors: DLC_ERR_BAD_ARG for a null (descriptors, points, cand, out_inliers, out_matches) or misaligned pointer,
+ * Q / N / P / H < 1, k outside 1..DLC_MAX_K, ld < H, ld_cand < k, an unknown model, tol outside 0..255, max_scale_x16
+ * neither 0 nor in 16..256, mutual neither 0 nor 1; DLC_ERR_BAD_SHAPE for P > DLC_VERIFY_MAX_PATCHES,
+ * Q > 2^31 / DLC_MAX_K or N >= 2^31; DLC_ERR_WORKSPACE for a workspace that is missing, too small or not 16-byte
+ * aligned.  Nothing is written then.  dlc_verify_pairs_workspace_bytes returns 0 for refused shapes.
+ */
+#define DLC_VERIFY_MAX_PATCHES 64
+enum { DLC_VERIFY_SIMILARITY = 0, DLC_VERIFY_TRANSLATION = 1 };
+size_t dlc_verify_pairs_workspace_bytes(int64_t Q, int k, int P);
+int dlc_verify_pairs(dlc_ctx* ctx, const double* q_desc, int64_t ldq /* doubles between patch rows, >= H */,
+                     const int32_t* q_pts /* [Q, P, 2] */, int64_t Q,
+                     const double* db_desc, int64_t ldd, const int32_t* db_pts /* [N, P, 2] */, int64_t N,
+                     int P, int64_t H, const int64_t* cand, int64_t ld_cand, int k,
+                     int model, int tol, int max_scale_x16, int mutual,
+                     int32_t* out_inliers, int32_t* out_matches, int32_t* out_hyp /* may be NULL */,
+                     uint64_t* out_mask /* may be NULL */, int32_t* out_match /* may be NULL */,
+                     double* out_dist /* may be NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- match: cosine similarity + top-k (BASELINE.json north_star; not in the reference) */
 /*
  * Row L2-normalisation (optional mean-centring first) of src[n,d] (DLC_F32 or
