@@ -13,6 +13,8 @@ include/dlc.h, with the reference's Python call surface on top:
     SeqSlam, DifferenceCalculator, SadKeyframeDatabase   (SeqSLAM's own front-end: patch-normalised grey thumbnails compared
                                    by the sum of absolute differences -- no weights; new)
         shift=S, width=w on them, on Engine.sad_rows and on SeqSlamLoopClosureDetector: the best of the lateral shifts -S .. S
+    Ldb, HammingCalculator, HammingKeyframeDatabase, LdbLoopClosureDetector   (a binary place descriptor: the global LDB code of
+                                   a grey thumbnail, 64 bytes a frame, compared by Hamming distance -- no weights; new)
     MathUtils                     (src/utils/MathUtils.py)
     tensor_wrapper (tw)           (src/utils/TensorflowWrapper.py)
     encode / match / match_topk   (BASELINE.json north_star; new)
@@ -40,6 +42,7 @@ from .cnn_vtl import CnnVtl
 from .similarity import SimilarityCalculator, SimilarityStream
 from .distance import DistanceCalculator, CnnVtlKeyframeDatabase
 from .seqslam import SeqSlam, DifferenceCalculator, SadKeyframeDatabase
+from .ldb import Ldb, HammingCalculator, HammingKeyframeDatabase
 from .matching import encode, match, match_topk, KeyframeDatabase, MatchPipeline, flatten_frame_descriptors, vlad_frame_descriptors
 from .dist import ShardedKeyframeDatabase, shard_bounds, merge_topk_torch
 from .input import CvInputParser, KeyPoint, grid_key_points, harris_key_points, read_ppm
@@ -47,6 +50,7 @@ from . import tensor_wrapper
 from . import sequence
 from .sequence import slope_offsets, sequence_topk, sequence_scores, sequence_chains, contrast_normalize, peak_topk, sequence_peaks, uniqueness_ratio
 from .loop_closure import LoopClosureDetector, SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector
+from .loop_closure import LdbLoopClosureDetector
 from .loop_closure import FusedLoopClosureDetector
 from . import fusion
 from .fusion import fuse_scores
@@ -61,7 +65,7 @@ from .verification import GeometricVerifier, verify_candidates
 from . import evaluate
 from .evaluate import ground_truth, pr_curve_cells, recall_at, pr_curve_queries, PRCurve, LoopClosureEvaluator
 
-__all__ = ["GeometricVerifier", "verify_candidates", "Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["Ldb", "HammingCalculator", "HammingKeyframeDatabase", "LdbLoopClosureDetector", "GeometricVerifier", "verify_candidates", "Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

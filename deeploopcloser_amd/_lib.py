@@ -110,6 +110,9 @@ SIGNATURES = {
     "dlc_sad_u8_shift_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _i64, _i64, _vp, _i64, _vp, _i64,
                                      _vp]),
     "dlc_seqslam_describe_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "dlc_ldb_row_bytes": (_i64, [C.POINTER(_int), _int]),
+    "dlc_ldb_describe_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, C.POINTER(_int), _int, _vp, _i64, _vp]),
+    "dlc_hamming_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dlc_sequence_topk_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "dlc_sequence_topk": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(C.c_int32), _int, _int,
                                  _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),

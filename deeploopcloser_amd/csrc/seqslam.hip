@@ -40,39 +40,10 @@ __device__ __forceinline__ unsigned sd_group_sum(unsigned v, int G) {
 __global__ __launch_bounds__(SD_THREADS) void seqslam_describe_kernel(const SdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char thumb[];          // T [h, w]
     const int tid = threadIdx.x;
-    const long long H = a.H, W = a.W, h = a.h, w = a.w;
-    const uint8_t* g = a.gray + (long long)blockIdx.x * H * W;
-    const int cells = a.h * a.w;
+    const uint8_t* g = a.gray + (long long)blockIdx.x * a.H * a.W;
 
-    // ---- area resize: T(y, x) = floor((2 sum wy wx gray + H W) / (2 H W)) ------------------------------------------------
-    {
-        const int G = a.g_resize, sub = tid & (G - 1), per = SD_THREADS / G;
-        for (int base = 0; base < cells; base += per) {
-            const int cell = base + tid / G;
-            unsigned acc = 0u;                                     // <= 255 H W < 2^31
-            if (cell < cells) {
-                const long long y = cell / a.w, x = cell % a.w;
-                // source rows whose interval [i h, (i + 1) h) meets [y H, (y + 1) H): i0 .. i1 - 1 (columns alike)
-                const long long i0 = y * H / h, i1 = ((y + 1) * H + h - 1) / h;
-                const long long j0 = x * W / w, j1 = ((x + 1) * W + w - 1) / w;
-                for (long long i = i0 + sub; i < i1; i += G) {
-                    const long long lo = i * h > y * H ? i * h : y * H, hi = (i + 1) * h < (y + 1) * H ? (i + 1) * h : (y + 1) * H;
-                    const unsigned wy = (unsigned)(hi - lo);       // > 0 inside i0 .. i1 - 1, <= h
-                    unsigned row = 0u;
-                    for (long long j = j0; j < j1; ++j) {
-                        const long long l2 = j * w > x * W ? j * w : x * W, h2 = (j + 1) * w < (x + 1) * W ? (j + 1) * w : (x + 1) * W;
-                        row += (unsigned)(h2 - l2) * g[i * W + j];
-                    }
-                    acc += wy * row;
-                }
-            }
-            acc = sd_group_sum(acc, G);
-            if (cell < cells && sub == 0) {
-                const unsigned long long hw = (unsigned long long)(H * W);
-                thumb[cell] = (unsigned char)((2ull * acc + hw) / (2ull * hw));
-            }
-        }
-    }
+    // ---- area resize: T(y, x) = floor((2 sum wy wx gray + H W) / (2 H W)) (dlc_hd.h) ------------------------------------
+    dlc_area_resize(g, a.H, a.W, a.h, a.w, thumb, tid, SD_THREADS, a.g_resize, [](unsigned v, int G) { return sd_group_sum(v, G); });
     __syncthreads();
 
     // ---- patch normalisation: 128 + strength (T - mean) / sample std, tile by tile ---------------------------------------
@@ -112,13 +83,6 @@ __global__ __launch_bounds__(SD_THREADS) void seqslam_describe_kernel(const SdAr
     }
 }
 
-// the power of two at or above v, at most 64
-int sd_group(int64_t v) {
-    int g = 1;
-    while (g < 64 && g < v) g <<= 1;
-    return g;
-}
-
 }  // namespace
 
 extern "C" int dlc_seqslam_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int h, int w,
@@ -142,8 +106,8 @@ extern "C" int dlc_seqslam_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_
     SdArgs a;
     a.gray = gray; a.out = out; a.ld_out = ld_out;
     a.H = H; a.W = W; a.h = h; a.w = w; a.patch = patch; a.strength = strength;
-    a.g_resize = sd_group(dlc::cdiv(SD_THREADS, (int64_t)h * w));
-    a.g_tile = sd_group((int64_t)patch * patch);
+    a.g_resize = dlc_lane_group(dlc::cdiv(SD_THREADS, (int64_t)h * w));
+    a.g_tile = dlc_lane_group((int64_t)patch * patch);
     const size_t lds = dlc::align_up((size_t)h * w, 16);
     hipLaunchKernelGGL(seqslam_describe_kernel, dim3((unsigned)frames), dim3(SD_THREADS), lds, (hipStream_t)stream, a);
     DLC_LAUNCH_CHECK(ctx, "seqslam_describe_kernel");

@@ -103,3 +103,20 @@ def create_difference_matrix(dataset_path, out_png=None, network=None, pattern="
     if out_png:
         _write_gray(out_png, distance_image(matrix))
     return matrix
+
+
+def create_hamming_matrix(dataset_path, out_png=None, network=None, pattern="*"):
+    """Frames -> binary LDB descriptors (ldb.Ldb: cell comparisons of a grey thumbnail, packed bits) -> int64 N x N matrix
+    of their Hamming distances [-> PNG, drawn as the distance matrix is].  Device-resident (pipeline.py): uint8 frames up,
+    descriptors stay in HBM, the matrix comes down once.  No weights are needed."""
+    from . import pipeline
+    from .ldb import Ldb
+    files = sorted(glob.glob(os.path.join(dataset_path, pattern)))
+    if not files:
+        raise ValueError("Specified dataset is empty or could not find dataset")
+    frames = np.stack([read_ppm(f) for f in files])                      # RGB
+    network = network or Ldb()
+    matrix = pipeline.ldb_hamming_matrix_from_frames(frames, network)
+    if out_png:
+        _write_gray(out_png, distance_image(matrix))
+    return matrix

@@ -1081,6 +1081,74 @@ class Engine:
         self._wrote(out)
         return out
 
+    # ---- binary place descriptors: global LDB codes, Hamming rows ------------------------------------------------------
+    @staticmethod
+    def _ldb_levels(levels):
+        """levels as the C int array of the LDB calls and the row's bytes (dlc_ldb_row_bytes: 0 refuses the list)."""
+        try:
+            arr = (C.c_int * len(levels))(*(int(g) for g in levels))
+        except (TypeError, ValueError):
+            raise ValueError("ldb: levels=%r must be a sequence of integers" % (levels,))
+        return arr, len(arr)
+
+    def ldb_row_bytes(self, levels):
+        """Bytes of an LDB row for `levels`: 16 * ceil(bits / 128) (dlc_ldb_row_bytes); ValueError for a list that is not
+        1 to 4 grid sizes, strictly ascending, each 2..8."""
+        arr, n = self._ldb_levels(levels)
+        nb = int(self.lib.dlc_ldb_row_bytes(arr, n))
+        if nb == 0:
+            raise ValueError("ldb: levels=%r must be 1 to 4 grid sizes, strictly ascending, each 2..8" % (tuple(levels),))
+        return nb
+
+    def ldb_describe(self, gray, size, levels, out=None):
+        """uint8 [F, row_bytes]: the global LDB code of every frame of gray (uint8 [F, H, W] on the device) -- the frame
+        area-resized to size = (h, w), then per grid size of `levels` three bits per pair of cells: sum, horizontal and
+        vertical gradient compared (dlc_ldb_describe_u8, include/dlc.h), exact.  out: a caller-kept uint8
+        [F, >= row_bytes] tensor or row-strided view (a database's rows: the bytes past row_bytes of a row keep their
+        value); the result is its first row_bytes columns."""
+        if not isinstance(gray, torch.Tensor) or gray.dtype != torch.uint8 or gray.dim() != 3 or gray.device != self.device:
+            raise ValueError("ldb_describe: uint8 [F, H, W] on %s expected" % self.device)
+        gray = gray.contiguous()
+        h, w = (int(v) for v in size)
+        f, hh, ww = gray.shape
+        if h < 1 or w < 1:
+            raise ValueError("ldb_describe: size=%r must be positive" % (size,))
+        nb = self.ldb_row_bytes(levels)
+        arr, n = self._ldb_levels(levels)
+        out = self._rows_out("ldb_describe: out", out, f, nb, torch.uint8, "a uint8", wider=True)
+        if f == 0:
+            return out[:, :nb]
+        ld_out = out.stride(0) if f > 1 else out.shape[1]
+        self._check(self.lib.dlc_ldb_describe_u8(self.ctx, _ptr(gray), f, hh, ww, h, w, arr, n, _ptr(out), ld_out,
+                                                  self._stream()))
+        self._wrote(out)
+        return out[:, :nb]
+
+    def hamming_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
+        """int64 [Q, N]: the Hamming distance of every query row of q [Q, D] uint8 to the rows of db [N, D] uint8, bytes
+        as packed bits (dlc_hamming_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r *
+        limit_step, 0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1, "not
+        offered", when the engine allocates the result.  d: the descriptor's bytes when the rows are padded (the bytes
+        past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows lie further apart than
+        N (its columns past N are left alone too)."""
+        d = self._int8_pair("hamming_rows", q, db, d, dtype=torch.uint8)
+        nq, n = q.shape[0], db.shape[0]
+        out = self._rows_out("hamming_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
+        if nq == 0 or n == 0:
+            return out
+        if d == 0:                                               # empty descriptors: every distance is 0
+            lim0, step = _limits(n, limit0, limit_step)
+            lim = lim0 + step * torch.arange(nq, device=self.device)
+            out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
+            return out
+        q = self._rows16_u8(q, d)
+        db = self._rows16_u8(db, d)
+        ld_out = out.stride(0) if nq > 1 else n
+        self._check(self.lib.dlc_hamming_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
+                                               *_limits(n, limit0, limit_step), _ptr(out), ld_out, self._stream()))
+        self._wrote(out)
+        return out
+
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
     # the dtype of what a score-row call derives from its rows: int64 from int64 rows, else float64
     _OUT_DTYPES = {torch.float64: torch.float64, torch.float32: torch.float64, torch.int64: torch.int64}

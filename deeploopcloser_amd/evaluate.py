@@ -206,10 +206,10 @@ def pr_curve_queries(scores, ids, hit, has_positive, lower_is_better=False):
 
 class LoopClosureEvaluator:
     """Ground-truth evaluation of a streaming detector -- any of the five: LoopClosureDetector (with or without
-    sequence=L), SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector.
+    sequence=L), SdavLoopClosureDetector, CnnVtlLoopClosureDetector, SeqSlamLoopClosureDetector, LdbLoopClosureDetector.
 
     positions: the position of every frame of the run, integers [F, 2] or [F] (ground_truth); radius: how near a key-frame
-    must lie to be the same place; exclusion: the detector's; lower_is_better: True for the distance and SAD detectors.
+    must lie to be the same place; exclusion: the detector's; lower_is_better: True for the distance, SAD and Hamming detectors.
     add(scores, ids, first_id) takes what query_and_insert returned for the frames first_id .. first_id + B - 1.  For
     frame t:  has_positive = some key-frame j < t - exclusion is within the radius;  hit = the candidate at slot 0 is
     within the radius and j < t - exclusion;  any_hit = the same of any of the k candidates.  result() -> (PRCurve of

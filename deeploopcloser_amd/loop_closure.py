@@ -13,6 +13,12 @@ top-k path and reports the candidates whose cosine score reaches `threshold`.
 --network seqslam --metric sad is SeqSLAM itself, front to back and without weights: patch-normalised grey thumbnails
 (--size, --patch, --strength), their sums of absolute differences, then the sequence search (SeqSlamLoopClosureDetector).
 
+    python -m deeploopcloser_amd.loop_closure DATASET_DIR --network ldb --metric hamming --sequence 10
+
+--network ldb --metric hamming is the binary route, also without weights: the global LDB code of a grey thumbnail (--size,
+--levels; 64 bytes a frame by default), Hamming distances, then everything the seqslam route has behind its rows
+(LdbLoopClosureDetector).
+
     python -m deeploopcloser_amd.loop_closure DATASET_DIR --fuse sad,distance --sequence 10
 
 --fuse MEMBER,MEMBER[,...] (sad, distance, cosine) runs several descriptors side by side and ranks by ONE fused score:
@@ -667,7 +673,82 @@ class CnnVtlLoopClosureDetector:
         return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True, chains=chains)
 
 
-class SeqSlamLoopClosureDetector:
+class _ByteRowsLoopClosureDetector:
+    """What the streaming detectors over byte descriptors and int64 lower-is-better rows share (SeqSlamLoopClosureDetector:
+    SAD rows; LdbLoopClosureDetector: Hamming rows): the checks, the resident row buffers and query_and_insert.  A
+    subclass names its threshold (LIMIT, the keyword of its constructor and the attribute that holds it), creates its
+    database and forms the rows of a batch (_rows_into)."""
+
+    LIMIT = None
+
+    def __init__(self, dim, k, limit, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains, track):
+        if not 1 <= k <= L.DLC_MAX_K:
+            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
+        if exclusion < 0:
+            raise ValueError("exclusion must be >= 0")
+        if limit is not None and limit < 0 and contrast is None:
+            raise ValueError("%s must be >= 0 (or None)" % self.LIMIT)
+        if dim < 1 or capacity < 1:
+            raise ValueError("dim and capacity must be positive")
+        if suppress is not None and not 0 <= suppress < 1 << 63:
+            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
+        self.k, self.exclusion = int(k), int(exclusion)
+        setattr(self, self.LIMIT, limit if limit is None else (int if contrast is None else float)(limit))
+        self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
+        self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
+        # (without sequence=L `suppress` is served here, by the peak selection over the frame rows themselves)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
+                                     suppress=None if self.sequence is None else self.suppress, steps=steps,
+                                     chains=self.chains, track=track)
+        self.tracker = None
+        if self._seq is not None:
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
+        self._rows = None                                    # without sequence: the batch's rows [b, capacity]
+
+    def __len__(self):
+        return len(self.db)
+
+    def _rows_into(self, q, limit0, out):
+        """The rows of the stored queries q against the database, query r in its first limit0 + r cells, into out."""
+        raise NotImplementedError
+
+    def query_and_insert(self, descriptors):
+        """The next B frames' uint8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (value [B, k] int64,
+        ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
+        key-frames afterwards.  With sequence=L value is the sum of the L frame values along the best line.  With
+        chains=True a third tensor, chain [B, k, L] int32."""
+        db = self.db
+        x = db.engine.to_device(descriptors)
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        first, _ = db.append(x)
+        b = x.shape[0]
+        if b == 0:
+            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
+            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
+        q = db.rows[first:first + b]
+        if self._seq is None:
+            if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
+                self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
+                                         dtype=torch.int64, device=db.engine.device)
+            rows = self._rows[:b, :first + b]
+            self._rows_into(q, first - self.exclusion, rows)
+            return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
+                                            lower_is_better=True)
+        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
+        self._rows_into(q, first - self.exclusion, self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
+        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
+
+    def loops(self, value, ids, first_id, chains=None):
+        """[(frame id, matched key-frame id, value)] of the candidates at or below the threshold (with sequence=L: the
+        sum of the L frame values along the candidate's line).  chains: the third result of query_and_insert with
+        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
+        return _loops(value, ids, first_id, getattr(self, self.LIMIT), lower_is_better=True, chains=chains)
+
+
+class SeqSlamLoopClosureDetector(_ByteRowsLoopClosureDetector):
     """The streaming question asked the way SeqSLAM asks it (Milford & Wyeth, ICRA 2012): every new frame's descriptor -- a
     patch-normalised grey thumbnail, uint8 [dim] (seqslam.SeqSlam) -- is compared with all resident frames more than
     `exclusion` frames older by the sum of absolute differences, and the k with the smallest difference (ties -> the older
@@ -690,18 +771,12 @@ class SeqSlamLoopClosureDetector:
 
     In both forms the lists do not depend on how the frames are batched."""
 
+    LIMIT = "max_difference"
+
     def __init__(self, dim, k=5, max_difference=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
                  contrast=None, suppress=None, steps=None, chains=False, shift=None, width=None, track=None):
-        if not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
-        if max_difference is not None and max_difference < 0 and contrast is None:
-            raise ValueError("max_difference must be >= 0 (or None)")
-        if dim < 1 or capacity < 1:
-            raise ValueError("dim and capacity must be positive")
-        if suppress is not None and not 0 <= suppress < 1 << 63:
-            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
+        super().__init__(dim, k, max_difference, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains,
+                         track)
         if shift is not None and shift < 0:
             raise ValueError("shift=%d must be >= 0" % shift)
         if shift:                                            # (None or 0: the plain rows, as Engine.sad_rows takes them)
@@ -713,59 +788,35 @@ class SeqSlamLoopClosureDetector:
                 raise ValueError("shift=%d outside 0..min(%d, width - 1 = %d)" % (shift, L.DLC_MAX_SHIFT, width - 1))
         self.shift = None if shift is None else int(shift)
         self.width = None if width is None else int(width)
-        self.k, self.exclusion = int(k), int(exclusion)
-        self.max_difference = max_difference if max_difference is None else (int if contrast is None else float)(max_difference)
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        # (without sequence=L `suppress` is served here, by the peak selection over the frame rows themselves)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=None if self.sequence is None else self.suppress, steps=steps,
-                                     chains=self.chains, track=track)
-        self.tracker = None
-        if self._seq is not None:
-            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
-        self._rows = None                                    # without sequence: the batch's difference rows [b, capacity]
         from .seqslam import SadKeyframeDatabase
         self.db = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
-    def __len__(self):
-        return len(self.db)
+    def _rows_into(self, q, limit0, out):
+        self.db.differences(q, limit0=limit0, limit_step=1, out=out, shift=self.shift, width=self.width)
 
-    def query_and_insert(self, descriptors):
-        """The next B frames' uint8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (diff [B, k] int64,
-        ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
-        key-frames afterwards.  With sequence=L diff is the sum of the L differences along the best line.  With
-        chains=True a third tensor, chain [B, k, L] int32."""
-        db = self.db
-        x = db.engine.to_device(descriptors)
-        if x.dim() == 1:
-            x = x.unsqueeze(0)
-        first, _ = db.append(x)
-        b = x.shape[0]
-        if b == 0:
-            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
-            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
-        q = db.rows[first:first + b]
-        if self._seq is None:
-            if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
-                self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
-                                         dtype=torch.int64, device=db.engine.device)
-            rows = self._rows[:b, :first + b]
-            db.differences(q, limit0=first - self.exclusion, limit_step=1, out=rows, shift=self.shift, width=self.width)
-            return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
-                                            lower_is_better=True)
-        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
-        db.differences(q, limit0=first - self.exclusion, limit_step=1, shift=self.shift, width=self.width,
-                       out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
-        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
 
-    def loops(self, diff, ids, first_id, chains=None):
-        """[(frame id, matched key-frame id, difference)] of the candidates at or below max_difference (with sequence=L:
-        the sum of the L differences along the candidate's line).  chains: the third result of query_and_insert with
-        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
-        return _loops(diff, ids, first_id, self.max_difference, lower_is_better=True, chains=chains)
+class LdbLoopClosureDetector(_ByteRowsLoopClosureDetector):
+    """SeqSlamLoopClosureDetector over BINARY descriptors: every new frame's packed bits, uint8 [dim] (ldb.Ldb), are
+    compared with all resident frames more than `exclusion` frames older by Hamming distance (dlc_hamming_rows), and the k
+    with the smallest distance (ties -> the older frame) at or below `max_distance` (all of them when None) are the loop
+    candidates.  No weights are involved, and a key-frame is dim bytes -- 64 for Ldb's defaults.
+
+    Everything behind the rows is SeqSlamLoopClosureDetector's, word for word: without `sequence` dlc_peak_topk_rows over
+    a resident int64 buffer (suppress = W keeps the picks more than W key-frames apart); sequence = L, slopes, contrast =
+    R, suppress = W, steps = (d_min, d_max), chains = True and track as there, max_distance then compared with the
+    sequence sum.  There is no lateral shift.  The lists do not depend on how the frames are batched."""
+
+    LIMIT = "max_distance"
+
+    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
+                 contrast=None, suppress=None, steps=None, chains=False, track=None):
+        super().__init__(dim, k, max_distance, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains,
+                         track)
+        from .ldb import HammingKeyframeDatabase
+        self.db = HammingKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+
+    def _rows_into(self, q, limit0, out):
+        self.db.distances(q, limit0=limit0, limit_step=1, out=out)
 
 
 FUSE_MEMBERS = ("cosine", "distance", "sad")
@@ -993,19 +1044,21 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="stream the frames of a dataset through the loop-closure detector")
     ap.add_argument("dataset_path")
     ap.add_argument("--pattern", default="*.ppm")
-    ap.add_argument("--network", choices=["sdav", "cnn_vtl", "seqslam"], default="cnn_vtl",
-                    help="the descriptor: SDAV, CnnVtl, or SeqSLAM's patch-normalised grey thumbnail (needs no weights; "
-                         "goes with --metric sad)")
+    ap.add_argument("--network", choices=["sdav", "cnn_vtl", "seqslam", "ldb"], default="cnn_vtl",
+                    help="the descriptor: SDAV, CnnVtl, SeqSLAM's patch-normalised grey thumbnail (needs no weights; "
+                         "goes with --metric sad) or the binary LDB code of a grey thumbnail (needs no weights; goes with "
+                         "--metric hamming)")
     ap.add_argument("--weights", help=".npz written by SDAV.save_weights (sdav) / AlexNet .npy blob (cnn_vtl)")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--threshold", type=float, default=None,
                     help="report candidates at or above this score (default: 0.9 for cosine, all k for similarity)")
-    ap.add_argument("--metric", choices=["cosine", "distance", "similarity", "sad"], default="cosine",
+    ap.add_argument("--metric", choices=["cosine", "distance", "similarity", "sad", "hamming"], default="cosine",
                     help="cosine of the descriptors, the reference's cnn_vtl distance (needs --network cnn_vtl), the "
                          "reference's SDAV similarity (needs --network sdav; the distinctive score comes from the first batch) "
-                         "or SeqSLAM's sum of absolute differences (needs --network seqslam)")
+                         "SeqSLAM's sum of absolute differences (needs --network seqslam) or the Hamming distance of binary "
+                         "codes (needs --network ldb)")
     ap.add_argument("--sequence", type=int, default=None, metavar="L",
-                    help="--metric similarity or sad: rank by the sum of the scores along a line of L frames (sequence search)")
+                    help="--metric similarity, sad or hamming: rank by the sum of the scores along a line of L frames (sequence search)")
     ap.add_argument("--contrast", type=int, default=None, metavar="R",
                     help="with --sequence: normalise every score against the R key-frames on either side of it first "
                          "(SeqSLAM's local contrast normalisation), R in 1..32")
@@ -1025,12 +1078,17 @@ def main(argv=None):
     ap.add_argument("--chains", action="store_true",
                     help="with --sequence: under every candidate a line `chain` with the L frame:key-frame pairs it was "
                          "matched along, oldest frame first")
-    ap.add_argument("--max-distance", type=int, default=None,
-                    help="--metric distance: report candidates at or below this distance (default: all k)")
+    ap.add_argument("--max-distance", type=float, default=None,
+                    help="--metric distance or hamming: report candidates at or below this distance, an integer (hamming "
+                         "with --sequence: the sum along the line, and any number with --contrast; default: all k)")
     ap.add_argument("--max-difference", type=float, default=None,
                     help="--metric sad: report candidates at or below this difference (with --sequence: the sum along the "
                          "line; default: all k)")
-    ap.add_argument("--size", default="32x64", metavar="HxW", help="--network seqslam: the thumbnail's rows x columns")
+    ap.add_argument("--size", default=None, metavar="HxW",
+                    help="--network seqslam or ldb: the thumbnail's rows x columns (default: 32x64 for seqslam, 48x48 for ldb)")
+    ap.add_argument("--levels", default=None, metavar="G,G[,...]",
+                    help="--network ldb: 1 to 4 grid sizes, strictly ascending, each 2..8; twice each must divide both sides "
+                         "of --size (default: 2,3,4)")
     ap.add_argument("--patch", type=int, default=8, help="--network seqslam: side of the normalisation tiles, 1..64")
     ap.add_argument("--strength", type=int, default=32,
                     help="--network seqslam: descriptor byte = 128 + strength * z-score, 1..127")
@@ -1156,15 +1214,35 @@ def main(argv=None):
         ap.error("--metric similarity needs --network sdav")
     if (args.network == "seqslam") != (args.metric == "sad"):
         ap.error("--network seqslam and --metric sad need each other")
+    if (args.network == "ldb") != (args.metric == "hamming"):
+        ap.error("--network ldb and --metric hamming need each other")
+    if args.levels is not None and args.network != "ldb":
+        ap.error("--levels needs --network ldb")
+    if args.size is None:
+        args.size = "48x48" if args.network == "ldb" else "32x64"
+    if args.max_distance is not None and not (args.metric == "hamming" and args.contrast is not None):
+        if args.max_distance < 0 or args.max_distance != int(args.max_distance):
+            ap.error("--max-distance must be a non-negative integer (any number with --metric hamming --contrast)")
+        args.max_distance = int(args.max_distance)
     if args.shift is not None and not thumbnails:
         ap.error("--shift needs --network seqslam (or --fuse with sad)")
-    if thumbnails:
+    if thumbnails or args.network == "ldb":
         try:
             args.size = tuple(int(v) for v in args.size.lower().split("x"))
         except ValueError:
             args.size = ()
         if len(args.size) != 2 or min(args.size) < 1 or args.size[0] * args.size[1] > 65536:
             ap.error("--size must be HxW, two positive integers with H * W <= 65536")
+    if args.network == "ldb":
+        from .ldb import ldb_bits
+        try:
+            args.levels = (2, 3, 4) if args.levels is None else tuple(int(v) for v in args.levels.split(","))
+            ldb_bits(args.levels)
+        except ValueError:
+            ap.error("--levels must be 1 to 4 integers, strictly ascending, each 2..8")
+        if any(v % (2 * g) for g in args.levels for v in args.size):
+            ap.error("--levels: twice every grid size must divide both sides of --size")
+    if thumbnails:
         if not 1 <= args.patch <= 64:
             ap.error("--patch must be 1..64")
         if not 1 <= args.strength <= 127:
@@ -1175,8 +1253,8 @@ def main(argv=None):
             if args.max_difference < 0 or args.max_difference != int(args.max_difference):
                 ap.error("--max-difference must be a non-negative integer (any number with --contrast)")
             args.max_difference = int(args.max_difference)
-    if args.sequence is not None and args.metric not in ("similarity", "sad") and args.fuse is None:
-        ap.error("--sequence needs --metric similarity or sad (or --fuse)")
+    if args.sequence is not None and args.metric not in ("similarity", "sad", "hamming") and args.fuse is None:
+        ap.error("--sequence needs --metric similarity, sad or hamming (or --fuse)")
     if args.sequence is not None and not 1 <= args.sequence <= 64:
         ap.error("--sequence must be 1..64")
     if args.contrast is not None and args.sequence is None:
@@ -1315,6 +1393,12 @@ def _stream(args, files):
         from .seqslam import SeqSlam
         net = SeqSlam(size=args.size, patch=args.patch, strength=args.strength)
         describe = lambda fs: pipeline.seqslam_descriptors_from_frames(np.stack([read_ppm(f) for f in fs]), net)
+    elif args.network == "ldb":
+        from . import pipeline
+        from .input import read_ppm
+        from .ldb import Ldb
+        net = Ldb(size=args.size, levels=args.levels)
+        describe = lambda fs: pipeline.ldb_descriptors_from_frames(np.stack([read_ppm(f) for f in fs]), net)
     else:
         from .cnn_vtl import CnnVtl
         from .input import read_ppm
@@ -1327,7 +1411,7 @@ def _stream(args, files):
     if args.positions is not None:
         from .evaluate import LoopClosureEvaluator, pr_line
         judge = LoopClosureEvaluator(args.positions, args.radius, args.exclusion,
-                                     lower_is_better=fused is None and args.metric in ("distance", "sad"))
+                                     lower_is_better=fused is None and args.metric in ("distance", "sad", "hamming"))
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
@@ -1356,6 +1440,10 @@ def _stream(args, files):
                                              contrast=args.contrast, suppress=args.suppress, steps=args.steps,
                                              chains=args.chains, shift=args.shift,
                                              width=None if args.shift is None else args.size[1], track=args.track)
+        elif det is None and args.metric == "hamming":
+            det = LdbLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance, exclusion=args.exclusion,
+                                         capacity=max(4096, len(files)), sequence=args.sequence, contrast=args.contrast,
+                                         suppress=args.suppress, steps=args.steps, chains=args.chains, track=args.track)
         elif det is None:
             det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
                                       dtype=args.dtype, center=True, capacity=max(4096, len(files)))

@@ -207,11 +207,9 @@ def cnn_vtl_distance_matrix_from_frames(frames, network, chunk_frames=None, devi
     return res
 
 
-def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None, timings=None):
-    """frames: uint8 [N, H, W, 3] RGB (or [N, H, W] grey), a host ndarray or a device tensor -> SeqSLAM descriptors uint8
-    [N, h * w] ON THE DEVICE (seqslam.SeqSlam: grey, area resize, patch normalisation).  A host array is uploaded in chunks
-    of `chunk_frames` frames whose transfer overlaps the previous chunk's kernels; a frame's descriptor does not depend on
-    its chunk.  out: a caller-kept uint8 [N, >= h * w] tensor or row view (a database's rows)."""
+def _byte_descriptors_from_frames(who, mark, frames, network, chunk_frames, out, timings):
+    """The body of seqslam_descriptors_from_frames and ldb_descriptors_from_frames: network.transform_tensor chunk by
+    chunk into uint8 [N, network.dim] on the device.  who / mark name the caller in the error and in the timings."""
     eng = network.engine
     n = int(frames.shape[0])
     if out is None:
@@ -219,7 +217,7 @@ def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None,
     cur = torch.cuda.current_stream(eng.device)
 
     def consume(dev, lo, hi):
-        m = _mark(timings, "SeqSlam.transform", cur)
+        m = _mark(timings, mark, cur)
         network.transform_tensor(dev, out=out[lo:hi])
         _done(timings, m, cur)
 
@@ -231,10 +229,44 @@ def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None,
     else:
         a = np.asarray(frames)
         if a.dtype != np.uint8:
-            raise ValueError("seqslam_descriptors_from_frames: frames must be uint8")
+            raise ValueError("%s: frames must be uint8" % who)
         n_chunks = max(1, -(-n // max(1, int(chunk_frames))))
         eng.for_each_chunk(a, -(-n // n_chunks), consume, first=FIRST_CHUNK_FRAMES)
     return out[:, :network.dim]
+
+
+def seqslam_descriptors_from_frames(frames, network, chunk_frames=256, out=None, timings=None):
+    """frames: uint8 [N, H, W, 3] RGB (or [N, H, W] grey), a host ndarray or a device tensor -> SeqSLAM descriptors uint8
+    [N, h * w] ON THE DEVICE (seqslam.SeqSlam: grey, area resize, patch normalisation).  A host array is uploaded in chunks
+    of `chunk_frames` frames whose transfer overlaps the previous chunk's kernels; a frame's descriptor does not depend on
+    its chunk.  out: a caller-kept uint8 [N, >= h * w] tensor or row view (a database's rows)."""
+    return _byte_descriptors_from_frames("seqslam_descriptors_from_frames", "SeqSlam.transform", frames, network,
+                                         chunk_frames, out, timings)
+
+
+def ldb_descriptors_from_frames(frames, network, chunk_frames=256, out=None, timings=None):
+    """frames: uint8 [N, H, W, 3] RGB (or [N, H, W] grey), a host ndarray or a device tensor -> binary LDB descriptors
+    uint8 [N, network.dim] ON THE DEVICE (ldb.Ldb: grey, area resize, the cell comparisons as packed bits), uploaded as
+    seqslam_descriptors_from_frames uploads.  out: a caller-kept uint8 [N, >= network.dim] tensor or row view."""
+    return _byte_descriptors_from_frames("ldb_descriptors_from_frames", "Ldb.transform", frames, network, chunk_frames,
+                                         out, timings)
+
+
+def ldb_hamming_matrix_from_frames(frames, network, chunk_frames=256, device_result=False, timings=None):
+    """Frames -> LDB descriptors -> the full N x N int64 matrix of their Hamming distances.  One upload, one download
+    (device_result=True: none)."""
+    eng = network.engine
+    cur = torch.cuda.current_stream(eng.device)
+    d8 = ldb_descriptors_from_frames(frames, network, chunk_frames, timings=timings)
+    m = _mark(timings, "hamming matrix", cur)
+    dm = eng.hamming_rows(d8, d8)
+    _done(timings, m, cur)
+    if device_result:
+        return dm
+    m = _mark(timings, "download of the matrix", cur)
+    res = eng.download(dm)
+    _done(timings, m, cur)
+    return res
 
 
 def seqslam_difference_matrix_from_frames(frames, network, chunk_frames=256, device_result=False, timings=None, shift=None):

@@ -283,6 +283,54 @@ int dlc_harris_keypoints_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, i
 int dlc_seqslam_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int h, int w,
                             int patch, int strength, uint8_t* out, int64_t ld_out, void* stream);
 
+/* ---- encode: a binary global descriptor, LDB over the thumbnail (not in the reference; needs no weights) ------------ */
+/*
+ * The global LDB code of a frame ("Local Difference Binary", Yang & Cheng, ISMAR 2012, taken over the whole down-sampled
+ * frame as ABLE-M does, Arroyo et al., IROS 2015): a few hundred bits, each the comparison of two grid cells of a
+ * thumbnail by their mean or by one of their two gradients.  Two codes are compared by their Hamming distance
+ * (dlc_hamming_rows), and the rows feed dlc_contrast_rows / dlc_sequence_topk / dlc_peak_topk_rows as the SAD rows do.
+ * Every bit is unchanged by a gain and an offset of the image (a T + b, a > 0, compares as T does).  Integers only: a
+ * function of the pixels alone, the same for every launch plan.
+ * THUMBNAIL.  gray is uint8 [frames, H, W].  T [h, w] is the AREA RESIZE of dlc_seqslam_describe_u8 above, the same
+ * formula, with no patch normalisation.  h == H and w == W is the identity.
+ * LEVELS.  levels[0 .. n_levels-1]: 1 to 4 grid sizes g, strictly ascending, each 2 <= g <= 8; 2 g must divide both h
+ * and w.  Level g cuts T into g x g cells of (h / g) x (w / g) pixels, row-major index c = cy * g + cx.  The four
+ * quadrants of a cell are (top | bottom) x (left | right), a half being exactly h / 2g rows or w / 2g columns.  Per cell,
+ * with the sums Q00, Q01, Q10, Q11 of T over the four quadrants (first index: 0 top, 1 bottom; second: 0 left, 1 right):
+ *     S  = Q00 + Q01 + Q10 + Q11
+ *     DX = (Q01 + Q11) - (Q00 + Q10)            (right minus left)
+ *     DY = (Q10 + Q11) - (Q00 + Q01)            (bottom minus top)
+ * All cells of a level have the same area, so sums are compared, not means.  With h * w <= 65536 every value fits int32.
+ * BITS, t counting from 0.  Levels go in the order given; within a level the pairs (a, b) of cells with a < b go a
+ * ascending, then b ascending; each pair gives three bits in the order S_a > S_b, DX_a > DX_b, DY_a > DY_b.  The
+ * comparisons are strict: a tie is 0.
+ *     bits(levels) = 3 * sum over the levels of g^2 (g^2 - 1) / 2        ((2,3,4): 486; (2,4,8): 6426; (8): 6048;
+ *                                                                         (5,6,7,8): 12366)
+ * Bit t is bit t & 7, least significant first, of byte t >> 3 of the frame's row.
+ *     row_bytes = 16 * ceil(bits / 128)                                  (what the row-bytes call below returns)
+ * The bits from `bits` to 8 * row_bytes - 1 are written as 0.
+ * WORKED EXAMPLE.  T is 4 x 4 (identity resize), levels (2):
+ *     1 2 5 5          cell   S   DX   DY
+ *     3 4 5 5           0    10    2    4
+ *     9 7 0 8           1    20    0    0
+ *     9 7 8 0           2    32   -4    0
+ *                       3    16    0    0
+ * 6 pairs, 18 bits: pair (0,1) 0 1 1, (0,2) 0 1 1, (0,3) 0 1 1, (1,2) 0 1 0, (1,3) 1 0 0, (2,3) 1 0 0.  The row is
+ * B6 95 00 followed by 13 zero bytes.
+ * OUTPUT.  out is uint8 [frames, ld_out], ld_out >= row_bytes.  Bytes row_bytes .. ld_out-1 of a row KEEP THEIR VALUE.
+ * out must not overlap gray.  A row pitch that is a multiple of 16 on a 16-byte aligned base is what dlc_hamming_rows
+ * takes.
+ * Limits, those of dlc_seqslam_describe_u8: frames >= 1, 1 <= h <= H, 1 <= w <= W, h * w <= 65536, H * W < 2^23.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, frames < 1, a bad level list (n_levels outside 1..4, a g outside 2..8, not
+ * strictly ascending) or ld_out < row_bytes; DLC_ERR_BAD_SHAPE for h, w, H, W outside the limits, or a 2 g that does not
+ * divide h or w.  Nothing is written then.
+ * No workspace; one launch on `stream` (one workgroup per frame, the thumbnail in LDS); never synchronises.
+ * The row-bytes call is host arithmetic: 0 for a bad level list.
+ */
+int64_t dlc_ldb_row_bytes(const int* levels, int n_levels);
+int dlc_ldb_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int h, int w,
+                        const int* levels, int n_levels, uint8_t* out, int64_t ld_out, void* stream);
+
 /* ---- encode: CnnVtl pieces (src/cnn_vtl/network/cnn_vtl.py:28-133) ------ */
 /*
  * im2col for tf.layers.conv2d on NHWC fp64 (cnn_vtl.py:33-93): x[n,h,w,c] ->
@@ -656,6 +704,29 @@ int dlc_sad_u8_shift_rows(dlc_ctx* ctx, const uint8_t* queries, int64_t Q, int64
                           const uint8_t* db, int64_t N, int64_t ldd, int h, int w, int max_shift,
                           int64_t limit0, int64_t limit_step,
                           int64_t* out, int64_t ld_out, int8_t* shift_out, int64_t ld_shift, void* stream);
+
+/*
+ * Hamming distance of packed binary descriptors as rows: out[r * ld_out + j] = sum_{p < D} popcount(q_r[p] ^ db_j[p]) on
+ * bytes (the number of differing bits of two dlc_ldb_describe_u8 codes, D = their row_bytes; any bit strings are taken),
+ * of query row r of queries [Q, D] (row stride ldq) against row j of db [N, D] (row stride ldd).  (Not
+ * dlc_cnnvtl_distance_rows, which is popcount(|a ^ b|) of SIGNED bytes.)  The contract is dlc_sad_u8_rows' word for word:
+ * written for 0 <= j < lim(r) = clamp(limit0 + r * limit_step, 0, N), any limit_step, negative included (limit_step = 0,
+ * limit0 = N: the full [Q, N] block -- the Hamming matrix is this call with queries = db); EVERY OTHER WORD OF out KEEPS
+ * ITS VALUE, the cells at or past lim(r) and the columns N .. ld_out-1; when every lim(r) is 0 nothing is launched and the
+ * call returns DLC_OK.
+ * out is int64 [Q, ld_out], ld_out >= N.  Both bases 16-byte aligned, ldq and ldd multiples of 16 bytes (>= D); bytes
+ * D .. ld-1 of a row may hold anything and change nothing; queries may be rows of db itself (both are only read); out
+ * must not overlap the operands.  D <= 2^24 (8 * D fits the 32-bit accumulator), N < 2^32, Q <= 2^20.
+ * No workspace; one launch on `stream` (the tiles of dlc_sad_u8_rows, xor and bit count on the staged words, plain 8-byte
+ * stores: no memset, no atomics); never synchronises.  Integers throughout: the result is exact and does not depend on
+ * the plan, nor on how the queries are batched.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer, Q, N or D < 1, ldq or ldd < D, ld_out < N or a misaligned base or pitch;
+ * DLC_ERR_BAD_SHAPE for D > 2^24, N >= 2^32 or Q > 2^20 (checked as stated: Q = 2^20 is taken).  Nothing is written then.
+ */
+int dlc_hamming_rows(dlc_ctx* ctx, const uint8_t* queries, int64_t Q, int64_t ldq,
+                     const uint8_t* db, int64_t N, int64_t ldd, int64_t D,
+                     int64_t limit0, int64_t limit_step,
+                     int64_t* out, int64_t ld_out, void* stream);
 
 /* ---- match: sequence-consistent search over a score matrix (not in the reference) ----------- */
 /*
