@@ -6,19 +6,7 @@ the kernel's window (2 Ed + 1e-8) is built on.  Worst-case-leaning data included
 import numpy as np
 import pytest
 
-
-def digits(q):
-    """q = s1 2^16 + s2 2^8 + s3 with s_i in [-128, 127] (sim_rows_kernel: the signed low byte, then (q + 128) >> 8)."""
-    s3 = ((q + 128) & 255) - 128
-    q1 = (q - s3) >> 8
-    s2 = ((q1 + 128) & 255) - 128
-    s1 = (q1 - s2) >> 8
-    assert np.all(s1 * 65536 + s2 * 256 + s3 == q) and s1.min() >= -128 and s1.max() <= 127
-    return s1, s2, s3
-
-
-def bound_ed(sv, h):
-    return 2.0 ** -23 * sv + h * (2.0 ** -24 + 2.0 ** -33 + 2.0 ** -46) + 1.004 * 2.0 ** -15 + 2.0 ** -16
+from filter_oracle import bound_ed, digits
 
 
 @pytest.mark.parametrize("h,kind", [(2500, "uniform"), (2500, "extreme"), (64, "uniform"), (8192, "small"), (2500, "sign")])
