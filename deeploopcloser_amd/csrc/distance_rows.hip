@@ -5,14 +5,11 @@
 //
 // One workgroup per (query tile, db tile) below the largest limit of the call, in the top-k scan's three tile shapes
 // (distance_tile.h); where the scan filters a tile's distances into its lists, this kernel stores them.  No split along
-// D, so no zeroed output and no atomics: every thread stores its acc[QR][4] once, guarded by j < lim(r) -- everything
-// else of `out` keeps its value.  Threads consecutive in tx write consecutive columns (coalesced 8-byte stores).
+// D, so no zeroed output and no atomics: every thread stores its acc[QR][4] once, guarded by j < lim(r) (tk_store_rows).
 // Integers throughout: the result is exact and the same for every plan.
 #include "distance_tile.h"
 
 namespace {
-
-constexpr int64_t DR_MAX_GRID_X = 1 << 16;     // db tiles beyond it are walked by the same workgroups (grid stride)
 
 template <int NTX, int QR>
 __global__ __launch_bounds__(256) void distance_rows_kernel(const int8_t* __restrict__ queries, long long Q, long long ldq,
@@ -26,16 +23,10 @@ __global__ __launch_bounds__(256) void distance_rows_kernel(const int8_t* __rest
 
     const int tid = threadIdx.x, tx = tid % NTX, ty = tid / NTX;
     const long long q0 = (long long)blockIdx.y * QT;
-    // rows this tile's queries may see: limits are linear in the query row, so the largest sits at an end
-    const long long qlast = (q0 + QT < Q ? q0 + QT : Q) - 1;
-    const long long la = dlc::row_limit(q0, N, limit0, limit_step), lb = dlc::row_limit(qlast, N, limit0, limit_step);
-    const long long lmax = la > lb ? la : lb;
+    const long long lmax = tk_tile_limit<QT>(q0, Q, N, limit0, limit_step);
     long long lq[QR];
 #pragma unroll
-    for (int r = 0; r < QR; ++r) {
-        const long long q = q0 + ty + NTY * r;
-        lq[r] = q < Q ? dlc::row_limit(q, N, limit0, limit_step) : 0;
-    }
+    for (int r = 0; r < QR; ++r) lq[r] = tk_query_limit(q0 + ty + NTY * r, Q, N, limit0, limit_step);
     for (long long j0 = (long long)blockIdx.x * DB; j0 < lmax; j0 += (long long)gridDim.x * DB) {
         u32x4_t va[PA], vb[PB];
         auto fetch = [&](long long k0) {
@@ -97,19 +88,7 @@ __global__ __launch_bounds__(256) void distance_rows_kernel(const int8_t* __rest
             }
             __syncthreads();
         }
-        // the store addresses are formed here, behind the loop: hoisted above it (they do not depend on it) they would
-        // hold 32 registers through it -- 176 instead of 134 in the 64 x 64 shape, a wave per SIMD less
-        int sx = tx, sy = ty;
-        asm volatile("" : "+v"(sx), "+v"(sy));
-#pragma unroll
-        for (int r = 0; r < QR; ++r) {
-            const long long q = q0 + sy + NTY * r;                 // (lq[r] = 0 where q >= Q: nothing is stored there)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const long long j = j0 + sx + NTX * c;
-                if (j < lq[r]) out[q * ld_out + j] = (long long)acc[r][c];
-            }
-        }
+        tk_store_rows<NTX>(acc, lq, q0, j0, tx, ty, out, ld_out);
     }
 }
 
@@ -118,33 +97,6 @@ __global__ __launch_bounds__(256) void distance_rows_kernel(const int8_t* __rest
 extern "C" int dlc_cnnvtl_distance_rows(dlc_ctx* ctx, const int8_t* queries, int64_t Q, int64_t ldq, const int8_t* db,
                                         int64_t N, int64_t ldd, int64_t D, int64_t limit0, int64_t limit_step,
                                         int64_t* out, int64_t ld_out, void* stream) {
-    if (!ctx) return DLC_ERR_BAD_ARG;
-    if (!queries || !db || !out || Q < 1 || N < 1 || D < 1 || ldq < D || ldd < D)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_rows: bad argument");
-    if (ld_out < N) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_rows: ld_out=%lld < N=%lld", (long long)ld_out, (long long)N);
-    if ((((uintptr_t)queries) & 15) || (((uintptr_t)db) & 15) || (ldq & 15) || (ldd & 15))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_rows: rows must be 16-byte aligned (bases, ldq, ldd)");
-    if (((uintptr_t)out) & 7) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_rows: out must be 8-byte aligned");
-    if (D > (1ll << 28)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_rows: D too large for int32 accumulation");
-    if (N > 0xffffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_rows: N must be below 2^32");
-    const TkPlan p = tk_plan(Q);
-    const int64_t qtiles = dlc::cdiv(Q, p.qt());
-    if (qtiles > 65535) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_rows: Q must not exceed 2^20");
-    // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t lmax = dlc::max_row_limit(0, Q - 1, N, limit0, limit_step);
-    if (lmax == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-    const int64_t tiles = dlc::cdiv(lmax, p.db());
-    const dim3 grid((unsigned)(tiles < DR_MAX_GRID_X ? tiles : DR_MAX_GRID_X), (unsigned)qtiles);
-    auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, queries, (long long)Q, (long long)ldq, db,
-                           (long long)N, (long long)ldd, (long long)D, (long long)limit0, (long long)limit_step,
-                           (long long*)out, (long long)ld_out);
-    };
-    if (p.ntx == 16) launch(distance_rows_kernel<16, 4>);
-    else if (p.qr == 4) launch(distance_rows_kernel<64, 4>);
-    else launch(distance_rows_kernel<64, 1>);
-    DLC_LAUNCH_CHECK(ctx, "distance_rows_kernel");
-    return DLC_OK;
+    return tk_rows_call(ctx, "distance_rows", "distance_rows_kernel", 1ll << 28, queries, Q, ldq, db, N, ldd, D, limit0,
+                        limit_step, out, ld_out, stream, [](auto s) { return distance_rows_kernel<s.ntx, s.qr>; });
 }

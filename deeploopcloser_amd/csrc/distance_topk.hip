@@ -45,16 +45,10 @@ __global__ __launch_bounds__(256) void distance_topk_scan_kernel(const int8_t* _
     for (int i = tid; i < QT * k; i += 256) list[i] = TK_EMPTY;
     if (tid < QT) { bound[tid] = TK_EMPTY; scnt[tid] = 0; }
 
-    // rows this tile's queries may see: limits are linear in the query row, so the largest sits at an end
-    const long long qlast = (q0 + QT < Q ? q0 + QT : Q) - 1;
-    const long long la = dlc::row_limit(q0, N, limit0, limit_step), lb = dlc::row_limit(qlast, N, limit0, limit_step);
-    const long long lmax = la > lb ? la : lb;
+    const long long lmax = tk_tile_limit<QT>(q0, Q, N, limit0, limit_step);
     long long lq[QR];
 #pragma unroll
-    for (int r = 0; r < QR; ++r) {
-        const long long q = q0 + ty + NTY * r;
-        lq[r] = q < Q ? dlc::row_limit(q, N, limit0, limit_step) : 0;
-    }
+    for (int r = 0; r < QR; ++r) lq[r] = tk_query_limit(q0 + ty + NTY * r, Q, N, limit0, limit_step);
     const long long slab0 = g * tiles_per_slab * DB;
     const long long slab1 = slab0 + tiles_per_slab * DB < lmax ? slab0 + tiles_per_slab * DB : lmax;
 
@@ -192,13 +186,10 @@ extern "C" int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int
                                         int64_t* out_dist, int64_t* out_idx, void* workspace, size_t workspace_bytes,
                                         void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (!queries || !db || !out_dist || !out_idx || !workspace || Q < 1 || N < 1 || D < 1 || ldq < D || ldd < D)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_topk: bad argument");
+    if (!out_dist || !out_idx || !workspace) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_topk: bad argument");
     if (k < 1 || k > DLC_MAX_K) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_topk: k=%d outside 1..%d", k, DLC_MAX_K);
-    if ((((uintptr_t)queries) & 15) || (((uintptr_t)db) & 15) || (ldq & 15) || (ldd & 15))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_topk: rows must be 16-byte aligned (bases, ldq, ldd)");
-    if (D > (1ll << 28)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_topk: D too large for int32 accumulation");
-    if (N > 0xffffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_topk: N must be below 2^32");
+    if (const int rc = tk_operands_check(ctx, "distance_topk", queries, Q, ldq, db, N, ldd, D, 1ll << 28); rc != DLC_OK)
+        return rc;
     if (Q > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_topk: Q too large");
     const size_t need = dlc_cnnvtl_distance_topk_workspace_bytes(Q, N, D, k);
     if (workspace_bytes < need)

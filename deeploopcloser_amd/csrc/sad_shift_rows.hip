@@ -2,9 +2,9 @@
 // work and SMART compare): dlc_sad_u8_shift_rows.  For a thumbnail of h rows and w columns and every shift -S <= s <= S
 //     sad_s(q, d) = sum over y < h, over x with 0 <= x < w and 0 <= x + s < w, of |q[y][x] - d[y][x + s]|
 //     v_s = floor(sad_s * w / (w - |s|)),   out = min_s v_s,   shift = the first s of the minimum in 0, -1, +1, -2, +2, ...
-// as int64 rows with the contract of dlc_sad_u8_rows (sad_rows.hip) word for word, plus the int8 shift of every cell.
+// as int64 rows with the contract of dlc_sad_u8_rows (u8_rows.hip) word for word, plus the int8 shift of every cell.
 //
-// The launch is sad_rows.hip's -- one workgroup per (query tile, db tile) below the largest limit of the call, the thread
+// The launch is the plain rows' -- one workgroup per (query tile, db tile) below the largest limit of the call, the thread
 // layouts of distance_tile.h (NTX threads across db rows, 256 / NTX across queries, QR queries per thread), grid stride
 // past 65 536 db tiles, no split along D, every thread storing its cells once under j < lim(r) -- with CB db rows per
 // thread instead of 4: all 2 ST + 1 sums of a pair are accumulated in one pass over the staged bytes, in registers, and
@@ -36,7 +36,6 @@
 
 namespace {
 
-constexpr int64_t SS_MAX_GRID_X = 1 << 16;     // db tiles beyond it are walked by the same workgroups (grid stride)
 constexpr int SS_SEG = 64;                     // columns of an image row per step
 constexpr int SS_HALO = 16;                    // db columns staged on either side of them
 constexpr int SS_AW = SS_SEG / 4, SS_BW = (SS_SEG + 2 * SS_HALO) / 4;   // words staged per query / db row and step
@@ -109,16 +108,10 @@ __global__ __launch_bounds__(256) void sad_shift_rows_kernel(const uint8_t* __re
 
     const int tid = threadIdx.x, tx = tid % NTX, ty = tid / NTX;
     const long long q0 = (long long)blockIdx.y * QT;
-    // rows this tile's queries may see: limits are linear in the query row, so the largest sits at an end
-    const long long qlast = (q0 + QT < Q ? q0 + QT : Q) - 1;
-    const long long la = dlc::row_limit(q0, N, limit0, limit_step), lb = dlc::row_limit(qlast, N, limit0, limit_step);
-    const long long lmax = la > lb ? la : lb;
+    const long long lmax = tk_tile_limit<QT>(q0, Q, N, limit0, limit_step);
     long long lq[QR];
 #pragma unroll
-    for (int r = 0; r < QR; ++r) {
-        const long long q = q0 + ty + NTY * r;
-        lq[r] = q < Q ? dlc::row_limit(q, N, limit0, limit_step) : 0;
-    }
+    for (int r = 0; r < QR; ++r) lq[r] = tk_query_limit(q0 + ty + NTY * r, Q, N, limit0, limit_step);
     const int spr = (w + SS_SEG - 1) / SS_SEG, steps = h * spr;      // segments per image row; steps of a tile
     for (long long j0 = (long long)blockIdx.x * DB; j0 < lmax; j0 += (long long)gridDim.x * DB) {
         unsigned acc[QR][CB][NS];
@@ -223,9 +216,8 @@ __global__ __launch_bounds__(256) void sad_shift_rows_kernel(const uint8_t* __re
             y = yn;
             c0 = cn;
         }
-        // the store addresses are formed behind the loop, as in sad_rows.hip (hoisted they hold registers through it)
         int sx = tx, sy = ty;
-        asm volatile("" : "+v"(sx), "+v"(sy));
+        tk_behind_loop(sx, sy);
 #pragma unroll
         for (int r = 0; r < QR; ++r) {
             const long long q = q0 + sy + NTY * r;                 // (lq[r] = 0 where q >= Q: nothing is stored there)
@@ -294,11 +286,8 @@ constexpr int ss_cb(int qr, int st) { return qr == 1 ? 4 : (st == 8 ? 1 : (st ==
 inline int ss_st(int S) { return S <= 1 ? 1 : (S <= 2 ? 2 : (S <= 4 ? 4 : 8)); }
 
 template <int NTX, int QR>
-void ss_launch_plan(SsArgs& a, int st, int64_t lmax, bool fast) {
-    auto grid_for = [&](int cb) {
-        const int64_t tiles = dlc::cdiv(lmax, (int64_t)NTX * cb);
-        a.grid.x = (unsigned)(tiles < SS_MAX_GRID_X ? tiles : SS_MAX_GRID_X);
-    };
+void ss_launch_plan(SsArgs& a, int st, int64_t lmax, unsigned qtiles, bool fast) {
+    auto grid_for = [&](int cb) { a.grid = tk_grid(lmax, NTX * cb, qtiles); };
     if (st == 1) { grid_for(ss_cb(QR, 1)); ss_launch<NTX, QR, ss_cb(QR, 1), 1>(a, fast); }
     else if (st == 2) { grid_for(ss_cb(QR, 2)); ss_launch<NTX, QR, ss_cb(QR, 2), 2>(a, fast); }
     else if (st == 4) { grid_for(ss_cb(QR, 4)); ss_launch<NTX, QR, ss_cb(QR, 4), 4>(a, fast); }
@@ -312,40 +301,23 @@ extern "C" int dlc_sad_u8_shift_rows(dlc_ctx* ctx, const uint8_t* queries, int64
                                      int64_t limit_step, int64_t* out, int64_t ld_out, int8_t* shift_out,
                                      int64_t ld_shift, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    if (!queries || !db || !out || Q < 1 || N < 1 || h < 1 || w < 1 || max_shift < 0)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: bad argument");
+    if (h < 1 || w < 1 || max_shift < 0) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: bad argument");
     if (max_shift > DLC_MAX_SHIFT || max_shift >= w)
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sad_u8_shift_rows: max_shift=%d outside 0..min(%d, w - 1 = %d)", max_shift,
                          DLC_MAX_SHIFT, w - 1);
     if (w > 65536) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sad_u8_shift_rows: w=%d exceeds 65536", w);
-    const int64_t D = (int64_t)h * w;
-    if (D > (1ll << 24))
-        return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sad_u8_shift_rows: h * w too large for 32-bit accumulation (255 * h * w)");
-    if (ldq < D || ldd < D) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: ldq or ldd below h * w");
-    if (ld_out < N)
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: ld_out=%lld < N=%lld", (long long)ld_out, (long long)N);
     if (shift_out && ld_shift < N)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: ld_shift=%lld < N=%lld", (long long)ld_shift, (long long)N);
-    if ((((uintptr_t)queries) & 15) || (((uintptr_t)db) & 15) || (ldq & 15) || (ldd & 15))
-        return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: rows must be 16-byte aligned (bases, ldq, ldd)");
-    if (((uintptr_t)out) & 7) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sad_u8_shift_rows: out must be 8-byte aligned");
-    if (N > 0xffffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sad_u8_shift_rows: N must be below 2^32");
-    if (Q > (1ll << 20)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sad_u8_shift_rows: Q must not exceed 2^20");
-    const TkPlan p = tk_plan(Q);
-    const int64_t qtiles = dlc::cdiv(Q, p.qt());                 // <= 65535 (grid y) for every Q <= 2^20
-    // rows any query sees (the limit is linear in the query row: its largest value is at one end)
-    const int64_t lmax = dlc::max_row_limit(0, Q - 1, N, limit0, limit_step);
-    if (lmax == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    // the rest as a plain row call of D = h * w bytes (255 * h * w fits the 32-bit accumulator for h * w <= 2^24)
+    if (const int rc = tk_rows_check(ctx, "sad_u8_shift_rows", queries, Q, ldq, db, N, ldd, (int64_t)h * w, 1ll << 24, out, ld_out);
+        rc != DLC_OK)
+        return rc;
     SsArgs a{queries, db, (long long)Q, (long long)ldq, (long long)N, (long long)ldd, (long long)limit0,
              (long long)limit_step, (long long)ld_out, (long long)ld_shift, h, w, max_shift, (long long*)out,
-             (signed char*)shift_out, dim3(1, (unsigned)qtiles), (hipStream_t)stream};
+             (signed char*)shift_out, dim3(), (hipStream_t)stream};
     const bool fast = w % 16 == 0;                               // image rows are 16-byte blocks of the descriptor rows
     const int st = ss_st(max_shift);
-    if (p.ntx == 16) ss_launch_plan<16, 4>(a, st, lmax, fast);
-    else if (p.qr == 4) ss_launch_plan<64, 4>(a, st, lmax, fast);
-    else ss_launch_plan<64, 1>(a, st, lmax, fast);
-    DLC_LAUNCH_CHECK(ctx, "sad_shift_rows_kernel");
-    return DLC_OK;
+    return tk_rows_launch(ctx, "sad_shift_rows_kernel", Q, N, limit0, limit_step, [&](auto s, int64_t lmax, unsigned qtiles) {
+        ss_launch_plan<s.ntx, s.qr>(a, st, lmax, qtiles, fast);
+    });
 }

@@ -964,17 +964,12 @@ class Engine:
                                                        _ptr(dist), _ptr(idx), _ptr(ws), ws.numel(), self._stream()))
         return dist, idx
 
-    def cnnvtl_distance_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
-        """int64 [Q, N]: the cnn_vtl distance of every query row of q [Q, D] int8 to the rows of db [N, D] int8
-        (dlc_cnnvtl_distance_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r * limit_step,
-        0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1 -- "not offered",
-        as sequence_scores writes it -- when the engine allocates the result.  d: the descriptor length when the rows
-        are padded (the bytes past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows
-        lie further apart than N (its columns past N are left alone too)."""
-        d = self._int8_pair("cnnvtl_distance_rows", q, db, d)
+    def _byte_rows(self, who, dtype, fn, q, db, d, limit0, limit_step, out):
+        """The plain row call `fn` (dlc_cnnvtl_distance_rows, dlc_sad_u8_rows, dlc_hamming_rows: one contract) behind the
+        public method `who` on rows of the byte type `dtype`."""
+        d = self._int8_pair(who, q, db, d, dtype=dtype)
         nq, n = q.shape[0], db.shape[0]
-        out = self._rows_out("cnnvtl_distance_rows: out", out, nq, n, torch.int64, "an int64",
-                             None if limit0 is None else -1)
+        out = self._rows_out(who + ": out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
         if nq == 0 or n == 0:
             return out
         if d == 0:                                               # empty descriptors: every distance is 0
@@ -982,14 +977,23 @@ class Engine:
             lim = lim0 + step * torch.arange(nq, device=self.device)
             out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
             return out
-        q = self._rows16(q, d)
-        db = self._rows16(db, d)
+        q = self._rows16(q.view(torch.int8), d).view(dtype)
+        db = self._rows16(db.view(torch.int8), d).view(dtype)
         ld_out = out.stride(0) if nq > 1 else n
-        self._check(self.lib.dlc_cnnvtl_distance_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                                       *_limits(n, limit0, limit_step), _ptr(out),
-                                                       ld_out, self._stream()))
+        self._check(fn(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d, *_limits(n, limit0, limit_step),
+                       _ptr(out), ld_out, self._stream()))
         self._wrote(out)
         return out
+
+    def cnnvtl_distance_rows(self, q, db, d=None, limit0=None, limit_step=0, out=None):
+        """int64 [Q, N]: the cnn_vtl distance of every query row of q [Q, D] int8 to the rows of db [N, D] int8
+        (dlc_cnnvtl_distance_rows, include/dlc.h), exact.  Query r is written in its first clamp(limit0 + r * limit_step,
+        0, N) cells (limit0 None = N: all of them); the other cells keep what `out` held, and hold -1 -- "not offered",
+        as sequence_scores writes it -- when the engine allocates the result.  d: the descriptor length when the rows
+        are padded (the bytes past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows
+        lie further apart than N (its columns past N are left alone too)."""
+        return self._byte_rows("cnnvtl_distance_rows", torch.int8, self.lib.dlc_cnnvtl_distance_rows, q, db, d, limit0,
+                               limit_step, out)
 
     # ---- SeqSLAM front-end: patch-normalised thumbnails, SAD difference rows ------------------------------------------
     def seqslam_describe(self, gray, size, patch, strength, out=None):
@@ -1032,7 +1036,7 @@ class Engine:
         if not shift:                                            # None or 0: today's path, call for call
             if shift_out is not None and shift_out is not False:
                 raise ValueError("sad_rows: shift_out needs shift")
-            return self._sad_rows_plain(q, db, d, limit0, limit_step, out)
+            return self._byte_rows("sad_rows", torch.uint8, self.lib.dlc_sad_u8_rows, q, db, d, limit0, limit_step, out)
         d = self._int8_pair("sad_rows", q, db, d, dtype=torch.uint8)
         if width is None:
             raise ValueError("sad_rows: shift needs width, the thumbnail's columns")
@@ -1059,27 +1063,6 @@ class Engine:
             if sh is not None:
                 self._wrote(sh)
         return (out, sh) if want_shift else out
-
-    def _sad_rows_plain(self, q, db, d, limit0, limit_step, out):
-        """sad_rows without a shift: dlc_sad_u8_rows."""
-        d = self._int8_pair("sad_rows", q, db, d, dtype=torch.uint8)
-        nq, n = q.shape[0], db.shape[0]
-        out = self._rows_out("sad_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
-        if nq == 0 or n == 0:
-            return out
-        if d == 0:                                               # empty descriptors: every difference is 0
-            lim0, step = _limits(n, limit0, limit_step)
-            lim = lim0 + step * torch.arange(nq, device=self.device)
-            out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
-            return out
-        q = self._rows16_u8(q, d)
-        db = self._rows16_u8(db, d)
-        ld_out = out.stride(0) if nq > 1 else n
-        self._check(self.lib.dlc_sad_u8_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                              *_limits(n, limit0, limit_step), _ptr(out), ld_out,
-                                              self._stream()))
-        self._wrote(out)
-        return out
 
     # ---- binary place descriptors: global LDB codes, Hamming rows ------------------------------------------------------
     @staticmethod
@@ -1131,23 +1114,7 @@ class Engine:
         offered", when the engine allocates the result.  d: the descriptor's bytes when the rows are padded (the bytes
         past d are ignored); out: a caller-kept int64 [Q, N] tensor, which may be a view whose rows lie further apart than
         N (its columns past N are left alone too)."""
-        d = self._int8_pair("hamming_rows", q, db, d, dtype=torch.uint8)
-        nq, n = q.shape[0], db.shape[0]
-        out = self._rows_out("hamming_rows: out", out, nq, n, torch.int64, "an int64", None if limit0 is None else -1)
-        if nq == 0 or n == 0:
-            return out
-        if d == 0:                                               # empty descriptors: every distance is 0
-            lim0, step = _limits(n, limit0, limit_step)
-            lim = lim0 + step * torch.arange(nq, device=self.device)
-            out.masked_fill_(torch.arange(n, device=self.device)[None, :] < lim[:, None], 0)
-            return out
-        q = self._rows16_u8(q, d)
-        db = self._rows16_u8(db, d)
-        ld_out = out.stride(0) if nq > 1 else n
-        self._check(self.lib.dlc_hamming_rows(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d,
-                                               *_limits(n, limit0, limit_step), _ptr(out), ld_out, self._stream()))
-        self._wrote(out)
-        return out
+        return self._byte_rows("hamming_rows", torch.uint8, self.lib.dlc_hamming_rows, q, db, d, limit0, limit_step, out)
 
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
     # the dtype of what a score-row call derives from its rows: int64 from int64 rows, else float64

@@ -59,7 +59,7 @@ def time_alternately_ms(fns, warmup, reps):
 
 
 def tile_plan(q):
-    """(queries, db rows, queries per thread) of a tile: tk_plan of csrc/distance_tile.h."""
+    """(queries, db rows, queries per thread) of a tile: tk_plan of deeploopcloser_amd/csrc/distance_tile.h."""
     if q <= 4:
         return 1, 256, 1
     big, mid = -(-q // 64) * 64, -(-q // 16) * 16

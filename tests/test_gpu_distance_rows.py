@@ -210,8 +210,11 @@ def test_bad_arguments(dlc):
         assert rc == _lib.DLC_ERR_BAD_ARG, kw
         with pytest.raises(ValueError):
             e._check(rc)
+    for rows in ((1 << 20) + 1, 1 << 22):                             # Q > 2^20, as the header states it (refused before any read)
+        assert e.lib.dlc_cnnvtl_distance_rows(e.ctx, vp(qs), rows, 32, vp(db), 50, 32, 32, 50, 0, vp(out), 50,
+                                              e._stream()) == _lib.DLC_ERR_BAD_SHAPE
     torch.cuda.synchronize()
-    assert not bool(out.any())                                         # the one good call wrote zeros; the refused ones nothing
+    assert not bool(out.any())                                       # the one good call wrote zeros; the refused ones nothing
 
 
 # ---- 7. the Python entry points -----------------------------------------------------------------------------------------

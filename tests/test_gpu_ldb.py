@@ -191,7 +191,7 @@ def padded_rows(rng, x, extra=16):
 
 
 def tile_plan(q):
-    """(queries, db rows) of a tile: tk_plan of csrc/distance_tile.h, restated."""
+    """(queries, db rows) of a tile: tk_plan of deeploopcloser_amd/csrc/distance_tile.h, restated."""
     if q <= 4:
         return 1, 256
     big, mid = -(-q // 64) * 64, -(-q // 16) * 16

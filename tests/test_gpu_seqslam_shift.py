@@ -46,7 +46,7 @@ def padded_rows(x, extra=16, fill=0xFF):
 
 # ---- 1. the sweep ---------------------------------------------------------------------------------------------------------
 def thread_plan(q):
-    """(threads across db rows, queries per thread): tk_plan of csrc/distance_tile.h, restated."""
+    """(threads across db rows, queries per thread): tk_plan of deeploopcloser_amd/csrc/distance_tile.h, restated."""
     if q <= 4:
         return 64, 1
     big, mid = -(-q // 64) * 64, -(-q // 16) * 16
