@@ -27,6 +27,7 @@ include/dlc.h, with the reference's Python call surface on top:
     PlaceTracker, track_places (and track= on the detectors): a Viterbi filter over score rows with a "no loop" state -- the place per frame and the smoothed labelling of the traversal; new
     Vlad, vlad_frame_descriptors (and pool= on describe_sdav, loop_closure --pool vlad; python -m deeploopcloser_amd.train_vlad): a k-means codebook of patch descriptors and VLAD pooling -- one orderless row per frame in front of KeyframeDatabase; new
     Pca (and loop_closure.describe_sdav_compact(pool=, pca=), pca= on sdav_place_descriptors_from_frames, loop_closure --pca; python -m deeploopcloser_amd.train_pca): PCA and whitening of a pooled row down to the <= 4096 columns the cosine top-k stores, by a projection whose sum order is stated -- the same bits alone or in a batch; new
+    Lsh, lsh_planes, HashedLoopClosureDetector (and Engine.lsh_quantize / lsh_hash, loop_closure --hash; python -m deeploopcloser_amd.train_lsh): sign-random-projection hashes -- a float descriptor scaled to int8, the signs of its exact integer products with seeded +-1 hyperplanes on the int8 matrix cores, packed: a deep descriptor at 128 bytes a key-frame on the Hamming path; new
     GeometricVerifier, verify_candidates (and Engine.verify_pairs, loop_closure --verify): geometric verification of loop candidates -- the frames' patches matched, every two-match similarity of the matched key-points tried in integer arithmetic, the agreeing matches counted: exact, a function of the pair alone; new
     ground_truth / pr_curve_cells / recall_at / pr_curve_queries / PRCurve / LoopClosureEvaluator   (ground-truth evaluation: PR curves, average precision, recall@K; new)
 
@@ -60,12 +61,15 @@ from . import vlad
 from .vlad import Vlad
 from . import pca
 from .pca import Pca
+from . import lsh
+from .lsh import Lsh, lsh_planes
+from .loop_closure import HashedLoopClosureDetector
 from . import verification
 from .verification import GeometricVerifier, verify_candidates
 from . import evaluate
 from .evaluate import ground_truth, pr_curve_cells, recall_at, pr_curve_queries, PRCurve, LoopClosureEvaluator
 
-__all__ = ["Ldb", "HammingCalculator", "HammingKeyframeDatabase", "LdbLoopClosureDetector", "GeometricVerifier", "verify_candidates", "Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
+__all__ = ["Lsh", "lsh_planes", "HashedLoopClosureDetector", "Ldb", "HammingCalculator", "HammingKeyframeDatabase", "LdbLoopClosureDetector", "GeometricVerifier", "verify_candidates", "Pca", "Vlad", "vlad_frame_descriptors", "PlaceTracker", "track_places", "fuse_scores", "FusedLoopClosureDetector", "ground_truth", "pr_curve_cells", "recall_at", "pr_curve_queries", "PRCurve", "LoopClosureEvaluator", "slope_offsets", "sequence_topk", "sequence_scores", "sequence_chains", "contrast_normalize", "peak_topk", "sequence_peaks", "uniqueness_ratio", "LoopClosureDetector", "SdavLoopClosureDetector", "CnnVtlLoopClosureDetector", "SeqSlamLoopClosureDetector", "SeqSlam", "DifferenceCalculator", "SadKeyframeDatabase", "CnnVtlKeyframeDatabase", "SimilarityStream", "SDAV", "DA", "SDA", "CnnVtl", "SimilarityCalculator", "DistanceCalculator", "MathUtils", "tensor_wrapper", "CvInputParser",
            "grid_key_points", "harris_key_points", "KeyPoint", "read_ppm",
            "encode", "match", "match_topk", "KeyframeDatabase", "MatchPipeline", "ShardedKeyframeDatabase", "Engine",
            "default_engine", "shard_bounds", "merge_topk_torch", "flatten_frame_descriptors"]

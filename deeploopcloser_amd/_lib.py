@@ -35,7 +35,10 @@ DLC_VLAD_NORM_NONE, DLC_VLAD_NORM_INTRA = 0, 1
 DLC_PCA_CHUNK = 1024         # columns of x of one serial chain of dlc_pca_project; the chunks' sums are added in order
 DLC_PCA_MAX_COMPONENTS, DLC_PCA_SPLIT_MAX_ROWS = 8192, 64
 DLC_PCA_PLAN_AUTO, DLC_PCA_PLAN_ONE_PASS, DLC_PCA_PLAN_SPLIT = 0, 1, 2
-DLC_VERIFY_MAX_PATCHES = 64  # the most patches of a frame dlc_verify_pairs matches (one bit of its inlier mask each)
+DLC_LSH_MAX_BITS, DLC_LSH_MAX_D = 8192, 131071   # dlc_lsh_hash_i8: 128 * 128 * D < 2^31, the int32 sum cannot overflow
+DLC_LSH_CHUNK, DLC_LSH_SPLIT_MAX_ROWS = 8192, 64  # bytes of D per split piece; the most rows the SPLIT plan takes
+DLC_LSH_PLAN_AUTO, DLC_LSH_PLAN_ONE_PASS, DLC_LSH_PLAN_SPLIT = 0, 1, 2
+DLC_VERIFY_MAX_PATCHES = 64 # the most patches of a frame dlc_verify_pairs matches (one bit of its inlier mask each)
 DLC_VERIFY_SIMILARITY, DLC_VERIFY_TRANSLATION = 0, 1
 
 _vp, _i64, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.c_double, C.c_float
@@ -112,6 +115,10 @@ SIGNATURES = {
     "dlc_seqslam_describe_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp]),
     "dlc_ldb_row_bytes": (_i64, [C.POINTER(_int), _int]),
     "dlc_ldb_describe_u8": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, C.POINTER(_int), _int, _vp, _i64, _vp]),
+    "dlc_lsh_quantize_i8": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "dlc_lsh_row_bytes": (_i64, [_int]),
+    "dlc_lsh_hash_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "dlc_lsh_hash_i8": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _i64, _vp, _i64, _int, _vp, _sz, _vp]),
     "dlc_hamming_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dlc_sequence_topk_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "dlc_sequence_topk": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, C.POINTER(C.c_int32), _int, _int,

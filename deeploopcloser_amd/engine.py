@@ -1116,6 +1116,82 @@ class Engine:
         N (its columns past N are left alone too)."""
         return self._byte_rows("hamming_rows", torch.uint8, self.lib.dlc_hamming_rows, q, db, d, limit0, limit_step, out)
 
+    # ---- sign-random-projection hashes: float rows -> int8 rows -> packed sign bits ------------------------------------
+    _LSH_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.bfloat16: L.DLC_BF16}
+    _LSH_PLANS = {"auto": L.DLC_LSH_PLAN_AUTO, "one_pass": L.DLC_LSH_PLAN_ONE_PASS, "split": L.DLC_LSH_PLAN_SPLIT}
+
+    def lsh_quantize(self, x, mean=None, out=None):
+        """int8 [rows, D]: every row of x [rows, D] (float64, float32 or bfloat16 on the device; a row-strided view is
+        taken as it is) scaled to -127 .. 127 by its own largest magnitude, after `mean` (float64 [D]; None: nothing) is
+        taken off -- q = rint((x - mean) * (127 / max |x - mean|)) in fp64, ties to even; a row that is all zero or holds
+        a NaN or an infinity becomes zeros (dlc_lsh_quantize_i8, include/dlc.h).  A row's bytes depend on that row and
+        the mean alone.  out: a caller-kept int8 [rows, >= D] tensor or row-strided view (the bytes past D of a row keep
+        their value); the result is its first D columns.  Allocated here, the rows lie a multiple of 16 bytes apart, as
+        lsh_hash takes them without a copy."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in self._LSH_DTYPES or x.device != self.device:
+            raise ValueError("lsh_quantize: x must be a 2-D float64, float32 or bfloat16 tensor on %s" % self.device)
+        rows, d = x.shape
+        if rows < 1 or d < 1:
+            raise ValueError("lsh_quantize: x is [%d, %d]: nothing to do" % (rows, d))
+        if d > L.DLC_LSH_MAX_D or rows >= 1 << 31:
+            raise ValueError("lsh_quantize: rows=%d, D=%d outside rows < 2^31, D <= %d" % (rows, d, L.DLC_LSH_MAX_D))
+        if x.stride(1) != 1 or (rows > 1 and x.stride(0) < d):
+            x = x.contiguous()
+        ldx = x.stride(0) if rows > 1 else max(d, x.stride(0))
+        if mean is not None:
+            if not isinstance(mean, torch.Tensor) or mean.dtype != torch.float64 or mean.device != self.device or \
+                    tuple(mean.shape) != (d,):
+                raise ValueError("lsh_quantize: mean must be a float64 tensor [%d] on %s" % (d, self.device))
+            mean = mean.contiguous()
+        if out is None:
+            out = torch.empty((rows, (d + 15) // 16 * 16), dtype=torch.int8, device=self.device)
+        else:
+            out = self._rows_out("lsh_quantize: out", out, rows, d, torch.int8, "an int8", wider=True)
+        ldq = out.stride(0) if rows > 1 else out.shape[1]
+        self._check(self.lib.dlc_lsh_quantize_i8(self.ctx, self._LSH_DTYPES[x.dtype], _ptr(x), rows, d, ldx, _ptr(mean), _ptr(out),
+                                                  ldq, self._stream()))
+        self._wrote(out)
+        return out[:, :d]
+
+    def lsh_row_bytes(self, bits):
+        """Bytes of a hash row of `bits` bits: 16 * ceil(bits / 128) (dlc_lsh_row_bytes); ValueError outside 1..8192."""
+        nb = int(self.lib.dlc_lsh_row_bytes(int(bits))) if -1 << 31 <= int(bits) < 1 << 31 else 0
+        if nb == 0:
+            raise ValueError("lsh: bits=%r outside 1..%d" % (bits, L.DLC_LSH_MAX_BITS))
+        return nb
+
+    def lsh_hash(self, q, planes, bits=None, out=None, plan="auto"):
+        """uint8 [rows, row_bytes]: bit t of row r is 1 iff the integer product of q[r] and planes[t] is positive (a tie is
+        0), bit t & 7 of byte t >> 3; the bits past `bits` are 0 (dlc_lsh_hash_i8, include/dlc.h).  q [rows, D] and planes
+        [>= bits, D] are int8 on the device, any values; bits None: every plane.  The sums are exact on the int8 matrix
+        cores, so a row's code depends on that row and the planes alone -- not on its batch or the plan ("one_pass": a
+        workgroup walks all of D; "split", <= 64 rows: pieces of D are spread over the chip; "auto" chooses).  out: a
+        caller-kept uint8 [rows, >= row_bytes] tensor or row-strided view -- rows of a HammingKeyframeDatabase, say; the
+        bytes past row_bytes of a row keep their value -- and the result is its first row_bytes columns."""
+        if plan not in self._LSH_PLANS:
+            raise ValueError("lsh_hash: plan=%r is none of %s" % (plan, sorted(self._LSH_PLANS)))
+        d = self._int8_pair("lsh_hash", q, planes, None)
+        rows, n = q.shape[0], planes.shape[0]
+        bits = n if bits is None else int(bits)
+        if rows < 1 or d < 1 or not 1 <= bits <= n:
+            raise ValueError("lsh_hash: q [%d, %d], %d planes and bits=%d: nothing to do" % (rows, d, n, bits))
+        if d > L.DLC_LSH_MAX_D or rows >= 1 << 31:
+            raise ValueError("lsh_hash: rows=%d, D=%d outside rows < 2^31, D <= %d" % (rows, d, L.DLC_LSH_MAX_D))
+        nb = self.lsh_row_bytes(bits)
+        code = self._LSH_PLANS[plan]
+        if code == L.DLC_LSH_PLAN_SPLIT and rows > L.DLC_LSH_SPLIT_MAX_ROWS:
+            raise ValueError("lsh_hash: plan 'split' takes at most %d rows, not %d" % (L.DLC_LSH_SPLIT_MAX_ROWS, rows))
+        out = self._rows_out("lsh_hash: out", out, rows, nb, torch.uint8, "a uint8", wider=True)
+        q = self._rows16(q, d)
+        planes = self._rows16(planes, d)
+        ld_out = out.stride(0) if rows > 1 else out.shape[1]
+        need = self.lib.dlc_lsh_hash_workspace_bytes(rows, d, bits, code)
+        ws = self.workspace("lsh_hash", need) if need else None
+        self._check(self.lib.dlc_lsh_hash_i8(self.ctx, _ptr(q), rows, d, q.stride(0), _ptr(planes), bits, planes.stride(0), _ptr(out),
+                                              ld_out, code, _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
+        self._wrote(out)
+        return out[:, :nb]
+
     _SEQ_DTYPES = {torch.float64: L.DLC_F64, torch.float32: L.DLC_F32, torch.int64: L.DLC_I64}
     # the dtype of what a score-row call derives from its rows: int64 from int64 rows, else float64
     _OUT_DTYPES = {torch.float64: torch.float64, torch.float32: torch.float64, torch.int64: torch.int64}

@@ -19,6 +19,13 @@ top-k path and reports the candidates whose cosine score reaches `threshold`.
 --levels; 64 bytes a frame by default), Hamming distances, then everything the seqslam route has behind its rows
 (LdbLoopClosureDetector).
 
+    python -m deeploopcloser_amd.loop_closure DATASET_DIR --network sdav --metric cosine --hash lsh.npz --sequence 10
+
+--hash FILE (the model of python -m deeploopcloser_amd.train_lsh) takes the deep descriptor to the binary route: the frame
+descriptor -- flattened or VLAD-pooled, PCA-projected or not -- is hashed by the signs of random projections (lsh.Lsh; 128
+bytes a key-frame at 1024 bits) and searched by Hamming distance with everything the ldb route has behind its rows
+(HashedLoopClosureDetector).
+
     python -m deeploopcloser_amd.loop_closure DATASET_DIR --fuse sad,distance --sequence 10
 
 --fuse MEMBER,MEMBER[,...] (sad, distance, cosine) runs several descriptors side by side and ranks by ONE fused score:
@@ -819,6 +826,35 @@ class LdbLoopClosureDetector(_ByteRowsLoopClosureDetector):
         self.db.distances(q, limit0=limit0, limit_step=1, out=out)
 
 
+class HashedLoopClosureDetector(LdbLoopClosureDetector):
+    """LdbLoopClosureDetector over the HASHES of float descriptors: every batch of rows [B, lsh.width] (float64, float32
+    or bfloat16; NumPy or tensors) goes through `lsh` (lsh.Lsh: the mean taken off, int8, the signs of the products with
+    its hyperplanes -- dlc_lsh_quantize_i8, dlc_lsh_hash_i8) and the codes, lsh.dim bytes a key-frame, through that
+    detector's body as they are: a deep descriptor searched at the binary path's cost.  Every option is
+    LdbLoopClosureDetector's, and so are the lists, those of that detector fed the same codes; max_distance is a Hamming
+    distance (with sequence=L the sum along the line).  A code depends on its row and the model alone, so the lists do
+    not depend on how the frames are batched."""
+
+    def __init__(self, lsh, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
+                 contrast=None, suppress=None, steps=None, chains=False, track=None):
+        if getattr(lsh, "dim", None) is None or not hasattr(lsh, "transform_tensor"):
+            raise ValueError("lsh must be an lsh.Lsh")
+        super().__init__(lsh.dim, k=k, max_distance=max_distance, exclusion=exclusion, capacity=capacity, device=device,
+                         sequence=sequence, slopes=slopes, contrast=contrast, suppress=suppress, steps=steps, chains=chains,
+                         track=track)
+        self.lsh = lsh
+
+    def query_and_insert(self, descriptors):
+        """The next B frames' float descriptors [B, lsh.width] -> what LdbLoopClosureDetector.query_and_insert returns for
+        their codes."""
+        x = descriptors if isinstance(descriptors, torch.Tensor) else np.asarray(descriptors)
+        if x.ndim == 1:
+            x = x[None]
+        if x.shape[0] == 0:
+            return super().query_and_insert(torch.empty((0, self.lsh.dim), dtype=torch.uint8, device=self.db.engine.device))
+        return super().query_and_insert(self.lsh.transform_tensor(x))
+
+
 FUSE_MEMBERS = ("cosine", "distance", "sad")
 FUSE_NORMS = ("zscore", "minmax", "none")
 
@@ -1113,6 +1149,11 @@ def main(argv=None):
     ap.add_argument("--pca", default=None, metavar="FILE",
                     help="--network sdav --metric cosine: project the frame descriptor (of either --pool) with the .npz "
                          "written by python -m deeploopcloser_amd.train_pca before it is stored and matched")
+    ap.add_argument("--hash", default=None, metavar="FILE",
+                    help="--network sdav --metric cosine: hash the frame descriptor (of either --pool, behind --pca if "
+                         "given) with the .npz written by python -m deeploopcloser_amd.train_lsh and search the codes by "
+                         "Hamming distance: everything --metric hamming takes behind its rows goes with it (--max-distance, "
+                         "--sequence, --contrast, --suppress, --steps, --chains, --track)")
     ap.add_argument("--exclusion", type=int, default=30)
     ap.add_argument("--batch", type=int, default=16, help="frames encoded and matched per step")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16")
@@ -1207,6 +1248,26 @@ def main(argv=None):
             ap.error("--pca: %s" % err)
         if pca_width != want:
             ap.error("--pca: its rows are %d wide, the frame descriptor %d" % (pca_width, want))
+    if args.hash is not None:
+        if args.fuse is not None or args.network != "sdav" or args.metric != "cosine":
+            ap.error("--hash needs --network sdav --metric cosine")
+        if args.verify is not None:
+            ap.error("--hash excludes --verify")
+        try:
+            with np.load(args.hash, allow_pickle=False) as z:
+                hash_width = int(z["width"])
+            want = SDAV_CLI_PATCHES * SDAV_CLI_WIDTH
+            if args.pool == "vlad":
+                with np.load(args.codebook, allow_pickle=False) as z:
+                    want = int(z["centroids"].shape[0]) * SDAV_CLI_WIDTH
+            if args.pca is not None:
+                with np.load(args.pca, allow_pickle=False) as z:
+                    want = int(z["basis"].shape[1])
+        except (OSError, ValueError, KeyError, IndexError) as err:
+            ap.error("--hash: %s" % err)
+        if hash_width != want:
+            ap.error("--hash: its rows are %d wide, the frame descriptor %d" % (hash_width, want))
+    hamming = args.metric == "hamming" or args.hash is not None      # the rows behind the descriptor are Hamming rows
     thumbnails = args.network == "seqslam" or (args.fuse is not None and "sad" in args.fuse)
     if args.metric == "distance" and args.network != "cnn_vtl":
         ap.error("--metric distance needs --network cnn_vtl")
@@ -1220,7 +1281,7 @@ def main(argv=None):
         ap.error("--levels needs --network ldb")
     if args.size is None:
         args.size = "48x48" if args.network == "ldb" else "32x64"
-    if args.max_distance is not None and not (args.metric == "hamming" and args.contrast is not None):
+    if args.max_distance is not None and not (hamming and args.contrast is not None):
         if args.max_distance < 0 or args.max_distance != int(args.max_distance):
             ap.error("--max-distance must be a non-negative integer (any number with --metric hamming --contrast)")
         args.max_distance = int(args.max_distance)
@@ -1253,7 +1314,7 @@ def main(argv=None):
             if args.max_difference < 0 or args.max_difference != int(args.max_difference):
                 ap.error("--max-difference must be a non-negative integer (any number with --contrast)")
             args.max_difference = int(args.max_difference)
-    if args.sequence is not None and args.metric not in ("similarity", "sad", "hamming") and args.fuse is None:
+    if args.sequence is not None and args.metric not in ("similarity", "sad", "hamming") and args.fuse is None and not hamming:
         ap.error("--sequence needs --metric similarity, sad or hamming (or --fuse)")
     if args.sequence is not None and not 1 <= args.sequence <= 64:
         ap.error("--sequence must be 1..64")
@@ -1355,7 +1416,7 @@ def _fused_stream(args, files):
 
 
 def _stream(args, files):
-    fused = verifier = None
+    fused = verifier = hashed = None
     local = []                                                   # --verify: the batch's (patch descriptors, key-points)
     if args.fuse is not None:
         describe, fused = _fused_stream(args, files)
@@ -1373,6 +1434,9 @@ def _stream(args, files):
             from .pca import Pca
             compact = Pca.load(args.pca)
             describe = lambda fs: describe_sdav_compact(fs, net, pool=pool, pca=compact)
+        if getattr(args, "hash", None) is not None:        # (nor --hash)
+            from .lsh import Lsh
+            hashed = Lsh.load(args.hash)
         if getattr(args, "verify", None) is not None:
             from .verification import GeometricVerifier, keep_accepted
             patches = net.input_shape[0]
@@ -1411,7 +1475,8 @@ def _stream(args, files):
     if args.positions is not None:
         from .evaluate import LoopClosureEvaluator, pr_line
         judge = LoopClosureEvaluator(args.positions, args.radius, args.exclusion,
-                                     lower_is_better=fused is None and args.metric in ("distance", "sad", "hamming"))
+                                     lower_is_better=fused is None and (args.metric in ("distance", "sad", "hamming") or
+                                                                        hashed is not None))
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
@@ -1440,6 +1505,10 @@ def _stream(args, files):
                                              contrast=args.contrast, suppress=args.suppress, steps=args.steps,
                                              chains=args.chains, shift=args.shift,
                                              width=None if args.shift is None else args.size[1], track=args.track)
+        elif det is None and hashed is not None:
+            det = HashedLoopClosureDetector(hashed, k=args.k, max_distance=args.max_distance, exclusion=args.exclusion,
+                                            capacity=max(4096, len(files)), sequence=args.sequence, contrast=args.contrast,
+                                            suppress=args.suppress, steps=args.steps, chains=args.chains, track=args.track)
         elif det is None and args.metric == "hamming":
             det = LdbLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance, exclusion=args.exclusion,
                                          capacity=max(4096, len(files)), sequence=args.sequence, contrast=args.contrast,

@@ -331,6 +331,63 @@ int64_t dlc_ldb_row_bytes(const int* levels, int n_levels);
 int dlc_ldb_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t frames, int H, int W, int h, int w,
                         const int* levels, int n_levels, uint8_t* out, int64_t ld_out, void* stream);
 
+/* ---- encode: sign-random-projection hashes, a float descriptor -> a Hamming code (not in the reference) -------------- */
+/*
+ * The bridge from the deep descriptors (searched by cosine, 8 KB a key-frame at 4096 bf16 columns) to the binary path
+ * (dlc_hamming_rows and everything behind its rows, 128 bytes a key-frame at 1024 bits): bit t of a row is the sign of its
+ * product with hyperplane t.  For random hyperplanes P(a bit differs) = angle / pi (Charikar, STOC 2002; on ConvNet place
+ * descriptors: Suenderhauf et al., IROS 2015).  The product is formed on INT8 operands, so every sum is an exact integer
+ * whatever the order, the tiling or the split: a code is bit for bit a function of the row and the model.
+ * QUANTISE (dlc_lsh_quantize_i8).  x is [rows, ldx] of DLC_F64, DLC_F32 or DLC_BF16 (ldx in elements) using its first D
+ * columns; mean fp64 [D] or NULL; q int8 [rows, ldq].  All arithmetic is fp64, every operation rounded on its own.  The
+ * conversion of x to double is exact.  For row r:  t_d = (double)x[r][d] - mean[d], or (double)x[r][d] when mean is NULL;
+ * m = max_d |t_d|.  If m == 0, or any t_d is a NaN or an infinity, the row is written as D zeros.  Otherwise s = 127.0 / m
+ * and q[r][d] = (int8) rint(t_d * s), ties to even, which lies in -127 .. 127 (t_d == 0 gives 0, and where 127.0 / m
+ * overflows the rounded product is clamped to +-127).  Only q[r][0 .. D-1] is written: bytes D .. ldq-1 KEEP THEIR VALUE.
+ * A row's bytes depend on that row and mean alone.  q must not overlap x or mean.  1 <= rows < 2^31, 1 <= D <=
+ * DLC_LSH_MAX_D, ldx >= D, ldq >= D.  One launch (a workgroup per row), no workspace.
+ * WORKED EXAMPLE.  x = (0.5, -1, 0.25, 0), no mean: m = 1, s = 127, products 63.5, -127, 31.75, 0 -> (64, -127, 32, 0);
+ * 63.5 ties to the even 64.
+ * HASH (dlc_lsh_hash_i8).  q is int8 [rows, ldq] and planes int8 [bits, ldp], both using their first D columns; ARBITRARY
+ * int8 in both (-128 included), not only +-1: learned hyperplanes fit the same call.
+ *     S(r, t) = sum over d < D of q[r][d] * planes[t][d]          exact in int32: 128 * 128 * DLC_LSH_MAX_D < 2^31
+ * Bit t of row r is 1 iff S(r, t) > 0; a tie is 0.  Bit t is bit t & 7, least significant first, of byte t >> 3 of the row.
+ *     row_bytes = 16 * ceil(bits / 128)                           (dlc_lsh_row_bytes; 0 for bits outside 1 .. MAX_BITS)
+ * The bits from `bits` to 8 * row_bytes - 1 are written as 0; bytes row_bytes .. ld_out-1 of a row KEEP THEIR VALUE -- the
+ * contract of dlc_ldb_describe_u8, so dlc_hamming_rows takes the rows as they are and out may be rows of a key-frame
+ * store.  Both q and planes are 16-byte aligned with ldq and ldp multiples of 16 and >= D.  Bytes D .. ld-1 of either may
+ * hold anything and change nothing (the K tail is masked; no byte past D of a row is read).  out must not overlap q or
+ * planes.  1 <= rows < 2^31, 1 <= D <= DLC_LSH_MAX_D, 1 <= bits <= DLC_LSH_MAX_BITS, ld_out >= row_bytes.
+ * WORKED EXAMPLE.  q = (3, -2, 0, 1) against planes (1, 1, 1, 1), (-1, 1, 1, -1), (1, 1, -1, -1), (1, -1, 1, 1): the sums
+ * are 2, -6, 0, 6, the bits 1 0 0 1, the row 09 followed by 15 zero bytes.
+ * PLANS.  DLC_LSH_PLAN_ONE_PASS: a workgroup owns a (row tile, bit tile) and walks all of D on the int8 matrix cores; no
+ * workspace, one launch.  DLC_LSH_PLAN_SPLIT (rows <= DLC_LSH_SPLIT_MAX_ROWS): a workgroup takes one DLC_LSH_CHUNK-byte
+ * piece of D for a tile and stores its int32 sums to the workspace [chunks][rows][8 * row_bytes] with plain stores (no
+ * atomics, no memset); a finish kernel adds a bit's chunks, takes the sign and packs: two launches, and the planes of one
+ * streamed frame are read by chunks x as many workgroups.  DLC_LSH_PLAN_AUTO: SPLIT iff rows <= DLC_LSH_SPLIT_MAX_ROWS and
+ * D > DLC_LSH_CHUNK (there is a second chunk to give away), else ONE_PASS.  The result does not depend on the plan: that
+ * is integer arithmetic, not a tolerance.
+ * dlc_lsh_hash_workspace_bytes(rows, D, bits, plan) is host arithmetic: the bytes the plan (AUTO: the plan it chooses)
+ * needs -- 0 under ONE_PASS, at least rows * chunks * bits * 4 under SPLIT -- and 0 for refused shapes.
+ * Errors: DLC_ERR_BAD_ARG for a null pointer (x, q, planes, out), a misaligned one, rows / D / bits < 1, a pitch below D
+ * (or, of the hash, not a multiple of 16), ld_out < row_bytes, an unknown dtype or plan, or an output overlapping an
+ * input; DLC_ERR_BAD_SHAPE for D > DLC_LSH_MAX_D, bits > DLC_LSH_MAX_BITS, rows >= 2^31 or SPLIT with more than
+ * DLC_LSH_SPLIT_MAX_ROWS rows; DLC_ERR_WORKSPACE for a workspace (SPLIT) that is missing, too small or not 16-byte aligned.
+ * Nothing is written then.  All launches on `stream`, none synchronises; memory and the workspace are the caller's.
+ */
+#define DLC_LSH_MAX_BITS 8192
+#define DLC_LSH_MAX_D 131071          /* 128 * 128 * D < 2^31: the int32 sum cannot overflow */
+#define DLC_LSH_CHUNK 8192            /* bytes of D per split piece */
+#define DLC_LSH_SPLIT_MAX_ROWS 64
+enum { DLC_LSH_PLAN_AUTO = 0, DLC_LSH_PLAN_ONE_PASS = 1, DLC_LSH_PLAN_SPLIT = 2 };
+int dlc_lsh_quantize_i8(dlc_ctx* ctx, int x_dtype /* DLC_F64 | DLC_F32 | DLC_BF16 */, const void* x, int64_t rows, int64_t D,
+                        int64_t ldx, const double* mean /* [D], may be NULL */, int8_t* q, int64_t ldq, void* stream);
+int64_t dlc_lsh_row_bytes(int bits);
+size_t dlc_lsh_hash_workspace_bytes(int64_t rows, int64_t D, int bits, int plan);
+int dlc_lsh_hash_i8(dlc_ctx* ctx, const int8_t* q, int64_t rows, int64_t D, int64_t ldq,
+                    const int8_t* planes /* [bits, ldp] */, int bits, int64_t ldp,
+                    uint8_t* out, int64_t ld_out, int plan, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- encode: CnnVtl pieces (src/cnn_vtl/network/cnn_vtl.py:28-133) ------ */
 /*
  * im2col for tf.layers.conv2d on NHWC fp64 (cnn_vtl.py:33-93): x[n,h,w,c] ->
