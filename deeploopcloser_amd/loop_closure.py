@@ -77,37 +77,28 @@ def first_k_eligible(scores, idx, limit, k):
     return s, i
 
 
-def _nothing_older(b, k, fill, dtype, device):
-    """(scores, ids) [b, k] of b frames none of which has a frame old enough yet: (fill, -1) in every slot."""
-    return (torch.full((b, k), fill, dtype=dtype, device=device),
-            torch.full((b, k), -1, dtype=torch.int64, device=device))
-
-
-def _empty_result(b, k, fill, dtype, device, chains, length):
-    """A detector's result for b frames none of which has a candidate: _nothing_older's (scores, ids), and with chains
-    the chain [b, k, L] too, -1 everywhere."""
-    out = _nothing_older(b, k, fill, dtype, device)
-    return out + (torch.full((b, k, length), -1, dtype=torch.int32, device=device),) if chains else out
-
-
 def _sequence_search(sequence, slopes, contrast, k, dtype, lower_is_better=False, suppress=None, steps=None, chains=False,
-                     track=None):
-    """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L."""
-    if sequence is not None:
-        return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps, chains, track)
-    if track is not None:
-        raise ValueError("track needs sequence=L (L = 1 searches the frame scores themselves)")
-    if chains:
-        raise ValueError("chains needs sequence=L")
-    if slopes is not None:
-        raise ValueError("slopes needs sequence=L")
-    if steps is not None:
-        raise ValueError("steps needs sequence=L")
-    if contrast is not None:
-        raise ValueError("contrast needs sequence=L")
-    if suppress is not None:
-        raise ValueError("suppress needs sequence=L (L = 1 ranks by the frame scores themselves)")
-    return None
+                     track=None, suppress_alone=False, length_alone=None):
+    """A detector's sequence search (_SequenceRows over rows of `dtype`), or None without sequence=L -- what needs
+    sequence=L is refused then; suppress_alone: `suppress` is not, the detector serves it; length_alone: the L that
+    stands for sequence=None, the search is made all the same."""
+    if sequence is None:
+        if track is not None:
+            raise ValueError("track needs sequence=L (L = 1 searches the frame scores themselves)")
+        if chains:
+            raise ValueError("chains needs sequence=L")
+        if slopes is not None:
+            raise ValueError("slopes needs sequence=L")
+        if steps is not None:
+            raise ValueError("steps needs sequence=L")
+        if contrast is not None:
+            raise ValueError("contrast needs sequence=L")
+        if suppress is not None and not suppress_alone:
+            raise ValueError("suppress needs sequence=L (L = 1 ranks by the frame scores themselves)")
+        if length_alone is None:
+            return None
+        sequence = length_alone
+    return _SequenceRows(sequence, slopes, k, dtype, contrast, lower_is_better, suppress, steps, chains, track)
 
 
 def _loops(values, ids, first_id, limit, lower_is_better=False, chains=None):
@@ -128,65 +119,141 @@ def _loops(values, ids, first_id, limit, lower_is_better=False, chains=None):
             for f, (r, c) in zip(found, zip(*np.nonzero(ok)))]
 
 
-class LoopClosureDetector:
-    """The cosine detector: every new frame against the key-frames more than `exclusion` frames older, the k best by the
-    cosine path's fp64 score (dlc_cosine_topk_older), candidates at or above `threshold`.
+class _StreamingDetector:
+    """What every streaming detector is made of: the search options, checked and kept once; the sequence step; the result
+    of frames that have no candidate; loops() and len().  A detector says where it differs with class attributes --
 
-    sequence = L (None: off, every path as it is without it -- the fused top-k, no score rows are formed) asks whether
-    the match holds over the last L frames, as the other two detectors do: a pair (frame t, older frame j) is scored by
-    the SUM of the L frame scores along a line through (t, j) of the score matrix, the best of the lines of `slopes` (an
-    int32 table [1..16, L]; default sequence.slope_offsets(L)), and the k best sums are the candidates.  The rows summed
-    are the scores' ordering KEYS -- int64, round-half-even(score * 2^40), the integer the top-k itself ranks by
-    (dlc_cosine_score_rows into a resident int64 buffer that keeps the last L - 1 rows, then dlc_sequence_topk on int64):
-    the sums are exact and free of summation order, the ranking (sum, then the older frame) is the top-k's own rule, and
-    sequence=1 returns the ids of sequence=None index for index.  The lists do not depend on the batching; a frame with
-    fewer than L - 1 predecessors gets (-inf, -1).  Scores are then float64, key sum * 2^-40 (exact), and `threshold` is
-    compared with that SUM of L scores, not with one score, as the SDAV detector's is: a mean of 0.9 is threshold=0.9 * L.
-    (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)
+        ROW_DTYPE        the rows its kernels form and the sequence search sums: int64 or float64
+        LOWER_IS_BETTER  the order of merit: distances (True) or scores
+        LIMIT            its threshold's name: the keyword of its constructor and the attribute that holds it
+        ALONE_DTYPE      the dtype of scores without sequence=L (float64; the cosine detector's float32)
+        K_MAX            the largest k without sequence=L (None: any -- the SDAV detector's ranking of whole rows)
+        SUPPRESS_ALONE   `suppress` is served without sequence=L too (the byte rows' peak selection, the fused rows)
+        LENGTH_ALONE     the L that stands for sequence=None (the fused detector's 1; None: no sequence search then)
 
-    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the key rows in front of the
-    sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values (no 2^-40 rescale: the keys'
-    scale cancels), `threshold` is compared with that sum, and an empty slot is (-inf, -1).
+    -- creates its store (`_store`, what len() counts) and forms its rows.  The options are the same on all of them; what
+    each does to the rows, launch by launch, is _SequenceRows' to tell:
+
+    sequence = L (None: off, every path as it is without it; 1..64) asks whether the match holds over the last L frames: a
+    pair (frame t, older frame j) is scored by the SUM of the L frame values along a line through (t, j) of the row
+    matrix, the best over the lines of `slopes` (an int32 table [1..16, L]; default sequence.slope_offsets(L)), and the k
+    best sums are the candidates (dlc_sequence_topk, include/dlc.h; Milford & Wyeth, ICRA 2012).  The detector keeps the
+    last L - 1 rows resident in front of each batch's rows, so the lists do not depend on how the frames were batched;
+    frame t's line may only touch values of frames old enough for the frame that produced them (row t - s offers the
+    frames below t - s - exclusion), and a frame with fewer than L - 1 predecessors gets empty slots.  The detector's
+    threshold is then compared with that SUM of L values, not with one value: a mean of 0.9 is threshold = 0.9 * L.
+
+    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the rows in front of the
+    sequence search.  Values are then the float64 sums of L normalised values, the threshold is compared with that sum,
+    and an empty slot is (-inf, -1) -- (+inf, -1) where lower is better.
 
     suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best key-frame, then
-    the best one more than W key-frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.
-    Scores, dtypes and empty slots are as without it.
+    the best one more than W key-frames from it, and so on -- instead of one peak and its neighbours.  Values, dtypes and
+    empty slots are as without it.
 
     steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
-    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
-    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
+    the best chain of L frame values that steps back d_min .. d_max key-frames from frame to frame, in place of the best
+    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Values,
     dtypes, empty slots, contrast and suppress are as with the lines.
 
     chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert returns a third
     tensor, chain int32 [B, k, L] -- for every candidate the key-frame id each of the last L frames was matched to, oldest
-    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs.
+    frame first; -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs.
 
     track = {steps, jump, gate, null_score, history} (needs sequence=L, L = 1 allowed; on every detector that searches
-    through _SequenceRows): a tracking.PlaceTracker runs over the same rows, after `contrast` and with the same limits --
-    here the int64 key rows, so jump, gate and null_score are integers in units of 2^-40.  It is `detector.tracker`:
-    tracker.path() is the smoothed labelling of every frame so far.  query_and_insert returns what it returns without."""
+    through _SequenceRows): a tracking.PlaceTracker runs over the same rows, after `contrast` and with the same limits.  It
+    is `detector.tracker`: tracker.path() is the smoothed labelling of every frame so far.  query_and_insert returns what
+    it returns without."""
+
+    ROW_DTYPE, LOWER_IS_BETTER, LIMIT, ALONE_DTYPE = torch.int64, False, "threshold", torch.float64
+    K_MAX, SUPPRESS_ALONE, LENGTH_ALONE = L.DLC_MAX_K, False, None
+
+    def __init__(self, k, limit, exclusion, sequence, slopes, contrast, suppress, steps, chains, track):
+        if self.K_MAX is None:
+            if k < 1:
+                raise ValueError("k must be >= 1")
+        elif not 1 <= k <= self.K_MAX:
+            raise ValueError("k=%d outside 1..%d" % (k, self.K_MAX))
+        if exclusion < 0:
+            raise ValueError("exclusion must be >= 0")
+        if self.LOWER_IS_BETTER:                             # a distance: a whole number, behind `contrast` any number
+            if limit is not None and limit < 0 and contrast is None:
+                raise ValueError("%s must be >= 0 (or None)" % self.LIMIT)
+            limit = limit if limit is None else (int if contrast is None else float)(limit)
+        if self.SUPPRESS_ALONE and suppress is not None and not 0 <= suppress < 1 << 63:
+            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)      # (else _SequenceRows looks at it)
+        self.k, self.exclusion = int(k), int(exclusion)
+        setattr(self, self.LIMIT, limit)
+        self.sequence = None if sequence is None else int(sequence)
+        self.contrast = None if contrast is None else int(contrast)
+        self.suppress = None if suppress is None else int(suppress)
+        self.chains = bool(chains)
+        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, self.ROW_DTYPE, self.LOWER_IS_BETTER,
+                                     self.suppress, steps, self.chains, track, self.SUPPRESS_ALONE, self.LENGTH_ALONE)
+        self.slopes = self.steps = self.tracker = None
+        if self._seq is not None:
+            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
+
+    def __len__(self):
+        return len(self._store)
+
+    def query_and_insert(self, descriptors):
+        """The next B frames (ids len(self) .. len(self)+B-1) -> (values [B, k], ids [B, k] int64) on the device, best
+        first, an empty slot where fewer than k key-frames are old enough; the frames are key-frames themselves
+        afterwards.  With sequence=L a value is the sum of the L frame values along the best line.  With chains=True a
+        third tensor, chain [B, k, L] int32.  What goes in, the values' dtype and the empty slot are the detector's."""
+        raise NotImplementedError
+
+    def _sequence_step(self, engine, b, first, capacity, fill):
+        """sequence=L: frames first .. first + b - 1, frame first + r against the key-frames below first + r - exclusion.
+        fill(out) forms their rows [b, first + b] with the detector's kernel where the search wants them -- behind the
+        L - 1 rows before them -- and the search's lists are the step's."""
+        fill(self._seq.raw_rows(b, capacity, engine)[:, :first + b])
+        return self._seq.search(engine, b, first + b, first - self.exclusion)
+
+    def _empty(self, b, device):
+        """The result for b frames none of which has a candidate, (fill, -1) in every slot [b, k]: scores are -inf, float64
+        with sequence=L and ALONE_DTYPE without; distances -1, int64, and behind `contrast` +inf, float64.  With chains
+        the chain [b, k, L] too, -1 everywhere."""
+        if not self.LOWER_IS_BETTER:
+            fill, dtype = float("-inf"), self.ALONE_DTYPE if self.sequence is None else torch.float64
+        elif self.contrast is not None:
+            fill, dtype = float("inf"), torch.float64
+        else:
+            fill, dtype = -1, self.ROW_DTYPE
+        out = (torch.full((b, self.k), fill, dtype=dtype, device=device),
+               torch.full((b, self.k), -1, dtype=torch.int64, device=device))
+        return out + (torch.full((b, self.k, self.sequence), -1, dtype=torch.int32, device=device),) if self.chains else out
+
+    def loops(self, values, ids, first_id, chains=None):
+        """[(frame id, matched key-frame id, value)] of the candidates at or above the detector's threshold -- at or below
+        it where lower is better; all of them where it is None -- the value with sequence=L being the sum of the L frame
+        values along the candidate's line.  chains: the third result of query_and_insert with chains=True -- every entry
+        then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
+        return _loops(values, ids, first_id, getattr(self, self.LIMIT), self.LOWER_IS_BETTER, chains)
+
+
+class LoopClosureDetector(_StreamingDetector):
+    """The cosine detector: every new frame against the key-frames more than `exclusion` frames older, the k best by the
+    cosine path's fp64 score (dlc_cosine_topk_older), candidates at or above `threshold`.  Without `sequence` that is the
+    fused top-k, no score rows are formed, and scores are float32.
+
+    The options are _StreamingDetector's.  With sequence=L the rows summed are the scores' ordering KEYS -- int64,
+    round-half-even(score * 2^40), the integer the top-k itself ranks by (dlc_cosine_score_rows into a resident int64
+    buffer that keeps the last L - 1 rows, then dlc_sequence_topk on int64): the sums are exact and free of summation
+    order, the ranking (sum, then the older frame) is the top-k's own rule, and sequence=1 returns the ids of
+    sequence=None index for index.  A frame with fewer than L - 1 predecessors gets (-inf, -1).  Scores are then float64,
+    key sum * 2^-40 (exact), and `threshold` is compared with that SUM of L scores, not with one score, as the SDAV
+    detector's is.  (Descriptors that hold a NaN or an infinity have the key INT64_MIN + 1; sums of several of them wrap.)
+    With contrast=R there is no 2^-40 rescale, the keys' scale cancels, and an empty slot is (-inf, -1).  track= sees the
+    int64 key rows, so jump, gate and null_score are integers in units of 2^-40."""
+
+    ALONE_DTYPE = torch.float32
 
     def __init__(self, dim, k=5, threshold=0.9, exclusion=30, dtype="bf16", center=False, capacity=4096,
                  device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, track=None):
-        if not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
-        self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        # the last L - 1 key rows, then the batch's
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, suppress=self.suppress,
-                                     steps=steps, chains=self.chains, track=track)
-        self.tracker = None
-        if self._seq is not None:
-            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
-        self.db = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
-
-    def __len__(self):
-        return len(self.db)
+        super().__init__(k, float(threshold), exclusion, sequence, slopes, contrast, suppress, steps, chains, track)
+        self.db = self._store = KeyframeDatabase.empty(dim, capacity=capacity, dtype=dtype, center=center, device=device)
 
     @property
     def max_batch(self):
@@ -204,8 +271,7 @@ class LoopClosureDetector:
             raise ValueError("descriptors must be [B, dim]")
         outs = [self._step(x[lo:lo + self.max_batch]) for lo in range(0, x.shape[0], self.max_batch)]
         if not outs:
-            return _empty_result(0, self.k, float("-inf"), torch.float32 if self.sequence is None else torch.float64,
-                                 self.db.engine.device, self.chains, self.sequence)
+            return self._empty(0, self.db.engine.device)
         if len(outs) == 1:                                   # (torch.cat of one tensor is a copy: two launches per batch)
             return outs[0]
         return tuple(torch.cat(t) for t in zip(*outs))
@@ -217,26 +283,18 @@ class LoopClosureDetector:
         g0 -= db.row_offset
         q = db.rows[g0:g0 + b]
         if self._seq is not None:
-            # the frames' key rows against the frames below g0 + r - exclusion, searched behind the L - 1 rows before them
-            db.score_keys(q, limit0=g0 - self.exclusion, limit_step=1,
-                          out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :g0 + b])
-            s, i, *chain = self._seq.search(db.engine, b, g0 + b, g0 - self.exclusion)
+            s, i, *chain = self._sequence_step(db.engine, b, g0, db.capacity, lambda out: db.score_keys(
+                q, limit0=g0 - self.exclusion, limit_step=1, out=out))
             if self.contrast is not None:                    # fp64 sums of normalised values as they are
                 return (s, i, *chain)
             # key sums -> scores: |sum| < 2^53 for L <= 64, so the conversion and the power of two are exact
             return (torch.where(i >= 0, s.to(torch.float64) * 2.0 ** -40, float("-inf")), i, *chain)
         n_search = g0 + b - 1 - self.exclusion             # what the newest frame of the batch may see
         if n_search <= 0:
-            return _nothing_older(b, k, float("-inf"), torch.float32, db.engine.device)
+            return self._empty(b, db.engine.device)
         # one score pass over what the newest frame may see; frame j of the batch keeps to the rows below g0 - exclusion + j
         # (dlc_cosine_topk_older -- the lists of a k + b - 1 match followed by dlc_topk_keep_older / first_k_eligible)
         return db.engine.match_topk(q, db.rows[:n_search], k, older_than=g0 - self.exclusion)
-
-    def loops(self, scores, ids, first_id, chains=None):
-        """[(frame id, matched key-frame id, score)] of the candidates at or above the threshold (with sequence=L: the sum
-        of the L scores along the candidate's line).  chains: the third result of query_and_insert with chains=True --
-        every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
-        return _loops(scores, ids, first_id, self.threshold, chains=chains)
 
 
 class _SequenceRows:
@@ -387,65 +445,30 @@ class _SequenceRows:
         return (s, i, *chain)
 
 
-class SdavLoopClosureDetector:
+class SdavLoopClosureDetector(_StreamingDetector):
     """The same question asked with the REFERENCE's similarity (SimilarityCalculator.similarity_score,
     src/sdav/similarity/SimilarityCalculator.py:12-49) instead of the cosine of flattened descriptors: every new frame's
     [P, H] SDAV descriptors are scored against all resident frames more than `exclusion` frames older through the
     streaming filter (similarity.SimilarityStream: the older frames' panel is resident, nothing is re-quantised), and the
     k best (score descending, ties -> the older frame) at or above `threshold` are the loop candidates.
 
-    sequence = L (None: off, every path as it is without it) asks whether the match holds over the last L frames: a pair
-    (frame t, older frame j) is scored by the sum of the L frame scores along a line through (t, j) of the score matrix,
-    the best of the lines of `slopes` (an int32 table [V, L]; default sequence.slope_offsets(L)), and the k best sums are
-    the candidates (dlc_sequence_topk, include/dlc.h; Milford & Wyeth, ICRA 2012).  The detector keeps the last L - 1 score
-    rows resident in front of each batch's rows, so the lists do not depend on how the frames were batched; frame t's
-    line may only touch scores of frames old enough for the frame that produced them (row t - s offers the frames below
-    t - s - exclusion), and a frame with fewer than L - 1 predecessors gets (-inf, -1).
+    The options are _StreamingDetector's, over float64 score rows (without `sequence` the k best of a frame's row,
+    dlc_topk_rows_f64, for any k; with it the search's own 1..DLC_MAX_K).  An empty slot is (-inf, -1), with contrast=R
+    too.  What is this detector's own is the stream's POISON word: a poisoned stream answers (NaN, -1) in every slot --
+    with contrast, suppress and steps as without them -- and -1 in every cell of a chain; submit() / result() launch the
+    contrast normalisation on the stream of the rows' consumers, and with chains=True result() returns the third tensor
+    as query_and_insert does."""
 
-    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the score rows in front of
-    the sequence search (_SequenceRows).  Scores are the float64 sums of L normalised values, `threshold` is compared
-    with that sum, and an empty slot is (-inf, -1); submit() / result() launch the normalisation on the stream of the
-    rows' consumers, and a poisoned stream answers (NaN, -1) as before.
-
-    suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the best frame, then the
-    best one more than W frames from it, and so on (_SequenceRows) -- instead of one peak and its neighbours.  Scores,
-    dtypes, empty slots and the poisoned answer are as without it.
-
-    steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
-    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
-    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
-    dtypes, empty slots, contrast and suppress are as with the lines.
-
-    chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert and result() return
-    a third tensor, chain int32 [B, k, L] -- for every candidate the frame id each of the last L frames was matched to,
-    oldest frame first (_SequenceRows); -1 where the slot is empty or the stream poisoned.  loops(..., chains=chain)
-    lists them as pairs."""
+    ROW_DTYPE, K_MAX = torch.float64, None
 
     def __init__(self, score_source, patches=30, width=2500, k=5, threshold=float("-inf"), exclusion=30, capacity=1024,
                  device=None, sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False, track=None,
                  **stream_args):
         from .similarity import SimilarityStream
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
-        self.k, self.threshold, self.exclusion = int(k), float(threshold), int(exclusion)
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        # the last L - 1 score rows, then the batch's
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, k, torch.float64, suppress=self.suppress,
-                                     steps=steps, chains=self.chains, track=track)
-        self.tracker = None
-        if self._seq is not None:
-            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
+        super().__init__(k, float(threshold), exclusion, sequence, slopes, contrast, suppress, steps, chains, track)
         self._slots, self._pending, self._tickets = [{}, {}], None, 0      # submit() / result(): two batches in flight
-        self.stream = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity, device=device,
-                                       **stream_args)
-
-    def __len__(self):
-        return len(self.stream)
+        self.stream = self._store = SimilarityStream(score_source, patches=patches, width=width, capacity=capacity,
+                                                     device=device, **stream_args)
 
     def query_and_insert(self, frames):
         """frames [B, P, H] (ids len(self) .. + B - 1) -> (scores [B, k] float64, ids [B, k] int64) on the device, best first,
@@ -488,7 +511,7 @@ class SdavLoopClosureDetector:
 
     def _nothing_older(self, b):
         """(-inf, -1) in every slot of b frames' lists; (NaN, -1) once the stream is poisoned."""
-        s, *rest = _empty_result(b, self.k, float("-inf"), torch.float64, self.stream.engine.device, self.chains, self.sequence)
+        s, *rest = self._empty(b, self.stream.engine.device)
         return (torch.where(self.poisoned != 0, float("nan"), s), *rest)
 
     # ---- two batches in flight ------------------------------------------------------------------------------------------
@@ -582,147 +605,32 @@ class SdavLoopClosureDetector:
         """[(frame id, older frame id, score)] at or above the threshold; raises when the stream has been poisoned (a value
         outside its fixed range: SimilarityStream.stats[1]).  chains: the third result of query_and_insert / result with
         chains=True -- every entry then ends in the candidate's L (frame id, older frame id) pairs, oldest first."""
-        found = _loops(scores, ids, first_id, self.threshold, chains=chains)
+        found = super().loops(scores, ids, first_id, chains)
         self._check_poison()
         return found
 
 
-class CnnVtlLoopClosureDetector:
-    """The streaming question asked with the REFERENCE's cnn_vtl measure (DistanceCalculator.calculate_distance,
-    src/cnn_vtl/similarity/DistanceCalculator.py:4-12) instead of the cosine of the descriptors: every new frame's int8
-    descriptor is compared with all resident frames more than `exclusion` frames older, and the k nearest (distance
-    ascending, ties -> the older frame) at or below `max_distance` (all of them when None) are the loop candidates.
-    A batch of B frames is one top-k launch: frame first + r sees the frames below first + r - exclusion
-    (dlc_cnnvtl_distance_topk with limit_step = 1), so the lists do not depend on how the frames are batched.
+class _ByteRowsLoopClosureDetector(_StreamingDetector):
+    """What the streaming detectors over byte descriptors and int64 lower-is-better rows share (CnnVtlLoopClosureDetector:
+    cnn_vtl distance rows; SeqSlamLoopClosureDetector: SAD rows; LdbLoopClosureDetector: Hamming rows): the checks of the
+    store's shape, query_and_insert and the path without `sequence` -- the batch's rows into a resident buffer, then the
+    peak selection over them.  A subclass names its threshold (LIMIT), creates its database and forms the rows of a batch
+    (_rows_into)."""
 
-    sequence = L (None: off, every path as it is without it -- the fused top-k, no distance rows are formed) asks
-    whether the match holds over the last L frames, as SdavLoopClosureDetector(sequence=L) does for the similarity: a pair
-    (frame t, older frame j) is scored by the SUM of the L frame distances along a line through (t, j) of the distance
-    matrix, the smallest over the lines of `slopes` (an int32 table [1..16, L]; default sequence.slope_offsets(L)), and the
-    k smallest sums are the candidates (dlc_cnnvtl_distance_rows into a resident int64 buffer that keeps the last L - 1
-    rows, then dlc_sequence_topk with lower_is_better).  The lists do not depend on the batching; a frame with fewer than
-    L - 1 predecessors gets (-1, -1).  max_distance is then compared with the sequence sum -- L distances, not one -- as the
-    SDAV detector's threshold is with its sum of scores.
-
-    contrast = R (None: off; needs sequence=L, R in 1..32): local contrast normalisation of the distance rows in front
-    of the sequence search (_SequenceRows).  Distances stay lower-is-better (the standard deviation is positive); dist is
-    then the float64 sum of L normalised values, max_distance is compared with that sum (it may be negative), and an
-    empty slot is (+inf, -1).
-
-    suppress = W (None: off; needs sequence=L, L = 1 allowed): the k candidates are k PLACES -- the nearest key-frame,
-    then the nearest one more than W key-frames from it, and so on (_SequenceRows) -- instead of one minimum and its
-    neighbours; with k = 2 and W = R_window / 2 the two distances are OpenSeqSLAM's min_value and min_value_2nd
-    (sequence.uniqueness_ratio).  Distances, dtypes and empty slots are as without it.
-
-    steps = (d_min, d_max) (None: off; needs sequence=L, excludes slopes; 0 <= d_min <= d_max <= 8): the ELASTIC search --
-    the best chain of L frame scores that steps back d_min .. d_max key-frames from frame to frame, in place of the best
-    straight line: a revisit whose speed changes inside the L frames (dlc_sequence_elastic_topk, include/dlc.h).  Scores,
-    dtypes, empty slots, contrast and suppress are as with the lines.
-
-    chains = True (needs sequence=L; with or without contrast, suppress and steps): query_and_insert returns a third
-    tensor, chain int32 [B, k, L] -- for every candidate the key-frame id each of the last L frames was matched to, oldest
-    frame first (_SequenceRows); -1 where the slot is empty.  loops(..., chains=chain) lists them as pairs."""
-
-    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
-                 contrast=None, suppress=None, steps=None, chains=False, track=None):
-        if not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
-        if max_distance is not None and max_distance < 0 and contrast is None:
-            raise ValueError("max_distance must be >= 0 (or None)")
-        if dim < 1 or capacity < 1:
-            raise ValueError("dim and capacity must be positive")
-        self.k, self.exclusion = int(k), int(exclusion)
-        self.max_distance = max_distance if max_distance is None else (int if contrast is None else float)(max_distance)
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        # the last L - 1 distance rows, then the batch's
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=self.suppress, steps=steps, chains=self.chains, track=track)
-        self.tracker = None
-        if self._seq is not None:
-            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
-        from .distance import CnnVtlKeyframeDatabase
-        self.db = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
-
-    def __len__(self):
-        return len(self.db)
-
-    def query_and_insert(self, descriptors):
-        """The next B frames' int8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (dist [B, k] int64,
-        ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
-        key-frames afterwards.  With sequence=L dist is the sum of the L distances along the best line.  With chains=True
-        a third tensor, chain [B, k, L] int32."""
-        db = self.db
-        x = db.engine.to_device(descriptors)
-        if x.dim() == 1:
-            x = x.unsqueeze(0)
-        first, _ = db.append(x)
-        b = x.shape[0]
-        if self.sequence is None:
-            return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
-                                                  limit0=first - self.exclusion, limit_step=1)
-        if b == 0:
-            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
-            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
-        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
-        db.distances(db.rows[first:first + b], limit0=first - self.exclusion, limit_step=1,
-                     out=self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
-        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
-
-    def loops(self, dist, ids, first_id, chains=None):
-        """[(frame id, matched key-frame id, distance)] of the candidates at or below max_distance (with sequence=L: the
-        sum of the L distances along the candidate's line).  chains: the third result of query_and_insert with
-        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
-        return _loops(dist, ids, first_id, self.max_distance, lower_is_better=True, chains=chains)
-
-
-class _ByteRowsLoopClosureDetector:
-    """What the streaming detectors over byte descriptors and int64 lower-is-better rows share (SeqSlamLoopClosureDetector:
-    SAD rows; LdbLoopClosureDetector: Hamming rows): the checks, the resident row buffers and query_and_insert.  A
-    subclass names its threshold (LIMIT, the keyword of its constructor and the attribute that holds it), creates its
-    database and forms the rows of a batch (_rows_into)."""
-
-    LIMIT = None
+    LOWER_IS_BETTER, LIMIT, SUPPRESS_ALONE = True, None, True
+    _rows = None                                             # without sequence: the batch's rows [b, capacity]
 
     def __init__(self, dim, k, limit, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains, track):
-        if not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
-        if limit is not None and limit < 0 and contrast is None:
-            raise ValueError("%s must be >= 0 (or None)" % self.LIMIT)
+        super().__init__(k, limit, exclusion, sequence, slopes, contrast, suppress, steps, chains, track)
         if dim < 1 or capacity < 1:
             raise ValueError("dim and capacity must be positive")
-        if suppress is not None and not 0 <= suppress < 1 << 63:
-            raise ValueError("suppress=%d outside 0..2^63-1" % suppress)
-        self.k, self.exclusion = int(k), int(exclusion)
-        setattr(self, self.LIMIT, limit if limit is None else (int if contrast is None else float)(limit))
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        # (without sequence=L `suppress` is served here, by the peak selection over the frame rows themselves)
-        self._seq = _sequence_search(self.sequence, slopes, self.contrast, self.k, torch.int64, lower_is_better=True,
-                                     suppress=None if self.sequence is None else self.suppress, steps=steps,
-                                     chains=self.chains, track=track)
-        self.tracker = None
-        if self._seq is not None:
-            self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, self._seq.tracker
-        self._rows = None                                    # without sequence: the batch's rows [b, capacity]
-
-    def __len__(self):
-        return len(self.db)
 
     def _rows_into(self, q, limit0, out):
         """The rows of the stored queries q against the database, query r in its first limit0 + r cells, into out."""
         raise NotImplementedError
 
     def query_and_insert(self, descriptors):
-        """The next B frames' uint8 descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (value [B, k] int64,
+        """The next B frames' byte descriptors [B, dim] (ids len(self) .. len(self)+B-1) -> (value [B, k] int64,
         ids [B, k] int64) on the device, nearest first, (-1, -1) where fewer than k frames are old enough; the frames are
         key-frames afterwards.  With sequence=L value is the sum of the L frame values along the best line.  With
         chains=True a third tensor, chain [B, k, L] int32."""
@@ -732,27 +640,64 @@ class _ByteRowsLoopClosureDetector:
             x = x.unsqueeze(0)
         first, _ = db.append(x)
         b = x.shape[0]
-        if b == 0:
-            fill, dtype = (float("inf"), torch.float64) if self.contrast is not None else (-1, torch.int64)
-            return _empty_result(0, self.k, fill, dtype, db.engine.device, self.chains, self.sequence)
-        q = db.rows[first:first + b]
         if self._seq is None:
-            if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
-                self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
-                                         dtype=torch.int64, device=db.engine.device)
-            rows = self._rows[:b, :first + b]
-            self._rows_into(q, first - self.exclusion, rows)
-            return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
-                                            lower_is_better=True)
-        # frame first + r against the frames below first + r - exclusion, searched behind the L - 1 rows before them
-        self._rows_into(q, first - self.exclusion, self._seq.raw_rows(b, db.capacity, db.engine)[:, :first + b])
-        return self._seq.search(db.engine, b, first + b, first - self.exclusion)
+            return self._alone(first, b)
+        if b == 0:
+            return self._empty(0, db.engine.device)
+        q = db.rows[first:first + b]
+        return self._sequence_step(db.engine, b, first, db.capacity, lambda out: self._rows_into(q, first - self.exclusion, out))
 
-    def loops(self, value, ids, first_id, chains=None):
-        """[(frame id, matched key-frame id, value)] of the candidates at or below the threshold (with sequence=L: the
-        sum of the L frame values along the candidate's line).  chains: the third result of query_and_insert with
-        chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs, oldest first."""
-        return _loops(value, ids, first_id, getattr(self, self.LIMIT), lower_is_better=True, chains=chains)
+    def _alone(self, first, b):
+        """Without sequence=L: the rows of frames first .. first + b - 1, then the k picks of every row, more than
+        `suppress` (None: 0) key-frames apart."""
+        db = self.db
+        if b == 0:
+            return self._empty(0, db.engine.device)
+        if self._rows is None or self._rows.shape[0] < b or self._rows.shape[1] < db.capacity:
+            self._rows = torch.empty((b if self._rows is None else max(b, self._rows.shape[0]), db.capacity),
+                                     dtype=torch.int64, device=db.engine.device)
+        rows = self._rows[:b, :first + b]
+        self._rows_into(db.rows[first:first + b], first - self.exclusion, rows)
+        return db.engine.peak_topk_rows(rows, self.k, self.suppress or 0, limit0=first - self.exclusion, limit_step=1,
+                                        lower_is_better=True)
+
+
+class CnnVtlLoopClosureDetector(_ByteRowsLoopClosureDetector):
+    """The streaming question asked with the REFERENCE's cnn_vtl measure (DistanceCalculator.calculate_distance,
+    src/cnn_vtl/similarity/DistanceCalculator.py:4-12) instead of the cosine of the descriptors: every new frame's int8
+    descriptor is compared with all resident frames more than `exclusion` frames older, and the k nearest (distance
+    ascending, ties -> the older frame) at or below `max_distance` (all of them when None) are the loop candidates.
+    A batch of B frames is one top-k launch: frame first + r sees the frames below first + r - exclusion
+    (dlc_cnnvtl_distance_topk with limit_step = 1), so the lists do not depend on how the frames are batched.  That is the
+    one path of its own -- the fused top-k, no distance rows are formed, and no `suppress` without `sequence`.
+
+    The options are _StreamingDetector's, over int64 distance rows, the smallest sums the candidates
+    (dlc_cnnvtl_distance_rows into a resident int64 buffer that keeps the last L - 1 rows, then dlc_sequence_topk with
+    lower_is_better).  A frame with fewer than L - 1 predecessors gets (-1, -1).  max_distance is then compared with the
+    sequence sum -- L distances, not one -- as the SDAV detector's threshold is with its sum of scores.  With contrast=R
+    distances stay lower-is-better (the standard deviation is positive); dist is then float64, max_distance may be
+    negative, and an empty slot is (+inf, -1).  With suppress=W, k = 2 and W = R_window / 2 the two distances are
+    OpenSeqSLAM's min_value and min_value_2nd (sequence.uniqueness_ratio)."""
+
+    LIMIT, SUPPRESS_ALONE = "max_distance", False
+
+    def __init__(self, dim, k=5, max_distance=None, exclusion=30, capacity=4096, device=None, sequence=None, slopes=None,
+                 contrast=None, suppress=None, steps=None, chains=False, track=None):
+        super().__init__(dim, k, max_distance, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains,
+                         track)
+        from .distance import CnnVtlKeyframeDatabase
+        self.db = self._store = CnnVtlKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+
+    def _rows_into(self, q, limit0, out):
+        self.db.distances(q, limit0=limit0, limit_step=1, out=out)
+
+    def _alone(self, first, b):
+        """Without sequence=L: one fused top-k launch, no rows are formed (and none for b = 0 either)."""
+        db = self.db
+        return db.engine.cnnvtl_distance_topk(db.rows[first:first + b], db.rows, self.k, d=db.dim,
+                                              limit0=first - self.exclusion, limit_step=1)
+
+
 
 
 class SeqSlamLoopClosureDetector(_ByteRowsLoopClosureDetector):
@@ -796,7 +741,7 @@ class SeqSlamLoopClosureDetector(_ByteRowsLoopClosureDetector):
         self.shift = None if shift is None else int(shift)
         self.width = None if width is None else int(width)
         from .seqslam import SadKeyframeDatabase
-        self.db = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+        self.db = self._store = SadKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
     def _rows_into(self, q, limit0, out):
         self.db.differences(q, limit0=limit0, limit_step=1, out=out, shift=self.shift, width=self.width)
@@ -820,7 +765,7 @@ class LdbLoopClosureDetector(_ByteRowsLoopClosureDetector):
         super().__init__(dim, k, max_distance, exclusion, capacity, sequence, slopes, contrast, suppress, steps, chains,
                          track)
         from .ldb import HammingKeyframeDatabase
-        self.db = HammingKeyframeDatabase.empty(dim, capacity=capacity, device=device)
+        self.db = self._store = HammingKeyframeDatabase.empty(dim, capacity=capacity, device=device)
 
     def _rows_into(self, q, limit0, out):
         self.db.distances(q, limit0=limit0, limit_step=1, out=out)
@@ -859,7 +804,7 @@ FUSE_MEMBERS = ("cosine", "distance", "sad")
 FUSE_NORMS = ("zscore", "minmax", "none")
 
 
-class FusedLoopClosureDetector:
+class FusedLoopClosureDetector(_StreamingDetector):
     """The streaming question asked with SEVERAL descriptors at once: every member keeps its own key-frame store and
     forms its own raw rows per batch -- each new frame against the key-frames more than `exclusion` frames older -- and
     ONE dlc_fuse_rows (include/dlc.h) turns them into one row: each member's row normalised within itself (`norm`:
@@ -880,6 +825,8 @@ class FusedLoopClosureDetector:
     depend on how the frames are batched.  Results are (scores float64 [B, k], ids int64 [B, k][, chain]), (-inf, -1)
     in empty slots; `threshold` (None: all k) is compared with the fused score -- with sequence=L the sum of L of them."""
 
+    ROW_DTYPE, SUPPRESS_ALONE, LENGTH_ALONE = torch.float64, True, 1
+
     def __init__(self, members, weights=None, norm="zscore", k=5, threshold=None, exclusion=30, capacity=4096, device=None,
                  sequence=None, slopes=None, contrast=None, suppress=None, steps=None, chains=False):
         from .distance import CnnVtlKeyframeDatabase
@@ -887,10 +834,6 @@ class FusedLoopClosureDetector:
         members = [tuple(m) if isinstance(m, (tuple, list)) else (m,) for m in members]
         if not 1 <= len(members) <= L.DLC_MAX_FUSE:
             raise ValueError("%d members outside 1..%d" % (len(members), L.DLC_MAX_FUSE))
-        if not 1 <= k <= L.DLC_MAX_K:
-            raise ValueError("k=%d outside 1..%d" % (k, L.DLC_MAX_K))
-        if exclusion < 0:
-            raise ValueError("exclusion must be >= 0")
         if capacity < 1:
             raise ValueError("capacity must be positive")
         if norm not in FUSE_NORMS:
@@ -898,20 +841,9 @@ class FusedLoopClosureDetector:
         w = np.ones(len(members)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
         if w.shape[0] != len(members) or not np.isfinite(w).all():
             raise ValueError("weights must be %d finite numbers" % len(members))
-        if sequence is None:
-            for name, value in (("chains", chains or None), ("slopes", slopes), ("steps", steps), ("contrast", contrast)):
-                if value is not None:
-                    raise ValueError("%s needs sequence=L" % name)
+        super().__init__(k, None if threshold is None else float(threshold), exclusion, sequence, slopes, contrast, suppress,
+                         steps, chains, None)                # (track: start_tracking)
         self.weights, self.norm = [float(v) for v in w], norm
-        self.k, self.exclusion = int(k), int(exclusion)
-        self.threshold = None if threshold is None else float(threshold)
-        self.sequence = None if sequence is None else int(sequence)
-        self.contrast = None if contrast is None else int(contrast)
-        self.suppress = None if suppress is None else int(suppress)
-        self.chains = bool(chains)
-        self._seq = _SequenceRows(1 if self.sequence is None else self.sequence, slopes, self.k, torch.float64, self.contrast,
-                                  False, self.suppress, steps, self.chains)
-        self.slopes, self.steps, self.tracker = self._seq.slopes, self._seq.steps, None
         self.kinds, self.dbs, self._options = [], [], []
         for spec in members:
             if not 2 <= len(spec) <= 3 or spec[0] not in FUSE_MEMBERS:
@@ -936,11 +868,8 @@ class FusedLoopClosureDetector:
             self.kinds.append(kind)
             self.dbs.append(db)
             self._options.append(opt)
-        self.engine = self.dbs[0].engine
+        self._store, self.engine = self.dbs[0], self.dbs[0].engine
         self.lower_is_better = [kind != "cosine" for kind in self.kinds]
-
-    def __len__(self):
-        return len(self.dbs[0])
 
     def start_tracking(self, track):
         """What track= is on the other detectors (LoopClosureDetector), asked for before the first frame: a
@@ -978,7 +907,7 @@ class FusedLoopClosureDetector:
         if any(x.dim() != 2 or x.shape[0] != b for x in xs):
             raise ValueError("query_and_insert: every member's descriptors must be [B, dim] with one B")
         if b == 0:
-            return _empty_result(0, self.k, float("-inf"), torch.float64, eng.device, self.chains, self.sequence)
+            return self._empty(0, eng.device)
         first = len(self)
         for db, x in zip(self.dbs, xs):
             if db.append(x)[0] != first:
@@ -990,15 +919,9 @@ class FusedLoopClosureDetector:
             ws = eng.workspace("fuse_member_%d" % i, b * capacity * 8)[:b * capacity * 8]
             raws.append(ws.view(dtype).view(b, capacity)[:, :n])
             self._member_rows(i, first, b, raws[-1])
-        eng.fuse_rows(raws, weights=self.weights, lower_is_better=self.lower_is_better, norm=self.norm,
-                      limit0=first - self.exclusion, limit_step=1, out=self._seq.raw_rows(b, capacity, eng)[:, :n])
-        return self._seq.search(eng, b, n, first - self.exclusion)
-
-    def loops(self, scores, ids, first_id, chains=None):
-        """[(frame id, matched key-frame id, fused score)] of the candidates at or above the threshold (None: all of
-        them; with sequence=L the score is the sum along the candidate's line).  chains: the third result of
-        query_and_insert with chains=True -- every entry then ends in the candidate's L (frame id, key-frame id) pairs."""
-        return _loops(scores, ids, first_id, self.threshold, chains=chains)
+        return self._sequence_step(eng, b, first, capacity, lambda out: eng.fuse_rows(
+            raws, weights=self.weights, lower_is_better=self.lower_is_better, norm=self.norm, limit0=first - self.exclusion,
+            limit_step=1, out=out))
 
 
 SDAV_CLI_PATCHES = 30       # patches of a frame of the CLI's SDAV: the concatenation is 30 * 2500 wide
@@ -1074,6 +997,25 @@ def describe_cnn_vtl(files, network=None, as_int8=False):
 def chain_line(pairs):
     """The CLI's line under a candidate: `chain`, then the L frame:key-frame pairs, oldest frame first, tab-separated."""
     return "chain\t" + "\t".join("%d:%d" % p for p in pairs)
+
+
+def _model_widths(ap, args, option):
+    """--codebook, --pca or --hash (`option`, given): (the width its .npz was fitted to, the width of what reaches it in
+    the stream) -- a patch descriptor in front of --codebook; the frame descriptor in front of --pca, the concatenation
+    or behind --pool vlad the codebook's K words; in front of --hash that, or --pca's M.  A file that cannot be read so is
+    the parser's error `--option: ...`."""
+    def read(name, key, axis=None):
+        with np.load(getattr(args, name), allow_pickle=False) as z:
+            return int(z[key] if axis is None else z[key].shape[axis])
+    try:
+        if option == "codebook":
+            return read("codebook", "centroids", 1), SDAV_CLI_WIDTH
+        frame = (read("codebook", "centroids", 0) if args.pool == "vlad" else SDAV_CLI_PATCHES) * SDAV_CLI_WIDTH
+        if option == "pca":
+            return read("pca", "basis", 0), frame
+        return read("hash", "width"), frame if args.pca is None else read("pca", "basis", 1)
+    except (OSError, ValueError, KeyError, IndexError) as err:
+        ap.error("--%s: %s" % (option, err))
 
 
 def main(argv=None):
@@ -1227,46 +1169,23 @@ def main(argv=None):
     elif args.codebook is not None:
         ap.error("--codebook needs --pool vlad")
     if args.codebook is not None:
-        try:
-            with np.load(args.codebook, allow_pickle=False) as z:
-                args.codebook_width = int(z["centroids"].shape[1])
-        except (OSError, ValueError, KeyError, IndexError) as err:
-            ap.error("--codebook: %s" % err)
-        if args.codebook_width != SDAV_CLI_WIDTH:
-            ap.error("--codebook: its words are %d wide, the encoder's descriptors %d" % (args.codebook_width, SDAV_CLI_WIDTH))
+        have, want = _model_widths(ap, args, "codebook")
+        if have != want:
+            ap.error("--codebook: its words are %d wide, the encoder's descriptors %d" % (have, want))
     if args.pca is not None:
         if args.fuse is not None or args.network != "sdav" or args.metric != "cosine":
             ap.error("--pca needs --network sdav --metric cosine")
-        try:
-            with np.load(args.pca, allow_pickle=False) as z:
-                pca_width = int(z["basis"].shape[0])
-            want = SDAV_CLI_PATCHES * SDAV_CLI_WIDTH
-            if args.pool == "vlad":
-                with np.load(args.codebook, allow_pickle=False) as z:
-                    want = int(z["centroids"].shape[0]) * SDAV_CLI_WIDTH
-        except (OSError, ValueError, KeyError, IndexError) as err:
-            ap.error("--pca: %s" % err)
-        if pca_width != want:
-            ap.error("--pca: its rows are %d wide, the frame descriptor %d" % (pca_width, want))
+        have, want = _model_widths(ap, args, "pca")
+        if have != want:
+            ap.error("--pca: its rows are %d wide, the frame descriptor %d" % (have, want))
     if args.hash is not None:
         if args.fuse is not None or args.network != "sdav" or args.metric != "cosine":
             ap.error("--hash needs --network sdav --metric cosine")
         if args.verify is not None:
             ap.error("--hash excludes --verify")
-        try:
-            with np.load(args.hash, allow_pickle=False) as z:
-                hash_width = int(z["width"])
-            want = SDAV_CLI_PATCHES * SDAV_CLI_WIDTH
-            if args.pool == "vlad":
-                with np.load(args.codebook, allow_pickle=False) as z:
-                    want = int(z["centroids"].shape[0]) * SDAV_CLI_WIDTH
-            if args.pca is not None:
-                with np.load(args.pca, allow_pickle=False) as z:
-                    want = int(z["basis"].shape[1])
-        except (OSError, ValueError, KeyError, IndexError) as err:
-            ap.error("--hash: %s" % err)
-        if hash_width != want:
-            ap.error("--hash: its rows are %d wide, the frame descriptor %d" % (hash_width, want))
+        have, want = _model_widths(ap, args, "hash")
+        if have != want:
+            ap.error("--hash: its rows are %d wide, the frame descriptor %d" % (have, want))
     hamming = args.metric == "hamming" or args.hash is not None      # the rows behind the descriptor are Hamming rows
     thumbnails = args.network == "seqslam" or (args.fuse is not None and "sad" in args.fuse)
     if args.metric == "distance" and args.network != "cnn_vtl":
@@ -1379,9 +1298,9 @@ def main(argv=None):
         return _stream(args, files)
 
 
-def _fused_stream(args, files):
-    """--fuse: (describe, make detector): one descriptor tensor per member and batch -- the thumbnails for sad, ONE CnnVtl
-    forward for distance and cosine -- and the FusedLoopClosureDetector over the first batch's widths."""
+def _fused_describe(args, files):
+    """--fuse: one descriptor tensor per member and batch -- the thumbnails for sad, ONE CnnVtl forward for distance and
+    cosine."""
     from .input import read_ppm
     thumbs = cnn = None
     if "sad" in args.fuse:
@@ -1398,28 +1317,48 @@ def _fused_stream(args, files):
         deep = describe_cnn_vtl(fs, cnn, as_int8=True) if cnn is not None else None
         sad = pipeline.seqslam_descriptors_from_frames(np.stack([read_ppm(f) for f in fs]), thumbs) if thumbs is not None else None
         return [sad if m == "sad" else (deep if m == "distance" else deep.to(torch.float32)) for m in args.fuse]
+    return describe
 
-    def detector(desc):
-        members = []
-        for m, d in zip(args.fuse, desc):
-            if m == "sad":
-                members.append((m, d.shape[1], {} if args.shift is None else {"shift": args.shift, "width": args.size[1]}))
-            elif m == "cosine":
-                members.append((m, d.shape[1], {"dtype": args.dtype, "center": True}))
-            else:
-                members.append((m, d.shape[1]))
-        return FusedLoopClosureDetector(members, weights=args.fuse_weights, norm=args.fuse_norm, k=args.k,
-                                        threshold=args.threshold, exclusion=args.exclusion, capacity=max(4096, len(files)),
-                                        sequence=args.sequence, contrast=args.contrast, suppress=args.suppress,
-                                        steps=args.steps, chains=args.chains)
-    return describe, detector
+
+def _detector(args, desc, n_files):
+    """The stream's detector, made when the first batch's descriptors `desc` are there: their widths are the store's."""
+    shared = dict(k=args.k, exclusion=args.exclusion, capacity=max(4096, n_files))
+    search = dict(sequence=args.sequence, contrast=args.contrast, suppress=args.suppress, steps=args.steps, chains=args.chains,
+                  track=args.track)
+    if args.fuse is not None:
+        options = {"sad": {} if args.shift is None else {"shift": args.shift, "width": args.size[1]},
+                   "cosine": {"dtype": args.dtype, "center": True}, "distance": {}}
+        track = search.pop("track")                              # (asked for before the first frame, not at construction)
+        det = FusedLoopClosureDetector([(m, d.shape[1], options[m]) for m, d in zip(args.fuse, desc)], weights=args.fuse_weights,
+                                       norm=args.fuse_norm, threshold=args.threshold, **shared, **search)
+        if track is not None:
+            det.start_tracking(track)
+        return det
+    if args.metric == "similarity":
+        # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
+        # has only seen its first batch when it must fix it
+        shared["capacity"] = max(1024, n_files)
+        return SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], threshold=args.threshold, **shared,
+                                       **search)
+    if args.metric == "distance":
+        return CnnVtlLoopClosureDetector(desc.shape[1], max_distance=args.max_distance, **shared)
+    if args.metric == "sad":
+        return SeqSlamLoopClosureDetector(desc.shape[1], max_difference=args.max_difference, shift=args.shift,
+                                          width=None if args.shift is None else args.size[1], **shared, **search)
+    if getattr(args, "hash", None) is not None:              # (callers that build the namespace themselves may not know --hash)
+        from .lsh import Lsh
+        return HashedLoopClosureDetector(Lsh.load(args.hash), max_distance=args.max_distance, **shared, **search)
+    if args.metric == "hamming":
+        return LdbLoopClosureDetector(desc.shape[1], max_distance=args.max_distance, **shared, **search)
+    return LoopClosureDetector(desc.shape[1], threshold=args.threshold, dtype=args.dtype, center=True, **shared)
 
 
 def _stream(args, files):
-    fused = verifier = hashed = None
+    fused = args.fuse is not None
+    verifier = None
     local = []                                                   # --verify: the batch's (patch descriptors, key-points)
-    if args.fuse is not None:
-        describe, fused = _fused_stream(args, files)
+    if fused:
+        describe = _fused_describe(args, files)
     elif args.network == "sdav":
         from .sdav import SDAV
         net = SDAV(dtype=args.encoder_dtype)
@@ -1434,9 +1373,6 @@ def _stream(args, files):
             from .pca import Pca
             compact = Pca.load(args.pca)
             describe = lambda fs: describe_sdav_compact(fs, net, pool=pool, pca=compact)
-        if getattr(args, "hash", None) is not None:        # (nor --hash)
-            from .lsh import Lsh
-            hashed = Lsh.load(args.hash)
         if getattr(args, "verify", None) is not None:
             from .verification import GeometricVerifier, keep_accepted
             patches = net.input_shape[0]
@@ -1475,47 +1411,18 @@ def _stream(args, files):
     if args.positions is not None:
         from .evaluate import LoopClosureEvaluator, pr_line
         judge = LoopClosureEvaluator(args.positions, args.radius, args.exclusion,
-                                     lower_is_better=fused is None and (args.metric in ("distance", "sad", "hamming") or
-                                                                        hashed is not None))
+                                     lower_is_better=not fused and (args.metric in ("distance", "sad", "hamming") or
+                                                                    getattr(args, "hash", None) is not None))
     det = None
     lat = []                                                     # wall-clock per step: file read -> descriptors -> match -> candidates on the host
     for lo in range(0, len(files), args.batch):
         chunk = files[lo:lo + args.batch]
         t0 = time.perf_counter()
         desc = describe(chunk)
-        if fused is None and args.metric == "similarity":
+        if not fused and args.metric == "similarity":
             desc = desc.view(len(chunk), net.input_shape[0], -1)         # [B, P, H]: the frames' patch descriptors
-        if det is None and fused is not None:
-            det = fused(desc)
-            if args.track is not None:
-                det.start_tracking(args.track)
-        elif det is None and args.metric == "similarity":
-            # the reference takes the distinctive score from the whole dataset (SimilarityCalculator.py:20-27); a stream
-            # has only seen its first batch when it must fix it
-            det = SdavLoopClosureDetector(desc, patches=desc.shape[1], width=desc.shape[2], k=args.k, threshold=args.threshold,
-                                          exclusion=args.exclusion, capacity=max(1024, len(files)), sequence=args.sequence,
-                                          contrast=args.contrast, suppress=args.suppress, steps=args.steps,
-                                          chains=args.chains, track=args.track)
-        elif det is None and args.metric == "distance":
-            det = CnnVtlLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance,
-                                            exclusion=args.exclusion, capacity=max(4096, len(files)))
-        elif det is None and args.metric == "sad":
-            det = SeqSlamLoopClosureDetector(desc.shape[1], k=args.k, max_difference=args.max_difference,
-                                             exclusion=args.exclusion, capacity=max(4096, len(files)), sequence=args.sequence,
-                                             contrast=args.contrast, suppress=args.suppress, steps=args.steps,
-                                             chains=args.chains, shift=args.shift,
-                                             width=None if args.shift is None else args.size[1], track=args.track)
-        elif det is None and hashed is not None:
-            det = HashedLoopClosureDetector(hashed, k=args.k, max_distance=args.max_distance, exclusion=args.exclusion,
-                                            capacity=max(4096, len(files)), sequence=args.sequence, contrast=args.contrast,
-                                            suppress=args.suppress, steps=args.steps, chains=args.chains, track=args.track)
-        elif det is None and args.metric == "hamming":
-            det = LdbLoopClosureDetector(desc.shape[1], k=args.k, max_distance=args.max_distance, exclusion=args.exclusion,
-                                         capacity=max(4096, len(files)), sequence=args.sequence, contrast=args.contrast,
-                                         suppress=args.suppress, steps=args.steps, chains=args.chains, track=args.track)
-        elif det is None:
-            det = LoopClosureDetector(desc.shape[1], k=args.k, threshold=args.threshold, exclusion=args.exclusion,
-                                      dtype=args.dtype, center=True, capacity=max(4096, len(files)))
+        if det is None:
+            det = _detector(args, desc, len(files))
         s, i, *chain = det.query_and_insert(desc)
         verdict = None
         if verifier is not None:

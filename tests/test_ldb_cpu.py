@@ -165,6 +165,16 @@ def test_detectors_share_one_body():
     assert issubclass(dlc.LdbLoopClosureDetector, base) and issubclass(dlc.SeqSlamLoopClosureDetector, base)
     for cls in (dlc.LdbLoopClosureDetector, dlc.SeqSlamLoopClosureDetector):
         assert "query_and_insert" not in vars(cls) and "loops" not in vars(cls)
+    # and all six stand on one base, which alone has loops and len(): the SDAV detector's loops adds its poison check
+    root = loop_closure._StreamingDetector
+    assert issubclass(base, root) and "loops" in vars(root) and "__len__" in vars(root)
+    for cls in (dlc.LoopClosureDetector, dlc.SdavLoopClosureDetector, dlc.CnnVtlLoopClosureDetector,
+                dlc.SeqSlamLoopClosureDetector, dlc.LdbLoopClosureDetector, dlc.FusedLoopClosureDetector):
+        assert issubclass(cls, root)
+        for c in cls.__mro__[:cls.__mro__.index(root)]:
+            assert "__len__" not in vars(c)
+            assert "loops" not in vars(c) or c is dlc.SdavLoopClosureDetector
+    assert issubclass(dlc.CnnVtlLoopClosureDetector, base) and "query_and_insert" not in vars(dlc.CnnVtlLoopClosureDetector)
 
 
 # ---- 4. the CLI's argument rules ------------------------------------------------------------------------------------------
