@@ -143,8 +143,7 @@ extern "C" int dlc_im2col_nhwc_f64(dlc_ctx* ctx, const double* x, int64_t n, int
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "im2col: bad argument");
     const int64_t m = n * oh * ow;
     if (m > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "im2col: too many output pixels for one launch");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)m), dim3(256), 0, (hipStream_t)stream, x, (long long)n, h, w, c, kh,
                        kw, stride, pad_top, pad_left, oh, ow, cols);
     DLC_LAUNCH_CHECK(ctx, "im2col_kernel");
@@ -156,8 +155,7 @@ extern "C" int dlc_maxpool3x3s2_nhwc_f64(dlc_ctx* ctx, const double* x, int64_t 
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!x || !y || n < 1 || h < 3 || w < 3 || c < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "maxpool: bad argument");
     const int oh = (h - 3) / 2 + 1, ow = (w - 3) / 2 + 1;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const long long total = (long long)n * oh * ow * c;
     long long blocks = dlc::cdiv(total, 256);
     if (blocks > 256 * 64) blocks = 256 * 64;
@@ -172,8 +170,7 @@ extern "C" int dlc_space_to_depth_nhwc_f64(dlc_ctx* ctx, const double* x, int64_
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!x || !y || n < 1 || h < 1 || w < 1 || c < 1 || s < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "space_to_depth: bad argument");
     if (h % s || w % s) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "space_to_depth: %d x %d is not a multiple of the block %d", h, w, s);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     long long blocks = dlc::cdiv((long long)n * h * w * c, 256);
     if (blocks > 256 * 64) blocks = 256 * 64;
     hipLaunchKernelGGL(space_to_depth_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long long)n, h, w,
@@ -225,8 +222,7 @@ int fold_minmax_f64(dlc_ctx* ctx, const double* x, int64_t n_img, int64_t per_im
 extern "C" int dlc_cnnvtl_frame_minmax_init(dlc_ctx* ctx, uint64_t* keys, int64_t n, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!keys || n < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "frame_minmax_init: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(minmax_init_kernel, dim3((unsigned)dlc::cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        (unsigned long long*)keys, (long long)n);
     DLC_LAUNCH_CHECK(ctx, "minmax_init_kernel");
@@ -243,8 +239,7 @@ extern "C" int dlc_quant_gather_i8(dlc_ctx* ctx, const double* const* segs, cons
     Segs s;
     const int rc = build_segs(ctx, segs, seg_sizes, n_segs, &s);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(minmax_decode_kernel, dim3((unsigned)dlc::cdiv(2 * n, 256)), dim3(256), 0, st,
                        (const unsigned long long*)keys, (long long)n, minmax);
@@ -264,8 +259,7 @@ extern "C" int dlc_minmax_quant_gather_i8(dlc_ctx* ctx, const double* const* seg
     Segs s;
     int rc = build_segs(ctx, segs, seg_sizes, n_segs, &s);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     // minmax doubles as the key scratch: [n,2] u64 keys first, decoded in place afterwards
     unsigned long long* keys = (unsigned long long*)minmax;

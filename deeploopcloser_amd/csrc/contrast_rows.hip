@@ -23,7 +23,6 @@ constexpr int CR_CELLS = 4;                    // consecutive cells of a lane
 constexpr int CR_SLAB = 64 * CR_CELLS;         // columns of a wave
 constexpr int CR_WAVES = 4;
 constexpr int CR_MAX_RADIUS = 32;
-constexpr int CR_MAX_BLOCKS = 1 << 20;         // more items than this: a workgroup takes several, one after the other
 
 struct CrArgs {
     const void* M;
@@ -161,9 +160,8 @@ extern "C" int dlc_contrast_rows(dlc_ctx* ctx, int dtype, const void* scores, in
     if (rows > 0x7fffffffffffffffll / a.slabs) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "contrast_rows: rows * n too large");
     a.items = rows * a.slabs; a.radius = radius;
     const int64_t want = dlc::cdiv(a.items, CR_WAVES);
-    const unsigned blocks = (unsigned)(want < CR_MAX_BLOCKS ? want : CR_MAX_BLOCKS);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    const unsigned blocks = dlc::capped_blocks(want);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     return rows_dispatch(dtype, [&](auto dt) { return cr_launch<dt.value>(ctx, a, blocks, st); });
 }

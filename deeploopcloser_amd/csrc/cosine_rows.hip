@@ -151,8 +151,7 @@ extern "C" int dlc_cosine_score_rows(dlc_ctx* ctx, int dtype, const void* Q, int
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
     const int64_t lmax = dlc::max_row_limit(0, q - 1, n, limit0, limit_step);
     if (lmax == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     auto launch = [&](auto kern, int qtile, int rtile) {
         const int64_t tiles = dlc::cdiv(lmax, rtile);
         const dim3 grid((unsigned)dlc::cdiv(q, qtile), (unsigned)(tiles < CR_MAX_GRID_Y ? tiles : CR_MAX_GRID_Y));

@@ -2578,8 +2578,7 @@ extern "C" int dlc_cosine_topk(dlc_ctx* ctx, int dtype, const void* Q, int64_t q
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_topk", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const bool direct = small_direct(mc, k);
     rc = arm_prune(ctx, mc, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc != DLC_OK) return rc;
@@ -2598,8 +2597,7 @@ extern "C" int dlc_cosine_topk_older(dlc_ctx* ctx, int dtype, const void* Q, int
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_topk_older", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const bool direct = small_direct(mc, k);
     rc = run_score(ctx, dtype, mc, (hipStream_t)stream, direct);
     if (rc != DLC_OK) return rc;
@@ -2614,8 +2612,7 @@ extern "C" int dlc_cosine_score_groups(dlc_ctx* ctx, int dtype, const void* Q, i
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_score_groups", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return run_score(ctx, dtype, mc, (hipStream_t)stream);
 }
 
@@ -2629,8 +2626,7 @@ extern "C" int dlc_cosine_select_topk(dlc_ctx* ctx, int dtype, const void* Q, in
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_select_topk", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return run_finish(ctx, dtype, mc, k, n, d, q, row_offset, out_scores, out_scores_f64, out_idx, out_status, workspace, flags,
                       tau_scale, (hipStream_t)stream);
 }
@@ -2646,8 +2642,7 @@ extern "C" int dlc_cosine_select_groups(dlc_ctx* ctx, int dtype, const void* Q, 
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_select_groups", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     FinishArgs f = finish_args(mc, k, n, d, q, 0);
     f.grp_ids = group_ids; f.grp_max = group_max;
     return run_select<FIN_GROUPS>(ctx, dtype, f, q, flags, (hipStream_t)stream);
@@ -2681,8 +2676,7 @@ extern "C" int dlc_cosine_rescore_topk(dlc_ctx* ctx, int dtype, const void* Q, i
     MatchCall mc;
     int rc = operands_only(ctx, "cosine_rescore_topk", dtype, Q, q, ldq, DB, n, lddb, d, k, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     FinishArgs f = finish_args(mc, k, n, d, q, row_offset);
     f.grp_ids = const_cast<int32_t*>(group_ids); f.grp_max = const_cast<float*>(group_max);
     f.all_max = all_group_max; f.parts = parts;
@@ -2702,8 +2696,7 @@ extern "C" int dlc_cosine_exhaustive_topk(dlc_ctx* ctx, int dtype, const void* Q
     MatchCall mc;
     int rc = prepare_match(ctx, "cosine_exhaustive_topk", dtype, Q, q, ldq, DB, n, lddb, d, k, workspace, workspace_bytes, &mc);
     if (rc != DLC_OK) return rc;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     FinishArgs f = finish_args(mc, k, n, d, q, row_offset);
     f.tau = tau; f.tau_scale = tau_scale;
     return run_exhaustive(ctx, dtype, f, q, lower, lower_stride, out_scores, out_scores_f64, out_idx, status, (hipStream_t)stream);
@@ -2743,8 +2736,7 @@ extern "C" int dlc_topk_keep_older(dlc_ctx* ctx, const float* scores, const int6
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!scores || !idx || !out_scores || !out_idx || rows < 1 || kk < 1 || kk > DLC_MAX_K || k < 1 || k > DLC_MAX_K)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "topk_keep_older: bad argument (1 <= kk, k <= %d)", DLC_MAX_K);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(keep_older_kernel, dim3((unsigned)dlc::cdiv(rows, (int64_t)4)), dim3(256), 0, (hipStream_t)stream, scores,
                        (const long long*)idx, (long long)rows, kk, (long long)limit0, k, out_scores, (long long*)out_idx);
     DLC_LAUNCH_CHECK(ctx, "keep_older_kernel");
@@ -2759,8 +2751,7 @@ extern "C" int dlc_topk_merge_strided(dlc_ctx* ctx, const double* scores_f64, in
     if (!scores_f64 || !idx || !out_idx || parts < 1 || q < 1 || k < 1 || k > DLC_MAX_K ||
         score_part_stride < q * k || idx_part_stride < q * k || !(tau >= 0.0))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "topk_merge: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return launch_merge(ctx, scores_f64, score_part_stride, idx, idx_part_stride, parts, q, k, bound, tau, tau_scale,
                         out_scores, out_scores_f64, out_idx, out_status, (hipStream_t)stream);
 }
@@ -2788,8 +2779,7 @@ extern "C" int dlc_cosine_scores(dlc_ctx* ctx, int dtype, const void* Q, int64_t
     if (need && (!workspace || workspace_bytes < need))
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cosine_scores: workspace %zu < %zu bytes", workspace_bytes, need);
     if (need && ((uintptr_t)workspace & 255)) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cosine_scores: workspace must be 256-byte aligned");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     GemmArgs a{};
     a.Q = (const char*)Q; a.DB = (const char*)DB;
     a.ldq_b = ldq * 2; a.lddb_b = lddb * 2;
@@ -2809,8 +2799,7 @@ extern "C" int dlc_l2_normalize_rows(dlc_ctx* ctx, int src_dtype, const void* sr
     if (ldd % BK) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: ldd=%lld must be a multiple of %d", (long long)ldd, BK);
     if (ldd > 0x7fffffff) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: ldd too large");
     if ((uintptr_t)dst & 3) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "l2_normalize_rows: dst must be 4-byte aligned");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     if (src_dtype != DLC_F32 && src_dtype != DLC_F64)
         return dlc::fail(ctx, DLC_ERR_UNSUPPORTED, "l2_normalize_rows: dtype pair %d -> %d", src_dtype, dst_dtype);
@@ -2922,8 +2911,7 @@ extern "C" int dlc_max_row_norm(dlc_ctx* ctx, int dtype, const void* rows, int64
     int rc = check_rows(ctx, "max_row_norm", dtype, rows, n, ld, d);
     if (rc != DLC_OK) return rc;
     if (!max_norm) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "max_row_norm: null output");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const unsigned grid = (unsigned)std::min<int64_t>(dlc::cdiv(n, 4), 256 * 16);
     if (dtype == DLC_BF16)
         hipLaunchKernelGGL(max_row_norm_kernel<dlc_bf16_tag>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)rows,
@@ -2940,8 +2928,7 @@ extern "C" int dlc_cosine_tau_scale(dlc_ctx* ctx, int dtype, const void* Q, int6
     int rc = check_rows(ctx, "cosine_tau_scale", dtype, Q, q, ldq, d);
     if (rc != DLC_OK) return rc;
     if (!tau_scale) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cosine_tau_scale: null output");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const unsigned grid = (unsigned)dlc::cdiv(q, 4);
     if (dtype == DLC_BF16)
         hipLaunchKernelGGL(tau_scale_kernel<dlc_bf16_tag>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)Q,

@@ -147,8 +147,7 @@ int tk_rows_launch(dlc_ctx* ctx, const char* kernel, int64_t Q, int64_t N, int64
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)
     const int64_t lmax = dlc::max_row_limit(0, Q - 1, N, limit0, limit_step);
     if (lmax == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     if (p.ntx == 16) launch(TkShape<16, 4>{}, lmax, qtiles);
     else if (p.qr == 4) launch(TkShape<64, 4>{}, lmax, qtiles);
     else launch(TkShape<64, 1>{}, lmax, qtiles);

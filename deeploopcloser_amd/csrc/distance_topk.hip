@@ -194,8 +194,7 @@ extern "C" int dlc_cnnvtl_distance_topk(dlc_ctx* ctx, const int8_t* queries, int
     const size_t need = dlc_cnnvtl_distance_topk_workspace_bytes(Q, N, D, k);
     if (workspace_bytes < need)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "distance_topk: workspace %zu < %zu bytes", workspace_bytes, need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
 
     // rows any query sees (the limit is linear in the query row: its largest value is at one end)

@@ -100,6 +100,14 @@ struct DeviceGuard {
 
 }  // namespace dlc
 
+// An entry point's step onto its context's device, behind its argument checks: the guard lives to the end of the
+// enclosing function and puts the caller's device back.
+#define DLC_ON_DEVICE(ctx)                                                                    \
+    dlc::DeviceGuard guard((ctx)->device);                                                    \
+    if (!guard.ok) return dlc::fail((ctx), DLC_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
+
+#include "entry.h"                              // dlc::overlap, check_workspace, split_plan, capped_blocks: HIP-free too
+
 // ---- device-side vector types ------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;

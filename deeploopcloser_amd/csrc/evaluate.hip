@@ -33,7 +33,6 @@ constexpr int EV_CELLS_PER_BIN = 16;              // ... and a workgroup has thi
 constexpr long long EV_FLUSH_ITEMS = (1ll << 31) / EV_CHUNK;       // items between two flushes of the u32 histogram
 constexpr int RK_TILE = 1024;                     // columns a slab of the rank pass is a multiple of
 constexpr int RK_MAX_WG = 2048;                   // workgroups the slab passes aim at (rows x slabs)
-constexpr int RK_MAX_BLOCKS = 1 << 20;            // more items than this: a workgroup takes several, one after the other
 
 struct EvMatrix {
     const void* M;
@@ -319,13 +318,13 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(const RkArgs a) {
 template <int DT>
 int rk_launch(dlc_ctx* ctx, const RkArgs& a, hipStream_t st) {
     const int64_t items = a.m.rows * a.G;
-    const unsigned row_blocks = (unsigned)(a.m.rows < RK_MAX_BLOCKS ? a.m.rows : RK_MAX_BLOCKS);
+    const unsigned row_blocks = dlc::capped_blocks(a.m.rows);
     if (a.G == 1) {
         hipLaunchKernelGGL(rank_rows_kernel<DT>, dim3(row_blocks), dim3(256), 0, st, a);
         DLC_LAUNCH_CHECK(ctx, "rank_rows_kernel");
         return DLC_OK;
     }
-    const unsigned blocks = (unsigned)(items < RK_MAX_BLOCKS ? items : RK_MAX_BLOCKS);
+    const unsigned blocks = dlc::capped_blocks(items);
     hipLaunchKernelGGL(rank_best_kernel<DT>, dim3(blocks), dim3(256), 0, st, a);
     DLC_LAUNCH_CHECK(ctx, "rank_best_kernel");
     hipLaunchKernelGGL(rank_beat_kernel<DT>, dim3(blocks), dim3(256), 0, st, a);
@@ -379,8 +378,7 @@ extern "C" int dlc_pr_cell_counts(dlc_ctx* ctx, int dtype, const void* scores, i
     a.nch = dlc::cdiv(cols, EV_CHUNK);
     a.items = rows * a.nch;                                           // (<= the items the workspace was sized by)
     const int64_t G = pr_workgroups(a.items, T);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     if (G > 0) {
         const size_t lds = (size_t)T * 8 + 2 * (size_t)(T + 1) * 4;   // 65 544 bytes at T = 4096
@@ -428,8 +426,7 @@ extern "C" int dlc_positive_rank_rows(dlc_ctx* ctx, int dtype, const void* score
     dlc::SlabSplit slabs = {1, 1};                                    // nothing offered: the one-launch form writes (-1, -1, 0)
     if (cols > 0) slabs = dlc::split_slabs(rows, dlc::cdiv(cols, RK_TILE), RK_MAX_WG);
     a.G = slabs.G; a.cols_per_slab = slabs.tiles_per_slab * RK_TILE;  // (G <= the slabs the workspace was sized by)
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     return rows_dispatch(dtype, [&](auto dt) { return rk_launch<dt.value>(ctx, a, st); });
 }

@@ -387,8 +387,7 @@ extern "C" int dlc_harris_keypoints_u8(dlc_ctx* ctx, const uint8_t* gray, int64_
     if (!workspace || workspace_bytes < need)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "harris_keypoints: workspace %zu < %zu bytes", workspace_bytes, need);
     if ((uintptr_t)workspace & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "harris_keypoints: workspace must be 256-byte aligned");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     // the tiles' candidate lists: responses, pixels, lengths (every length is written by its tile's workgroup)
     const size_t lists = (size_t)frames * (size_t)harris_tiles(H, W);
@@ -410,8 +409,7 @@ extern "C" int dlc_harris_keypoints_u8(dlc_ctx* ctx, const uint8_t* gray, int64_
 extern "C" int dlc_rgb_to_gray_u8(dlc_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, uint8_t* gray, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!rgb || !gray || n_pixels < 1) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "rgb_to_gray: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const int vec = (((uintptr_t)rgb | (uintptr_t)gray) & 3) == 0;
     long long blocks = dlc::cdiv(vec ? dlc::cdiv(n_pixels, (int64_t)4) : n_pixels, 256);
     if (blocks > 256 * 32) blocks = 256 * 32;
@@ -431,8 +429,7 @@ extern "C" int dlc_extract_patches(dlc_ctx* ctx, const uint8_t* gray, int64_t fr
     if (H < patch_size || W < patch_size)
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "extract_patches: image %dx%d smaller than the %d patch", H, W, patch_size);
     if (frames * P > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "extract_patches: too many patches");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     dim3 grid((unsigned)dlc::cdiv(frames * P, (int64_t)EP_PATCHES));
     if (out_dtype == DLC_F64)
         hipLaunchKernelGGL(extract_patches_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, gray, H, W,

@@ -16,6 +16,7 @@
 //   Loads and stores are 16 bytes per lane where the cell's address allows it (an 8-byte element whose group starts in
 //   the upper half of its 16 bytes goes as 8 + 16 + 8), element by element at a row's limit.
 #include "score_rows.h"
+#include "lds_tree.h"
 
 // every product and every sum rounded on its own (hipcc contracts a * b + c into an fma otherwise), as NumPy's are
 #pragma clang fp contract(off)
@@ -27,7 +28,6 @@ constexpr int FR_CHUNK = 256;                  // columns of a wave: 64 lanes x 
 constexpr int FR_SLAB = 4096;                  // columns of a SLAB workgroup: 16 chunks
 constexpr int FR_BLOCK = 4096;                 // tree nodes folded in LDS at a time
 constexpr int FR_TOP = 2048;                   // blocks of a row: 2^31 / 256 / 4096
-constexpr int FR_MAX_BLOCKS = 1 << 20;         // more items than this: a workgroup takes several, one after the other
 // AUTO (docs/LAB.md 25: ROW against SLAB over rows 16 .. 2048 x n 4096 .. 262144): SLAB wins from two slabs of offered
 // columns on while there are fewer rows than two per compute unit -- 256 rows yes, 512 no, at every n measured
 constexpr int FR_SLAB_MIN_COLS = 2 * FR_SLAB;
@@ -120,37 +120,22 @@ __device__ __forceinline__ double fr_wave_sum(const double (&v)[4]) {
     return s;
 }
 
-// a[0 .. cnt) (written, not yet synchronised), padded with -0.0 to a power of two and folded neighbour with neighbour
-__device__ __forceinline__ double fr_lds_tree(double* a, int cnt) {
-    int P = 1;
-    while (P < cnt) P <<= 1;
-    for (int t = cnt + (int)threadIdx.x; t < P; t += FR_THREADS) a[t] = -0.0;
-    __syncthreads();
-    for (int s = 1; s < P; s <<= 1) {
-        for (int t = threadIdx.x; t < P / (2 * s); t += FR_THREADS) a[2 * s * t] = a[2 * s * t] + a[2 * s * t + s];
-        __syncthreads();
-    }
-    const double v = a[0];
-    __syncthreads();                                                  // (a is free again)
-    return v;
-}
-
 // TREE of C >= 1 nodes; fill(base, cnt) puts nodes base .. base + cnt - 1 into node[0 .. cnt)
 template <class Fill>
 __device__ __forceinline__ double fr_tree(long long C, double* node, double* top, Fill fill) {
     const long long nblk = (C + FR_BLOCK - 1) / FR_BLOCK;
     if (nblk == 1) {
         fill(0, (int)C);
-        return fr_lds_tree(node, (int)C);
+        return dlc_lds_tree<FR_THREADS>(node, (int)C);
     }
     for (long long b = 0; b < nblk; ++b) {
         const long long left = C - b * FR_BLOCK;
         const int cnt = left < FR_BLOCK ? (int)left : FR_BLOCK;
         fill(b * FR_BLOCK, cnt);
-        const double v = fr_lds_tree(node, cnt);
+        const double v = dlc_lds_tree<FR_THREADS>(node, cnt);
         if (threadIdx.x == 0) top[b] = v;
     }
-    return fr_lds_tree(top, (int)nblk);
+    return dlc_lds_tree<FR_THREADS>(top, (int)nblk);
 }
 
 // the order of the numbers, -0.0 below +0.0 (dlc_f64_key); never called with a NaN
@@ -381,7 +366,7 @@ size_t fr_workspace(int64_t rows, int64_t n, int m) {
 template <int NORM>
 int fr_launch(dlc_ctx* ctx, const FrArgs& a, bool slab, hipStream_t st) {
     const long long items = slab ? a.items : a.rows;
-    const unsigned blocks = (unsigned)(items < FR_MAX_BLOCKS ? items : FR_MAX_BLOCKS);
+    const unsigned blocks = dlc::capped_blocks(items);
     if (!slab) {
         hipLaunchKernelGGL((fuse_row_kernel<NORM>), dim3(blocks), dim3(FR_THREADS), 0, st, a);
         DLC_LAUNCH_CHECK(ctx, "fuse_row_kernel");
@@ -431,14 +416,12 @@ extern "C" int dlc_fuse_rows(dlc_ctx* ctx, int m, const int* dtypes, const void*
     const int rc = rows_check(ctx, "fuse_rows", s0, nullptr, DLC_ERR_BAD_SHAPE);
     if (rc != DLC_OK) return rc;
     const size_t need = fr_workspace(rows, n, m);
-    const bool ws_ok = need != 0 && workspace && workspace_bytes >= need && !(((uintptr_t)workspace) & 15);
-    if (plan == DLC_FUSE_PLAN_SLAB && !ws_ok)
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "fuse_rows: the SLAB plan needs %zu bytes of 16-byte aligned workspace", need);
+    const bool ws_ok = dlc::workspace_ok(workspace, workspace_bytes, need);
+    if (plan == DLC_FUSE_PLAN_SLAB && !ws_ok) return dlc::check_workspace(ctx, "fuse_rows", workspace, workspace_bytes, need);
     // columns any row offers (limits are linear in the row, so the largest sits at an end)
     const int64_t cols = dlc::max_row_limit(0, rows - 1, n, limit0, limit_step);
     if (cols == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     bool slab = plan == DLC_FUSE_PLAN_SLAB;
     if (plan == DLC_FUSE_PLAN_AUTO && ws_ok && cols >= FR_SLAB_MIN_COLS) {
         int cus = 0;

@@ -586,8 +586,7 @@ extern "C" int dlc_conv2d_nhwc_f64_stats(dlc_ctx* ctx, const double* x, int64_t 
         pad_top < 0 || pad_left < 0 || oh < 1 || ow < 1)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "conv2d: bad argument");
     if (act < DLC_ACT_NONE || act > DLC_ACT_RELU) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "conv2d: act %d", act);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const dlc_gemm::ConvGeom cv{h, w, c, kw, stride, pad_top, pad_left, oh, ow, (unsigned long long*)frame_keys};
     dlc_gemm::GemmCall call{DLC_F64, DLC_B_KN, act, n * oh * ow, cout, (int64_t)kh * kw * c, x, 0, kernel, cout, bias, out, cout,
                             (hipStream_t)stream};
@@ -606,8 +605,7 @@ extern "C" int dlc_gemm_bias_act(dlc_ctx* ctx, int dtype, int blayout, int act, 
                                  const void* A, int64_t lda, const void* B, int64_t ldb, const void* bias, void* C,
                                  int64_t ldc, void* stream) {
     if (!ctx) return DLC_ERR_BAD_ARG;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return dlc_gemm::gemm_bias_act(ctx, dtype, blayout, act, M, N, K, A, lda, B, ldb, bias, C, ldc, (hipStream_t)stream);
 }
 
@@ -630,8 +628,7 @@ extern "C" int dlc_bias_act(dlc_ctx* ctx, int dtype, int act, int64_t M, int64_t
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!A || !C || M < 1 || N < 1 || lda < N || ldc < N) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "bias_act: bad argument");
     if (act < DLC_ACT_NONE || act > DLC_ACT_RELU) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "bias_act: act %d", act);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     long long blocks = dlc::cdiv(M * N, 256);
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (dtype == DLC_F64)
@@ -690,8 +687,7 @@ extern "C" int dlc_sdav_encode(dlc_ctx* ctx, int dtype, int64_t rows, int n_laye
     const size_t need = dlc_sdav_encode_workspace_bytes(rows, dims, n_layers, dtype);
     if ((n_layers > 1 || sdav_pad_width(rows, dims, dtype) > 0) && (!workspace || workspace_bytes < need))
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sdav_encode: workspace %zu < %zu bytes", workspace_bytes, need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const int64_t kpad = sdav_pad_width(rows, dims, dtype);
     const size_t pad_bytes = dlc::align_up((size_t)rows * (size_t)kpad * 8, 256);
     const size_t half = (need - pad_bytes) / 2;

@@ -676,8 +676,7 @@ extern "C" int dlc_sdav_split_prepare(dlc_ctx* ctx, int n_layers, const int64_t*
     if ((uintptr_t)panels & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_split_prepare: panels must be 256-byte aligned");
     for (int l = 0; l < n_layers; ++l)
         if (!W[l]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_split_prepare: W[%d] is null", l);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return dlc_gemm::split_prepare(ctx, n_layers, dims, W, (char*)panels, (hipStream_t)stream);
 }
 
@@ -700,8 +699,7 @@ extern "C" int dlc_sdav_encode_split(dlc_ctx* ctx, int64_t rows, int n_layers, c
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "sdav_encode_split: workspace %zu < %zu bytes", workspace_bytes, need);
     if (((uintptr_t)workspace & 255) || ((uintptr_t)panels & 255))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_encode_split: workspace and panels must be 256-byte aligned");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return dlc_gemm::split_encode(ctx, rows, n_layers, dims, x, (const char*)panels, b, out, (char*)workspace, (hipStream_t)stream);
 }
 
@@ -1057,8 +1055,7 @@ extern "C" int dlc_cnnvtl_split_prepare(dlc_ctx* ctx, int n_layers, const int32_
     if ((uintptr_t)panels & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_split_prepare: panels must be 256-byte aligned");
     for (int l = 0; l < n_layers; ++l)
         if (!W[l]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_split_prepare: W[%d] is null", l);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     for (int l = 0; l < n_layers; ++l) {
         const dlc_gemm::CsGeom g = dlc_gemm::cs_geom(geom, l);
         const int64_t dims[2] = {(int64_t)g.kh * g.kw * g.cin, g.cout};
@@ -1091,8 +1088,7 @@ extern "C" int dlc_cnnvtl_encode_split(dlc_ctx* ctx, int dtype, const void* x, i
     if (!dlc_gemm::conv_ws(n, h0, w0, c0, n_layers, geom, &W)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "cnnvtl_encode_split: bad geometry");
     if (!workspace || workspace_bytes < W.total)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cnnvtl_encode_split: workspace %zu < %zu bytes", workspace_bytes, W.total);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* in0 = (float*)(ws + W.in0);
@@ -1136,8 +1132,7 @@ extern "C" int dlc_cnnvtl_layers_split(dlc_ctx* ctx, const float* x, int64_t n, 
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "cnnvtl_layers_split: workspace %zu < %zu bytes", workspace_bytes, W.total);
     for (int l = layer_a; l <= layer_b; ++l)
         if (!feats[l - layer_a]) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "cnnvtl_layers_split: feats[%d] is null", l - layer_a);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return dlc_gemm::conv_run_layers(ctx, n, W, n_layers, geom, layer_a, layer_b, x, (const char*)panels, b, feats, nullptr,
                                      (char*)workspace, nullptr, (int*)status, (hipStream_t)stream);
 }

@@ -168,8 +168,7 @@ extern "C" int dlc_host_to_device(dlc_ctx* ctx, void* dst_device, const void* sr
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!dst_device || !src_host) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "host_to_device: null pointer");
     if (bytes == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     std::lock_guard<std::mutex> lk(*ctx->host_lock);
     dlc_host_staging* s;
     int rc = dlc::staging_get(ctx, &s);
@@ -192,8 +191,7 @@ extern "C" int dlc_device_to_host(dlc_ctx* ctx, void* dst_host, const void* src_
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!dst_host || !src_device) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "device_to_host: null pointer");
     if (bytes == 0) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     std::lock_guard<std::mutex> lk(*ctx->host_lock);
     dlc_host_staging* s;
     int rc = dlc::staging_get(ctx, &s);

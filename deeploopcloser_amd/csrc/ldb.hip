@@ -163,8 +163,7 @@ extern "C" int dlc_ldb_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_t fr
     if (ld_out < row_bytes)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "ldb_describe: ld_out=%lld < row bytes=%lld", (long long)ld_out, (long long)row_bytes);
     if (frames > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "ldb_describe: frames must be below 2^31");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     LdbArgs a;
     a.gray = gray; a.out = out; a.ld_out = ld_out;
     a.H = H; a.W = W; a.h = h; a.w = w;

@@ -211,21 +211,11 @@ bool lsh_shape_ok(int64_t rows, int64_t D, int bits) {
 }
 
 // the plan a call runs, -1 for an unknown one or a SPLIT with too many rows
-int lsh_plan(int64_t rows, int64_t D, int plan) {
-    if (plan == DLC_LSH_PLAN_ONE_PASS) return plan;
-    if (plan == DLC_LSH_PLAN_SPLIT) return rows <= DLC_LSH_SPLIT_MAX_ROWS ? plan : -1;
-    if (plan != DLC_LSH_PLAN_AUTO) return -1;
-    return (rows <= DLC_LSH_SPLIT_MAX_ROWS && D > DLC_LSH_CHUNK) ? DLC_LSH_PLAN_SPLIT : DLC_LSH_PLAN_ONE_PASS;
-}
+int lsh_plan(int64_t rows, int64_t D, int plan) { return dlc::split_plan(plan, rows, DLC_LSH_SPLIT_MAX_ROWS, D > DLC_LSH_CHUNK); }
 
 size_t lsh_workspace(int64_t rows, int64_t D, int bits, int plan) {
     if (!lsh_shape_ok(rows, D, bits) || lsh_plan(rows, D, plan) != DLC_LSH_PLAN_SPLIT) return 0;
     return dlc::align_up((size_t)rows * (size_t)dlc::cdiv(D, DLC_LSH_CHUNK) * (size_t)lsh_row_bytes(bits) * 8 * 4, 256);
-}
-
-bool lsh_overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return q && a < b + bytes2 && b < a + bytes;
 }
 
 template <int WR, int WC, int MT, int NT>
@@ -274,10 +264,9 @@ extern "C" int dlc_lsh_quantize_i8(dlc_ctx* ctx, int x_dtype, const void* x, int
     if (D > DLC_LSH_MAX_D || rows > 0x7fffffffll)
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "lsh_quantize: D=%lld > %d or rows=%lld >= 2^31", (long long)D, DLC_LSH_MAX_D, (long long)rows);
     const size_t q_bytes = (size_t)((rows - 1) * ldq + D);
-    if (lsh_overlap(q, q_bytes, x, (size_t)((rows - 1) * ldx + D) * xe) || lsh_overlap(q, q_bytes, mean, (size_t)D * 8))
+    if (dlc::overlap(q, q_bytes, x, (size_t)((rows - 1) * ldx + D) * xe) || dlc::overlap(q, q_bytes, mean, (size_t)D * 8))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "lsh_quantize: q overlaps an input");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     LshQuantArgs a;
     a.x = x; a.mean = mean; a.q = q; a.D = D; a.ldx = ldx; a.ldq = ldq;
     const dim3 grid((unsigned)rows), block(LSH_Q_THREADS);
@@ -313,15 +302,16 @@ extern "C" int dlc_lsh_hash_i8(dlc_ctx* ctx, const int8_t* q, int64_t rows, int6
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "lsh_hash: DLC_LSH_PLAN_SPLIT takes at most %d rows, not %lld", DLC_LSH_SPLIT_MAX_ROWS,
                          (long long)rows);
     const size_t out_bytes = (size_t)((rows - 1) * ld_out + row_bytes);
-    if (lsh_overlap(out, out_bytes, q, (size_t)((rows - 1) * ldq + D)) ||
-        lsh_overlap(out, out_bytes, planes, (size_t)((int64_t)(bits - 1) * ldp + D)))
+    if (dlc::overlap(out, out_bytes, q, (size_t)((rows - 1) * ldq + D)) ||
+        dlc::overlap(out, out_bytes, planes, (size_t)((int64_t)(bits - 1) * ldp + D)))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "lsh_hash: out overlaps an input");
     const bool split = run == DLC_LSH_PLAN_SPLIT;
     const size_t need = lsh_workspace(rows, D, bits, run);
-    if (split && (!need || !workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15)))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "lsh_hash: needs %zu bytes of 16-byte aligned workspace", need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    if (split) {
+        const int rc = dlc::check_workspace(ctx, "lsh_hash", workspace, workspace_bytes, need);
+        if (rc != DLC_OK) return rc;
+    }
+    DLC_ON_DEVICE(ctx);
     LshArgs a;
     a.q = q; a.planes = planes; a.out = out; a.part = split ? (int*)workspace : nullptr;
     a.rows = rows; a.D = D; a.ldq = ldq; a.ldp = ldp; a.ld_out = ld_out;

@@ -1330,8 +1330,7 @@ extern "C" int dlc_cnnvtl_distance_matrix(dlc_ctx* ctx, const int8_t* desc, int6
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!desc || !out || N < 1 || D < 1 || ldd < D) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distance_matrix: bad argument");
     if (D > (1ll << 28)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_matrix: D too large for int32 accumulation");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const unsigned t = (unsigned)dlc::cdiv(N, DT);
     if (t > 65535) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "distance_matrix: N too large");
     // descriptor chunks: enough workgroups for ~3 per CU, each at least 4 steps of 64 bytes
@@ -1367,8 +1366,7 @@ extern "C" int dlc_sdav_distinctive_score(dlc_ctx* ctx, const double* dataset, i
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!dataset || !score || rows < 1 || H < 1 || H > 0x7fffffff)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "distinctive_score: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     if (range) hipLaunchKernelGGL(range_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)range);
     if ((H & 1) == 0 && ((uintptr_t)dataset & 15) == 0 && (long long)DSD_RB * H * 8 < 0x7fffffffll) {
         constexpr int C = DLC_DSD_COLS, lds = DSD_NB * DSD_RB * C * 8;
@@ -1399,8 +1397,7 @@ extern "C" int dlc_sdav_similarity_matrix(dlc_ctx* ctx, const double* desc, int6
     const SimWs w = sim_ws(N, P, H, flags, chunk_bytes);
     if (!workspace || workspace_bytes < w.total)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "similarity_matrix: workspace %zu < %zu bytes", workspace_bytes, w.total);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     double* nrm2 = (double*)(ws + w.nrm2);
@@ -1534,8 +1531,7 @@ extern "C" int dlc_sdav_stream_init(dlc_ctx* ctx, void* state, size_t state_byte
     int rc = stream_check(ctx, "sdav_stream_init", state, state_bytes, capacity, P, H);
     if (rc != DLC_OK) return rc;
     if (!(hi > lo) || !(hi - lo < INFINITY)) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_init: need lo < hi, both finite");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const StreamWs w = stream_ws(capacity, P, H);
     char* ws = (char*)state;
     // the batched query's strip (gram_argmin_i8_strip) gathers padding columns from a zero group and reads |v|^2 = 0 for them
@@ -1554,8 +1550,7 @@ extern "C" int dlc_sdav_stream_append(dlc_ctx* ctx, void* state, size_t state_by
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_append: frames [%lld, %lld) outside the capacity %lld", (long long)n_old,
                          (long long)n_total, (long long)capacity);
     if (n_total == n_old) return DLC_OK;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const StreamWs w = stream_ws(capacity, P, H);
     char* ws = (char*)state;
     const int64_t g_first = n_old * P / 16, g_last = dlc::cdiv(n_total * P, (int64_t)16);
@@ -1645,8 +1640,7 @@ extern "C" int dlc_sdav_stream_query(dlc_ctx* ctx, void* state, size_t state_byt
     if (rc != DLC_OK) return rc;
     if (!desc || !score || (!row_out && f > 0) || f < 0 || f >= capacity)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sdav_stream_query: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     const StreamWs w = stream_ws(capacity, P, H);
     return stream_query_impl(ctx, state, capacity, P, H, desc, f, 1, a, b, row_out, 0, stats,
                              (unsigned char*)((char*)state + w.bi), 0, stream);
@@ -1679,8 +1673,7 @@ static int batch_query(dlc_ctx* ctx, const char* what, void* state, size_t state
     const BatchWs bw = batch_ws(capacity, P, n_queries);
     if (!workspace || workspace_bytes < bw.total)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, bw.total);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     if ((uintptr_t)workspace & 255) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: workspace must be 256-byte aligned", what);
     return stream_query_impl(ctx, state, capacity, P, H, desc, f_first, n_queries, a, b, rows_out, ld_rows, stats,
                              (unsigned char*)workspace + bw.bi, bw.pitch, stream, (char*)workspace, &bw, stage);
@@ -1707,8 +1700,7 @@ extern "C" int dlc_topk_rows_f64(dlc_ctx* ctx, const double* scores, int64_t row
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!scores || !out_scores || !out_idx || rows < 1 || ld < 1 || k < 1 || k > DLC_MAX_K || rows > 0x7fffffffll)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "topk_rows_f64: bad argument");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(topk_rows_f64_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, scores, (long long)ld,
                        (long long)limit0, (long long)limit_step, k, out_scores, (long long*)out_idx, (const long long*)poison);
     DLC_LAUNCH_CHECK(ctx, "topk_rows_f64_kernel");

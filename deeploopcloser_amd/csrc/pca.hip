@@ -22,7 +22,6 @@ namespace {
 constexpr int PC_THREADS = 256;
 constexpr int PC_SLAB = 128;                   // columns of x of an LDS slab (divides DLC_PCA_CHUNK)
 constexpr int PC_FLIGHT = 8;                   // basis rows a thread loads before it sums them
-constexpr long long PC_MAX_BLOCKS = 1 << 20;   // more items than this: a workgroup takes several, one after the other
 constexpr long long PC_FILL = 256;             // AUTO: ONE_PASS once it has this many workgroups (one per CU)
 
 struct PcArgs {
@@ -139,30 +138,19 @@ __global__ __launch_bounds__(PC_THREADS) void pca_finish_kernel(const PcArgs a) 
     }
 }
 
-unsigned pc_blocks(long long items) { return (unsigned)(items < PC_MAX_BLOCKS ? items : PC_MAX_BLOCKS); }
-
 bool pc_shape_ok(int64_t rows, int64_t D, int M) {
     return rows >= 1 && D >= 1 && M >= 1 && M <= DLC_PCA_MAX_COMPONENTS && rows <= 0x7fffffffll && D <= 0x7fffffffll;
 }
 
 // the plan a call runs: DLC_PCA_PLAN_ONE_PASS or DLC_PCA_PLAN_SPLIT; -1 for a plan that is unknown or not allowed
 int pc_plan(int64_t rows, int64_t D, int M, int plan) {
-    if (plan == DLC_PCA_PLAN_ONE_PASS) return plan;
-    if (plan == DLC_PCA_PLAN_SPLIT) return rows <= DLC_PCA_SPLIT_MAX_ROWS ? plan : -1;
-    if (plan != DLC_PCA_PLAN_AUTO) return -1;
     const long long tiles = dlc::cdiv(rows, rows <= 2 ? 2 : 8) * dlc::cdiv(M, rows > 2 && M > 256 ? 512 : 256);
-    return (rows <= DLC_PCA_SPLIT_MAX_ROWS && D > DLC_PCA_CHUNK && tiles < PC_FILL) ? DLC_PCA_PLAN_SPLIT : DLC_PCA_PLAN_ONE_PASS;
+    return dlc::split_plan(plan, rows, DLC_PCA_SPLIT_MAX_ROWS, D > DLC_PCA_CHUNK && tiles < PC_FILL);
 }
 
 size_t pc_workspace(int64_t rows, int64_t D, int M, int plan) {
     if (!pc_shape_ok(rows, D, M) || pc_plan(rows, D, M, plan) != DLC_PCA_PLAN_SPLIT) return 0;
     return dlc::align_up((size_t)rows * (size_t)dlc::cdiv(D, DLC_PCA_CHUNK) * (size_t)M * 8, 256);
-}
-
-// [p, p + bytes) and [q, q + bytes2) share a byte
-bool pc_overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return q && a < b + bytes2 && b < a + bytes;
 }
 
 template <typename BT>
@@ -171,12 +159,12 @@ int pc_launch(dlc_ctx* ctx, PcArgs a, bool split, hipStream_t st) {
     a.row_tiles = dlc::cdiv(a.rows, rt);
     a.col_tiles = dlc::cdiv(a.M, PC_THREADS * ct);
     a.items = a.row_tiles * a.col_tiles * (split ? a.chunks : 1);
-    const dim3 grid(pc_blocks(a.items)), block(PC_THREADS);
+    const dim3 grid(dlc::capped_blocks(a.items)), block(PC_THREADS);
     if (split) {
         if (rt == 2) hipLaunchKernelGGL((pca_partial_kernel<BT, 2, 1, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((pca_partial_kernel<BT, 8, 1, true>), grid, block, 0, st, a);
         DLC_LAUNCH_CHECK(ctx, "pca_partial_kernel (split)");
-        hipLaunchKernelGGL(pca_finish_kernel, dim3(pc_blocks(dlc::cdiv(a.rows * a.M, PC_THREADS))), block, 0, st, a);
+        hipLaunchKernelGGL(pca_finish_kernel, dim3(dlc::capped_blocks(dlc::cdiv(a.rows * a.M, PC_THREADS))), block, 0, st, a);
         DLC_LAUNCH_CHECK(ctx, "pca_finish_kernel");
     } else {
         if (rt == 2) hipLaunchKernelGGL((pca_partial_kernel<BT, 2, 1, false>), grid, block, 0, st, a);
@@ -218,15 +206,16 @@ extern "C" int dlc_pca_project(dlc_ctx* ctx, const double* x, int64_t rows, int6
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "pca_project: DLC_PCA_PLAN_SPLIT takes at most %d rows, not %lld",
                          DLC_PCA_SPLIT_MAX_ROWS, (long long)rows);
     const size_t out_bytes = (size_t)((rows - 1) * ld_out + M) * 8;
-    if (pc_overlap(out, out_bytes, x, (size_t)((rows - 1) * ldx + D) * 8) || pc_overlap(out, out_bytes, mean, (size_t)D * 8) ||
-        pc_overlap(out, out_bytes, basis, (size_t)((D - 1) * ldb + M) * be) || pc_overlap(out, out_bytes, scale, (size_t)M * 8))
+    if (dlc::overlap(out, out_bytes, x, (size_t)((rows - 1) * ldx + D) * 8) || dlc::overlap(out, out_bytes, mean, (size_t)D * 8) ||
+        dlc::overlap(out, out_bytes, basis, (size_t)((D - 1) * ldb + M) * be) || dlc::overlap(out, out_bytes, scale, (size_t)M * 8))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "pca_project: out overlaps an input");
     const bool split = run == DLC_PCA_PLAN_SPLIT;
     const size_t need = pc_workspace(rows, D, M, run);
-    if (split && (!need || !workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15)))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "pca_project: needs %zu bytes of 16-byte aligned workspace", need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    if (split) {
+        const int rc = dlc::check_workspace(ctx, "pca_project", workspace, workspace_bytes, need);
+        if (rc != DLC_OK) return rc;
+    }
+    DLC_ON_DEVICE(ctx);
     PcArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.mean = mean; a.basis = basis; a.scale = scale; a.out = out; a.part = split ? (double*)workspace : nullptr;

@@ -25,7 +25,6 @@ namespace {
 constexpr int PK_CHUNK = 256;              // columns of a chunk
 constexpr int PK_CELLS = PK_CHUNK / 64;    // cells of a lane
 constexpr int PK_MAX_WG = 2048;            // workgroups the chunk pass aims at (rows x slabs)
-constexpr int PK_MAX_BLOCKS = 1 << 20;     // more items than this: a workgroup takes several, one after the other
 
 struct PkArgs {
     const void* M;
@@ -217,10 +216,9 @@ extern "C" int dlc_peak_topk_rows(dlc_ctx* ctx, int dtype, const void* scores, i
     if (cols > 0) slabs = dlc::split_slabs(rows, dlc::cdiv(cols, PK_CHUNK), PK_MAX_WG);
     a.G = slabs.G; a.chunks_per_slab = slabs.tiles_per_slab;
     const int64_t items = rows * a.G;                             // (<= rows * nch: the workspace's size was formed)
-    const unsigned chunk_blocks = cols > 0 ? (unsigned)(items < PK_MAX_BLOCKS ? items : PK_MAX_BLOCKS) : 0u;
-    const unsigned pick_blocks = (unsigned)(rows < PK_MAX_BLOCKS ? rows : PK_MAX_BLOCKS);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    const unsigned chunk_blocks = cols > 0 ? dlc::capped_blocks(items) : 0u;
+    const unsigned pick_blocks = dlc::capped_blocks(rows);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     return rows_dispatch(dtype, [&](auto dt) { return pk_launch<dt.value>(ctx, a, chunk_blocks, pick_blocks, st); });
 }

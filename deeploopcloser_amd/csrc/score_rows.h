@@ -83,7 +83,7 @@ inline int rows_check(dlc_ctx* ctx, const char* who, const ScoreRows& s, const v
 // `need` bytes of 16-byte aligned workspace; need = 0 is the caller's "the sizes do not fit" (its _workspace_bytes).
 inline int rows_check_workspace(dlc_ctx* ctx, const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
     if (need == 0) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "%s: rows * n too large", who);
-    if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
+    if (!dlc::workspace_ok(workspace, workspace_bytes, need))
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (or not 16-byte aligned)", who,
                          workspace ? workspace_bytes : (size_t)0, need);
     return DLC_OK;

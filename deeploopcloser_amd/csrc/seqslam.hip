@@ -101,8 +101,7 @@ extern "C" int dlc_seqslam_describe_u8(dlc_ctx* ctx, const uint8_t* gray, int64_
     if (ld_out < (int64_t)h * w)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "seqslam_describe: ld_out=%lld < h * w=%d", (long long)ld_out, h * w);
     if (frames > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "seqslam_describe: frames must be below 2^31");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     SdArgs a;
     a.gray = gray; a.out = out; a.ld_out = ld_out;
     a.H = H; a.W = W; a.h = h; a.w = w; a.patch = patch; a.strength = strength;

@@ -230,8 +230,7 @@ extern "C" int dlc_sequence_topk(dlc_ctx* ctx, int dtype, const void* scores, in
                   workspace_bytes, dlc_sequence_topk_workspace_bytes(rows, n, L, n_slopes, k), a);
     if (rc != DLC_OK) return rc;
     const int64_t rows_out = rows - row0;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
 
     // columns any output row offers (limits are linear in the row); the dense output covers the matrix's n columns

@@ -203,8 +203,7 @@ extern "C" int dlc_sequence_elastic_chains(dlc_ctx* ctx, int dtype, const void* 
     if (d_min < 0 || d_min > d_max || d_max > DLC_MAX_STEP)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "sequence_elastic_chains: steps %d..%d: need 0 <= d_min <= d_max <= %d", d_min,
                          d_max, DLC_MAX_STEP);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     a.d_min = d_min; a.d_max = d_max;
     a.W = ((L - 1) * (d_max - d_min) + 1 + 63) / 64 * 64;         // <= 64 * CH_MAX_Q
     const size_t lds = dlc::align_up((size_t)a.W * 8 + (size_t)L * a.W, 16);   // <= 36 KB
@@ -234,8 +233,7 @@ extern "C" int dlc_sequence_chains(dlc_ctx* ctx, int dtype, const void* scores, 
     int maxoff = 0;
     const int bad_table = sq_pack_offsets(ctx, "sequence_chains", offsets, n_slopes, L, &offs, &maxoff);
     if (bad_table != DLC_OK) return bad_table;
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     a.V = n_slopes;
     const dim3 grid((unsigned)dlc::cdiv(a.slots, 4));
     hipStream_t st = (hipStream_t)stream;

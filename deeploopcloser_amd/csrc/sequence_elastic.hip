@@ -177,8 +177,7 @@ extern "C" int dlc_sequence_elastic_topk(dlc_ctx* ctx, int dtype, const void* sc
     const int64_t rows_out = rows - row0;
     const int64_t blocks = dlc::cdiv(rows_out, EL_ROWS);
     if (rows_out > 0x7fffffffll) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "sequence_elastic_topk: too many rows for one launch");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
 
     // columns any output row offers (limits are linear in the row); the dense output covers the matrix's n columns

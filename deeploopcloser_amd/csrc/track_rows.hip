@@ -495,8 +495,7 @@ extern "C" int dlc_track_rows(dlc_ctx* ctx, int dtype, const void* scores, int64
         a.part = (unsigned long long*)(w + 2 * p.v_bytes);
         a.ustate = (long long*)(w + 2 * p.v_bytes + p.part_bytes);
     }
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     return rows_dispatch(dtype, [&](auto dt) { return tr_launch<dt.value>(ctx, a, p, st); });
 }
@@ -514,8 +513,7 @@ extern "C" int dlc_track_backtrace(dlc_ctx* ctx, int64_t rows, int64_t n, const 
     if (end == DLC_TRACK_END_FILTERED ? !place_last : (end < -1 || end >= n))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "%s: end=%lld is no column, -1 or DLC_TRACK_END_FILTERED with place_last", who,
                          (long long)end);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(track_backtrace_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long)rows, (long long)n,
                        (const signed char*)out_back, (long long)ld_back, (const signed char*)out_backU, (const long long*)g,
                        (const long long*)place_last, (long long)end, (long long*)out_path);

@@ -537,8 +537,7 @@ int train_step_impl(dlc_ctx* ctx, const char* what, int layer, int64_t batch, in
     const TrainWs w = train_ws(rows, (int)batch, dims, layer, xt0 == nullptr);
     if (!workspace || workspace_bytes < w.total)
         return dlc::fail(ctx, DLC_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, w.total);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     auto P = [&](size_t off) { return (double*)(ws + off); };
@@ -743,8 +742,7 @@ extern "C" int dlc_random_mask_f64(dlc_ctx* ctx, double* mask, int64_t n, int64_
     if (!ctx) return DLC_ERR_BAD_ARG;
     if (!mask || n < 1 || n_zeros < 0 || n_zeros > n) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "random_mask: bad argument");
     if (n > (1ll << 26)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "random_mask: n=%lld too large (one workgroup walks the keys)", (long long)n);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(random_mask_kernel, dim3(1), dim3(RM_THREADS), 0, (hipStream_t)stream, mask, (long long)n,
                        (long long)n_zeros, (unsigned long long)seed, (unsigned long long)counter);
     DLC_LAUNCH_CHECK(ctx, "random_mask_kernel");
@@ -757,8 +755,7 @@ extern "C" int dlc_salt_pepper_mask_f64(dlc_ctx* ctx, double* zeros, double* one
     if (!zeros || !ones || zeros == ones || n < 1 || n_zeros < 0 || n_zeros > n)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "salt_pepper_mask: bad argument");
     if (n > (1ll << 26)) return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "salt_pepper_mask: n=%lld too large (one workgroup walks the keys)", (long long)n);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(random_mask_kernel, dim3(1), dim3(RM_THREADS), 0, st, zeros, (long long)n, (long long)n_zeros,
                        (unsigned long long)seed, (unsigned long long)counter);
@@ -775,8 +772,7 @@ extern "C" int dlc_da_corrupt_f64(dlc_ctx* ctx, const double* x, const double* z
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_corrupt: bad argument");
     if (out == x && ldo != cols)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "da_corrupt: in place (out == x) needs ldo == cols");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     hipLaunchKernelGGL(corrupt_rows_kernel, dim3(grid_for(rows * ldo)), dim3(256), 0, (hipStream_t)stream, x, zeros, ones,
                        (long long)rows, (long long)cols, out, (long long)ldo);
     DLC_LAUNCH_CHECK(ctx, "corrupt_rows_kernel");

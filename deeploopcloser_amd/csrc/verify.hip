@@ -28,7 +28,6 @@ constexpr int VF_CHUNK = 128;                  // columns of an LDS chunk x cell
 constexpr int VF_AHEAD = 8;                    // columns x cells a side whose LDS values a thread reads ahead of its chains
 constexpr int VF_THREADS = 256;                // threads of a resolve workgroup
 constexpr int VF_PITCH = DLC_VERIFY_MAX_PATCHES + 1;       // of the table in LDS: odd, so a row scan and a column scan spread over the banks
-constexpr long long VF_MAX_BLOCKS = 1 << 20;   // more items than this: a workgroup takes several, one after the other
 constexpr long long VF_SPREAD = 512;           // workgroups a coarser tile must still give (two waves per CU)
 constexpr int VF_MAX_COORD = 8191;
 
@@ -297,8 +296,6 @@ __global__ __launch_bounds__(VF_THREADS) void verify_resolve_kernel(const VfReso
     }
 }
 
-unsigned vf_blocks(long long items) { return (unsigned)(items < VF_MAX_BLOCKS ? items : VF_MAX_BLOCKS); }
-
 size_t vf_workspace(int64_t Q, int k, int P) {
     if (Q < 1 || k < 1 || k > DLC_MAX_K || P < 1 || P > DLC_VERIFY_MAX_PATCHES || Q > 0x7fffffffll / DLC_MAX_K) return 0;
     return dlc::align_up((size_t)Q * (size_t)k * (size_t)P * (size_t)P * 8, 256);
@@ -344,11 +341,9 @@ extern "C" int dlc_verify_pairs(dlc_ctx* ctx, const double* q_desc, int64_t ldq,
     if (P > DLC_VERIFY_MAX_PATCHES || Q > 0x7fffffffll / DLC_MAX_K || N > 0x7fffffffll)
         return dlc::fail(ctx, DLC_ERR_BAD_SHAPE, "verify_pairs: P=%d > %d, Q=%lld > 2^31 / %d or N=%lld >= 2^31", P,
                          DLC_VERIFY_MAX_PATCHES, (long long)Q, DLC_MAX_K, (long long)N);
-    const size_t need = vf_workspace(Q, k, P);
-    if (!need || !workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "verify_pairs: needs %zu bytes of 16-byte aligned workspace", need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    const int rw = dlc::check_workspace(ctx, "verify_pairs", workspace, workspace_bytes, vf_workspace(Q, k, P));
+    if (rw != DLC_OK) return rw;
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     const long long pairs = (long long)Q * k;
     double* table = out_dist ? out_dist : (double*)workspace;
@@ -356,13 +351,13 @@ extern "C" int dlc_verify_pairs(dlc_ctx* ctx, const double* q_desc, int64_t ldq,
     const int ct = vf_cells(pairs, P);
     ta.tiles = (int)dlc::cdiv(P, ct * 8);
     ta.items = pairs * ta.tiles * ta.tiles;
-    if (ct == 4) hipLaunchKernelGGL((verify_table_kernel<4>), dim3(vf_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
-    else if (ct == 2) hipLaunchKernelGGL((verify_table_kernel<2>), dim3(vf_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
-    else hipLaunchKernelGGL((verify_table_kernel<1>), dim3(vf_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
+    if (ct == 4) hipLaunchKernelGGL((verify_table_kernel<4>), dim3(dlc::capped_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
+    else if (ct == 2) hipLaunchKernelGGL((verify_table_kernel<2>), dim3(dlc::capped_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
+    else hipLaunchKernelGGL((verify_table_kernel<1>), dim3(dlc::capped_blocks(ta.items)), dim3(VF_WAVE), 0, st, ta);
     DLC_LAUNCH_CHECK(ctx, "verify_table_kernel");
     const VfResolveArgs ra = {table, q_pts, db_pts, (const long long*)cand, out_inliers, out_matches, out_hyp,
                               (unsigned long long*)out_mask, out_match, N, ld_cand, pairs, k, P, model, tol, max_scale_x16, mutual};
-    hipLaunchKernelGGL(verify_resolve_kernel, dim3(vf_blocks(pairs)), dim3(VF_THREADS), 0, st, ra);
+    hipLaunchKernelGGL(verify_resolve_kernel, dim3(dlc::capped_blocks(pairs)), dim3(VF_THREADS), 0, st, ra);
     DLC_LAUNCH_CHECK(ctx, "verify_resolve_kernel");
     return DLC_OK;
 }

@@ -17,6 +17,7 @@
 //   K-MEANS: assign (distances to the workspace), block sums, per-block counts / inertia / changed, and one finishing
 //          launch whose thread (k, h) folds its column of block sums in place, neighbour with neighbour, and divides.
 #include "dlc_internal.h"
+#include "lds_tree.h"
 
 // every difference, product and sum rounded on its own (hipcc contracts a * b + c into an fma otherwise)
 #pragma clang fp contract(off)
@@ -29,7 +30,6 @@ constexpr int VL_WALK = 8;                    // rows of a member sum whose load
 constexpr int VL_ACC = 8192;                   // doubles of LDS accumulators, [K][TW]
 constexpr int VL_TREE = 2048;                  // tree nodes folded in LDS at a time
 constexpr int VL_TREE_TOP = 512;               // 2048 * 2048 * 512 = 2^31 leaves
-constexpr long long VL_MAX_BLOCKS = 1 << 20;   // more items than this: a workgroup takes several, one after the other
 constexpr unsigned long long VL_NAN_BITS = 0x7ff8000000000000ull;
 
 struct VlAssignArgs {
@@ -193,21 +193,6 @@ __global__ __launch_bounds__(VL_THREADS) void vlad_member_sum_kernel(const VlSum
     }
 }
 
-// a[0 .. cnt) (written, not yet synchronised), padded with -0.0 to a power of two and folded neighbour with neighbour
-__device__ __forceinline__ double vl_lds_tree(double* a, int cnt) {
-    int P = 1;
-    while (P < cnt) P <<= 1;
-    for (int t = cnt + (int)threadIdx.x; t < P; t += VL_THREADS) a[t] = -0.0;
-    __syncthreads();
-    for (int s = 1; s < P; s <<= 1) {
-        for (int t = threadIdx.x; t < P / (2 * s); t += VL_THREADS) a[2 * s * t] = a[2 * s * t] + a[2 * s * t + s];
-        __syncthreads();
-    }
-    const double v = a[0];
-    __syncthreads();                           // (a is free again)
-    return v;
-}
-
 // TREE of C >= 1 leaves leaf(0) .. leaf(C - 1), in every thread of a workgroup of VL_THREADS
 template <class Leaf>
 __device__ __forceinline__ double vl_tree(long long C, double* node, double* mid, double* top, Leaf leaf) {
@@ -220,15 +205,15 @@ __device__ __forceinline__ double vl_tree(long long C, double* node, double* mid
             const long long base = (T * VL_TREE + m) * VL_TREE, left = C - base;
             const int cnt = left < VL_TREE ? (int)left : VL_TREE;
             for (int j = threadIdx.x; j < cnt; j += VL_THREADS) node[j] = leaf(base + j);
-            const double v = vl_lds_tree(node, cnt);
+            const double v = dlc_lds_tree<VL_THREADS>(node, cnt);
             if (nmid == 1) return v;
             if (threadIdx.x == 0) mid[m] = v;
         }
-        const double v = vl_lds_tree(mid, mcnt);
+        const double v = dlc_lds_tree<VL_THREADS>(mid, mcnt);
         if (ntop == 1) return v;
         if (threadIdx.x == 0) top[T] = v;
     }
-    return vl_lds_tree(top, (int)ntop);
+    return dlc_lds_tree<VL_THREADS>(top, (int)ntop);
 }
 
 struct VlNormArgs {
@@ -325,8 +310,6 @@ __global__ __launch_bounds__(VL_THREADS) void kmeans_finish_kernel(const VlStepA
     }
 }
 
-unsigned vl_blocks(long long items) { return (unsigned)(items < VL_MAX_BLOCKS ? items : VL_MAX_BLOCKS); }
-
 int vl_tile_width(int K) {
     int tw = VL_THREADS;
     while ((long long)K * tw > VL_ACC) tw >>= 1;
@@ -353,13 +336,13 @@ int vl_assign_launch(dlc_ctx* ctx, const double* x, long long rows, long long H,
     VlAssignArgs a = {x, c, assign, dist, rows, H, ldx, ldc, 0, K};
     if (K <= 16) {
         a.row_tiles = dlc::cdiv(rows, 128);
-        hipLaunchKernelGGL((vlad_assign_kernel<8, 1>), dim3(vl_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
+        hipLaunchKernelGGL((vlad_assign_kernel<8, 1>), dim3(dlc::capped_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
     } else if (K <= 32) {
         a.row_tiles = dlc::cdiv(rows, 64);
-        hipLaunchKernelGGL((vlad_assign_kernel<4, 2>), dim3(vl_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
+        hipLaunchKernelGGL((vlad_assign_kernel<4, 2>), dim3(dlc::capped_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
     } else {
         a.row_tiles = dlc::cdiv(rows, 64);
-        hipLaunchKernelGGL((vlad_assign_kernel<4, 4>), dim3(vl_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
+        hipLaunchKernelGGL((vlad_assign_kernel<4, 4>), dim3(dlc::capped_blocks(a.row_tiles)), dim3(VL_THREADS), 0, st, a);
     }
     DLC_LAUNCH_CHECK(ctx, "vlad_assign_kernel");
     return DLC_OK;
@@ -378,12 +361,6 @@ size_t vl_step_workspace(int64_t rows, int64_t H, int K) {
     return dlc::align_up(8 * ((size_t)rows + nb * (size_t)K * (size_t)H + nb * ((size_t)K + 2)), 256);
 }
 
-// [p, p + bytes) and [q, q + bytes2) share a byte
-bool vl_overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + bytes2 && b < a + bytes;
-}
-
 }  // namespace
 
 extern "C" int dlc_vlad_assign(dlc_ctx* ctx, const double* x, int64_t rows, int64_t H, int64_t ldx, const double* centroids,
@@ -393,8 +370,7 @@ extern "C" int dlc_vlad_assign(dlc_ctx* ctx, const double* x, int64_t rows, int6
     if (rc != DLC_OK) return rc;
     if (!out_assign || (((uintptr_t)out_assign) & 3) || (((uintptr_t)out_dist) & 7))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "vlad_assign: out_assign is null or an output is not aligned to its element");
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    DLC_ON_DEVICE(ctx);
     return vl_assign_launch(ctx, x, rows, H, ldx, centroids, K, ldc, out_assign, out_dist, (hipStream_t)stream);
 }
 
@@ -416,11 +392,9 @@ extern "C" int dlc_vlad_encode(dlc_ctx* ctx, const double* x, int64_t frames, in
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "vlad_encode: out is null or an output is not aligned to its element");
     if (ld_out < (int64_t)K * H)
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "vlad_encode: ld_out=%lld < K * H=%lld", (long long)ld_out, (long long)K * H);
-    const size_t need = vl_encode_workspace(frames, P, H, K);
-    if (!need || !workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "vlad_encode: needs %zu bytes of 16-byte aligned workspace", need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    const int rw = dlc::check_workspace(ctx, "vlad_encode", workspace, workspace_bytes, vl_encode_workspace(frames, P, H, K));
+    if (rw != DLC_OK) return rw;
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     int* assign = out_assign ? out_assign : (int*)workspace;
     const long long rows = (long long)frames * P;
@@ -429,11 +403,11 @@ extern "C" int dlc_vlad_encode(dlc_ctx* ctx, const double* x, int64_t frames, in
     VlSumArgs s = {x, centroids, assign, out, rows, P, frames, H, ldx, ldc, ld_out, 0, 0, K, vl_tile_width(K)};
     s.htiles = dlc::cdiv(H, s.tw);
     s.items = frames * s.htiles;
-    hipLaunchKernelGGL((vlad_member_sum_kernel<true>), dim3(vl_blocks(s.items)), dim3(s.tw), 0, st, s);
+    hipLaunchKernelGGL((vlad_member_sum_kernel<true>), dim3(dlc::capped_blocks(s.items)), dim3(s.tw), 0, st, s);
     DLC_LAUNCH_CHECK(ctx, "vlad_member_sum_kernel (residuals)");
     if (norm == DLC_VLAD_NORM_INTRA) {
         const VlNormArgs n = {out, (long long)frames * K, H, ld_out, K};
-        hipLaunchKernelGGL(vlad_intra_norm_kernel, dim3(vl_blocks(n.items)), dim3(VL_THREADS), 0, st, n);
+        hipLaunchKernelGGL(vlad_intra_norm_kernel, dim3(dlc::capped_blocks(n.items)), dim3(VL_THREADS), 0, st, n);
         DLC_LAUNCH_CHECK(ctx, "vlad_intra_norm_kernel");
     }
     return DLC_OK;
@@ -454,15 +428,13 @@ extern "C" int dlc_kmeans_step(dlc_ctx* ctx, const double* x, int64_t rows, int6
         ((((uintptr_t)out_assign) | ((uintptr_t)prev_assign)) & 3))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "kmeans_step: a pointer is not aligned to its element");
     if (ldc_out < H) return dlc::fail(ctx, DLC_ERR_BAD_ARG, "kmeans_step: ldc_out=%lld < H=%lld", (long long)ldc_out, (long long)H);
-    if (vl_overlap(c_in, (size_t)(((int64_t)K - 1) * ldc + H) * 8, c_out, (size_t)(((int64_t)K - 1) * ldc_out + H) * 8))
+    if (dlc::overlap(c_in, (size_t)(((int64_t)K - 1) * ldc + H) * 8, c_out, (size_t)(((int64_t)K - 1) * ldc_out + H) * 8))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "kmeans_step: c_out overlaps c_in");
-    if (prev_assign && vl_overlap(prev_assign, (size_t)rows * 4, out_assign, (size_t)rows * 4))
+    if (prev_assign && dlc::overlap(prev_assign, (size_t)rows * 4, out_assign, (size_t)rows * 4))
         return dlc::fail(ctx, DLC_ERR_BAD_ARG, "kmeans_step: out_assign overlaps prev_assign");
-    const size_t need = vl_step_workspace(rows, H, K);
-    if (!need || !workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15))
-        return dlc::fail(ctx, DLC_ERR_WORKSPACE, "kmeans_step: needs %zu bytes of 16-byte aligned workspace", need);
-    dlc::DeviceGuard guard(ctx->device);
-    if (!guard.ok) return dlc::fail(ctx, DLC_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
+    const int rw = dlc::check_workspace(ctx, "kmeans_step", workspace, workspace_bytes, vl_step_workspace(rows, H, K));
+    if (rw != DLC_OK) return rw;
+    DLC_ON_DEVICE(ctx);
     hipStream_t st = (hipStream_t)stream;
     const long long nb = dlc::cdiv(rows, DLC_KMEANS_BLOCK), KH = (long long)K * H;
     double* dist = (double*)workspace;
@@ -477,11 +449,12 @@ extern "C" int dlc_kmeans_step(dlc_ctx* ctx, const double* x, int64_t rows, int6
     VlSumArgs s = {x, c_in, out_assign, a.S, rows, DLC_KMEANS_BLOCK, nb, H, ldx, ldc, KH, 0, 0, K, vl_tile_width(K)};
     s.htiles = dlc::cdiv(H, s.tw);
     s.items = nb * s.htiles;
-    hipLaunchKernelGGL((vlad_member_sum_kernel<false>), dim3(vl_blocks(s.items)), dim3(s.tw), 0, st, s);
+    hipLaunchKernelGGL((vlad_member_sum_kernel<false>), dim3(dlc::capped_blocks(s.items)), dim3(s.tw), 0, st, s);
     DLC_LAUNCH_CHECK(ctx, "vlad_member_sum_kernel (block sums)");
-    hipLaunchKernelGGL(kmeans_block_stats_kernel, dim3(vl_blocks(dlc::cdiv(nb * (K + 1), VL_THREADS))), dim3(VL_THREADS), 0, st, a);
+    hipLaunchKernelGGL(kmeans_block_stats_kernel, dim3(dlc::capped_blocks(dlc::cdiv(nb * (K + 1), VL_THREADS))), dim3(VL_THREADS), 0,
+                       st, a);
     DLC_LAUNCH_CHECK(ctx, "kmeans_block_stats_kernel");
-    hipLaunchKernelGGL(kmeans_finish_kernel, dim3(vl_blocks(dlc::cdiv(KH + K + 1, VL_THREADS))), dim3(VL_THREADS), 0, st, a);
+    hipLaunchKernelGGL(kmeans_finish_kernel, dim3(dlc::capped_blocks(dlc::cdiv(KH + K + 1, VL_THREADS))), dim3(VL_THREADS), 0, st, a);
     DLC_LAUNCH_CHECK(ctx, "kmeans_finish_kernel");
     return DLC_OK;
 }

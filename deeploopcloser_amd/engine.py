@@ -934,6 +934,36 @@ class Engine:
                              "apart" % (what, kind, rows, ">= " if wider else "", n, self.device, n))
         return t
 
+    @staticmethod
+    def _ld_out(t, rows, width):
+        """The pitch the library is told for a result _rows_out has passed: one row has none of its own."""
+        return t.stride(0) if rows > 1 else width
+
+    @staticmethod
+    def _row_strided(t, rows, width):
+        """A checked 2-D operand [rows, >= width] -> (t, ld): a view with unit column stride and rows at least `width`
+        apart is taken as it is, anything else made contiguous."""
+        if t.stride(1) != 1 or (rows > 1 and t.stride(0) < width):
+            t = t.contiguous()
+        return t, t.stride(0) if rows > 1 else max(width, t.stride(0))
+
+    def _f64_vector(self, who, what, v, n):
+        """An optional fp64 vector [n] on the device (a mean, a scale): None, or v made contiguous."""
+        if v is None:
+            return None
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.device != self.device or tuple(v.shape) != (n,):
+            raise ValueError("%s: %s must be a float64 tensor [%d] on %s" % (who, what, n, self.device))
+        return v.contiguous()
+
+    @staticmethod
+    def _split_plan(who, plan, rows, codes, max_rows):
+        """The plan word of a call whose "split" plan takes at most max_rows rows -> its code (codes: word -> code)."""
+        if plan not in codes:
+            raise ValueError("%s: plan=%r is none of %s" % (who, plan, sorted(codes)))
+        if plan == "split" and rows > max_rows:
+            raise ValueError("%s: plan 'split' takes at most %d rows, not %d" % (who, max_rows, rows))
+        return codes[plan]
+
     def cnnvtl_distance_topk(self, q, db, k, d=None, limit0=None, limit_step=0, out=None):
         """(dist [Q, k] int64, idx [Q, k] int64): the k rows of db [N, D] int8 nearest to each query row of q [Q, D] int8 by
         the cnn_vtl distance, distance ascending, ties -> the lower row; query r sees the first min(N, limit0 + r *
@@ -979,9 +1009,8 @@ class Engine:
             return out
         q = self._rows16(q.view(torch.int8), d).view(dtype)
         db = self._rows16(db.view(torch.int8), d).view(dtype)
-        ld_out = out.stride(0) if nq > 1 else n
         self._check(fn(self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d, *_limits(n, limit0, limit_step),
-                       _ptr(out), ld_out, self._stream()))
+                       _ptr(out), self._ld_out(out, nq, n), self._stream()))
         self._wrote(out)
         return out
 
@@ -1011,9 +1040,8 @@ class Engine:
         out = self._rows_out("seqslam_describe: out", out, f, h * w, torch.uint8, "a uint8", wider=True)
         if f == 0:
             return out[:, :h * w]
-        ld_out = out.stride(0) if f > 1 else out.shape[1]
         self._check(self.lib.dlc_seqslam_describe_u8(self.ctx, _ptr(gray), f, hh, ww, h, w, int(patch), int(strength),
-                                                      _ptr(out), ld_out, self._stream()))
+                                                      _ptr(out), self._ld_out(out, f, h * w), self._stream()))
         self._wrote(out)
         return out[:, :h * w]
 
@@ -1057,8 +1085,8 @@ class Engine:
             db = self._rows16_u8(db, d)
             self._check(self.lib.dlc_sad_u8_shift_rows(
                 self.ctx, _ptr(q), nq, q.stride(0), _ptr(db), n, db.stride(0), d // width, width, shift,
-                *_limits(n, limit0, limit_step), _ptr(out), out.stride(0) if nq > 1 else n,
-                None if sh is None else _ptr(sh), 0 if sh is None else (sh.stride(0) if nq > 1 else n), self._stream()))
+                *_limits(n, limit0, limit_step), _ptr(out), self._ld_out(out, nq, n),
+                None if sh is None else _ptr(sh), 0 if sh is None else self._ld_out(sh, nq, n), self._stream()))
             self._wrote(out)
             if sh is not None:
                 self._wrote(sh)
@@ -1101,9 +1129,8 @@ class Engine:
         out = self._rows_out("ldb_describe: out", out, f, nb, torch.uint8, "a uint8", wider=True)
         if f == 0:
             return out[:, :nb]
-        ld_out = out.stride(0) if f > 1 else out.shape[1]
-        self._check(self.lib.dlc_ldb_describe_u8(self.ctx, _ptr(gray), f, hh, ww, h, w, arr, n, _ptr(out), ld_out,
-                                                  self._stream()))
+        self._check(self.lib.dlc_ldb_describe_u8(self.ctx, _ptr(gray), f, hh, ww, h, w, arr, n, _ptr(out),
+                                                  self._ld_out(out, f, nb), self._stream()))
         self._wrote(out)
         return out[:, :nb]
 
@@ -1135,21 +1162,14 @@ class Engine:
             raise ValueError("lsh_quantize: x is [%d, %d]: nothing to do" % (rows, d))
         if d > L.DLC_LSH_MAX_D or rows >= 1 << 31:
             raise ValueError("lsh_quantize: rows=%d, D=%d outside rows < 2^31, D <= %d" % (rows, d, L.DLC_LSH_MAX_D))
-        if x.stride(1) != 1 or (rows > 1 and x.stride(0) < d):
-            x = x.contiguous()
-        ldx = x.stride(0) if rows > 1 else max(d, x.stride(0))
-        if mean is not None:
-            if not isinstance(mean, torch.Tensor) or mean.dtype != torch.float64 or mean.device != self.device or \
-                    tuple(mean.shape) != (d,):
-                raise ValueError("lsh_quantize: mean must be a float64 tensor [%d] on %s" % (d, self.device))
-            mean = mean.contiguous()
+        x, ldx = self._row_strided(x, rows, d)
+        mean = self._f64_vector("lsh_quantize", "mean", mean, d)
         if out is None:
             out = torch.empty((rows, (d + 15) // 16 * 16), dtype=torch.int8, device=self.device)
         else:
             out = self._rows_out("lsh_quantize: out", out, rows, d, torch.int8, "an int8", wider=True)
-        ldq = out.stride(0) if rows > 1 else out.shape[1]
         self._check(self.lib.dlc_lsh_quantize_i8(self.ctx, self._LSH_DTYPES[x.dtype], _ptr(x), rows, d, ldx, _ptr(mean), _ptr(out),
-                                                  ldq, self._stream()))
+                                                  self._ld_out(out, rows, d), self._stream()))
         self._wrote(out)
         return out[:, :d]
 
@@ -1168,8 +1188,6 @@ class Engine:
         workgroup walks all of D; "split", <= 64 rows: pieces of D are spread over the chip; "auto" chooses).  out: a
         caller-kept uint8 [rows, >= row_bytes] tensor or row-strided view -- rows of a HammingKeyframeDatabase, say; the
         bytes past row_bytes of a row keep their value -- and the result is its first row_bytes columns."""
-        if plan not in self._LSH_PLANS:
-            raise ValueError("lsh_hash: plan=%r is none of %s" % (plan, sorted(self._LSH_PLANS)))
         d = self._int8_pair("lsh_hash", q, planes, None)
         rows, n = q.shape[0], planes.shape[0]
         bits = n if bits is None else int(bits)
@@ -1178,17 +1196,15 @@ class Engine:
         if d > L.DLC_LSH_MAX_D or rows >= 1 << 31:
             raise ValueError("lsh_hash: rows=%d, D=%d outside rows < 2^31, D <= %d" % (rows, d, L.DLC_LSH_MAX_D))
         nb = self.lsh_row_bytes(bits)
-        code = self._LSH_PLANS[plan]
-        if code == L.DLC_LSH_PLAN_SPLIT and rows > L.DLC_LSH_SPLIT_MAX_ROWS:
-            raise ValueError("lsh_hash: plan 'split' takes at most %d rows, not %d" % (L.DLC_LSH_SPLIT_MAX_ROWS, rows))
+        code = self._split_plan("lsh_hash", plan, rows, self._LSH_PLANS, L.DLC_LSH_SPLIT_MAX_ROWS)
         out = self._rows_out("lsh_hash: out", out, rows, nb, torch.uint8, "a uint8", wider=True)
         q = self._rows16(q, d)
         planes = self._rows16(planes, d)
-        ld_out = out.stride(0) if rows > 1 else out.shape[1]
         need = self.lib.dlc_lsh_hash_workspace_bytes(rows, d, bits, code)
         ws = self.workspace("lsh_hash", need) if need else None
         self._check(self.lib.dlc_lsh_hash_i8(self.ctx, _ptr(q), rows, d, q.stride(0), _ptr(planes), bits, planes.stride(0), _ptr(out),
-                                              ld_out, code, _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
+                                              self._ld_out(out, rows, nb), code, _ptr(ws), ws.numel() if ws is not None else 0,
+                                              self._stream()))
         self._wrote(out)
         return out[:, :nb]
 
@@ -1213,9 +1229,8 @@ class Engine:
         n = scores.shape[1] if n is None else int(n)
         if rows < 1 or n < 1 or n > scores.shape[1]:
             raise ValueError("%s: scores [%d, %d] with n=%d: nothing to %s" % (who, rows, scores.shape[1], n, nothing))
-        if scores.stride(1) != 1 or (rows > 1 and scores.stride(0) < n):
-            scores = scores.contiguous()
-        return scores, rows, n, scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+        scores, ld = self._row_strided(scores, rows, n)
+        return scores, rows, n, ld
 
     def _offset_table(self, who, offsets, length):
         """The HOST table offsets [V, L] of a line search as the library takes it: (V, the int32 table's pointer)."""
@@ -1355,10 +1370,9 @@ class Engine:
             raise ValueError("contrast_rows: radius=%d outside 1..32" % int(radius))
         out = self._rows_out("contrast_rows: out", out, rows, n, torch.float64, "a float64",
                              float("nan") if limit0 is not None or limit_step != 0 else None, wider=True)
-        ld_out = out.stride(0) if rows > 1 else n
         self._check(self.lib.dlc_contrast_rows(self.ctx, self._SEQ_DTYPES[scores.dtype], _ptr(scores), rows, n, ld,
                                                 *_limits(n, limit0, limit_step), int(radius), _ptr(out),
-                                                ld_out, self._stream()))
+                                                self._ld_out(out, rows, n), self._stream()))
         self._wrote(out)
         return out[:, :n]
 
@@ -1403,7 +1417,6 @@ class Engine:
             lds.append(ld)
         out = self._rows_out("fuse_rows: out", out, rows, n, torch.float64, "a float64",
                              float("nan") if limit0 is not None or limit_step != 0 else None, wider=True)
-        ld_out = out.stride(0) if rows > 1 else n
         ws, need = None, 0
         if self._FUSE_PLANS[plan] != L.DLC_FUSE_PLAN_ROW:
             need = self.lib.dlc_fuse_rows_workspace_bytes(rows, n, m)
@@ -1414,8 +1427,8 @@ class Engine:
             self.ctx, m, (C.c_int * m)(*[self._SEQ_DTYPES[s.dtype] for s in mats]),
             (C.c_void_p * m)(*[s.data_ptr() for s in mats]), (C.c_int64 * m)(*lds), (C.c_double * m)(*w.tolist()),
             (C.c_int * m)(*[int(v) for v in lib]), rows, n, *_limits(n, limit0, limit_step),
-            self._FUSE_NORMS[norm], self._FUSE_PLANS[plan], _ptr(out), ld_out, _ptr(ws), ws.numel() if ws is not None else 0,
-            self._stream()))
+            self._FUSE_NORMS[norm], self._FUSE_PLANS[plan], _ptr(out), self._ld_out(out, rows, n), _ptr(ws),
+            ws.numel() if ws is not None else 0, self._stream()))
         self._wrote(out)
         return out[:, :n]
 
@@ -1431,9 +1444,8 @@ class Engine:
             raise ValueError("%s: %s is [%d, %d]: nothing to do" % (who, what, rows, h))
         if width is not None and h != width:
             raise ValueError("%s: %s is %d wide, the rows are %d" % (who, what, h, width))
-        if t.stride(1) != 1 or (rows > 1 and t.stride(0) < h):
-            t = t.contiguous()
-        return t, rows, h, t.stride(0) if rows > 1 else max(h, t.stride(0))
+        t, ld = self._row_strided(t, rows, h)
+        return t, rows, h, ld
 
     def _codebook(self, who, centroids, width):
         c, k, _, ldc = self._f64_rows(who, "the codebook", centroids, width)
@@ -1470,20 +1482,14 @@ class Engine:
             raise ValueError("vlad_encode: %d rows are no whole number of frames of %d patches" % (rows, patches))
         frames = rows // patches
         c, k, ldc = self._codebook("vlad_encode", centroids, h)
-        if out is None:
-            out = torch.empty((frames, k * h), dtype=torch.float64, device=self.device)
-        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float64 or out.device != self.device or \
-                out.shape[0] != frames or out.shape[1] < k * h or out.stride(1) != 1 or (frames > 1 and out.stride(0) < k * h):
-            raise ValueError("vlad_encode: out must be a float64 tensor [%d, >= %d] on %s with unit column stride"
-                             % (frames, k * h, self.device))
-        ld_out = out.stride(0) if frames > 1 else max(k * h, out.stride(0))
+        out = self._rows_out("vlad_encode: out", out, frames, k * h, torch.float64, "a float64", wider=True)
         a = torch.empty(rows, dtype=torch.int32, device=self.device) if with_assign else None
         need = self.lib.dlc_vlad_encode_workspace_bytes(frames, patches, h, k)
         if need == 0:
             raise ValueError("vlad_encode: frames=%d, H=%d, K=%d outside the supported sizes" % (frames, h, k))
         ws = self.workspace("vlad_encode", need)
         self._check(self.lib.dlc_vlad_encode(self.ctx, _ptr(x), frames, patches, h, ldx, _ptr(c), k, ldc, self._VLAD_NORMS[norm],
-                                             _ptr(out), ld_out, _ptr(a), _ptr(ws), ws.numel(), self._stream()))
+                                             _ptr(out), self._ld_out(out, frames, k * h), _ptr(a), _ptr(ws), ws.numel(), self._stream()))
         self._wrote(out)
         return (out[:, :k * h], a) if with_assign else out[:, :k * h]
 
@@ -1520,8 +1526,6 @@ class Engine:
         row's bits depend on the row and the model alone, not on its batch or the plan.  plan "one_pass": a workgroup
         walks all of D; "split" (<= 64 rows): the chunks are spread over the chip; "auto" chooses.  out: a float64
         tensor [rows, >= M] with unit column stride to write into (columns past M keep their bits)."""
-        if plan not in self._PCA_PLANS:
-            raise ValueError("pca_project: plan=%r is none of %s" % (plan, sorted(self._PCA_PLANS)))
         x, rows, d, ldx = self._f64_rows("pca_project", "x", x)
         if not isinstance(basis, torch.Tensor) or basis.dim() != 2 or basis.dtype not in (torch.float64, torch.float32) or \
                 basis.device != self.device or basis.shape[0] != d or basis.shape[1] < 1:
@@ -1529,32 +1533,18 @@ class Engine:
         m = basis.shape[1]
         if m > L.DLC_PCA_MAX_COMPONENTS:
             raise ValueError("pca_project: %d components outside 1..%d" % (m, L.DLC_PCA_MAX_COMPONENTS))
-        if basis.stride(1) != 1 or (d > 1 and basis.stride(0) < m):
-            basis = basis.contiguous()
-        ldb = basis.stride(0) if d > 1 else max(m, basis.stride(0))
-        for what, v, n in (("mean", mean, d), ("scale", scale, m)):
-            if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.device != self.device or
-                                  tuple(v.shape) != (n,)):
-                raise ValueError("pca_project: %s must be a float64 tensor [%d] on %s" % (what, n, self.device))
-        mean = mean.contiguous() if mean is not None else None
-        scale = scale.contiguous() if scale is not None else None
-        if out is None:
-            out = torch.empty((rows, m), dtype=torch.float64, device=self.device)
-        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float64 or out.device != self.device or \
-                out.shape[0] != rows or out.shape[1] < m or out.stride(1) != 1 or (rows > 1 and out.stride(0) < m):
-            raise ValueError("pca_project: out must be a float64 tensor [%d, >= %d] on %s with unit column stride"
-                             % (rows, m, self.device))
-        ld_out = out.stride(0) if rows > 1 else max(m, out.stride(0))
-        code = self._PCA_PLANS[plan]
-        if code == L.DLC_PCA_PLAN_SPLIT and rows > L.DLC_PCA_SPLIT_MAX_ROWS:
-            raise ValueError("pca_project: plan 'split' takes at most %d rows, not %d" % (L.DLC_PCA_SPLIT_MAX_ROWS, rows))
+        basis, ldb = self._row_strided(basis, d, m)
+        mean = self._f64_vector("pca_project", "mean", mean, d)
+        scale = self._f64_vector("pca_project", "scale", scale, m)
+        out = self._rows_out("pca_project: out", out, rows, m, torch.float64, "a float64", wider=True)
+        code = self._split_plan("pca_project", plan, rows, self._PCA_PLANS, L.DLC_PCA_SPLIT_MAX_ROWS)
         if rows >= 1 << 31 or d >= 1 << 31:
             raise ValueError("pca_project: rows=%d, D=%d outside the supported sizes" % (rows, d))
         need = self.lib.dlc_pca_project_workspace_bytes(rows, d, m, code)
         ws = self.workspace("pca_project", need) if need else None
         self._check(self.lib.dlc_pca_project(
             self.ctx, _ptr(x), rows, d, ldx, _ptr(mean), L.DLC_F64 if basis.dtype == torch.float64 else L.DLC_F32, _ptr(basis), m,
-            ldb, _ptr(scale), _ptr(out), ld_out, code, _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
+            ldb, _ptr(scale), _ptr(out), self._ld_out(out, rows, m), code, _ptr(ws), ws.numel() if ws is not None else 0, self._stream()))
         self._wrote(out)
         return out[:, :m]
 
@@ -1610,9 +1600,7 @@ class Engine:
                 cand.shape[0] != q or not 1 <= cand.shape[1] <= L.DLC_MAX_K:
             raise ValueError("%s: cand must be an int64 tensor [%d, 1..%d] on %s" % (who, q, L.DLC_MAX_K, self.device))
         k = cand.shape[1]
-        if cand.stride(1) != 1 or (q > 1 and cand.stride(0) < k):
-            cand = cand.contiguous()
-        ld_cand = cand.stride(0) if q > 1 else max(k, cand.stride(0))
+        cand, ld_cand = self._row_strided(cand, q, k)
         need = self.lib.dlc_verify_pairs_workspace_bytes(q, k, p)
         if need == 0:
             raise ValueError("%s: Q=%d, k=%d, P=%d outside the supported sizes" % (who, q, k, p))
@@ -1704,7 +1692,7 @@ class Engine:
             o_back = back
         elif back:
             o_back = torch.empty((rows, n), dtype=torch.int8, device=self.device)
-        ld_back = 0 if o_back is None else (o_back.stride(0) if rows > 1 else max(n, o_back.stride(0)))
+        ld_back = 0 if o_back is None else self._ld_out(o_back, rows, n)
         o_dense = torch.empty((rows, n), dtype=out_dtype, device=self.device) if dense else None
         place, g = (torch.empty(rows, dtype=torch.int64, device=self.device) for _ in range(2))
         o_G, o_U = (torch.empty(rows, dtype=out_dtype, device=self.device) for _ in range(2))
@@ -1744,7 +1732,7 @@ class Engine:
             raise ValueError("%s: end=%d is no column of %d, -1 or DLC_TRACK_END_FILTERED" % (who, end, n))
         path = torch.empty(rows, dtype=torch.int64, device=self.device)
         self._check(self.lib.dlc_track_backtrace(
-            self.ctx, rows, n, _ptr(back), back.stride(0) if rows > 1 else max(n, back.stride(0)), _ptr(backU), _ptr(g),
+            self.ctx, rows, n, _ptr(back), self._ld_out(back, rows, n), _ptr(backU), _ptr(g),
             _ptr(place_last if end == L.DLC_TRACK_END_FILTERED else None), end, _ptr(path), self._stream()))
         return path
 
@@ -1759,9 +1747,7 @@ class Engine:
             raise ValueError("%s: truth [%d, %d] does not cover scores [%d, %d]" % (who, truth.shape[0], truth.shape[1], rows, n))
         if truth.dtype == torch.bool:
             truth = truth.view(torch.uint8)
-        if truth.stride(1) != 1 or (rows > 1 and truth.stride(0) < n):
-            truth = truth.contiguous()
-        return truth, truth.stride(0) if rows > 1 else max(n, truth.stride(0))
+        return self._row_strided(truth, rows, n)
 
     def sorted_thresholds(self, thresholds, is_int):
         """The threshold table pr_cell_counts hands to the library, on the device: the numbers of `thresholds` (a sequence
@@ -2156,7 +2142,7 @@ class Engine:
             return ret
         if d == 0:
             raise ValueError("cosine_score_rows: empty descriptors")
-        ld_out = (o_s if o_s is not None else o_k).stride(0) if nq > 1 else n
+        ld_out = self._ld_out(o_s if o_s is not None else o_k, nq, n)
         if both and nq > 1 and o_k.stride(0) != ld_out:
             raise ValueError("cosine_score_rows: out and out_keys must have one row stride (%d, %d)" % (ld_out, o_k.stride(0)))
         self._check(self.lib.dlc_cosine_score_rows(self.ctx, _TORCH_TO_DLC[q.dtype], _ptr(q), nq, q.stride(0), _ptr(db), n,

@@ -1,7 +1,7 @@
 """One build-and-run recipe for the kernel texts that run on the host (tests/test_{contrast,fuse,vlad,pca}_host_cpu.py):
 a kernel's .hip is compiled as C++ in front of tests/host_sanitize/<name>/driver.cpp, against the shared stand-in
-tests/host_sanitize/dlc_internal.h and the library's own include/dlc.h, csrc/dlc_hd.h and csrc/score_rows.h, and run as
-a stand-alone program under AddressSanitizer + UBSan."""
+tests/host_sanitize/dlc_internal.h and the library's own include/dlc.h, csrc/dlc_hd.h, csrc/entry.h, csrc/lds_tree.h and
+csrc/score_rows.h, and run as a stand-alone program under AddressSanitizer + UBSan."""
 import os
 import shutil
 import subprocess
@@ -24,8 +24,8 @@ def run(tmp_path, name, kernel):
     (tmp_path / "include").mkdir()
     shutil.copy(os.path.join(ROOT, "include", "dlc.h"), str(tmp_path / "include"))
     shutil.copy(os.path.join(csrc, kernel + ".hip"), str(work / (kernel + ".cpp")))
-    for path in (os.path.join(csrc, "dlc_hd.h"), os.path.join(csrc, "score_rows.h"),
-                 os.path.join(san, "dlc_internal.h"), os.path.join(san, name, "driver.cpp")):
+    for path in [os.path.join(csrc, h) for h in ("dlc_hd.h", "entry.h", "lds_tree.h", "score_rows.h")] + \
+            [os.path.join(san, "dlc_internal.h"), os.path.join(san, name, "driver.cpp")]:
         shutil.copy(path, str(work))
     exe = str(work / (name + "_host"))
     subprocess.check_call([CLANG] + FLAGS + [str(work / "driver.cpp"), "-o", exe])

@@ -42,11 +42,16 @@ inline long long __double_as_longlong(double v) { long long d; memcpy(&d, &v, 8)
 namespace dlc {
 struct DeviceGuard { bool ok = true; explicit DeviceGuard(int) {} };
 }
+#define DLC_ON_DEVICE(ctx)                                                                                         \
+    dlc::DeviceGuard guard((ctx)->device);                                                                         \
+    if (!guard.ok) return dlc::fail((ctx), DLC_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
 #define DLC_LAUNCH_CHECK(ctx, what)
 #define DLC_HIP_CHECK(ctx, expr)                                                                                   \
     do {                                                                                                           \
         if ((expr) != hipSuccess) return dlc::fail((ctx), DLC_ERR_HIP, "%s failed (%s:%d)", #expr, __FILE__, __LINE__); \
     } while (0)
+
+#include "entry.h"
 
 // ---- the launcher ------------------------------------------------------------------------------------------------------
 namespace emu {

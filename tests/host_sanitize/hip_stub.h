@@ -153,6 +153,9 @@ struct DeviceGuard {
     explicit DeviceGuard(int) {}
 };
 }  // namespace dlc
+#define DLC_ON_DEVICE(ctx)                                                                                         \
+    dlc::DeviceGuard guard((ctx)->device);                                                                         \
+    if (!guard.ok) return dlc::fail((ctx), DLC_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
 #define DLC_HIP_CHECK(ctx, expr)                                                                                   \
     do {                                                                                                           \
         hipError_t e__ = (expr);                                                                                   \
