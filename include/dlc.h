@@ -435,6 +435,11 @@ int dlc_maxpool3x3s2_nhwc_f64(dlc_ctx* ctx, const double* x, int64_t n, int h, i
  * (`cols`: DEVICE int64 indices into the concatenated row -- the boolean mask of
  * :118-128 as a sorted list).  minmax is a [n,2] fp64 DEVICE scratch the call
  * fills (min,max per row); out is [n, n_cols] int8.  n <= 65535 per call.
+ * Outside what the reference defines:
+ *   - a column index outside [0, width) writes byte 0;
+ *   - min and max are taken over the row's non-NaN cells (fmin / fmax);
+ *   - a cell whose scaled value is NaN or beyond +-9e18 writes byte 0: a constant row (255/0), a row holding an
+ *     infinity and a row whose spread overflows the scale are all zeros, and so is a NaN cell.
  */
 int dlc_minmax_quant_gather_i8(dlc_ctx* ctx, const double* const* segs, const int64_t* seg_sizes, int n_segs,
                                int64_t n, const int64_t* cols, int64_t n_cols, double* minmax,
